@@ -8,13 +8,19 @@ message layer with fused tail)) with the graph plan cached and inputs resident i
 N > 1 (launched by torch.distributed.run): the SAME graph sharded by destination range,
 one rank per GPU, all-gather of h per layer over RCCL -> "scaling": "strong".
 
-Extra objects on the line:
+A plain run sets up, warms up, times --steps forwards and prints the line.  --dump-outputs DIR
+also writes the last timed forward's output to DIR/out.npy (float32; every row, or a fixed
+seeded sample of rows when the output exceeds DUMP_BYTES); the inputs depend only on the
+arguments, so two builds can be compared output for output.
+
+Extra objects on the line, measured with --full only (runs of their own after the timed steps):
   roofline     — the dominant kernel (message layer): achieved = algorithmic flops / mean
                  launch duration (HIP events on the launch stream), against the fp32 matrix
                  peak, which binds this kernel before HBM does; the HBM
                  view (algorithmic bytes / duration vs 8 TB/s) is reported beside it.
   cpu_baseline — the oracle (CPU restatement of the reference op sequence) timed on the host
-                 cores on a bounded sample of the same workload.
+                 cores on a bounded sample of the same workload (--no-cpu-baseline skips it).
+  dist         — N > 1: every rank's compute / exchange split of a forward.
 """
 
 from __future__ import annotations
@@ -48,6 +54,20 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s
 FP32_MATRIX_PEAK_TF = 157.3    # MI355X_MICROARCH.md: v_mfma_f32_* peak (= fp32 vector peak)
 F16_MATRIX_PEAK_TF = 2500.0    # MI355X_MICROARCH.md: dense bf16/fp16 MFMA peak
 L2_STREAM_CEILING_GBS = 33000.0  # tools/micro/l2stream.hip on this chip: L2-resident streaming into registers, all 256 CUs
+DUMP_BYTES = 32 << 20          # --dump-outputs: outputs larger than this are written as a sample of rows
+DUMP_SEED = 20240601           # the sample's rows: the same for every build and run
+
+
+def dump_outputs(out, path):
+    """Write the forward's output [N, d] as path/out.npy (float32): every row, or DUMP_BYTES worth of rows drawn without
+    replacement by a fixed seed, in ascending order."""
+    N, d = out.shape
+    rows = DUMP_BYTES // (4 * d)
+    if N > rows:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(N, size=rows, replace=False))
+        out = out.index_select(0, torch.from_numpy(idx).to(out.device))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "out.npy"), out.detach().float().cpu().numpy())
 
 
 def layer_bytes(N, E, R, d):
@@ -190,10 +210,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline, the CPU baseline and (N > 1) the per-rank split")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's output to DIR/out.npy (a fixed sample of rows beyond %d MiB)" % (DUMP_BYTES >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--hip-graph", action="store_true",
                     help="single GPU: a step replays the captured HIP graph of the warm forward (HyperGNN.graphed)")
-    ap.add_argument("--kernel-reps", type=int, default=10, help="timed launches of the message kernel for the roofline")
+    ap.add_argument("--kernel-reps", type=int, default=10, help="--full: timed launches of the message kernel for the roofline")
     ap.add_argument("--dist-mode", default=os.environ.get("GHF_DIST_MODE", "dst"), choices=["dst", "edges"],
                     help="N > 1: destination shards + all-gather (default) or edge-range shards + reduction (BASELINE config 4 as written)")
     ap.add_argument("--exchange", default=os.environ.get("GHF_DIST_EXCHANGE", "auto"), choices=["auto", "allgather", "pairs", "sparse"],
@@ -202,6 +226,8 @@ def main():
     ap.add_argument("--balance", default=os.environ.get("GHF_DIST_BALANCE", "rows"), choices=["rows", "edges"])
     ap.add_argument("--weak", action="store_true", help="N > 1: one full workload per GPU (nodes and edges scale with N)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -300,7 +326,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     sync()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -308,9 +334,11 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     ms_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     dist_detail = None
-    if world > 1:
+    if world > 1 and args.full:
         # where a forward goes on every rank: the same forward with the exchange switched off (compute only), and with the
         # kernels switched off (exchange only); "exposed" = what the full forward takes beyond its compute
         def timed(profile, reps=3):
@@ -345,8 +373,8 @@ def main():
                     "rows_needed = distinct source rows of this rank's in-edges that other ranks own (the exchange's floor per "
                     "layer), rows_received = what this exchange delivers per inner layer (-1: edge-range mode)"}
 
-    line = None
-    if rank == 0:
+    roofline = None
+    if rank == 0 and args.full:
         # ---- dominant kernel: one message layer (K2+K3), timed alone with HIP events on its stream ----
         plan = model.plan_for(edge_index, edge_texts, N, dev) if world == 1 else runner.plan_for(edge_index, edge_texts, N, dev)
         with torch.no_grad():
@@ -436,6 +464,8 @@ def main():
                         "ceiling": L2_STREAM_CEILING_GBS, "unit": "GB/s",
                         "source": "TCC_REQ_sum x 128 B (same PMC file); ceiling measured by tools/micro/l2stream.hip"},
                     "note": roofline_note(wide, plan, d)}
+    line = None
+    if rank == 0:
         line = {
             "metric": "edges/s (HyperGNN forward)", "value": E / (ms_step * 1e-3), "unit": "edges/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
@@ -449,12 +479,14 @@ def main():
                            if runner.mode == "dst" else f"edge-range shards x{world}, reduce-scatter of partial sums + all-gather per layer")},
             "cold_forward_ms": t_cold * 1e3, "setup_s": t_setup,
             "whole_forward_hbm_gbs": (L * layer_bytes(N, E, R, d) + 2 * N * d * 4) / (ms_step * 1e-3) / 1e9,
-            "roofline": roofline,
         }
+        if roofline is not None:
+            line["roofline"] = roofline
         if dist_detail is not None:
             line["dist"] = dist_detail
+        if world > 1:
             line["scaling"] = "weak" if args.weak else "strong"
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             full = (x.cpu().numpy(), ei_np, edge_texts) if args.workload != "c5" else None    # (C5: 64M strings, 16 GB of h)
             line["cpu_baseline"] = cpu_baseline(cfg, full=full)
     if world > 1:

@@ -12,10 +12,10 @@ print(sys.argv[1], "->", x["mode"], x["exchange"], x["exchange_candidates_ms"], 
       "rows needed/received", [(r["rows_needed_per_layer"], r["rows_received_per_layer"]) for r in x["per_rank"]])
 PY
 done <<'LIST'
-c2 --exchange auto
-c3 --exchange sparse
-c2 --dist-mode edges
-c2 --balance edges
-c2 --exchange sparse --balance edges
+c2 --full --exchange auto
+c3 --full --exchange sparse
+c2 --full --dist-mode edges
+c2 --full --balance edges
+c2 --full --exchange sparse --balance edges
 LIST
 exit $rc
