@@ -93,6 +93,7 @@ SIGNATURES = {
     "ghf_score_pairs_fwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp]),
     "ghf_rows_pack": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "ghf_rows_unpack": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+    "ghf_rows_accumulate": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp]),
     "ghf_tail_fwd": (_i32, [_vp, _vp, _vp, _vp, _f32, _i64, _i64, _i32, _vp, _vp, _vp]),
     "ghf_set_range_flag": (_i32, [_vp]),
 }
@@ -867,3 +868,23 @@ def rows_unpack(tables, idx: torch.Tensor, packed: torch.Tensor) -> None:
     if packed.numel() != idx.numel() * (rb + xb):
         raise ValueError(f"rows_unpack: message of {packed.numel()} bytes for {idx.numel()} rows of {rb + xb}")
     _check(load().ghf_rows_unpack(_ptr(packed), _ptr(idx), idx.numel(), rows.size(0), _ptr(rows), rb, _ptr(extra), xb, _stream()), "ghf_rows_unpack")
+
+
+def rows_accumulate(rows: torch.Tensor, idx: Optional[torch.Tensor], packed: torch.Tensor) -> torch.Tensor:
+    """rows[idx[i]] += packed[i] in place (fp32 [nrows, d] and [n, d]; idx None = rows 0..n-1) — ghf_rows_accumulate, the
+    adjoint of rows_unpack.  idx entries must be distinct; entries outside [0, nrows) are skipped."""
+    if rows.dim() != 2 or not rows.is_contiguous() or rows.dtype != torch.float32:
+        raise ValueError(f"rows_accumulate: rows must be a contiguous float32 [nrows, d] tensor, got {rows.dtype} {tuple(rows.shape)}")
+    rows = _req(rows, torch.float32, "rows")
+    nrows, d = rows.shape
+    packed = _req(packed, torch.float32, "packed")
+    if idx is not None:
+        if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous():
+            raise ValueError(f"rows_accumulate: idx must be a contiguous 1-D int64 tensor, got {idx.dtype} {tuple(idx.shape)}")
+        if idx.device != rows.device:
+            raise ValueError(f"rows_accumulate: idx lives on {idx.device}, rows on {rows.device}")
+    n = idx.numel() if idx is not None else packed.numel() // max(d, 1)
+    if packed.device != rows.device or packed.numel() != n * d:
+        raise ValueError(f"rows_accumulate: message of {packed.numel()} floats on {packed.device} for {n} rows of {d} on {rows.device}")
+    _check(load().ghf_rows_accumulate(_ptr(packed), _ptr(idx), n, nrows, _ptr(rows), d, _stream()), "ghf_rows_accumulate")
+    return rows

@@ -109,10 +109,11 @@ def _layer_weights(plan: GraphPlan, Wm: Optional[torch.Tensor], Ws: Optional[tor
     return _native.weights_pack(Wm, Ws, transpose, R, d, plan.wlayout), None
 
 
-def _message(x: torch.Tensor, plan: GraphPlan, W, W_self, bias: torch.Tensor, flags: int, x_split=None, residual=None) -> torch.Tensor:
+def _message(x: torch.Tensor, plan: GraphPlan, W, W_self, bias: torch.Tensor, flags: int, x_split=None, residual=None,
+             zero_out: bool = False) -> torch.Tensor:
     """A message pass without tail (NO_TAIL / RAW_SUM) on the plan's kernel: the destination-block or generic kernel, or —
-    CSR plans of wide rows — the relation-stationary layer."""
-    out = torch.empty_like(x)
+    CSR plans of wide rows — the relation-stationary layer.  zero_out: rows the plan's kernel does not write read zero."""
+    out = torch.zeros_like(x) if zero_out else torch.empty_like(x)
     if plan.block_nodes == 1 and _native.rs_supported(x.size(1)) and plan.E > 0:
         if plan.rs is None:
             plan.rs = build_rs(plan)
@@ -128,12 +129,13 @@ def _message(x: torch.Tensor, plan: GraphPlan, W, W_self, bias: torch.Tensor, fl
     return out
 
 
-def _raw_message(x: torch.Tensor, plan: GraphPlan, W, W_self, zero_bias: torch.Tensor, zero_half: int, x_split=None, residual=None) -> torch.Tensor:
+def _raw_message(x: torch.Tensor, plan: GraphPlan, W, W_self, zero_bias: torch.Tensor, zero_half: int, x_split=None, residual=None,
+                 zero_out: bool = False) -> torch.Tensor:
     # GHF_FLAG_ZERO_*: "this half must not be read" (include/ghf.h) — the block kernels honour it; the others are handed
     # packs whose other half really is zero (MessageLayerFn.backward) and no flag
     if not _native.side_output_supported(plan, x.size(1)):
         zero_half = 0
-    return _message(x, plan, W, W_self, zero_bias, _native.GHF_FLAG_RAW_SUM | zero_half, x_split, residual)
+    return _message(x, plan, W, W_self, zero_bias, _native.GHF_FLAG_RAW_SUM | zero_half, x_split, residual, zero_out)
 
 
 class _SplitCarry:
@@ -209,59 +211,68 @@ class MessageLayerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         h, agg, W_msg, W_self, gamma = ctx.saved_tensors
-        tp: TrainPlan = ctx.tp
-        plan = tp.fwd
-        g = grad_out.contiguous().float()
-        # both gradient passes gather the same rows of G: two-piece plans get them cut by the same launch
-        split_G = (ctx.needs_input_grad[0] and plan.wlayout in _native.SPLIT_LAYOUTS and tp.rev.wlayout == plan.wlayout
-                   and plan.block_nodes > 1)
-        dpre, G, Gs, dgamma, dbeta = _native.tail_bwd(g, agg, h, gamma.detach(), ctx.eps, plan.indeg, drop=ctx.drop,
-                                                      split_layout=plan.wlayout if split_G else None)
-        side = None
-        scales = {}
-        if Gs is not None and ctx.h_scales is not None and plan.wlayout == _native.WLAYOUT_SPLIT2H:
-            scales = dict(h_scales=ctx.h_scales, G_scales=_native.split_row_scales(Gs, G.size(0), G.size(1)))
-        if tp.slice_tab is not None:
-            if _EO_SIDE and ctx.needs_input_grad[0]:
-                # the weight gradients (bound by their row gathers) beside the two gradient passes (bound inside the CU): two
-                # streams, joined before the results leave
-                main = torch.cuda.current_stream(h.device)
-                side = _side_stream(h.device)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    dW, db = _native.edge_outer(h, G, tp.src_by_rel, tp.dst_by_rel, tp.slice_tab, tp.slice_off, plan.R, exact=plan.force_exact, order=tp.slice_order, **scales)
-            else:
-                dW, db = _native.edge_outer(h, G, tp.src_by_rel, tp.dst_by_rel, tp.slice_tab, tp.slice_off, plan.R, exact=plan.force_exact, order=tp.slice_order, **scales)
-            d = h.size(1)
-            dWm, dWs = dW[:, :d], dW[:, d:]
-        else:
-            dWm = _native.group_outer(h, tp.src_by_rel, G, tp.dst_by_rel, tp.goff)
-            dWs = _native.group_outer(h, tp.dst_by_rel, G, tp.dst_by_rel, tp.goff)
-            db = _native.group_outer(None, None, G, tp.dst_by_rel, tp.goff).reshape(plan.R, -1)
-        dh = None
-        if ctx.needs_input_grad[0]:
-            if tp.zero_bias is None or tp.zero_bias.shape != (plan.R, h.size(1)):      # (one fill per plan, not one per layer and step)
-                tp.zero_bias = torch.zeros(plan.R, h.size(1), dtype=torch.float32, device=h.device)
-            zero_b = tp.zero_bias
-            if _ONE_PACK and plan.wlayout == tp.rev.wlayout and plan.wlayout in _native.SPLIT_LAYOUTS:
-                # one packed tensor serves both passes: each declares the half it does not read zero (ZERO_SRC / ZERO_DST)
-                Wf, Wf2 = _layer_weights(plan, W_msg.detach(), W_self.detach(), transpose=True)
-                Wr, Wr2 = Wf, Wf2
-            else:
-                Wf, Wf2 = _layer_weights(plan, None, W_self.detach(), transpose=True)       # self term: rows keyed by destination
-                Wr, Wr2 = _layer_weights(tp.rev, W_msg.detach(), None, transpose=True)      # message term: scattered to the sources
-            if Gs is not None and _native.side_output_supported(plan, h.size(1)) and _native.side_output_supported(tp.rev, h.size(1)):
-                # the three terms are added in the two passes' tails: dpre + self term, then + message term
-                t1 = _raw_message(G, plan, Wf, Wf2, zero_b, _native.GHF_FLAG_ZERO_SRC, Gs, residual=dpre)
-                dh = _raw_message(G, tp.rev, Wr, Wr2, zero_b, _native.GHF_FLAG_ZERO_DST, Gs, residual=t1)
-            else:
-                dh = _native.add3(dpre, _raw_message(G, plan, Wf, Wf2, zero_b, _native.GHF_FLAG_ZERO_SRC, Gs),
-                                  _raw_message(G, tp.rev, Wr, Wr2, zero_b, _native.GHF_FLAG_ZERO_DST, Gs), out=dpre)
-        if side is not None:
-            main.wait_stream(side)
-            dW.record_stream(main)
-            db.record_stream(main)
+        dh, dWm, dWs, db, dgamma, dbeta = layer_backward(grad_out, h, agg, W_msg, W_self, gamma, ctx.eps, ctx.tp, ctx.drop,
+                                                         ctx.h_scales, ctx.needs_input_grad[0])
         return dh, dWm, dWs, db, dgamma, dbeta, None, None, None
+
+
+def layer_backward(grad_out, h, agg, W_msg, W_self, gamma, eps: float, tp: TrainPlan, drop=None, h_scales=None,
+               need_dh: bool = True, shard: bool = False):
+    """(dh, dW_msg, dW_self, db, dgamma, dbeta) of one layer (MessageLayerFn.backward).  shard: `tp.fwd` is a destination shard's
+    plan (dist.ShardedHyperGNN) — its kernels write the owned rows only, so the outputs of the passes on it start from zeros
+    (`grad_out` is zero outside the owned rows, and so are dpre and G there)."""
+    plan = tp.fwd
+    g = grad_out.contiguous().float()
+    # both gradient passes gather the same rows of G: two-piece plans get them cut by the same launch
+    split_G = (need_dh and plan.wlayout in _native.SPLIT_LAYOUTS and tp.rev.wlayout == plan.wlayout
+               and plan.block_nodes > 1)
+    dpre, G, Gs, dgamma, dbeta = _native.tail_bwd(g, agg, h, gamma.detach(), eps, plan.indeg, drop=drop,
+                                                  split_layout=plan.wlayout if split_G else None)
+    side = None
+    scales = {}
+    if Gs is not None and h_scales is not None and plan.wlayout == _native.WLAYOUT_SPLIT2H:
+        scales = dict(h_scales=h_scales, G_scales=_native.split_row_scales(Gs, G.size(0), G.size(1)))
+    if tp.slice_tab is not None:
+        if _EO_SIDE and need_dh:
+            # the weight gradients (bound by their row gathers) beside the two gradient passes (bound inside the CU): two
+            # streams, joined before the results leave
+            main = torch.cuda.current_stream(h.device)
+            side = _side_stream(h.device)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                dW, db = _native.edge_outer(h, G, tp.src_by_rel, tp.dst_by_rel, tp.slice_tab, tp.slice_off, plan.R, exact=plan.force_exact, order=tp.slice_order, **scales)
+        else:
+            dW, db = _native.edge_outer(h, G, tp.src_by_rel, tp.dst_by_rel, tp.slice_tab, tp.slice_off, plan.R, exact=plan.force_exact, order=tp.slice_order, **scales)
+        d = h.size(1)
+        dWm, dWs = dW[:, :d], dW[:, d:]
+    else:
+        dWm = _native.group_outer(h, tp.src_by_rel, G, tp.dst_by_rel, tp.goff)
+        dWs = _native.group_outer(h, tp.dst_by_rel, G, tp.dst_by_rel, tp.goff)
+        db = _native.group_outer(None, None, G, tp.dst_by_rel, tp.goff).reshape(plan.R, -1)
+    dh = None
+    if need_dh:
+        if tp.zero_bias is None or tp.zero_bias.shape != (plan.R, h.size(1)):      # (one fill per plan, not one per layer and step)
+            tp.zero_bias = torch.zeros(plan.R, h.size(1), dtype=torch.float32, device=h.device)
+        zero_b = tp.zero_bias
+        if _ONE_PACK and plan.wlayout == tp.rev.wlayout and plan.wlayout in _native.SPLIT_LAYOUTS:
+            # one packed tensor serves both passes: each declares the half it does not read zero (ZERO_SRC / ZERO_DST)
+            Wf, Wf2 = _layer_weights(plan, W_msg.detach(), W_self.detach(), transpose=True)
+            Wr, Wr2 = Wf, Wf2
+        else:
+            Wf, Wf2 = _layer_weights(plan, None, W_self.detach(), transpose=True)       # self term: rows keyed by destination
+            Wr, Wr2 = _layer_weights(tp.rev, W_msg.detach(), None, transpose=True)      # message term: scattered to the sources
+        if Gs is not None and _native.side_output_supported(plan, h.size(1)) and _native.side_output_supported(tp.rev, h.size(1)):
+            # the three terms are added in the two passes' tails: dpre + self term, then + message term
+            t1 = _raw_message(G, plan, Wf, Wf2, zero_b, _native.GHF_FLAG_ZERO_SRC, Gs, residual=dpre, zero_out=shard)
+            dh = _raw_message(G, tp.rev, Wr, Wr2, zero_b, _native.GHF_FLAG_ZERO_DST, Gs, residual=t1)
+        else:
+            dh = _native.add3(dpre, _raw_message(G, plan, Wf, Wf2, zero_b, _native.GHF_FLAG_ZERO_SRC, Gs, zero_out=shard),
+                              _raw_message(G, tp.rev, Wr, Wr2, zero_b, _native.GHF_FLAG_ZERO_DST, Gs), out=dpre)
+    if side is not None:
+        main.wait_stream(side)
+        dW.record_stream(main)
+        db.record_stream(main)
+    return dh, dWm, dWs, db, dgamma, dbeta
 
 
 class WeightGeneratorFn(torch.autograd.Function):

@@ -522,6 +522,11 @@ int ghf_rows_unpack(const void* packed, const int64_t* idx, int64_t n, int64_t n
     return launch_rows_pack(true, rows, row_bytes, extra, extra_bytes, idx, n, nrows, (void*)packed, (hipStream_t)stream);
 }
 
+int ghf_rows_accumulate(const float* packed, const int64_t* idx, int64_t n, int64_t nrows, float* rows, int d, void* stream) {
+    GHF_REQUIRE(rows && (packed || n == 0), "rows_accumulate: null pointer argument");
+    return launch_rows_accumulate(packed, idx, n, nrows, rows, d, (hipStream_t)stream);
+}
+
 int ghf_score_pairs_fwd(const float* a, const float* b, const int64_t* ia, const int64_t* ib, int64_t rows_a, int64_t rows_b,
                         int64_t n, int d, float* scores, void* stream) {
     GHF_REQUIRE(a && b && (scores || n == 0), "score_pairs_fwd: null pointer argument");

@@ -6,6 +6,9 @@
 // for the two-piece kernels a row of the split form (4d bytes: hi and lo fp16 planes) AND its power-of-two scale (4 bytes),
 // which ghf_split_rows keeps in two regions of one buffer — `rows` [N][row_bytes] and `extra` [N][extra_bytes].  One message
 // row = row_bytes + extra_bytes bytes; one wave per row at a time, 16 bytes per lane.  HBM-bound copies: no arithmetic.
+//
+// The training backward runs the exchange in reverse (dist.py: ShardedHyperGNN, training across GPUs): the gradient rows a
+// rank computed for other ranks' rows travel back to their owners, which add them to their own (ghf_rows_accumulate).
 #include "common.h"
 
 namespace ghf {
@@ -49,6 +52,40 @@ int launch_rows_pack(bool unpack, void* rows, int64_t row_bytes, void* extra, in
     const unsigned grid = (unsigned)(want < 256 * 32 ? want : 256 * 32);
     if (unpack) rows_pack_kernel<true><<<grid, 256, 0, stream>>>((char*)rows, row_bytes, (char*)extra, extra_bytes, idx, n, nrows, (char*)packed);
     else rows_pack_kernel<false><<<grid, 256, 0, stream>>>((char*)rows, row_bytes, (char*)extra, extra_bytes, idx, n, nrows, (char*)packed);
+    GHF_LAUNCH_CHECK();
+    return GHF_OK;
+}
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// rows[idx[i]][k] += packed[i][k], one fp32 add per element; idx entries are distinct within one launch, so every element has
+// one writer (no atomics) and the sum over several launches follows their order.
+__global__ __launch_bounds__(256) void rows_accumulate_kernel(const float* __restrict__ packed, const int64_t* __restrict__ idx,
+                                                              int64_t n, int64_t nrows, float* __restrict__ rows, int d) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+    for (int64_t i = wave; i < n; i += nwaves) {
+        const int64_t r = idx ? idx[i] : i;
+        if (r < 0 || r >= nrows) continue;
+        const float* __restrict__ m = packed + i * d;
+        float* __restrict__ p = rows + r * d;
+        for (int k = lane * 4; k < d; k += 256) {
+            f32x4 a = *(const f32x4*)(p + k);
+            const f32x4 b = *(const f32x4*)(m + k);
+            a += b;
+            *(f32x4*)(p + k) = a;
+        }
+    }
+}
+
+int launch_rows_accumulate(const float* packed, const int64_t* idx, int64_t n, int64_t nrows, float* rows, int d, hipStream_t stream) {
+    GHF_REQUIRE(n >= 0 && nrows >= 0, "rows_accumulate: negative row count");
+    GHF_REQUIRE(d > 0 && d % 4 == 0, "rows_accumulate: d must be a positive multiple of 4");
+    GHF_REQUIRE((((uintptr_t)rows | (uintptr_t)packed) & 15) == 0, "rows_accumulate: misaligned buffer");
+    if (n == 0) return GHF_OK;
+    const int64_t want = cdiv(n, 4);
+    const unsigned grid = (unsigned)(want < 256 * 32 ? want : 256 * 32);
+    rows_accumulate_kernel<<<grid, 256, 0, stream>>>(packed, idx, n, nrows, rows, d);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }

@@ -223,13 +223,84 @@ class NativeOps:
         norm = model.layer_norms[l]
         _native.tail_fwd(agg, h, norm.weight.detach(), norm.bias.detach(), norm.eps, h_out, row0=lo, rows=hi - lo)
 
+    # -- training (ShardedHyperGNN._forward_train) ---------------------------------------------------------
+    def train_inputs(self, model, x: torch.Tensor, plan, device):
+        """(h0 [N, d], [(W_msg, W_self, bias, gamma, beta) per layer]) recorded by autograd, on every rank alike: the text
+        encoder, the generators and the input projection of the single-GPU training forward (their Functions unchanged)."""
+        from .autograd import InputProjFn
+        te = model.text_encoder(plan.unique_texts, device)
+        layers = [(*gen.generate_with_grad(te), norm.weight, norm.bias)
+                  for gen, norm in zip(model.weight_generators, model.layer_norms)]
+        return InputProjFn.apply(x, model.input_proj.weight, model.input_proj.bias, None), layers
+
+    def train_layer_begin(self, model, l: int, nat, h: torch.Tensor, plan) -> dict:
+        """Once per layer, every row of h in place: the weights packed for the plan's kernel, the split rows it gathers, and
+        (two-piece plans) the rows' scales the weight gradients read."""
+        from .autograd import _layer_weights
+        W_msg, W_self, bias, gamma, beta = (t.detach() for t in nat)
+        W, W2 = _layer_weights(plan, W_msg, W_self, transpose=False)
+        st = dict(weights=(W, W2, bias.contiguous()), gamma=gamma, beta=beta, split=self.split_rows(plan, h), h_scales=None)
+        if st["split"] is not None and plan.wlayout == _native.WLAYOUT_SPLIT2H and _native.side_output_supported(plan, h.size(1)):
+            st["h_scales"] = _native.split_row_scales(st["split"], h.size(0), h.size(1)).clone()
+        self.layer_begin(model, l, st["weights"], h, plan)
+        return st
+
+    def layer_rows_train(self, model, l: int, st: dict, h, plan, h_out, agg, lo: int, hi: int) -> None:
+        """The recorded layer forward on my rows [lo, hi) (MessageLayerFn.forward): h_out and the aggregate before the tail
+        (`agg`, for ghf_tail_bwd) — one launch with the side output, else GHF_FLAG_NO_TAIL + ghf_tail_fwd."""
+        W, W2, bias = st["weights"]
+        eps = model.layer_norms[l].eps
+        d = h.size(1)
+        if _native.side_output_supported(plan, d):
+            _native.message_layer_fwd(h, plan, W, W2, bias, plan.wlayout, st["gamma"], st["beta"], eps, h_out, row0=lo,
+                                      rows=hi - lo, h_split=st["split"], agg_out=agg)
+            return
+        if plan.block_nodes == 1 and _native.rs_supported(d):
+            if plan.E > 0:                              # (pass 1 ran in train_layer_begin; without edges agg stays zero)
+                _native.segment_tail_fwd(plan.rs.scratch(plan.E, d, h.device), plan.rs, None, None, None, 0.0, agg, row0=lo,
+                                         rows=hi - lo, flags=_native.GHF_FLAG_NO_TAIL, exact=plan.force_exact)
+        elif plan.E > 0:
+            _native.message_layer_fwd(h, plan, W, W2, bias, plan.wlayout, None, None, 0.0, agg, row0=lo, rows=hi - lo,
+                                      flags=_native.GHF_FLAG_NO_TAIL, h_split=st["split"])
+        _native.tail_fwd(agg, h, st["gamma"], st["beta"], eps, h_out, row0=lo, rows=hi - lo)
+
+    def layer_backward(self, model, l: int, nat, st: dict, h, agg, plan, g, need_dh: bool = True):
+        """(dh, dW_msg, dW_self, db, dgamma, dbeta) of my shard: `g` is zero outside my rows; the weight gradients are sums over
+        my edges; dh = dpre + the self term on my rows + the message term on the SOURCE rows of my edges (any rank's rows).
+        The shard's TrainPlan (the owner plan, and its edges reversed) is built once per plan."""
+        from .autograd import build_train_plan, layer_backward
+        W_msg, W_self, bias, gamma, beta = nat
+        eps = model.layer_norms[l].eps
+        if plan.E == 0:                                 # no in-edges on this rank: the tail alone
+            dpre, _, _, dgamma, dbeta = _native.tail_bwd(g, agg, h, gamma.detach(), eps, plan.indeg)
+            R, d = W_msg.shape[0], h.size(1)
+            z = torch.zeros(R, d, d, dtype=torch.float32, device=h.device)
+            return dpre, z, torch.zeros_like(z), torch.zeros(R, d, dtype=torch.float32, device=h.device), dgamma, dbeta
+        if plan.train is None:
+            src, dst, rel = plan.edge_arrays()
+            plan.train = build_train_plan(torch.stack([src, dst]), rel, plan, h.size(1), h.device, exact=plan.force_exact)
+        return layer_backward(g, h, agg, W_msg, W_self, gamma, eps, plan.train, h_scales=st["h_scales"], need_dh=need_dh,
+                              shard=True)
+
+    def accumulate_rows(self, rows: torch.Tensor, idx: Optional[torch.Tensor], packed: torch.Tensor) -> None:
+        """rows[idx[i]] += packed[i] (idx None: rows[i]) — ghf_rows_accumulate (csrc/exchange.hip)."""
+        _native.rows_accumulate(rows, idx, packed)
+
 
 class ShardedHyperGNN:
     """Runs ``HyperGNN.forward`` across the ranks of a process group; every rank returns the full [N, d].
 
     mode: "dst" | "edges"; exchange: "allgather" | "pairs" | "sparse" (dst mode); balance: "rows" | "edges" (dst mode; "edges"
     implies a pairwise exchange, whose messages may differ in size).  Defaults from GHF_DIST_MODE / GHF_DIST_EXCHANGE /
-    GHF_DIST_BALANCE / GHF_DIST_CHUNKS."""
+    GHF_DIST_BALANCE / GHF_DIST_CHUNKS.
+
+    Training: when the model is in training mode, grad mode is on and some parameter or `node_features` requires grad, the
+    output carries a grad_fn (mode="dst", every exchange and balance; mode="edges" and dropout > 0 raise NotImplementedError).
+    Convention: the backward reads, on each rank, only the rows of the output gradient that the rank owns.  So when every
+    rank computes the same loss from the replicated output (score_edges / score_triple over all edges, as the reference demo
+    does), every rank ends with the single-process gradient; when each rank's loss reads only its own rows, with the
+    gradient of the sum of the ranks' losses.  Either way the gradients are complete and bitwise identical on every rank, and
+    an optimizer step keeps the replicas in sync without DDP.  Otherwise the forward is the inference path, under no_grad."""
 
     def __init__(self, model, group: Optional[dist.ProcessGroup] = None, ops=None, chunks: Optional[int] = None,
                  mode: Optional[str] = None, exchange: Optional[str] = None, balance: Optional[str] = None) -> None:
@@ -514,8 +585,20 @@ class ShardedHyperGNN:
         return self._plan
 
     # -- forward ----------------------------------------------------------------------------------------
-    @torch.no_grad()
     def forward(self, node_features: torch.Tensor, edge_index: torch.Tensor, edge_texts: List[str]) -> torch.Tensor:
+        """The full [N, d] output on every rank.  Recorded for a backward (`_forward_train`) only in training mode, with grad
+        mode on and some parameter or `node_features` requiring grad; otherwise the inference forward, under no_grad."""
+        if self._wants_training(node_features):
+            return self._forward_train(node_features, edge_index, edge_texts)
+        return self._forward_infer(node_features, edge_index, edge_texts)
+
+    def _wants_training(self, node_features: torch.Tensor) -> bool:
+        m = self.model
+        return (bool(getattr(m, "training", False)) and torch.is_grad_enabled()
+                and (node_features.requires_grad or any(p.requires_grad for p in m.parameters())))
+
+    @torch.no_grad()
+    def _forward_infer(self, node_features: torch.Tensor, edge_index: torch.Tensor, edge_texts: List[str]) -> torch.Tensor:
         if edge_index.size(1) != len(edge_texts):
             raise ValueError(f"edge_index has {edge_index.size(1)} edges but edge_texts has {len(edge_texts)} entries")
         N, device = node_features.size(0), node_features.device
@@ -638,4 +721,229 @@ class ShardedHyperGNN:
             h, h_next = h_next, h
         return h[:N]
 
+    # -- training across GPUs ---------------------------------------------------------------------------
+    def _forward_train(self, node_features: torch.Tensor, edge_index: torch.Tensor, edge_texts: List[str]) -> torch.Tensor:
+        """The recorded forward ("Training across GPUs").  Upstream of the layers everything is replicated and
+        recorded by the single-GPU Functions (text encoder, generators, input projection); the layers are one Function,
+        ShardedLayersFn, whose forward runs the fp32 row exchange every layer and whose backward runs the exchange's adjoint
+        and all-reduces the weight gradients — its gradients leave complete and identical on every rank."""
+        if edge_index.size(1) != len(edge_texts):
+            raise ValueError(f"edge_index has {edge_index.size(1)} edges but edge_texts has {len(edge_texts)} entries")
+        model = self.model
+        if self.mode != "dst":
+            raise NotImplementedError(f"ShardedHyperGNN: training runs on destination shards (mode='dst'); mode={self.mode!r} "
+                                      "is inference only (its backward would be an all-gather of G and a reduce-scatter of dh)")
+        if getattr(model, "dropout", 0.0) > 0.0 or any(g.dropout > 0.0 for g in getattr(model, "weight_generators", [])):
+            raise NotImplementedError("ShardedHyperGNN: no training with dropout > 0 (every rank would have to draw the same "
+                                      "masks); set dropout=0 or call .eval()")
+        N, device = node_features.size(0), node_features.device
+        plan = self.plan_for(edge_index, edge_texts, N, device)
+        guard = isinstance(self.ops, NativeOps) and model._guarded(plan) and self.profile == "full"
+        if guard:
+            flag = _native.range_flag(device)
+            flag.zero_()
+        h0, layers = self.ops.train_inputs(model, node_features, plan, device)
+        flat = [t for lw in layers for t in lw]
+        out = ShardedLayersFn.apply(self, plan, h0, *flat)
+        self.last_range_flags = 0
+        if guard:
+            word = self._reduce_guard(flag)
+            self.last_range_flags = word
+            if word:
+                # as the inference forward: every rank reruns the layers on the same shards planned for the exact kernels
+                # (the reduced word is the same everywhere); the first recording is dropped
+                out = ShardedLayersFn.apply(self, self.plan_for(edge_index, edge_texts, N, device, exact=True), h0, *flat)
+        return out
+
+    def _reduce_guard(self, flag: torch.Tensor) -> int:
+        """The range-guard bits OR-ed over the ranks (MAX per bit)."""
+        word = flag.cpu() if self.backend == "gloo" else flag
+        bits = torch.stack([(word >> i) & 1 for i in range(3)]).flatten()
+        dist.all_reduce(bits, op=dist.ReduceOp.MAX, group=self.group)
+        return sum(int(b) << i for i, b in enumerate(bits.tolist()))
+
+    def _layers_fwd(self, plan, h0: torch.Tensor, layers) -> Tuple[torch.Tensor, List]:
+        """Every layer on my rows, then the exchange of its fp32 rows (chunked, as _forward_rows — also where inference would
+        exchange split rows: the weight gradients need fp32 h of every source row).  Saves per layer the input rows h, the
+        aggregate of my rows (zero elsewhere: ghf_tail_bwd reads every row) and the kernels' per-layer state."""
+        model, ops, spec = self.model, self.ops, self._spec
+        N, d, device = h0.size(0), h0.size(1), h0.device
+        self.stats = {"bytes_recv": 0.0}
+        h, saved = h0.contiguous(), []
+        for l, nat in enumerate(layers):
+            st = ops.train_layer_begin(model, l, nat, h, plan)
+            agg = torch.zeros(N, d, dtype=h.dtype, device=device)
+            # rows the sparse exchange does not send stay zero, not stale: the backward's tail reads them (times a zero g)
+            h_out = torch.zeros(spec.padded_rows, d, dtype=h.dtype, device=device)
+            self._run_chunked(h_out, spec, lambda lo, hi: ops.layer_rows_train(model, l, st, h, plan, h_out[:N], agg, lo, hi),
+                              full_rows=l == len(layers) - 1)
+            saved.append((h, agg, st))
+            h = h_out[:N]
+        return (h if spec.padded_rows == N else h.clone()), saved
+
+    def _layers_bwd(self, ctx, grad_out: torch.Tensor, layers, need_dh0: bool):
+        """Per layer, in reverse: my shard's backward on my rows of the gradient, the adjoint exchange of dh (the rows of
+        other ranks' nodes to their owners, summed there), the all-reduce of the weight gradients; at the end dh0 of my
+        rows all-gathered.  Returns (dh0 [N, d] or None, [(dW_msg, dW_self, db, dgamma, dbeta) per layer])."""
+        model, ops, spec, plan = self.model, self.ops, ctx.spec, ctx.plan
+        N = grad_out.size(0)
+        self.stats["bytes_recv_bwd"] = 0.0
+        g = self._own_rows(grad_out.contiguous(), spec)
+        grads: List = [None] * len(layers)
+        dh = None
+        for l in range(len(layers) - 1, -1, -1):
+            h, agg, st = ctx.saved[l]
+            need_dh = l > 0 or need_dh0
+            dh, dWm, dWs, db, dgamma, dbeta = ops.layer_backward(model, l, layers[l], st, h, agg, plan, g, need_dh)
+            grads[l] = self._all_reduce_grads([dWm, dWs, db, dgamma, dbeta])
+            if need_dh:
+                self._reduce_rows(dh, spec, ctx.sparse)
+                if l > 0:
+                    g = self._own_rows(dh, spec)
+        if not need_dh0:
+            return None, grads
+        full = torch.empty(spec.padded_rows, dh.size(1), dtype=dh.dtype, device=dh.device)
+        full[:N].copy_(dh)
+        self._full_rows = True
+        for c in range(spec.chunks):
+            self._gather_bufs([full], spec, c)
+        return full[:N], grads
+
+    @staticmethod
+    def _own_rows(t: torch.Tensor, spec: ShardSpec) -> torch.Tensor:
+        """t on my rows, zero elsewhere."""
+        out = torch.zeros_like(t)
+        for lo, hi in spec.owned():
+            out[lo:hi] = t[lo:hi]
+        return out
+
+    def _all_reduce_grads(self, ts: List[torch.Tensor]) -> List[torch.Tensor]:
+        """The sum over the ranks of a layer's weight gradients (every rank's are partial sums over its edges / rows): one
+        all-reduce of the concatenation, whose result is the same on every rank."""
+        flat = torch.cat([t.reshape(-1) for t in ts])
+        if self.world > 1:
+            if flat.is_cuda and self.backend == "gloo":
+                host = flat.cpu()
+                dist.all_reduce(host, group=self.group)
+                flat.copy_(host)
+            else:
+                dist.all_reduce(flat, group=self.group)
+        return [p.view(t.shape) for p, t in zip(torch.split(flat, [t.numel() for t in ts]), ts)]
+
+    def _reduce_rows(self, dh: torch.Tensor, spec: ShardSpec, sparse: Optional[dict]) -> None:
+        """The adjoint of the forward's exchange, in place on dh [N, d]: the rows of peer p's slots go to p, which adds them
+        to its own; afterwards my rows of dh are complete (other rows: undefined)."""
+        if self.world == 1:
+            return
+        for c in range(spec.chunks):
+            if self.exchange == "sparse" and sparse is not None:
+                self._reduce_sparse(dh, sparse, c)
+            elif self.exchange == "pairs" or self.exchange == "sparse" or not spec.uniform:
+                self._reduce_pairs(dh, spec, c)
+            else:
+                self._reduce_chunk(dh, spec, c)
+
+    def _reduce_chunk(self, dh: torch.Tensor, spec: ShardSpec, c: int) -> None:
+        """Adjoint of the chunk all-gather: a reduce-scatter of the chunk (gloo has none: all-reduce, then my slot)."""
+        N, d = dh.shape
+        lo, hi = spec.chunk_rows(c)
+        a, b = spec.slot(c)
+        if hi <= N:
+            stage = dh[lo:hi]
+        else:                                                  # the chunk that reaches past N: padded with zero rows
+            stage = torch.zeros(hi - lo, d, dtype=dh.dtype, device=dh.device)
+            if N > lo:
+                stage[: N - lo].copy_(dh[lo:N])
+        self.stats["bytes_recv_bwd"] += (self.world - 1) * spec.S * d * dh.element_size()
+        if self._fused_gather:
+            mine = torch.empty(spec.S, d, dtype=dh.dtype, device=dh.device)
+            dist.reduce_scatter_tensor(mine, stage.contiguous(), group=self.group)
+            if b > a:
+                dh[a:b].copy_(mine[: b - a])
+            return
+        red = stage.cpu() if stage.is_cuda else stage.clone()
+        dist.all_reduce(red, group=self.group)
+        if b > a:
+            dh[a:b].copy_(red[a - lo: b - lo])
+
+    def _reduce_pairs(self, dh: torch.Tensor, spec: ShardSpec, c: int) -> None:
+        """Adjoint of _gather_pairs: to every peer my rows of its slot of chunk c, from every peer its rows of my slot, added
+        to mine in rank order (so the bits do not depend on arrival order)."""
+        N = dh.size(0)
+        a, b = (min(x, N) for x in spec.slot(c))
+        bounce = dh.is_cuda and self.backend == "gloo"
+        ops, recvs, keep = [], {}, []
+        for p in range(self.world):
+            if p == self.rank:
+                continue
+            lo, hi = (min(x, N) for x in spec.slot(c, p))
+            if hi > lo:
+                t = dh[lo:hi].cpu() if bounce else dh[lo:hi].contiguous()
+                keep.append(t)
+                ops.append(dist.P2POp(dist.isend, t, p, group=self.group))
+            if b > a:
+                r = torch.empty((b - a,) + tuple(dh.shape[1:]), dtype=dh.dtype, device="cpu" if bounce else dh.device)
+                ops.append(dist.P2POp(dist.irecv, r, p, group=self.group))
+                recvs[p] = r
+                self.stats["bytes_recv_bwd"] += r.numel() * r.element_size()
+        if ops:
+            for req in dist.batch_isend_irecv(ops):
+                req.wait()
+        for p in sorted(recvs):
+            self.ops.accumulate_rows(dh[a:b], None, recvs[p].to(dh.device) if bounce else recvs[p])
+
+    def _reduce_sparse(self, dh: torch.Tensor, sparse: dict, c: int) -> None:
+        """Adjoint of _gather_sparse: to peer p the rows of its slot that my edges read (recv[c][p] — my only nonzero rows
+        outside my slots), from peer q its rows of my slot that q read (send[c][q]), added at their places in rank order."""
+        send_idx, recv_idx = sparse["send"][c], sparse["recv"][c]
+        bounce = dh.is_cuda and self.backend == "gloo"
+        native = hasattr(self.ops, "pack_rows") and dh.is_cuda
+        d = dh.size(1)
+        ops, recvs, keep = [], {}, []
+        for p in range(self.world):
+            if p == self.rank:
+                continue
+            if recv_idx[p].numel():
+                if native:
+                    t = self.ops.pack_rows([dh], recv_idx[p]).view(dh.dtype).view(-1, d)
+                else:
+                    t = dh.index_select(0, recv_idx[p])
+                t = t.cpu() if bounce else t
+                keep.append(t)
+                ops.append(dist.P2POp(dist.isend, t, p, group=self.group))
+            if send_idx[p].numel():
+                r = torch.empty(send_idx[p].numel(), d, dtype=dh.dtype, device="cpu" if bounce else dh.device)
+                ops.append(dist.P2POp(dist.irecv, r, p, group=self.group))
+                recvs[p] = r
+                self.stats["bytes_recv_bwd"] += r.numel() * r.element_size()
+        if ops:
+            for req in dist.batch_isend_irecv(ops):
+                req.wait()
+        for p in sorted(recvs):
+            self.ops.accumulate_rows(dh, send_idx[p], recvs[p].to(dh.device) if bounce else recvs[p])
+
     __call__ = forward
+
+
+class ShardedLayersFn(torch.autograd.Function):
+    """Every message layer of a ShardedHyperGNN, recorded: inputs h0 [N, d] (replicated) and per layer (W_msg, W_self, bias,
+    gamma, beta) (replicated, natural layout); output the full [N, d] on every rank.  The backward reads only this rank's
+    rows of its incoming gradient and returns gradients that are complete and bitwise identical on every rank."""
+
+    @staticmethod
+    def forward(ctx, runner: "ShardedHyperGNN", plan, h0: torch.Tensor, *flat: torch.Tensor):
+        layers = [tuple(flat[i:i + 5]) for i in range(0, len(flat), 5)]
+        out, saved = runner._layers_fwd(plan, h0, layers)
+        ctx.runner, ctx.plan, ctx.spec, ctx.sparse, ctx.saved = runner, plan, runner._spec, runner._sparse, saved
+        ctx.save_for_backward(*flat)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        flat = ctx.saved_tensors
+        layers = [tuple(flat[i:i + 5]) for i in range(0, len(flat), 5)]
+        dh0, grads = ctx.runner._layers_bwd(ctx, grad_out, layers, need_dh0=ctx.needs_input_grad[2])
+        out = []
+        for lw, gl in zip(layers, grads):
+            out += [gt.to(t.dtype) for gt, t in zip(gl, lw)]
+        return (None, None, dh0, *out)

@@ -397,6 +397,10 @@ int ghf_rows_pack(const void* rows, int64_t row_bytes, const void* extra, int64_
                   int64_t nrows, void* packed, void* stream);
 int ghf_rows_unpack(const void* packed, const int64_t* idx, int64_t n, int64_t nrows, void* rows, int64_t row_bytes, void* extra,
                     int64_t extra_bytes, void* stream);
+/* The adjoint of the exchange (training across GPUs): rows[idx[i]][k] += packed[i][k] (fp32), i < n, k < d; idx NULL = row i
+ * itself.  idx entries distinct within one call (no atomics; callers add the peers' messages one call after another, in
+ * rank order); entries outside [0, nrows) skipped.  d a multiple of 4, 16-byte aligned buffers.  One fp32 add per element. */
+int ghf_rows_accumulate(const float* packed, const int64_t* idx, int64_t n, int64_t nrows, float* rows, int d, void* stream);
 
 #ifdef __cplusplus
 }
