@@ -46,6 +46,10 @@ SIGNATURES = {
     "ghf_plan_max_items": (_i64, [_i64, _i64, _i32, _i32, _i32, _i32]),
     "ghf_plan_build": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp]),
+    "ghf_subgraph_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "ghf_subgraph_hops": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _sz, _vp, _vp]),
+    "ghf_subgraph_nodes": (_i32, [_vp, _i64, _i32, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "ghf_subgraph_edges": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _sz, _vp, _vp, _vp, _vp]),
     "ghf_weightgen_fwd": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _vp]),
     "ghf_weightgen_fwd_batched": (_i32, [_i32, _vp, C.POINTER(_vp), C.POINTER(_vp), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
@@ -270,6 +274,38 @@ def message_config(d: int, kernel: Optional[str] = None) -> Tuple[int, int, int,
                 else:
                     os.environ["GHF_KERNEL"] = old
     return bn.value, wl.value, cr.value, sc.value
+
+
+def subgraph(plan, seeds: torch.Tensor, k: int) -> dict:
+    """The k-hop in-neighbourhood of `seeds` (int64, on the plan's device, ids in [0, N)) in `plan`'s graph
+    (include/ghf.h: ghf_subgraph_*): dist [N] int32, node_list [m_k] int64 ordered by (dist, id), new_id [N] int64 (-1 beyond
+    k hops), m: the host list m_0..m_k (m_j = nodes within j hops: the first m_j entries of node_list), and the induced edges
+    edge_index [2, E'] / rel [E'] int64 (destinations within k - 1 hops), renumbered, in the plan's sorted order.  One host
+    sync (the counts)."""
+    lib = load()
+    seeds = _req(seeds, torch.int64, "seeds")
+    dev, N, E = seeds.device, plan.N, plan.E
+    ws_bytes = lib.ghf_subgraph_workspace_bytes(N, E, k)
+    if ws_bytes == 0:
+        raise ValueError(f"subgraph: bad sizes N={N} E={E} k={k}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    dist = torch.empty(N, dtype=torch.int32, device=dev)
+    node_list = torch.empty(N, dtype=torch.int64, device=dev)
+    new_id = torch.empty(N, dtype=torch.int64, device=dev)
+    counts = torch.empty(k + 2, dtype=torch.int64, device=dev)           # m_0 .. m_k, E'
+    edge_out = torch.empty((2, max(E, 1)), dtype=torch.int64, device=dev)
+    rel_out = torch.empty(max(E, 1), dtype=torch.int64, device=dev)
+    key, src, st = _ptr(plan.sorted_key), _ptr(plan.sorted_src), _stream()
+    _check(lib.ghf_subgraph_hops(key, src, N, E, plan.R, plan.block_nodes, _ptr(seeds), seeds.numel(), k, _ptr(ws), ws_bytes,
+                                 _ptr(dist), st), "ghf_subgraph_hops")
+    _check(lib.ghf_subgraph_nodes(_ptr(dist), N, k, _ptr(ws), ws_bytes, _ptr(node_list), _ptr(new_id), _ptr(counts), st),
+           "ghf_subgraph_nodes")
+    _check(lib.ghf_subgraph_edges(key, src, N, E, plan.R, plan.block_nodes, _ptr(dist), _ptr(new_id), k, _ptr(ws), ws_bytes,
+                                  _ptr(edge_out), _ptr(rel_out), counts.data_ptr() + 8 * (k + 1), st), "ghf_subgraph_edges")
+    c = counts.cpu().tolist()
+    m, E_sub = c[:k + 1], c[k + 1]
+    return dict(dist=dist, node_list=node_list[:m[k]], new_id=new_id, m=m,
+                edge_index=edge_out[:, :E_sub] if E else edge_out[:, :0], rel=rel_out[:E_sub])
 
 
 def exact_config(d: int) -> Tuple[int, int, int, int]:

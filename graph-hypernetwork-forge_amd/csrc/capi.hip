@@ -527,6 +527,31 @@ int ghf_rows_accumulate(const float* packed, const int64_t* idx, int64_t n, int6
     return launch_rows_accumulate(packed, idx, n, nrows, rows, d, (hipStream_t)stream);
 }
 
+size_t ghf_subgraph_workspace_bytes(int64_t N, int64_t E, int k) { return subgraph_workspace_bytes(N, E, k); }
+
+int ghf_subgraph_hops(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
+                      const int64_t* seeds, int64_t S, int k, void* workspace, size_t workspace_bytes, int32_t* dist, void* stream) {
+    GHF_REQUIRE(workspace && dist && (seeds || S == 0) && ((sorted_key && sorted_src) || E == 0),
+                "subgraph_hops: null pointer argument");
+    return launch_subgraph_hops(sorted_key, sorted_src, N, E, R, block_nodes, seeds, S, k, workspace, workspace_bytes, dist,
+                                (hipStream_t)stream);
+}
+
+int ghf_subgraph_nodes(const int32_t* dist, int64_t N, int k, void* workspace, size_t workspace_bytes, int64_t* node_list,
+                       int64_t* new_id, int64_t* m, void* stream) {
+    GHF_REQUIRE(dist && workspace && node_list && new_id && m, "subgraph_nodes: null pointer argument");
+    return launch_subgraph_nodes(dist, N, k, workspace, workspace_bytes, node_list, new_id, m, (hipStream_t)stream);
+}
+
+int ghf_subgraph_edges(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
+                       const int32_t* dist, const int64_t* new_id, int k, void* workspace, size_t workspace_bytes,
+                       int64_t* edge_out, int64_t* rel_out, int64_t* num_edges, void* stream) {
+    GHF_REQUIRE(dist && new_id && workspace && num_edges && ((sorted_key && sorted_src && edge_out && rel_out) || E == 0),
+                "subgraph_edges: null pointer argument");
+    return launch_subgraph_edges(sorted_key, sorted_src, N, E, R, block_nodes, dist, new_id, k, workspace, workspace_bytes,
+                                 edge_out, rel_out, num_edges, (hipStream_t)stream);
+}
+
 int ghf_score_pairs_fwd(const float* a, const float* b, const int64_t* ia, const int64_t* ib, int64_t rows_a, int64_t rows_b,
                         int64_t n, int d, float* scores, void* stream) {
     GHF_REQUIRE(a && b && (scores || n == 0), "score_pairs_fwd: null pointer argument");

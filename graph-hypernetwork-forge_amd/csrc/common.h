@@ -194,6 +194,15 @@ int launch_combine_split(const MsgArgs& a, hipStream_t stream);     // sums the 
 size_t group_workspace_bytes(int64_t E);
 int launch_group_edges(const int64_t* rel, int64_t E, int R, void* ws, size_t ws_bytes, int64_t* perm, int64_t* goff,
                        hipStream_t stream);
+// subgraph.hip
+size_t subgraph_workspace_bytes(int64_t N, int64_t E, int k);
+int launch_subgraph_hops(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
+                         const int64_t* seeds, int64_t S, int k, void* ws, size_t ws_bytes, int32_t* dist, hipStream_t stream);
+int launch_subgraph_nodes(const int32_t* dist, int64_t N, int k, void* ws, size_t ws_bytes, int64_t* node_list,
+                          int64_t* new_id, int64_t* m, hipStream_t stream);
+int launch_subgraph_edges(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
+                          const int32_t* dist, const int64_t* new_id, int k, void* ws, size_t ws_bytes, int64_t* edge_out,
+                          int64_t* rel_out, int64_t* num_edges, hipStream_t stream);
 // backward.hip
 int launch_tail_bwd(const float* g_out, const float* agg, const float* h, const float* gamma, float eps, const int32_t* indeg,
                     int64_t N, int d, float* dpre, float* G, void* G_split, float* dgb, float* workspace, const float* drop,

@@ -1,0 +1,269 @@
+// subgraph.hip — the k-hop in-neighbourhood of a seed list, for HyperGNN.forward_nodes (no counterpart in the reference).
+//
+// An L-layer HyperGNN row is a function of the rows within L hops upstream of it (every layer is a mean over a row's in-edges
+// plus a self term, a residual and a LayerNorm of that row: reference hypergnn.py:190-230, 288-296).  Three stages, all on
+// the full graph's plan (ghf_plan_build), integer arithmetic only, no result depending on the order in which work lands:
+//   hops:  dist[v] = min(hops from v to a seed along edges u -> v), k + 1 beyond k.  One edge-parallel pass per hop: an edge
+//          whose destination is at distance j and whose source is unvisited sets the source to j + 1 — every writer writes
+//          the same value.  A pass that discovers nothing makes the later passes return at once (a device word, no sync).
+//   nodes: node_list = every node with dist <= k ordered by (dist, id), its inverse new_id and m[j] = #{dist <= j}.  Per
+//          distance: flags, an exclusive scan, a scatter.  The nodes with dist <= j are the first m[j] rows.
+//   edges: every edge whose destination has dist <= k - 1 (its source then has dist <= k), renumbered, in the plan's order:
+//          flags, an exclusive scan, a scatter (a stable compaction).
+// Edges are read from the plan's compact arrays (8 bytes each), decoded as plan.py: GraphPlan.edge_arrays does:
+//   block plans (BN > 1): key = (dst / BN) * R * BN + rel * BN + dst % BN, source in bits 0..27 of sorted_src (run head above);
+//   CSR plans (BN == 1):  key = dst * R + rel, sorted_src = the source.
+#include "common.h"
+
+#include <hipcub/hipcub.hpp>
+
+namespace ghf {
+
+struct EdgeCode {
+    uint32_t R, BN, RBN;
+};
+
+__device__ __forceinline__ void sub_decode(uint32_t key, int32_t raw, const EdgeCode c, uint32_t& src, uint32_t& dst,
+                                           uint32_t& rel) {
+    if (c.BN == 1) {
+        dst = key / c.R;
+        rel = key - dst * c.R;
+        src = (uint32_t)raw;
+    } else {
+        const uint32_t blk = key / c.RBN, rem = key - blk * c.RBN;
+        dst = blk * c.BN + rem % c.BN;
+        rel = rem / c.BN;
+        src = (uint32_t)raw & (uint32_t)SRC_MASK;
+    }
+}
+
+static unsigned sub_grid(int64_t n) {
+    const int64_t g = cdiv(n > 0 ? n : 1, 256);
+    return (unsigned)(g < 8192 ? g : 8192);
+}
+
+// ---- hops ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sub_dist_init_kernel(int32_t* __restrict__ dist, int64_t N, int k,
+                                                            int32_t* __restrict__ found) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (int64_t v = t; v < N; v += stride) dist[v] = k + 1;
+    if (t < k) found[t] = 0;
+}
+
+__global__ __launch_bounds__(256) void sub_dist_seeds_kernel(const int64_t* __restrict__ seeds, int64_t S, int64_t N,
+                                                             int32_t* __restrict__ dist) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < S; i += stride) {
+        const int64_t v = seeds[i];
+        if (v >= 0 && v < N) dist[v] = 0;                   // (duplicates write the same value)
+    }
+}
+
+// hop j: sources of edges into distance-j nodes that are still unvisited get distance j + 1
+__global__ __launch_bounds__(256) void sub_hop_kernel(const uint32_t* __restrict__ sorted_key, const int32_t* __restrict__ sorted_src,
+                                                      int64_t N, int64_t E, EdgeCode c, int j, int k, int32_t* dist,
+                                                      int32_t* found) {
+    if (j > 0 && found[j - 1] == 0) return;                 // hop j - 1 reached nobody: no node is at distance j
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int any = 0;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += stride) {
+        uint32_t s, t, r;
+        sub_decode(sorted_key[e], sorted_src[e], c, s, t, r);
+        if (t >= (uint64_t)N || s >= (uint64_t)N) continue;
+        if (dist[t] == j && dist[s] > k) {
+            dist[s] = j + 1;                                // every writer of dist[s] in this pass writes j + 1
+            any = 1;
+        }
+    }
+    if (any) atomicOr(&found[j], 1);
+}
+
+// ---- nodes -----------------------------------------------------------------------------------------------------------
+// f[v] = (dist[v] == j), f[N] = 0; the first level also clears new_id
+__global__ __launch_bounds__(256) void sub_level_flags_kernel(const int32_t* __restrict__ dist, int64_t N, int j,
+                                                              int32_t* __restrict__ f, int64_t* __restrict__ new_id) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v <= N; v += stride) {
+        if (v == N) {
+            f[v] = 0;
+            continue;
+        }
+        f[v] = dist[v] == j;
+        new_id[v] = -1;
+    }
+}
+
+// the nodes at distance j go to node_list[m[j-1] + pos[v]]; m[j] = m[j-1] + count; f[] = the flags of distance j + 1
+__global__ __launch_bounds__(256) void sub_level_scatter_kernel(const int32_t* __restrict__ dist, int64_t N, int j, int k,
+                                                                const int32_t* __restrict__ pos, int32_t* __restrict__ f,
+                                                                int64_t* __restrict__ node_list, int64_t* __restrict__ new_id,
+                                                                int64_t* m) {
+    const int64_t base = j > 0 ? m[j - 1] : 0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v <= N; v += stride) {
+        if (v == N) {
+            m[j] = base + pos[N];
+            continue;
+        }
+        const int32_t dv = dist[v];
+        if (dv == j) {
+            const int64_t p = base + pos[v];
+            node_list[p] = v;
+            new_id[v] = p;
+        }
+        if (j < k) f[v] = dv == j + 1;                      // (f[N] stays 0)
+    }
+}
+
+// ---- edges -----------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool sub_keep(uint32_t s, uint32_t t, int64_t N, const int32_t* __restrict__ dist, int k) {
+    return t < (uint64_t)N && s < (uint64_t)N && dist[t] <= k - 1;
+}
+
+__global__ __launch_bounds__(256) void sub_edge_flags_kernel(const uint32_t* __restrict__ sorted_key,
+                                                             const int32_t* __restrict__ sorted_src, int64_t N, int64_t E,
+                                                             EdgeCode c, const int32_t* __restrict__ dist, int k,
+                                                             int32_t* __restrict__ f) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e <= E; e += stride) {
+        if (e == E) {
+            f[e] = 0;
+            continue;
+        }
+        uint32_t s, t, r;
+        sub_decode(sorted_key[e], sorted_src[e], c, s, t, r);
+        f[e] = sub_keep(s, t, N, dist, k);
+    }
+}
+
+__global__ __launch_bounds__(256) void sub_edge_scatter_kernel(const uint32_t* __restrict__ sorted_key,
+                                                               const int32_t* __restrict__ sorted_src, int64_t N, int64_t E,
+                                                               EdgeCode c, const int32_t* __restrict__ dist,
+                                                               const int64_t* __restrict__ new_id, int k,
+                                                               const int32_t* __restrict__ pos, int64_t* __restrict__ edge_out,
+                                                               int64_t* __restrict__ rel_out, int64_t* __restrict__ num_edges) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e <= E; e += stride) {
+        if (e == E) {
+            num_edges[0] = pos[E];
+            continue;
+        }
+        uint32_t s, t, r;
+        sub_decode(sorted_key[e], sorted_src[e], c, s, t, r);
+        if (!sub_keep(s, t, N, dist, k)) continue;
+        const int64_t p = pos[e];
+        edge_out[p] = new_id[s];
+        edge_out[E + p] = new_id[t];
+        rel_out[p] = r;
+    }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------
+static size_t sub_scan_bytes(int64_t n) {
+    size_t tb = 0;
+    hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const int32_t*)nullptr, (int32_t*)nullptr, (int)n, (hipStream_t)0);
+    return tb;
+}
+
+// [found: k int32][f: n int32][pos: n int32][scan temp], n = max(N, E) + 1
+size_t subgraph_workspace_bytes(int64_t N, int64_t E, int k) {
+    if (N <= 0 || E < 0 || k < 1) return 0;
+    const int64_t n = (N > E ? N : E) + 1;
+    return align_up((size_t)k * 4, 256) + 2 * align_up((size_t)n * 4, 256) + align_up(sub_scan_bytes(n), 256);
+}
+
+struct SubWs {
+    int32_t* found;
+    int32_t* f;
+    int32_t* pos;
+    void* tmp;
+    size_t tmp_bytes;
+};
+
+static SubWs sub_ws(void* ws, int64_t N, int64_t E, int k) {
+    const int64_t n = (N > E ? N : E) + 1;
+    char* p = (char*)ws;
+    SubWs w;
+    w.found = (int32_t*)p;  p += align_up((size_t)k * 4, 256);
+    w.f = (int32_t*)p;      p += align_up((size_t)n * 4, 256);
+    w.pos = (int32_t*)p;    p += align_up((size_t)n * 4, 256);
+    w.tmp = p;
+    w.tmp_bytes = sub_scan_bytes(n);
+    return w;
+}
+
+static int sub_check(int64_t N, int64_t E, int R, int BN, int k, void* ws, size_t ws_bytes, const char* what) {
+    GHF_REQUIRE(N > 0 && N < (1ll << 31) - 1 && E >= 0 && E < (1ll << 31) - 1, "%s: needs 0 < N < 2^31 - 1, 0 <= E < 2^31 - 1", what);
+    GHF_REQUIRE(R > 0 && BN > 0 && k >= 1, "%s: R, block_nodes and k must be positive", what);
+    GHF_REQUIRE((uint64_t)cdiv(N, BN) * (uint64_t)BN * (uint64_t)R < 0xFFFFFFFFull, "%s: not a plan's key space", what);
+    GHF_REQUIRE(ws_bytes >= subgraph_workspace_bytes(N, E, k), "%s: workspace too small", what);
+    GHF_REQUIRE(((uintptr_t)ws & 255) == 0, "%s: workspace must be 256-byte aligned", what);
+    return GHF_OK;
+}
+
+static EdgeCode sub_code(int R, int BN) {
+    EdgeCode c;
+    c.R = (uint32_t)R;
+    c.BN = (uint32_t)BN;
+    c.RBN = (uint32_t)R * (uint32_t)BN;
+    return c;
+}
+
+int launch_subgraph_hops(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
+                         const int64_t* seeds, int64_t S, int k, void* ws, size_t ws_bytes, int32_t* dist, hipStream_t stream) {
+    const int rc = sub_check(N, E, R, BN, k, ws, ws_bytes, "subgraph_hops");
+    if (rc) return rc;
+    GHF_REQUIRE(S >= 0, "subgraph_hops: negative seed count");
+    const SubWs w = sub_ws(ws, N, E, k);
+    sub_dist_init_kernel<<<sub_grid(N > k ? N : k), 256, 0, stream>>>(dist, N, k, w.found);
+    GHF_LAUNCH_CHECK();
+    if (S > 0) {
+        sub_dist_seeds_kernel<<<sub_grid(S), 256, 0, stream>>>(seeds, S, N, dist);
+        GHF_LAUNCH_CHECK();
+    }
+    if (E == 0) return GHF_OK;
+    const EdgeCode c = sub_code(R, BN);
+    for (int j = 0; j < k; ++j) {
+        sub_hop_kernel<<<sub_grid(E), 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, j, k, dist, w.found);
+        GHF_LAUNCH_CHECK();
+    }
+    return GHF_OK;
+}
+
+int launch_subgraph_nodes(const int32_t* dist, int64_t N, int k, void* ws, size_t ws_bytes, int64_t* node_list,
+                          int64_t* new_id, int64_t* m, hipStream_t stream) {
+    GHF_REQUIRE(N > 0 && N < (1ll << 31) - 1 && k >= 1, "subgraph_nodes: needs 0 < N < 2^31 - 1 and k >= 1");
+    GHF_REQUIRE(ws_bytes >= subgraph_workspace_bytes(N, 0, k), "subgraph_nodes: workspace too small");
+    GHF_REQUIRE(((uintptr_t)ws & 255) == 0, "subgraph_nodes: workspace must be 256-byte aligned");
+    SubWs w = sub_ws(ws, N, 0, k);
+    // (the nodes stage only needs N + 1 entries of the flag and position arrays: a workspace sized for (N, E) also serves)
+    const unsigned g = sub_grid(N + 1);
+    sub_level_flags_kernel<<<g, 256, 0, stream>>>(dist, N, 0, w.f, new_id);
+    GHF_LAUNCH_CHECK();
+    for (int j = 0; j <= k; ++j) {
+        GHF_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(w.tmp, w.tmp_bytes, (const int32_t*)w.f, w.pos, (int)(N + 1), stream));
+        sub_level_scatter_kernel<<<g, 256, 0, stream>>>(dist, N, j, k, w.pos, w.f, node_list, new_id, m);
+        GHF_LAUNCH_CHECK();
+    }
+    return GHF_OK;
+}
+
+int launch_subgraph_edges(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
+                          const int32_t* dist, const int64_t* new_id, int k, void* ws, size_t ws_bytes, int64_t* edge_out,
+                          int64_t* rel_out, int64_t* num_edges, hipStream_t stream) {
+    const int rc = sub_check(N, E, R, BN, k, ws, ws_bytes, "subgraph_edges");
+    if (rc) return rc;
+    SubWs w = sub_ws(ws, N, E, k);
+    const EdgeCode c = sub_code(R, BN);
+    const unsigned g = sub_grid(E + 1);
+    sub_edge_flags_kernel<<<g, 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, dist, k, w.f);
+    GHF_LAUNCH_CHECK();
+    GHF_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(w.tmp, w.tmp_bytes, (const int32_t*)w.f, w.pos, (int)(E + 1), stream));
+    sub_edge_scatter_kernel<<<g, 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, dist, new_id, k, w.pos, edge_out, rel_out,
+                                                   num_edges);
+    GHF_LAUNCH_CHECK();
+    return GHF_OK;
+}
+
+}  // namespace ghf

@@ -26,7 +26,8 @@ import torch
 import torch.nn as nn
 
 from .. import _native
-from ..plan import GraphPlan, PlanCache, build_plan, build_rs, exact_plan, relation_ids
+from ..plan import GraphPlan, PlanCache, build_plan, build_rs, empty_plan, exact_plan, plan_config, relation_ids
+from ..plan import CSR_CONFIG
 from ..plan import check_pool
 from .weight_generator import WeightGenerator, check_dropout, draw_mask, require_inference, wants_grad
 
@@ -153,6 +154,7 @@ class HyperGNN(nn.Module):
         self._plans = PlanCache()
         self._wg_stream = None
         self.last_range_flags = 0        # what the range guard saw in the last forward (include/ghf.h: ghf_set_range_flag)
+        self.last_subgraph = None        # the last forward_nodes call's subgraph: m (rows within j hops), edges, plan geometry
 
     # -- plan ------------------------------------------------------------------------------
     def plan_for(self, edge_index: torch.Tensor, edge_texts: Sequence[str], num_nodes: int,
@@ -214,6 +216,14 @@ class HyperGNN(nn.Module):
         if node_features.dim() != 2 or node_features.size(1) != self.node_feat_dim:
             raise ValueError(f"node_features must be [N, {self.node_feat_dim}], got {tuple(node_features.shape)}")
         grad = wants_grad(self, node_features) or self._dropping()
+        plan = self._ids_plan(edge_index, edge_rel_ids, relation_texts, node_features, grad)
+        if grad:
+            return self._forward_recorded(node_features, plan, edge_index)
+        return self.forward_planned(node_features, plan)
+
+    def _ids_plan(self, edge_index: torch.Tensor, edge_rel_ids: torch.Tensor, relation_texts: Sequence[str],
+                  node_features: torch.Tensor, grad: bool) -> GraphPlan:
+        """forward_ids' cached plan, keyed on the two tensors' identity."""
         device, N = node_features.device, node_features.size(0)
         texts = list(relation_texts)
         key = ("ids", edge_index.data_ptr(), tuple(edge_index.shape), edge_index._version, str(edge_index.device),
@@ -224,9 +234,7 @@ class HyperGNN(nn.Module):
             wide = not grad and _native.prefer_rs(self.hidden_dim, len(texts))
             plan = build_plan(edge_index, edge_rel_ids, texts, N, self.hidden_dim, device, force_generic=wide)   # ids out of range: IndexError
             self._plans.put(key, plan, edge_index, (edge_rel_ids, texts))
-        if grad:
-            return self._forward_recorded(node_features, plan, edge_index)
-        return self.forward_planned(node_features, plan)
+        return plan
 
     # -- forward (reference :236-298) -----------------------------------------------------
     def forward(self, node_features: torch.Tensor, edge_index: torch.Tensor, edge_texts: List[str]) -> torch.Tensor:
@@ -254,6 +262,81 @@ class HyperGNN(nn.Module):
             plan = self._plan_lookup(edge_index, edge_texts, node_features.size(0), device, training=False)[0]
             out = self.forward_planned(node_features, plan)
         return out
+
+    # -- node batches: the rows of a few nodes from their k-hop subgraph (include/ghf.h: ghf_subgraph_*) ---------------
+    def forward_nodes(self, node_features: torch.Tensor, edge_index: torch.Tensor, edge_texts: List[str],
+                      nodes: torch.Tensor) -> torch.Tensor:
+        """``forward(node_features, edge_index, edge_texts)[nodes]`` computed on the nodes' ``num_layers``-hop
+        in-neighbourhood only: an L-layer row depends on the rows within L hops upstream of it (reference hypergnn.py:190-230,
+        288-296), so the result is exact, not sampled.  `nodes`: a 1-D int32 / int64 tensor (device or CPU), duplicates and
+        negative ids (as torch indexing) allowed.  Gradients reach the parameters and `node_features`; dropout masks in
+        training mode are drawn over the subgraph's rows (random as in ``forward``, not the full forward's draws)."""
+        if edge_index.size(1) != len(edge_texts):                     # reference :252-256
+            raise ValueError(f"edge_index has {edge_index.size(1)} edges but "
+                             f"edge_texts has {len(edge_texts)} entries")
+        if node_features.dim() != 2 or node_features.size(1) != self.node_feat_dim:
+            raise ValueError(f"node_features must be [N, {self.node_feat_dim}], got {tuple(node_features.shape)}")
+        seeds = self._seed_ids(nodes, node_features)
+        grad = wants_grad(self, node_features) or self._dropping()
+        plan = self._plan_lookup(edge_index, edge_texts, node_features.size(0), node_features.device, training=grad)[0]
+        return self._forward_nodes(node_features, plan, seeds, grad, edge_index)
+
+    def forward_nodes_ids(self, node_features: torch.Tensor, edge_index: torch.Tensor, edge_rel_ids: torch.Tensor,
+                          relation_texts: Sequence[str], nodes: torch.Tensor) -> torch.Tensor:
+        """``forward_nodes`` for callers that already hold relation ids (see ``forward_ids``)."""
+        if edge_rel_ids.dim() != 1 or edge_index.size(1) != edge_rel_ids.numel():
+            raise ValueError(f"edge_index has {edge_index.size(1)} edges but edge_rel_ids has {edge_rel_ids.numel()} entries")
+        if node_features.dim() != 2 or node_features.size(1) != self.node_feat_dim:
+            raise ValueError(f"node_features must be [N, {self.node_feat_dim}], got {tuple(node_features.shape)}")
+        seeds = self._seed_ids(nodes, node_features)
+        grad = wants_grad(self, node_features) or self._dropping()
+        plan = self._ids_plan(edge_index, edge_rel_ids, relation_texts, node_features, grad)
+        return self._forward_nodes(node_features, plan, seeds, grad, edge_index)
+
+    @staticmethod
+    def _seed_ids(nodes: torch.Tensor, node_features: torch.Tensor) -> torch.Tensor:
+        """`nodes` checked as torch indexing checks them, negative ids wrapped: int64 on node_features' device."""
+        if not isinstance(nodes, torch.Tensor) or nodes.dim() != 1:
+            raise ValueError(f"nodes must be a 1-D tensor of node ids, got {getattr(nodes, 'shape', type(nodes))}")
+        if nodes.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"nodes must be int32 or int64, got {nodes.dtype}")
+        if not node_features.is_cuda:
+            raise RuntimeError("HyperGNN computes on an MI355X HIP device only; node_features is on the CPU and there is "
+                               "no CPU path")
+        N = node_features.size(0)
+        if nodes.numel():
+            lo, hi = (int(v) for v in torch.aminmax(nodes))
+            if lo < -N or hi >= N:
+                raise IndexError(f"nodes hold ids outside [-{N}, {N}) (range {lo}..{hi})")
+        ids = nodes.to(device=node_features.device, dtype=torch.int64)
+        return torch.where(ids < 0, ids + N, ids)
+
+    def _forward_nodes(self, x: torch.Tensor, plan: GraphPlan, seeds: torch.Tensor, grad: bool,
+                       edge_index: torch.Tensor) -> torch.Tensor:
+        """The rows `seeds` (int64, in range) of the forward on `plan`'s graph, from the seeds' k-hop subgraph: its nodes
+        ordered by (hop distance, id), so that the rows within j hops are a prefix; inference layer l (0-based) then computes
+        the first m_{k-1-l} rows only (the last layer: the seeds).  The sub-plan is built per call and not cached."""
+        k, d, device = self.num_layers, self.hidden_dim, x.device
+        if seeds.numel() == 0:
+            return x.new_zeros((0, d), dtype=torch.float32)
+        sub = _native.subgraph(plan, seeds, k)
+        m, n = sub["m"], sub["m"][k]
+        xs = x.index_select(0, sub["node_list"])                     # differentiable: gradients reach node_features
+        rows = sub["new_id"].index_select(0, seeds)
+        config = CSR_CONFIG if plan.block_nodes == 1 else None        # (the full plan's kernel family: wide rows stay wide)
+        if sub["edge_index"].size(1) == 0:
+            if grad:                                                  # (no edge to train through: the full recorded forward)
+                self.last_subgraph = dict(m=m, edges=0, block_nodes=plan.block_nodes, wlayout=plan.wlayout)
+                return self._forward_recorded(x, plan, edge_index).index_select(0, seeds)
+            sub_plan = empty_plan(n, plan.unique_texts, config or plan_config(d, 0, n), device)
+        else:
+            sub_plan = build_plan(sub["edge_index"], sub["rel"], plan.unique_texts, n, d, device, force_generic=config is not None)
+        self.last_subgraph = dict(m=m, edges=sub_plan.E, block_nodes=sub_plan.block_nodes, wlayout=sub_plan.wlayout)
+        if grad:
+            out = self._forward_recorded(xs, sub_plan, sub["edge_index"])
+        else:
+            out = self.forward_planned(xs, sub_plan, rows_per_layer=[m[k - 1 - l] for l in range(k)])
+        return out.index_select(0, rows)
 
     # -- range guard of the two-fp16-piece kernels (include/ghf.h: ghf_set_range_flag) ---------------------------
     def _guarded(self, plan: GraphPlan) -> bool:
@@ -389,12 +472,14 @@ class HyperGNN(nn.Module):
         return weights, ready
 
     def forward_planned(self, node_features: torch.Tensor, plan: GraphPlan,
-                        exchange=None, guard: bool = True) -> torch.Tensor:
+                        exchange=None, guard: bool = True, rows_per_layer: Optional[Sequence[int]] = None) -> torch.Tensor:
         """Forward with an explicit plan.  `exchange(h)` (multi-GPU) runs after every layer to
         make all rows of h visible on this rank; the plan's row range says which rows it computes.
         Range guard: the kernels that cut rows / weights into two fp16 pieces flag inputs whose dynamic range those do not
         hold; the forward then ends with one 4-byte read of that flag (the only host sync of a warm forward;
-        GHF_RANGE_GUARD=0 removes it) and, if it is set, runs again on the exact fp32 kernels."""
+        GHF_RANGE_GUARD=0 removes it) and, if it is set, runs again on the exact fp32 kernels (over every row).
+        rows_per_layer[l]: layer l needs correct outputs on its first rows_per_layer[l] rows only (forward_nodes: a prefix
+        that shrinks layer by layer, the rows of layer l + 1 among them)."""
         require_inference(self, node_features, what=".forward_planned")
         if self._dropping():
             raise NotImplementedError("HyperGNN.forward_planned: dropout in training mode runs through forward() / forward_ids() "
@@ -408,7 +493,7 @@ class HyperGNN(nn.Module):
             flag.zero_()
             reader = _native.RangeFlagRead(flag)
         early = reader is not None and os.environ.get("GHF_GUARD_EARLY", "1") != "0"           # (0: read at the end, for A/B)
-        out = self._forward_planned(x, plan, exchange, before_last=reader.arm if early else None)
+        out = self._forward_planned(x, plan, exchange, before_last=reader.arm if early else None, rows_per_layer=rows_per_layer)
         if guard:
             bits = reader.value()
             self.last_range_flags = bits
@@ -416,10 +501,11 @@ class HyperGNN(nn.Module):
                 return self._forward_exact(x, plan, bits)
         return out
 
-    def _forward_planned(self, x: torch.Tensor, plan: GraphPlan, exchange=None, before_last=None) -> torch.Tensor:
+    def _forward_planned(self, x: torch.Tensor, plan: GraphPlan, exchange=None, before_last=None,
+                         rows_per_layer: Optional[Sequence[int]] = None) -> torch.Tensor:
         """before_last(): called right before the last layer is enqueued (nothing after that point raises a range-guard
         bit on the block kernels: _native.RangeFlagRead); the wide-row path cuts rows inside its last layer and is not
-        given an early point."""
+        given an early point.  rows_per_layer: see forward_planned (the wide-row path runs every row of every layer)."""
         device = x.device
         if plan.block_nodes == 1 and _native.rs_supported(self.hidden_dim):
             return self._forward_wide(x, plan, exchange)
@@ -444,6 +530,13 @@ class HyperGNN(nn.Module):
         h = _native.input_proj_fwd(x, self.input_proj.weight.detach(), self.input_proj.bias.detach(), h_split=hs,
                                    split_layout=plan.wlayout if split else 0)
         h_next = torch.empty_like(h)
+        if rows_per_layer is not None:
+            # A shrunk layer computes whole destination blocks: rows past its prefix gather rows the layer before left
+            # unwritten.  Their results are never read by a row that matters, but they must stay finite (the range guard
+            # inspects every row a layer writes): the buffers that have no value yet start as zeros.
+            h_next.zero_()
+            if split:
+                hs_next.zero_()
         # (enqueued after the input projection: streams can share a hardware queue, and packets queue in host order)
         if not batched:
             weights, ready = self.generate_all(text_embs, plan.wlayout, side_stream=side, after=te_done, first=w0)
@@ -456,6 +549,8 @@ class HyperGNN(nn.Module):
             if l == last and before_last is not None:
                 before_last()
             fused = split and exchange is None and l < last
+            if rows_per_layer is not None:                # whole blocks (the block kernels' row ranges end on one or at N)
+                lo, hi = 0, min(plan.N, -(-rows_per_layer[l] // plan.block_nodes) * plan.block_nodes)
             _native.message_layer_fwd(h, plan, W, W_self, bias, plan.wlayout, norm.weight.detach(),
                                       norm.bias.detach(), norm.eps, h_next, row0=lo, rows=hi - lo,
                                       h_split=hs, h_split_out=hs_next if fused else None)

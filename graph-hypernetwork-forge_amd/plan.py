@@ -307,6 +307,31 @@ class GraphPlan:
         return i0, i1 - i0, (self._partial if self.n_slots else None)
 
 
+def empty_plan(N: int, unique_texts: List[str], config: Tuple[int, int, int, int], device: torch.device,
+               rel: Optional[torch.Tensor] = None, row_range: Optional[Tuple[int, int]] = None) -> GraphPlan:
+    """A plan of N rows and no edges (every row "isolated") in the geometry `config` (plan_config's tuple): a shard without
+    in-edges, or the subgraph of seeds without in-edges (HyperGNN.forward_nodes)."""
+    bn, wl, cr, _ = config
+    R = len(unique_texts)
+    lo, hi = (0, N) if row_range is None else row_range
+    nseg = N if bn == 1 else ((N + bn - 1) // bn) * R
+    z = lambda n: torch.zeros(n, dtype=torch.int32, device=device)  # noqa: E731
+    nb = (N + bn - 1) // bn
+    if rel is None:
+        rel = torch.zeros(0, dtype=torch.int64, device=device)
+    empty = GraphPlan(N=N, E=0, R=R, block_nodes=bn, wlayout=wl, unique_texts=unique_texts, rel_ids=rel,
+                      sorted_key=z(1), sorted_src=z(1), seg_off=z(nseg + 1), indeg=z(N), chunk_rows=cr,
+                      row_lo=lo, row_hi=hi)
+    if bn > 1:                                # one empty work item per block
+        items = np.zeros((nb, 4), dtype=np.int32)
+        items[:, 0], items[:, 3] = np.arange(nb), -1
+        empty.chunk_tab, empty.blk_chunk_off = z(2), z(nb + 1)
+        empty.item_tab = torch.from_numpy(items.reshape(-1)).to(device)
+        empty.item_off_host = np.arange(nb + 1, dtype=np.int32)
+        empty.blk_item_off = torch.from_numpy(empty.item_off_host).to(device)
+    return empty
+
+
 def build_plan(edge_index: torch.Tensor, rel_ids: torch.Tensor, unique_texts: List[str], N: int, d: int,
                device: torch.device, force_generic: bool = False,
                row_range: Optional[Tuple[int, int]] = None,
@@ -351,20 +376,7 @@ def build_plan(edge_index: torch.Tensor, rel_ids: torch.Tensor, unique_texts: Li
         ei = ei[:, keep].contiguous()
         rel = rel[keep].contiguous()
         if ei.size(1) == 0:                      # a shard without in-edges: empty plan, every row is "isolated"
-            nseg = N if bn == 1 else ((N + bn - 1) // bn) * R
-            z = lambda n: torch.zeros(n, dtype=torch.int32, device=device)  # noqa: E731
-            nb = (N + bn - 1) // bn
-            empty = GraphPlan(N=N, E=0, R=R, block_nodes=bn, wlayout=wl, unique_texts=unique_texts, rel_ids=rel,
-                              sorted_key=z(1), sorted_src=z(1), seg_off=z(nseg + 1), indeg=z(N), chunk_rows=cr,
-                              row_lo=lo, row_hi=hi)
-            if bn > 1:                                # one empty work item per block
-                items = np.zeros((nb, 4), dtype=np.int32)
-                items[:, 0], items[:, 3] = np.arange(nb), -1
-                empty.chunk_tab, empty.blk_chunk_off = z(2), z(nb + 1)
-                empty.item_tab = torch.from_numpy(items.reshape(-1)).to(device)
-                empty.item_off_host = np.arange(nb + 1, dtype=np.int32)
-                empty.blk_item_off = torch.from_numpy(empty.item_off_host).to(device)
-            return empty
+            return empty_plan(N, unique_texts, (bn, wl, cr, sc), device, rel=rel, row_range=(lo, hi))
     pl = _native.plan_build(ei, rel, N, R, bn, cr, sc)
     status = pl["status"].cpu().numpy()           # the only host sync of the plan
     st = int(status[0])

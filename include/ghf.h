@@ -111,6 +111,35 @@ int ghf_plan_build(const int64_t* edge_index /* [2,E] row 0 = src, row 1 = dst *
                    int32_t* chunk_tab, int32_t* blk_chunk_off, int32_t* item_tab, int32_t* blk_item_off,
                    int32_t* status, void* stream);
 
+/* ---- node-batch subgraph: the k-hop in-neighbourhood of a seed list (HyperGNN.forward_nodes) -------------------
+ * No counterpart in the reference: a k-layer HyperGNN row depends only on the rows within k hops upstream of it
+ * (models/hypergnn.py:190-230, 288-296: a mean over the row's in-edges, a self term, a residual and a LayerNorm of that
+ * row), so the rows of a batch of seeds can be computed on that subgraph alone.  All three calls read the edges of a plan of
+ * ghf_plan_build (sorted_key / sorted_src [E], N, R, block_nodes as built), decoded as its comment above says: block plans
+ * (block_nodes > 1) carry the source in bits 0..27 of sorted_src, CSR plans the whole word.  Integer arithmetic only; no
+ * result depends on the order in which the device runs the work.  One caller-allocated workspace serves all three:
+ *   ghf_subgraph_workspace_bytes: its size (256-byte aligned), 0 for bad sizes.
+ *   ghf_subgraph_hops:  dist [N] int32: dist[v] = the fewest edges u -> v on a path from v to a seed, k + 1 where that
+ *                       exceeds k.  seeds [S] int64: duplicates allowed; ids outside [0, N) are skipped (validate them
+ *                       first).  At most k passes over the edges; once a pass discovers nothing the later ones return at
+ *                       once (a word of the workspace: no host sync).
+ *   ghf_subgraph_nodes: from dist: node_list [N] int64, whose first m[k] entries are the nodes with dist <= k ordered by
+ *                       (dist, node id) (the rest is not written); new_id [N] int64: v's position in node_list, -1 beyond
+ *                       k hops; m [k+1] int64: m[j] = the number of nodes with dist <= j — they are the first m[j] entries.
+ *   ghf_subgraph_edges: the edges whose destination has dist <= k - 1 (their sources have dist <= k), in the plan's sorted
+ *                       order (a stable compaction): edge_out [2, E] int64 (row stride E): edge_out[p] = new_id[src],
+ *                       edge_out[E + p] = new_id[dst]; rel_out [E] int64: the relation id, p < E'; num_edges [1] int64 = E'.
+ * Requires 0 < N < 2^31 - 1, 0 <= E < 2^31 - 1, k >= 1 and the plan's ceil(N/BN)*BN*R < 2^32. */
+size_t ghf_subgraph_workspace_bytes(int64_t N, int64_t E, int k);
+int ghf_subgraph_hops(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
+                      const int64_t* seeds, int64_t S, int k, void* workspace, size_t workspace_bytes, int32_t* dist,
+                      void* stream);
+int ghf_subgraph_nodes(const int32_t* dist, int64_t N, int k, void* workspace, size_t workspace_bytes, int64_t* node_list,
+                       int64_t* new_id, int64_t* m /* [k+1] */, void* stream);
+int ghf_subgraph_edges(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
+                       const int32_t* dist, const int64_t* new_id, int k, void* workspace, size_t workspace_bytes,
+                       int64_t* edge_out /* [2, E] */, int64_t* rel_out /* [E] */, int64_t* num_edges /* [1] */, void* stream);
+
 /* ---- K1: weight generation ------------------------------------------------------
  * Replaces models/weight_generator.py:137-141 (three nn.Sequential heads, reshape,
  * * exp(log_scale)) for B = R relation embeddings at once.
