@@ -10,58 +10,14 @@ from typing import List
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
-# GHF_VARIANT=stamps selects the diagnostic build (-DGHF_STAMPS, in-kernel s_memtime stamps), GHF_VARIANT=ablate the
-# one whose message kernels honour GHF_DEBUG_FLAGS (-DGHF_ABLATE: pieces of work switched off, wrong results);
-# neither is ever the product
-VARIANT = os.environ.get("GHF_VARIANT", "")
-OBJ_DIR = os.path.join(CSRC, "_obj" + ("_" + VARIANT if VARIANT else ""))
-LIB_PATH = os.path.join(PKG_DIR, "libghf_hip" + ("_" + VARIANT if VARIANT else "") + ".so")
+OBJ_DIR = os.path.join(CSRC, "_obj")
+LIB_PATH = os.path.join(PKG_DIR, "libghf_hip.so")
 INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
 
 SOURCES = ["capi.hip", "plan.hip", "text_encoder.hip", "score.hip", "backward.hip", "weightgen.hip", "weightgen_bwd.hip", "input_proj.hip", "message_generic.hip", "message_pp.hip", "message_bx.hip", "message_rs.hip", "exchange.hip", "subgraph.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(INCLUDE, "ghf.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"]
-import re as _re
-if "stamps" in VARIANT:
-    FLAGS.append("-DGHF_STAMPS")
-if VARIANT == "ablate":
-    FLAGS.append("-DGHF_ABLATE")
-_b = _re.search(r"baux(\d+)", VARIANT)
-if _b:
-    FLAGS.append("-DGHF_B_AUX=" + _b.group(1))
-_x = _re.search(r"bxexp(\d+)", VARIANT)
-if _x:
-    FLAGS.append("-DGHF_BXEXP=" + _x.group(1))         # compile-time ablations of message_bx.hip (timing only)
-for _k in ("NPW", "CR", "LATE", "DEFER", "IDXWAIT", "TAILNT", "SRCNT", "PRE0"):               # message_bx.hip geometry / protocol: e.g. GHF_VARIANT=bxNPW80_bxCR64
-    _g = _re.search(r"bx%s(\d+)" % _k, VARIANT)
-    if _g:
-        FLAGS.append("-DGHF_BX_%s=%s" % (_k, _g.group(1)))
-for _k in ("NPW", "CR", "DEFER"):                         # message_bx.hip, hidden 64: e.g. GHF_VARIANT=b64NPW96_b64CR128
-    _g = _re.search(r"b64%s(\d+)" % _k, VARIANT)
-    if _g:
-        FLAGS.append("-DGHF_BX64_%s=%s" % (_k, _g.group(1)))
-_r = _re.search(r"rsexp(\d+)", VARIANT)
-if _r:
-    FLAGS.append("-DGHF_RSEXP=" + _r.group(1))          # message_rs.hip pass-1 ablations (timing only)
-_i = _re.search(r"ipexp(\d+)", VARIANT)
-if _i:
-    FLAGS.append("-DGHF_IPEXP=" + _i.group(1))          # input_proj.hip timing experiments
-_e = _re.search(r"eoNS(\d)(\d)", VARIANT)
-if _e:                                                   # backward.hip: edge_outer_h's register sets of source / destination rows in flight
-    FLAGS += ["-DGHF_EO_STAGES_A=" + _e.group(1), "-DGHF_EO_STAGES_B=" + _e.group(2)]
-_e = _re.search(r"wgHU(\d+)", VARIANT)
-if _e:
-    FLAGS.append("-DGHF_WG_HU=" + _e.group(1))          # weightgen.hip: output units per wave and batch of wg_hidden_kernel
-_e = _re.search(r"eoSRCLAST(\d)", VARIANT)
-if _e:
-    FLAGS.append("-DGHF_EO_SRC_LAST=" + _e.group(1))    # backward.hip: edge_outer_h's source rows requested and cut last
-_e = _re.search(r"eoexp(\d+)", VARIANT)
-if _e:
-    FLAGS.append("-DGHF_EOEXP=" + _e.group(1))          # backward.hip: edge_outer_h ablations (timing only)
-if "eopin" in VARIANT:
-    FLAGS.append("-DGHF_EO_PIN")
-if "eoslow" in VARIANT:
-    FLAGS.append("-DGHF_EO_SLOW_FRAG")                  # debug: edge_outer_h fragments read element by element
+
 
 def hipcc_path() -> str:
     for cand in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):

@@ -26,7 +26,6 @@ their contractions are ``A^T B`` over rows, i.e. ``ghf_group_outer`` again (``_n
 
 from __future__ import annotations
 
-import os
 import weakref
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
@@ -78,14 +77,13 @@ def build_train_plan(edge_index: torch.Tensor, rel_ids: torch.Tensor, fwd: Graph
         if tab:
             tp.slice_tab = torch.tensor(tab, dtype=torch.int64).to(device)
             tp.slice_off = torch.tensor(soff, dtype=torch.int64).to(device)
-            if _EO_ORDER:
-                # Destinations ascend inside a relation, so a slice's place in its relation (as a fraction of the relation's
-                # slices) says which band of destination rows it reads.  Launched band by band — every relation's slice of the
-                # band together — the workgroups in flight share that band's rows of h and G (Infinity Cache) instead of each
-                # relation sweeping all N rows alone.  Same bits: ghf.h, ghf_edge_outer.
-                place = [((k + 0.5) / (soff[r + 1] - soff[r]), r) for r in range(fwd.R) for k in range(soff[r + 1] - soff[r])]
-                order = sorted(range(len(tab)), key=place.__getitem__)
-                tp.slice_order = torch.tensor(order, dtype=torch.int32).to(device)
+            # Destinations ascend inside a relation, so a slice's place in its relation (as a fraction of the relation's
+            # slices) says which band of destination rows it reads.  Launched band by band — every relation's slice of the
+            # band together — the workgroups in flight share that band's rows of h and G (Infinity Cache) instead of each
+            # relation sweeping all N rows alone.  Same bits: ghf.h, ghf_edge_outer.
+            place = [((k + 0.5) / (soff[r + 1] - soff[r]), r) for r in range(fwd.R) for k in range(soff[r + 1] - soff[r])]
+            order = sorted(range(len(tab)), key=place.__getitem__)
+            tp.slice_order = torch.tensor(order, dtype=torch.int32).to(device)
     return tp
 
 
@@ -157,24 +155,11 @@ class _SplitCarry:
         self.ref, self.version, self.split = weakref.ref(h), h._version, split
 
 
-# GHF_EO_SIDE=1: the weight gradients on a second stream beside the two gradient passes.  Round 2: 49.1 -> 48.7 ms per C3
-# training step.  Round 3 (same box, tools/ab_train.sh): 45.0-45.9 ms with, 45.1-45.5 without — the three kernels contend for
-# the same gather path (beside the contraction the self-term pass took 4.8 ms, alone 2.4): off, one stream fewer.
-_EO_SIDE = os.environ.get("GHF_EO_SIDE", "0") != "0"
-_WG_FUSED_BWD = int(os.environ.get("GHF_WG_FUSED_BWD", "1"))       # WeightGeneratorFn.backward through ghf_weightgen_bwd: 0 never, 1 small generators, 2 always
+# The weight gradients run on the main stream: on a second stream beside the two gradient passes they were no faster (round 3,
+# DESIGN_HISTORY.md: the three kernels contend for the same gather path).
+_WG_FUSED_BWD = 1                 # WeightGeneratorFn.backward through ghf_weightgen_bwd: 0 never, 1 small generators, 2 always
 WG_FUSED_MAX = 1 << 18            # ... "small": relations x d_in x d_out (config 2: 2^17, config 3: 2^20)
-_IP_EDGE_OUTER = os.environ.get("GHF_IP_EDGE_OUTER", "1") != "0"   # InputProjFn.backward: dW / db through ghf_edge_outer
-_EO_ORDER = os.environ.get("GHF_EO_ORDER", "1") != "0"     # ghf_edge_outer's slices launched band by band (build_train_plan)
-_ONE_PACK = os.environ.get("GHF_BWD_ONE_PACK", "1") != "0"   # the two gradient passes share one packed weight tensor (three pack
-                                                             # launches fewer per step; within the box noise of tools/ab_train.sh)
-_SIDE_STREAMS: dict = {}
-
-
-def _side_stream(device) -> torch.cuda.Stream:
-    key = torch.device(device).index or 0
-    if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
-    return _SIDE_STREAMS[key]
+_IP_EDGE_OUTER = True             # InputProjFn.backward: dW / db through ghf_edge_outer (where it applies)
 
 
 class MessageLayerFn(torch.autograd.Function):
@@ -228,21 +213,11 @@ def layer_backward(grad_out, h, agg, W_msg, W_self, gamma, eps: float, tp: Train
                and plan.block_nodes > 1)
     dpre, G, Gs, dgamma, dbeta = _native.tail_bwd(g, agg, h, gamma.detach(), eps, plan.indeg, drop=drop,
                                                   split_layout=plan.wlayout if split_G else None)
-    side = None
     scales = {}
     if Gs is not None and h_scales is not None and plan.wlayout == _native.WLAYOUT_SPLIT2H:
         scales = dict(h_scales=h_scales, G_scales=_native.split_row_scales(Gs, G.size(0), G.size(1)))
     if tp.slice_tab is not None:
-        if _EO_SIDE and need_dh:
-            # the weight gradients (bound by their row gathers) beside the two gradient passes (bound inside the CU): two
-            # streams, joined before the results leave
-            main = torch.cuda.current_stream(h.device)
-            side = _side_stream(h.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                dW, db = _native.edge_outer(h, G, tp.src_by_rel, tp.dst_by_rel, tp.slice_tab, tp.slice_off, plan.R, exact=plan.force_exact, order=tp.slice_order, **scales)
-        else:
-            dW, db = _native.edge_outer(h, G, tp.src_by_rel, tp.dst_by_rel, tp.slice_tab, tp.slice_off, plan.R, exact=plan.force_exact, order=tp.slice_order, **scales)
+        dW, db = _native.edge_outer(h, G, tp.src_by_rel, tp.dst_by_rel, tp.slice_tab, tp.slice_off, plan.R, exact=plan.force_exact, order=tp.slice_order, **scales)
         d = h.size(1)
         dWm, dWs = dW[:, :d], dW[:, d:]
     else:
@@ -254,7 +229,7 @@ def layer_backward(grad_out, h, agg, W_msg, W_self, gamma, eps: float, tp: Train
         if tp.zero_bias is None or tp.zero_bias.shape != (plan.R, h.size(1)):      # (one fill per plan, not one per layer and step)
             tp.zero_bias = torch.zeros(plan.R, h.size(1), dtype=torch.float32, device=h.device)
         zero_b = tp.zero_bias
-        if _ONE_PACK and plan.wlayout == tp.rev.wlayout and plan.wlayout in _native.SPLIT_LAYOUTS:
+        if plan.wlayout == tp.rev.wlayout and plan.wlayout in _native.SPLIT_LAYOUTS:
             # one packed tensor serves both passes: each declares the half it does not read zero (ZERO_SRC / ZERO_DST)
             Wf, Wf2 = _layer_weights(plan, W_msg.detach(), W_self.detach(), transpose=True)
             Wr, Wr2 = Wf, Wf2
@@ -268,10 +243,6 @@ def layer_backward(grad_out, h, agg, W_msg, W_self, gamma, eps: float, tp: Train
         else:
             dh = _native.add3(dpre, _raw_message(G, plan, Wf, Wf2, zero_b, _native.GHF_FLAG_ZERO_SRC, Gs, zero_out=shard),
                               _raw_message(G, tp.rev, Wr, Wr2, zero_b, _native.GHF_FLAG_ZERO_DST, Gs), out=dpre)
-    if side is not None:
-        main.wait_stream(side)
-        dW.record_stream(main)
-        db.record_stream(main)
     return dh, dWm, dWs, db, dgamma, dbeta
 
 

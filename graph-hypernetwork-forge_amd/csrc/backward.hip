@@ -13,8 +13,6 @@
 #include "common.h"
 #include <type_traits>
 
-#include <stdlib.h>
-#include <string.h>
 
 namespace ghf {
 
@@ -661,19 +659,6 @@ __global__ __launch_bounds__(256) void rowscale_absmax_kernel(const float* __res
     if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(out + blockIdx.y, __float_as_uint(m));
 }
 
-#ifndef GHF_EO_SRC_LAST
-#define GHF_EO_SRC_LAST 1
-#endif
-#ifndef GHF_EO_STAGES_A
-#define GHF_EO_STAGES_A 2  // register sets of gathered SOURCE rows in flight in edge_outer_h_kernel (2 or 3)
-#endif
-#ifndef GHF_EO_STAGES_B
-#define GHF_EO_STAGES_B 2  // ... of destination rows (of h and G)
-#endif
-constexpr int EO_STAGES_A = GHF_EO_STAGES_A, EO_STAGES_B = GHF_EO_STAGES_B;
-#ifndef GHF_EOEXP
-#define GHF_EOEXP 0      // timing experiments (wrong results): 1 no products, 2 no row gathers, 4 no cutting / LDS writes, 8 one barrier less
-#endif
 __device__ __forceinline__ unsigned eo_off(int row, int ch) { return 256u * row + 16u * (unsigned)(ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
 
 template <bool OFF32>   // h and G below 4 GB each: 32-bit byte offsets (see Idx)
@@ -724,14 +709,14 @@ __global__ __launch_bounds__(512) void edge_outer_h_kernel(
     // flight.  With one set, a tile's rows had one tile's MFMAs (~0.7 us) to arrive and the workgroup waited for them every
     // iteration (4.7 TB/s over the chip).  With two they have a step and a bit, ~2 us against a loaded round trip of ~2.6 us:
     // the gathers alone (no products, no cutting) run at 9.5 TB/s of HBM + Infinity Cache — 1.6 ms at C3 — the products and the
-    // cutting alone take as long, and the two together 2.6 ms (round 4's ablations, GHF_EOEXP).  A third set would cover the
+    // cutting alone take as long, and the two together 2.6 ms (round 4's ablations).  A third set would cover the
     // round trip, but does not fit: three whole sets (72 registers beside the 64 accumulators, the 40 of a step's fragments
     // and ~20 LDS addresses) spill ~30 registers inside the loop and the launch takes 3.9 ms instead of 2.9; a third set for the
     // source rows only (NSA = 3, NSB = 2: the rows that come from HBM, the destination rows of a band of slices launched
     // together sit in the Infinity Cache) still spills 19, because the trip is then six steps long and hipcc's allocation over
     // it needs ~45 registers more than over two.  Two and two it stays; what is left is a pipeline that keeps the rows in LDS
     // (LDS-DMA ring, as message_rs.hip's pass 1) instead of registers.
-    constexpr int NSA = OFF32 ? EO_STAGES_A : 2, NSB = OFF32 ? EO_STAGES_B : 2;
+    constexpr int NSA = 2, NSB = 2;
     f32x4 sa[NSA][LPR], sb[NSB][2][LPR];
     // (positions inside the slice in 32 bits — a slice holds a few thousand edges; the index arrays from the slice's first edge)
     const int nedge = (int)(e1 - e0);
@@ -762,7 +747,6 @@ __global__ __launch_bounds__(512) void edge_outer_h_kernel(
     auto gather_a = [&](f32x4 (&S)[LPR], const IdxA& I) {
 #pragma unroll
         for (int j = 0; j < LPR; ++j) {
-            if (GHF_EOEXP & 2) { S[j] = (f32x4){1.f * I.s[j], 0.f, 0.f, 0.f}; continue; }
             if (OFF32) S[j] = *(const f32x4*)((const char*)h + I.s[j]);
             else S[j] = *(const f32x4*)(h + (size_t)I.s[j] * ld + xa_col + 4 * ((t + NT * j) % F4));
         }
@@ -770,7 +754,6 @@ __global__ __launch_bounds__(512) void edge_outer_h_kernel(
     auto gather_b = [&](f32x4 (&S)[2][LPR], const IdxB& I) {
 #pragma unroll
         for (int j = 0; j < LPR; ++j) {
-            if (GHF_EOEXP & 2) { S[0][j] = S[1][j] = (f32x4){1.f * I.v[j], 1.f * I.d[j], 0.f, 0.f}; continue; }
             if (OFF32) {
                 S[0][j] = *(const f32x4*)((const char*)h + I.v[j]);
                 S[1][j] = *(const f32x4*)((const char*)G + I.d[j]);
@@ -785,13 +768,9 @@ __global__ __launch_bounds__(512) void edge_outer_h_kernel(
     // requested in): row-major images.  Rows past the slice's end (copies of its last edge's rows) are cut as zeros by a zero
     // scale (a copy of a row the sums hold anyway: 0 x inf could only put a NaN where the result is no number already).
     auto commit_unit = [&](int buf, int k, int unit, int tile) __attribute__((always_inline)) {   // tile's rows: sa[k % NSA], sb[k % NSB], k = tile mod TRIP
-#if GHF_EO_SRC_LAST
         // units in the order the rows were requested in: the destination rows of h and G first, the source rows — the ones that
         // come from HBM rather than the Infinity Cache — last: half a step more for them to arrive
         const int j = unit < 2 * LPR ? unit / 2 : unit - 2 * LPR, reg = unit < 2 * LPR ? 1 + unit % 2 : 0;
-#else
-        const int j = unit / 3, reg = unit % 3;
-#endif
         char* base = eoh_lds + (size_t)buf * 6 * IMG;
         const int row = (t + NT * j) / F4, c4 = (t + NT * j) % F4;
         const unsigned o = eo_off(row, c4 >> 1) + 8u * (c4 & 1);
@@ -814,14 +793,6 @@ __global__ __launch_bounds__(512) void edge_outer_h_kernel(
     // 8Q .. 8Q+7 — two transposed reads (rows 8Q.. and 8Q+4..); lane 4q+p of a 16-lane group supplies row r0+q, columns 4p..
     const int gq = c16 >> 2, gp = c16 & 3;
     auto frag = [&](const char* img, int fb) -> eo_f16x8 {
-#ifdef GHF_EO_SLOW_FRAG
-        {   // (debug) the same fragment, element by element
-            eo_f16x8 r;
-            const int col = fb + c16;
-            for (int e = 0; e < 8; ++e) r[e] = *(const _Float16*)(img + eo_off(8 * Q + e, col >> 3) + 2 * (col & 7));
-            return r;
-        }
-#endif
         const int ch = (fb >> 3) + (gp >> 1);
         typedef __fp16 h4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
         const auto p0 = (__attribute__((address_space(3))) h4_t*)(img + eo_off(8 * Q + gq, ch) + 8u * (gp & 1));
@@ -852,13 +823,8 @@ __global__ __launch_bounds__(512) void edge_outer_h_kernel(
         constexpr int K = decltype(K_)::value;
         load_idx_a(tile + NSA + 1, ixa[(K + NSA + 1) & 1]);
         load_idx_b(tile + NSB + 1, ixb[(K + NSB + 1) & 1]);
-#if GHF_EO_SRC_LAST
-        gather_b(sb[K % NSB], ixb[(K + NSB) & 1]);
+        gather_b(sb[K % NSB], ixb[(K + NSB) & 1]);        // (the source rows last: see commit_unit)
         gather_a(sa[K % NSA], ixa[(K + NSA) & 1]);
-#else
-        gather_a(sa[K % NSA], ixa[(K + NSA) & 1]);
-        gather_b(sb[K % NSB], ixb[(K + NSB) & 1]);
-#endif
         __builtin_amdgcn_sched_barrier(0);                // (the loads stay at the top of the step: left alone hipcc sinks them to its end)
         const char* base = eoh_lds + (size_t)(K & 1) * 6 * IMG;
         const char* ximg = base + (rg >> 1) * 2 * IMG;    // rows 0..127 of [X_src | X_dst] are the source image, 128..255 the destination one
@@ -878,21 +844,18 @@ __global__ __launch_bounds__(512) void edge_outer_h_kernel(
         for (int ai = 0; ai < 4; ++ai) {
             const int fb = (rg & 1) * 64 + 16 * ai;
             const eo_f16x8 ah = frag(ximg, fb), al = frag(ximg + IMG, fb);
-            if (!(GHF_EOEXP & 1)) {
 #pragma unroll
-                for (int bi = 0; bi < 4; ++bi) {
-                    acc[ai][bi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[bi], acc[ai][bi], 0, 0, 0);
-                    acc[ai][bi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[bi], acc[ai][bi], 0, 0, 0);
-                    acc[ai][bi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[bi], acc[ai][bi], 0, 0, 0);
-                }
+            for (int bi = 0; bi < 4; ++bi) {
+                acc[ai][bi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[bi], acc[ai][bi], 0, 0, 0);
+                acc[ai][bi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[bi], acc[ai][bi], 0, 0, 0);
+                acc[ai][bi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[bi], acc[ai][bi], 0, 0, 0);
             }
-            if (ai < 3 && !(GHF_EOEXP & 4)) {
+            if (ai < 3) {
                 commit_unit((K & 1) ^ 1, K + 1, 2 * ai, tile + 1);
                 commit_unit((K & 1) ^ 1, K + 1, 2 * ai + 1, tile + 1);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if (GHF_EOEXP & 4) { for (int j = 0; j < LPR; ++j) bsum[j] += sa[(K + 1) % NSA][j] + sb[(K + 1) % NSB][0][j] + sb[(K + 1) % NSB][1][j]; }
         // (The two halves of a step touch different buffers, so their order is free.  Taken in opposite orders by the two
         // waves that share a SIMD — one's products beside the other's cutting — the launch got SLOWER: 2.92 -> 3.35 ms at C3,
         // round 4.  Every wave in the same half at the same time it stays.)
@@ -951,10 +914,9 @@ int launch_edge_outer(const float* h, const float* G, const int64_t* src, const 
     float* partial = workspace;
     float* partial_b = workspace + (size_t)nslices * 2 * D * D;
     const unsigned gx = (unsigned)cdiv((int64_t)2 * D * D / 4 + D, 256);
-    // d % 128 == 0: two fp16 pieces on the 16-bit matrix pipe (edge_outer_h_kernel); GHF_EDGE_OUTER=exact keeps the fp32 MFMAs
-    static const bool exact = getenv("GHF_EDGE_OUTER") && !strcmp(getenv("GHF_EDGE_OUTER"), "exact");
+    // d % 128 == 0: two fp16 pieces on the 16-bit matrix pipe (edge_outer_h_kernel)
     unsigned* amax = (unsigned*)(partial_b + (size_t)nslices * D);     // two words behind the partial sums: max |h|, max |G|
-    const bool pieces = D == 128 && !exact && N > 0;      // (N <= 0: the caller asks for the exact fp32 chain, ghf.h)
+    const bool pieces = D == 128 && N > 0;                // (N <= 0: the caller asks for the exact fp32 chain, ghf.h)
     int* guard = nullptr;                                  // four counters behind the two maxima (ghf.h: the workspace's last 64 floats)
     if (pieces) {
         GHF_HIP_CHECK(hipMemsetAsync(amax, 0, 6 * sizeof(unsigned), stream));
@@ -963,11 +925,8 @@ int launch_edge_outer(const float* h, const float* G, const int64_t* src, const 
             // workgroups of them cost ~0.1 ms per call at N = 10^6, 128 next to nothing; the scales are 4 MB per tensor)
             const unsigned ag = (unsigned)(cdiv(N, 256 * 4) < 128 ? cdiv(N, 256 * 4) : 128);
             rowscale_absmax_kernel<<<dim3(ag, 2), 256, 0, stream>>>(h_rowscale, G_rowscale, N, amax);
-            static const bool guarded = !(getenv("GHF_EO_GUARD") && !strcmp(getenv("GHF_EO_GUARD"), "0"));
-            if (guarded) {
-                guard = (int*)(amax + 2);
-                rowscale_guard_kernel<<<dim3(ag, 2), 256, 0, stream>>>(h_rowscale, G_rowscale, N, amax, guard);
-            }
+            guard = (int*)(amax + 2);
+            rowscale_guard_kernel<<<dim3(ag, 2), 256, 0, stream>>>(h_rowscale, G_rowscale, N, amax, guard);
         } else {
             const unsigned ag = (unsigned)(cdiv(N * d, 256 * 16) < 2048 ? cdiv(N * d, 256 * 16) : 2048);
             absmax_kernel<<<dim3(ag, 2), 256, 0, stream>>>(h, G, N * d, amax);

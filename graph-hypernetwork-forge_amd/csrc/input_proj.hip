@@ -11,8 +11,6 @@
 // Shapes the tile does not cover (F % 16, d % 16, d > 256) take a vector-ALU kernel.
 #include "common.h"
 
-#include <stdlib.h>
-#include <string.h>
 
 namespace ghf {
 
@@ -20,9 +18,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 ip_f16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int IP_MT = 2;       // m-tiles (16 rows each) per wave
-#ifndef GHF_IPEXP
-#define GHF_IPEXP 0           // timing experiments only (GHF_VARIANT=ipexp<mask>): 1 no fp32 stores, 2 no piece stores, 4 no range guard
-#endif
 
 // SPLIT: also write the rows in GHF_WLAYOUT_SPLIT2H form (ghf_split_rows) for the first message layer's gathers: a row
 // lives in the four lanes {c16, c16 + 16, c16 + 32, c16 + 48}, so its largest magnitude is two lane exchanges away.
@@ -121,10 +116,9 @@ __global__ __launch_bounds__(256) void input_proj_mfma_kernel(const float* __res
         }
         if (r < N) {
             float* __restrict__ o = h0 + (size_t)r * D + 4 * q;
-            if (!(GHF_IPEXP & 1))
 #pragma unroll
-                for (int t = 0; t < NT; ++t) *(f32x4*)(o + 16 * t) = v[t];
-            if (SPLIT && !(GHF_IPEXP & 2)) {
+            for (int t = 0; t < NT; ++t) *(f32x4*)(o + 16 * t) = v[t];
+            if (SPLIT) {
                 _Float16* __restrict__ sp = (_Float16*)(h_split + (size_t)r * (4 * D)) + 4 * q;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
@@ -141,7 +135,7 @@ __global__ __launch_bounds__(256) void input_proj_mfma_kernel(const float* __res
                 }
             }
         }
-        if (SPLIT && !(GHF_IPEXP & 4)) {                  // range guard (common.h); all lanes take part in the reduction
+        if (SPLIT) {                                      // range guard (common.h); all lanes take part in the reduction
             float tiny = 0.f, nz = 0.f;
 #pragma unroll
             for (int t = 0; t < NT; ++t)
@@ -401,10 +395,8 @@ int launch_input_proj(const float* x, const float* W_in, const float* b_in, int6
     const bool fuse = h_split && split_layout == GHF_WLAYOUT_SPLIT2H;
     const bool aligned = ((((uintptr_t)x | (uintptr_t)W_in | (uintptr_t)b_in | (uintptr_t)h0 | (uintptr_t)h_split) & 15) == 0);
     const bool mfma_ok = aligned && (F % 16) == 0 && (d % 16) == 0 && d <= 256;
-    // callers on the two-piece path (they ask for the SPLIT2H rows): the projection on fp16 pieces too, where its tile fits;
-    // GHF_INPUT_PROJ=exact keeps the fp32 MFMAs (A/B)
-    static const bool ip_exact = getenv("GHF_INPUT_PROJ") && !strcmp(getenv("GHF_INPUT_PROJ"), "exact");
-    const bool pieces_ok = fuse && aligned && !ip_exact && (F % 32) == 0 && F <= 128 && (d % 16) == 0 && d <= 128 && N >= 1024;
+    // callers on the two-piece path (they ask for the SPLIT2H rows): the projection on fp16 pieces too, where its tile fits
+    const bool pieces_ok = fuse && aligned && (F % 32) == 0 && F <= 128 && (d % 16) == 0 && d <= 128 && N >= 1024;
     if (pieces_ok) {
         const int64_t nblk = cdiv(N, (int64_t)4 * 16 * IP_MT);
         const unsigned grid = (unsigned)(nblk < 512 ? nblk : 512);       // two workgroups per CU, each cuts W_in once and walks its tiles

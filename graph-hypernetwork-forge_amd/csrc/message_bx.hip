@@ -19,7 +19,7 @@
 //     VALU instruction relative to M0) turns that into two instructions per row and lane.  Rows in order, chunks in
 //     order, no atomics: bitwise reproducible.  (Round 2 folded node by node — a table node -> row, every owner lane
 //     reading its node's row or zeros: 48 ds_read_b128 + 96 packed adds per lane and chunk whatever the chunk held,
-//     3,000 + 1,540 of the helpers' 8,700 cycles per chunk: tools/stamps_bx.py.)
+//     3,000 + 1,540 of the helpers' 8,700 cycles per chunk: round 2's in-kernel stamps.)
 //   * the helpers gather the A tiles with LDS-DMA (buffer_load_dwordx4 ... lds, per-lane source address, 1 KiB per wave
 //     instruction, the XOR swizzle applied on the source side): no staging registers, no ds_write;
 //   * the fused tail runs from LDS after the helpers have dumped their registers there (two halves of the block).
@@ -28,20 +28,19 @@
 // rows' scales and node ids); a KiB for DMA pieces past a tile, a row of zeros, sixteen flag words.
 // ONE workgroup barrier per chunk.  During chunk k (between barriers k and k + 1):
 //   consumers: stage Y(k-1) into P1[(k-1)&1] (behind the barrier every consumer is through with that tile; flag "staged");
-//              phase 0 (h_src x W_msg) from P0[k&1]; wait for the flag "destination rows of chunk k landed"; phase 1
-//              (h_dst x W_self) from P1[k&1]; the accumulators keep Y(k) until the next barrier
-//   helpers:   DMA P0[(k+1)&1] <- source rows of chunk k+1 (HBM: a whole chunk to land); counted vmcnt wait: the destination
-//              rows of chunk k, requested at the end of chunk k-1, are in (flag "landed"); wait for "staged", fold Y(k-1) out
-//              of P1[(k-1)&1]; once all four have folded (flag words), DMA that tile <- destination rows of chunk k+1 (L2; may
-//              land after the barrier); the descriptor pipeline (chunk_tab entry k+5, edge words k+4, row
-//              scales k+3, publish k+2); counted vmcnt wait: the source rows of chunk k+1 are in
+//              phase 0 (h_src x W_msg) from P0[k&1]; phase 1 (h_dst x W_self) from P1[k&1]; the accumulators keep Y(k)
+//              until the next barrier
+//   helpers:   DMA P0[(k+1)&1] <- source rows of chunk k+1 (HBM: a whole chunk to land); wait for "staged", fold Y(k-1) out
+//              of P1[(k-1)&1]; once all four have folded (flag words), DMA that tile <- destination rows of chunk k+1 (L2);
+//              the descriptor pipeline (chunk_tab entry k+5, edge words k+4, row scales k+3, publish k+2); vmcnt(0): both
+//              tiles of chunk k+1 are in before the barrier
 // The indexing mode's switch (round 4: the cause of round 3's "unexplained hazard").  s_set_gpr_idx_on writes MODE.gpr_idx_en; a
 // VALU instruction issued in the very next slot is not guaranteed to see it — the same class as the ISA's "s_setreg of MODE ->
 // vector instruction" rule, which the assembler's and hipcc's hazard handling do not apply to this instruction.  With one helper
 // wave per SIMD (hidden 128, one workgroup per CU) it never showed; at four waves per SIMD (hidden 64, two workgroups per CU) the
 // first indexed add of a four-row block went wrong a few times per launch whenever the schedule put the helpers last at the
 // chunk barrier (round 3's b64DEFER1: 40 of 40 launches, bxLATE0: 300 of 300) and the damage was not confined to the sums: whole
-// 8-row DMA pieces were then gathered with a zeroed id register — from row 0 of h (tools/diag_rows.py).  Located by a
+// 8-row DMA pieces were then gathered with a zeroed id register — from row 0 of h.  Located by a
 // single-pad bisect inside the asm block (profiles/r04_hazard_bisect.txt): wait states behind s_set_gpr_idx_on alone make both
 // builds clean, wait states anywhere else do not; a fold without the mode (a select chain over the 48 sums) is clean too; M0
 // traffic and mode switches without a VALU instruction inside are harmless; one wait state is enough (0 of 60), BX_IDX_WAIT
@@ -54,7 +53,6 @@
 // (GHF_FLAG_ZERO_SRC / GHF_FLAG_ZERO_DST): that half's gathers and products are compiled out.
 #include "common.h"
 
-#include <stdlib.h>
 #include <type_traits>
 
 namespace ghf {
@@ -113,140 +111,40 @@ __device__ __forceinline__ int opaque_lane(int lane) {
     return lane + z;
 }
 
-#ifndef GHF_BX_TAILNT
-#define GHF_BX_TAILNT 1      // 1: the tail's loads of h and its stores are non-temporal (each line is touched once per launch: 2.94 -> 2.92 ms per C3 launch)
-#endif
-template <class T> __device__ __forceinline__ T bx_tail_ld(const T* p) {
-#if defined(GHF_BX_TAILNT) && GHF_BX_TAILNT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-template <class T> __device__ __forceinline__ void bx_tail_st(T* p, T v) {
-#if defined(GHF_BX_TAILNT) && GHF_BX_TAILNT
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
-#ifndef GHF_BX_NPW
-#define GHF_BX_NPW 96        // nodes per helper wave at d = 128 (BN = 4 NPW; two registers per node and lane)
-#endif
-// Compile-time ablations (GHF_VARIANT=bxexp<mask>, timing only, wrong results; tools/pmc_attr.sh): 1 no B refills, 2 no A-tile
-// DMA, 4 no MFMAs, 8 no fold, 16 no staging writes, 32 no tail, 64 no descriptor pipeline (words / scales / publish / table),
-// 128 one relation's weights for every chunk, 256 / 512 the destination / source rows' gathers without memory access
-#ifndef GHF_BXEXP
-#define GHF_BXEXP 0
-#endif
-#ifndef GHF_BX_LATE
-#define GHF_BX_LATE 0         // 0 (round 4): every gathered tile is waited for (vmcnt(0)) BEFORE the chunk barrier and read behind it — the
-                              // guide's order for LDS-DMA.  1 (rounds 2-3): the destination-row tile of chunk k+1 may land after the barrier,
-                              // behind a flag the consumers wait for before phase 1, and the first phase's first fragments are prefetched:
-                              // measured the same within the box noise in round 4 (2.90-2.93 vs 2.92-2.93 ms at C3, 0.165 vs 0.164 at C2), so
-                              // the shortcut is off
-#endif
-#ifndef GHF_BX_DEFER
-#define GHF_BX_DEFER 1        // 1: a chunk's rows are staged AFTER the next barrier (see the consumers' loop): no hand-shake among the
-                              // consumers, 3.25 -> 3.13 ms at C3 together with GHF_BX_LATE and the helpers' batched descriptor reads
-#endif
-#ifndef GHF_BX_CR
-#define GHF_BX_CR 76         // rows per chunk
-#endif
-#ifndef GHF_BX64_NPW
-#define GHF_BX64_NPW 48      // hidden 64: nodes per helper wave (one register per node and lane): blocks of 192 nodes
-#endif
-#ifndef GHF_BX64_CR
-#define GHF_BX64_CR 64       // hidden 64: rows per chunk (see BxCfg<64>)
-#endif
-#ifndef GHF_BX64_DEFER
-#define GHF_BX64_DEFER 0     // hidden 64: GHF_BX_DEFER's choice for this size (measured slower there: 0.168 vs 0.164 ms per C2 launch)
-#endif
-#ifndef GHF_BX_SRCNT
-#define GHF_BX_SRCNT 0       // 1: the source rows' gathers non-temporal.  Round 4, same box: 2.92 (1) vs 2.85 ms (0) per C3 launch — a source row
-                             // is gathered ~10 times per layer by different blocks, and with the default policy the Infinity Cache serves part
-                             // of those (the DESTINATION rows non-temporal: 3.12 ms — they live on the caches between their ~10 uses)
-#endif
-#ifndef GHF_B_AUX
-#define GHF_B_AUX 0          // cache-policy bits of the consumers' weight-fragment loads (experiment: GHF_VARIANT=baux<n>)
-#endif
-#ifndef GHF_BX_IDXWAIT
-#define GHF_BX_IDXWAIT 4     // wait states behind s_set_gpr_idx_on / _off in the fold (header: "The indexing mode's switch"); 0 = round 3
-#endif
-#if GHF_BX_IDXWAIT == 0
-#define BX_IDX_WAIT ""
-#elif GHF_BX_IDXWAIT == 1
-#define BX_IDX_WAIT "s_nop 0\n\t"
-#elif GHF_BX_IDXWAIT == 2
-#define BX_IDX_WAIT "s_nop 1\n\t"
-#elif GHF_BX_IDXWAIT == 4
+// the tail's loads of h and its stores are non-temporal (each line is touched once per launch: 2.94 -> 2.92 ms per C3 launch)
+template <class T> __device__ __forceinline__ T bx_tail_ld(const T* p) { return __builtin_nontemporal_load(p); }
+template <class T> __device__ __forceinline__ void bx_tail_st(T* p, T v) { __builtin_nontemporal_store(v, p); }
+// wait states behind s_set_gpr_idx_on / _off in the fold (header: "The indexing mode's switch"; round 3 had none)
 #define BX_IDX_WAIT "s_nop 3\n\t"
-#elif GHF_BX_IDXWAIT == 8
-#define BX_IDX_WAIT "s_nop 7\n\t"
-#else
-#define BX_IDX_WAIT "s_nop 7\n\ts_nop 7\n\t"
-#endif
-// measured and fixed (round 2-3 A/B records in DESIGN_HISTORY.md): A fragments two positions ahead; weight refills behind their
-// k-step's MFMAs (scheduling barriers); staged rows drained before their flag; the first phase's first fragments requested
-// behind the barrier; non-temporal source gathers; ZERO_SRC as a first phase; the tail's batches of three four-row groups
-constexpr int GHF_BX_AD = 2, GHF_BX_TGB = 3;
-
-// Diagnostic build only (-DGHF_STAMPS): per-wave s_memtime totals per segment.
-// consumers: 0 barrier wait, 1 phase-0 stage, 2 phase-1 stage, 3 staging writes
-// helpers:   0 barrier wait, 1 DMA issue, 2 fold + table clear, 3 wait for the P1 pieces, 4 descriptor work, 6 epilogue + tail
-#ifdef GHF_STAMPS
-__device__ unsigned long long ghf_bx_stamp_buf[8192 * 8 * 8];
-__device__ unsigned long long ghf_bx_life_buf[8192 * 3];     // per workgroup: first stamp, last stamp, (XCC id << 32) | HW_ID
-#define BX_STAMP_DECL unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_last = 0, st_first = 0
-#define BX_STAMP(i)                                                                            \
-    do {                                                                                       \
-        unsigned long long _t;                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory");             \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
-        if ((i) >= 0) st_acc[(i) < 0 ? 0 : (i)] += _t - st_last;                               \
-        else st_first = _t;                                                                    \
-        st_last = _t;                                                                          \
-    } while (0)
-#define BX_STAMP_FLUSH()                                                                       \
-    do {                                                                                       \
-        if (lane == 0 && blockIdx.x < 8192)                                                    \
-            for (int i = 0; i < 8; ++i) ghf_bx_stamp_buf[((size_t)blockIdx.x * 8 + w) * 8 + i] = st_acc[i]; \
-        if (lane == 0 && w == 0 && blockIdx.x < 8192) {  /* the workgroup's life and place: tools/stamps_gap.py */ \
-            unsigned _hw, _xcc;                                                                \
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(_hw), "=s"(_xcc)); \
-            ghf_bx_life_buf[(size_t)blockIdx.x * 3] = st_first;                                \
-            ghf_bx_life_buf[(size_t)blockIdx.x * 3 + 1] = st_last;                             \
-            ghf_bx_life_buf[(size_t)blockIdx.x * 3 + 2] = ((unsigned long long)_xcc << 32) | _hw; \
-        }                                                                                      \
-    } while (0)
-#else
-#define BX_STAMP_DECL
-#define BX_STAMP(i)
-#define BX_STAMP_FLUSH()
-#endif
-
+// measured and fixed (A/B records in DESIGN_HISTORY.md): A fragments two positions ahead; weight refills behind their
+// k-step's MFMAs (scheduling barriers); staged rows drained before their flag; every gathered tile waited for (vmcnt(0))
+// before the chunk barrier, not behind a flag (round 4: the same time); the first phase's first fragments requested inside
+// its stage, not behind the barrier; the source rows' gathers with the default cache policy (round 4: 2.85 vs 2.92 ms per C3
+// launch non-temporal — the Infinity Cache serves part of a source row's ~10 gathers per layer); ZERO_SRC as a first phase;
+// the tail's batches of three four-row groups
+constexpr int BX_AD = 2, BX_TGB = 3;
 
 template <int D> struct BxCfg;
 template <> struct BxCfg<128> {
-    static constexpr int NPW = GHF_BX_NPW, CR = GHF_BX_CR;
+    static constexpr int NPW = 96, CR = 76;        // nodes per helper wave (two registers per node and lane), rows per chunk
     static constexpr int BN = 4 * NPW;             // four helper waves
     static constexpr int MTC = (CR + 15) / 16;     // row tiles per chunk
-    static constexpr bool YT = false;               // (a fifth tile for the staged rows was measured and dropped: round 2)
-    static constexpr size_t LDS = (size_t)(YT ? 5 : 4) * 2 * CR * 256 + 4 * (4 * 16 * MTC + 4) * 4 + 1024 + 512 + 64;
+    static constexpr bool DEFER = true;            // a chunk's rows are staged after the next barrier (see the consumers' loop)
+    // (a fifth tile for the staged rows was measured and dropped: round 2)
+    static constexpr size_t LDS = (size_t)4 * 2 * CR * 256 + 4 * (4 * 16 * MTC + 4) * 4 + 1024 + 512 + 64;
 };
 // hidden 64: a chunk is [rows, 128] x [128, 64] — a quarter of the matrix work per row, so the fixed cost per chunk (~7,000
 // cycles: barrier, hand-shakes, the descriptor pipeline, two DMA round trips) decides, and two workgroups per CU hide it
 // behind each other: 71 KB of LDS and <= 128 registers per workgroup.  Blocks of 192 nodes: at C2's 32 relations a block and
 // relation hold ~60 rows — one chunk of <= 64 rows, not a full one and a remainder — and C2's 100 k nodes make 521 workgroups
 // for the 512 slots.  Round 3: 0.220 -> 0.155 ms per C2 launch against 256-node blocks, 112-row chunks, one workgroup per CU.
-// GHF_BX64_DEFER = 0 here: the deferred staging is slower at this size (0.168 vs 0.164 ms per C2 launch, same box).  (Round 3
-// shipped without it because that build was not bitwise reproducible: the indexing mode's switch — see the header.)
+// No deferred staging here: it is slower at this size (0.168 vs 0.164 ms per C2 launch, same box).  (Round 3 shipped without
+// it because that build was not bitwise reproducible: the indexing mode's switch — see the header.)
 template <> struct BxCfg<64> {
-    static constexpr int NPW = GHF_BX64_NPW, CR = GHF_BX64_CR;
+    static constexpr int NPW = 48, CR = 64;        // one register per node and lane
     static constexpr int BN = 4 * NPW;
     static constexpr int MTC = (CR + 15) / 16;
-    static constexpr bool YT = false;
+    static constexpr bool DEFER = false;
     static constexpr size_t LDS = (size_t)4 * 2 * CR * 128 + 4 * (4 * 16 * MTC + 4) * 4 + 1024 + 512 + 64;
 };
 
@@ -255,15 +153,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // The helpers' block sums: tuples of 32 registers (16 at hidden 64) pinned to v64 .. — every asm that touches them names them
 // with these constraints, so the register allocator keeps them there and the indexed adds can name v64 + index.
 #define BX_PIN_128(s) "+{v[64:95]}"(s[0]), "+{v[96:127]}"(s[1]), "+{v[128:159]}"(s[2]), "+{v[160:191]}"(s[3]), "+{v[192:223]}"(s[4]), "+{v[224:255]}"(s[5])
-#if GHF_BX64_NPW == 64
-#define BX_PIN_64(s) "+{v[64:79]}"(s[0]), "+{v[80:95]}"(s[1]), "+{v[96:111]}"(s[2]), "+{v[112:127]}"(s[3])
-#elif GHF_BX64_NPW == 48
-#define BX_PIN_64(s) "+{v[64:79]}"(s[0]), "+{v[80:95]}"(s[1]), "+{v[96:111]}"(s[2])
-#elif GHF_BX64_NPW == 32
-#define BX_PIN_64(s) "+{v[64:79]}"(s[0]), "+{v[80:95]}"(s[1])
-#else
-#error "GHF_BX64_NPW: 32, 48 or 64"
-#endif
+#define BX_PIN_64(s) "+{v[64:79]}"(s[0]), "+{v[80:95]}"(s[1]), "+{v[96:111]}"(s[2])        // (BxCfg<64>::NPW = 48)
 
 struct BxChunk { int r; int e0; int rows; };
 
@@ -283,16 +173,14 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
     // ZERO_SRC (SKIP = 1, the backward's pass over the forward plan) runs as the one-phase kernel of ZERO_DST does — its rows
     // gathered a whole chunk ahead into the P0 tiles, no hand-shake for a late tile — with the destination ids, the
     // destination half of the weights and the destination rows' scales in that phase: as a second phase without a first one
-    // its gathers were issued behind the fold and waited for at the next chunk's start (2.41 -> 2.34 ms per C3 launch, same box,
-    // GHF_VARIANT=bxSWAP10 for the old form; the 4.8 ms of round 2's training profile was this launch beside the weight
-    // gradients' kernel on a second stream)
+    // its gathers were issued behind the fold and waited for at the next chunk's start (2.41 -> 2.34 ms per C3 launch, same box;
+    // the 4.8 ms of round 2's training profile was this launch beside the weight gradients' kernel on a second stream)
     constexpr bool SWAP1 = SKIP == 1;
     constexpr int skip = SWAP1 ? 2 : SKIP;
     constexpr int P0_IDS = SWAP1 ? 3 : 2;          // which ids the P0 tiles' rows follow (2: source, 3: destination)
     constexpr int P0_HALF = SWAP1 ? 1 : 0;         // the half of the weights (and the row scales) of the P0 phase
-    constexpr bool P0_NT = GHF_BX_SRCNT && !SWAP1;   // (a destination row is gathered once per in-edge: default cache policy)
     constexpr int BN = C::BN, MTC = C::MTC, CR = C::CR, NPW = C::NPW;
-    constexpr bool DEFER = D == 64 ? (GHF_BX64_DEFER != 0) : (GHF_BX_DEFER != 0);
+    constexpr bool DEFER = C::DEFER;
     constexpr int NWV = 8, TW = 4;            // waves per workgroup, per role
     constexpr int KS = D / 32;                // k-steps of 32 per phase
     constexpr int NKS = 2 * KS;
@@ -320,14 +208,12 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
     // two rows share a 256-byte bank line, so the key is (row / 2) mod 8 — either way the 16 rows of a fragment read hit every
     // bank once
     auto akey = [](int row) -> int { return D == 128 ? (row & 15) : ((row >> 1) & 7); };
-    // P0[2] source-row tiles, P1[2] destination-row tiles; a chunk's staged rows Y overwrite its own P1 tile — or, where
-    // five tiles fit (YT: rows per chunk <= 60), have a tile of their own: then neither DMA waits for the fold
-    constexpr bool YT = C::YT;
-    constexpr unsigned P0_OFF = 0, P1_OFF = 2 * TILE, Y_OFF = 4 * TILE, META_OFF = (YT ? 5 : 4) * TILE,
+    // P0[2] source-row tiles, P1[2] destination-row tiles; a chunk's staged rows Y overwrite its own P1 tile
+    constexpr unsigned P0_OFF = 0, P1_OFF = 2 * TILE, META_OFF = 4 * TILE,
                        DUMMY_OFF = META_OFF + 4 * MSTR * 4, ZERO_OFF = DUMMY_OFF + 1024,       // ZERO: a staged row of zeros (512 bytes)
                        FLAG_OFF = ZERO_OFF + 512;         // FLAG: 4 helper words (chunks folded), 4 consumer words (chunks whose tiles are read),
-                                                          // 4 helper words (chunks whose destination-row tile has landed), 4 consumer
-                                                          // words (the last chunk's hand-shake when staging is deferred)
+                                                          // 4 unused words, 4 consumer words (the last chunk's hand-shake when staging
+                                                          // is deferred)
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lds0 = (unsigned)(size_t)(lptr_t)smem;       // LDS byte address of smem (0 unless static LDS exists)
@@ -348,8 +234,6 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
     const int nchunks = c_end - c_begin;
     int vzero;
     asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));    // opaque 0: keeps the descriptor loads on the vector path
-    BX_STAMP_DECL;
-    BX_STAMP(-1);
 
     auto load_desc = [&](int k) -> i32x2 {                              // past the end: the item's first chunk (ignored)
         const int c = c_begin + (k < nchunks ? k : 0) + vzero;
@@ -369,7 +253,6 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
     // 16 bytes per lane, and a row reduction is four DPP steps inside its 16-lane row — for four rows at once.  (One wave
     // per row, two columns per lane, took 1,800 cycles per row: ~110 dependent instructions, 2- and 4-byte stores.)
     auto tail_half = [&](int half, auto gb_c) __attribute__((always_inline)) {          // gb_c: four-row groups in flight per wave
-        if (GHF_BXEXP & 32) return;
         const float* acc_lds = (const float*)smem;       // dump rows, natural column order
         // a lane's CPL columns: 4 (lane mod 16) + 64 i + (0..3), i < NV — every 16-byte load / store of a row's 16 lanes is one
         // contiguous 256 bytes (whole 128-byte lines per instruction); adjacent columns per lane left half of each line to the
@@ -561,34 +444,28 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             for (int i = 0; i < 6; ++i) ia[i] = id_addr(j, which, i, lane);
             lds_ld_b32_x6(ia, id);
         };
-        auto dma_issue = [&](unsigned tile_off, int rows, bool nt, int lane, const int (&id)[6]) {
-            if (GHF_BXEXP & 2) return;
+        auto dma_issue = [&](unsigned tile_off, int rows, int lane, const int (&id)[6]) {
 #pragma unroll
             for (int i_ = 0; i_ < RBW; ++i_) {
                 const int i = i_;
                 const int rb = hw + TW * i, row = RPP * rb + lane / LPR;
-                // (a piece without live rows is issued too when GHF_BX_LATE: every lane past the buffer — zeros, no memory
-                // access — so that the number of DMA instructions per tile is a constant the counted waits can name)
-                if (!GHF_BX_LATE && RPP * rb >= rows) continue;
+                if (RPP * rb >= rows) continue;
                 const int g = (lane & (LPR - 1)) ^ akey(row);
                 // dead rows: an offset past the end of the buffer (zeros, no memory access)
-                // (GHF_BXEXP 256 / 512: the destination / source tile's loads all past the buffer — same instructions, no memory access)
-                const bool no_mem = ((GHF_BXEXP & 256) && tile_off >= P1_OFF) || ((GHF_BXEXP & 512) && tile_off < P1_OFF);
-                const int voff = (row < rows && !no_mem) ? (int)((uint32_t)id[i] * (uint32_t)HROW) + (g << 4) : (int)0xFFFFF000u;
+                const int voff = row < rows ? (int)((uint32_t)id[i] * (uint32_t)HROW) + (g << 4) : (int)0xFFFFF000u;
                 // a piece past the tile (RBN not a multiple of 4 waves) lands in a scratch KiB
                 const unsigned dst = rb < RBN ? tile_off + (unsigned)rb * 1024u : DUMMY_OFF;
 #pragma unroll
                 for (int pl = 0; pl < NPL; ++pl) {
                     const unsigned d = __builtin_amdgcn_readfirstlane(dst + (rb < RBN ? pl * PLANE : 0));
-                    if (nt) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsH, (lptr_t)(smem + d), 16, voff + pl * ROWB, 0, 0, 2);
-                    else    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsH, (lptr_t)(smem + d), 16, voff + pl * ROWB, 0, 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsH, (lptr_t)(smem + d), 16, voff + pl * ROWB, 0, 0, 0);
                 }
             }
         };
-        auto dma_tile = [&](unsigned tile_off, int j, int which, const BxChunk& c, bool nt, int lane) {
+        auto dma_tile = [&](unsigned tile_off, int j, int which, const BxChunk& c, int lane) {
             int id[6];
             dma_ids(j, which, lane, id);
-            dma_issue(tile_off, c.rows, nt, lane, id);
+            dma_issue(tile_off, c.rows, lane, id);
         };
         // ---- fold chunk j's staged rows into the registers, row by row -------------------------------------------
         // Y [row][position], the two 32-position halves of a 64-position group swapped when (row >> 2) & 1 (the consumers'
@@ -614,7 +491,7 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             return FoldPlan{n0, n1, ra, cnt};
         };
         auto fold_rows = [&](int j, const FoldPlan& fp, int lane) __attribute__((always_inline)) {
-            const unsigned Y = lds0 + (YT ? Y_OFF : P1_OFF + (unsigned)(j & 1) * TILE);
+            const unsigned Y = lds0 + (P1_OFF + (unsigned)(j & 1) * TILE);
             const int ra = fp.ra, cnt = fp.cnt;
             const unsigned zrow = lds0 + ZERO_OFF + (unsigned)(PL * 4 * lane), lb = (unsigned)(PL * 4 * lane);
             typedef typename std::conditional<D == 128, f32x2, float>::type yv_t;
@@ -651,7 +528,7 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
 #define BX_ROW128(i) "s_set_gpr_idx_idx %[i" #i "]\n\tv_pk_add_f32 v[64:65], %[y" #i "], v[64:65]\n\t"
 #define BX_ROW64(i) "s_set_gpr_idx_idx %[i" #i "]\n\tv_add_f32 v64, %[y" #i "], v64\n\t"
 #define BX_ROW_OPS [i0] "s"(ix[0]), [i1] "s"(ix[1]), [i2] "s"(ix[2]), [i3] "s"(ix[3]), [y0] "v"(y[0]), [y1] "v"(y[1]), [y2] "v"(y[2]), [y3] "v"(y[3])
-                // BX_IDX_WAIT: wait states behind BOTH mode switches.  Measured (round 4, tools/hazard_r4*.sh): without them behind
+                // BX_IDX_WAIT: wait states behind BOTH mode switches.  Measured (round 4): without them behind
                 // s_set_gpr_idx_on the first add of a block went wrong a few times per launch at four waves per SIMD (hidden 64,
                 // two workgroups per CU) — see the kernel header, "The indexing mode's switch".
                 if constexpr (D == 128)
@@ -729,18 +606,14 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
         __builtin_amdgcn_s_barrier();                      // barrier A: descriptors 0 and 1 visible to all helper waves
         // (raw barriers in this role: __syncthreads() drains every LDS-DMA in flight — vmcnt(0) — before it)
         if (nchunks > 0) {
-            if (!(skip & 1)) dma_tile(P0_OFF, 0, P0_IDS, ch[0], P0_NT, lane);
-            if (!(skip & 2)) dma_tile(P1_OFF, 0, 3, ch[0], false, lane);
+            if (!(skip & 1)) dma_tile(P0_OFF, 0, P0_IDS, ch[0], lane);
+            if (!(skip & 2)) dma_tile(P1_OFF, 0, 3, ch[0], lane);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (GHF_BX_LATE && lane == 0) lds_st_b32(lds0 + FLAG_OFF + 32 + 4 * hw, 1);   // chunk 0's destination rows are in
         }
-        // DMA instructions per tile and helper wave (constant: dma_tile) — what the counted waits below leave in flight
-        constexpr int N_SRC = (skip & 1) ? 0 : RBW * NPL, N_DST = ((skip & 2) || YT) ? 0 : RBW * NPL;
         int sid[6] = {0, 0, 0, 0, 0, 0};                     // source ids of the NEXT chunk's rows (read at the end of a chunk)
         if (nchunks > 0 && !(skip & 1)) dma_ids(1, P0_IDS, lane, sid);
         for (int k = 0; k < nchunks; ++k) {
             __builtin_amdgcn_s_barrier();                  // ---- chunk k
-            BX_STAMP(0);
             const int l0 = opaque_lane(lane);
             if (k > 0) {                                   // everything requested during the last chunk has arrived
                 wdP = wdN;
@@ -751,23 +624,11 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
                 ch[4] = decode(d5);
                 asm volatile("" : "+v"(wdP.src), "+v"(wdP.key), "+v"(scP.u), "+v"(scP.v), "+v"(wdN.src), "+v"(wdN.key));
             }
-            if (!(GHF_BXEXP & 64)) publish(k + 2, ch[2], wdP, scP, l0);
-            BX_STAMP(4);
-            if (!(skip & 1)) dma_issue(P0_OFF + ((k + 1) & 1) * TILE, ch[1].rows, P0_NT, l0, sid);
-            if (YT && !(skip & 2)) dma_tile(P1_OFF + ((k + 1) & 1) * TILE, k + 1, 3, ch[1], false, l0);
-            if (GHF_BX_LATE && N_DST > 0) {
-                // chunk k's destination rows (requested at the end of chunk k-1) have landed once only the source-row DMAs
-                // just issued are in flight: tell the consumers, who need that tile for phase 1 only
-                if (k > 0) {
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_SRC) : "memory");
-                    if (lane == 0) lds_st_b32(lds0 + FLAG_OFF + 32 + 4 * hw, k + 1);
-                }
-            }
-            BX_STAMP(1);
-            if (k > 0 && !(GHF_BXEXP & 8)) {
+            publish(k + 2, ch[2], wdP, scP, l0);
+            if (!(skip & 1)) dma_issue(P0_OFF + ((k + 1) & 1) * TILE, ch[1].rows, l0, sid);
+            if (k > 0) {
                 const FoldPlan fp = fold_plan(k - 1, prev_rows, l0);
                 if (DEFER) wait_flags(lds0 + FLAG_OFF + 16, k);   // all four consumer waves have staged Y(k-1)
-                BX_STAMP(5);                               // (stamps: the wait for the staged rows)
                 fold_rows(k - 1, fp, l0);
             }
             BX_LGKM0();
@@ -775,41 +636,30 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             // the destination ids of chunk k+1's rows (its tile's DMA): one round trip taken while the other helper waves catch up
             int did[6];
             if (!(skip & 2)) dma_ids(k + 1, 3, opaque_lane(lane), did);
-            BX_STAMP(2);
-            // without a tile of their own the staged rows sit where the next destination rows go: every helper wave must have
-            // folded them first
+            // the staged rows sit where the next destination rows go: every helper wave must have folded them first
             wait_flags(lds0 + FLAG_OFF, k + 1);
-            BX_STAMP(3);
             const int l1 = opaque_lane(lane);
             // the next requests of the descriptor pipeline: behind the loops above (a load in flight across a loop makes hipcc
             // wait for everything — the source-row DMA included — at the loop), ahead of the rest of the chunk (requested
             // at its end they were waited for right behind the next barrier)
-            if (!(GHF_BXEXP & 64)) {
-                scN = load_scales(ch[3], wdN);
-                wdL = load_words(ch[4], l1);
-            }
+            scN = load_scales(ch[3], wdN);
+            wdL = load_words(ch[4], l1);
             d5 = load_desc(k + 5);
-            if (!YT && !(skip & 2)) dma_issue(P1_OFF + ((k + 1) & 1) * TILE, ch[1].rows, false, l1, did);
-            BX_STAMP(1);
+            if (!(skip & 2)) dma_issue(P1_OFF + ((k + 1) & 1) * TILE, ch[1].rows, l1, did);
             prev_rows = ch[0].rows;
             if (!(skip & 1)) dma_ids(k + 2, P0_IDS, l1, sid);     // (published at this chunk's start by every helper wave; all are past their flag)
-            // the source rows of chunk k+1 (requested at this chunk's start) must be in before the barrier; GHF_BX_LATE: the
-            // destination-row DMAs issued last stay in flight across it
-            // (counted in DMA instructions only — one per builtin; the descriptor loads before them are waited for as well:
-            // how many instructions the compiler makes of those is not this code's to assume)
-            if (GHF_BX_LATE && N_DST > 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N_DST) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            // both tiles of chunk k+1 (the source rows requested at this chunk's start, the destination rows just now) must be
+            // in before the barrier
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             BX_LGKM0();
-            BX_STAMP(4);
         }
         __builtin_amdgcn_s_barrier();                      // ---- epilogue: the last chunk's rows
-        if (nchunks > 0 && !(GHF_BXEXP & 8)) {
+        if (nchunks > 0) {
             const int le = opaque_lane(lane);
             fold_rows(nchunks - 1, fold_plan(nchunks - 1, prev_rows, le), le);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no DMA may still be landing when the tiles are reused below
         BX_LGKM0();
-        BX_STAMP(5);
         if constexpr (D == 128) asm volatile("" : BX_PIN_128(sm)); else asm volatile("" : BX_PIN_64(sm));
         // dump row HPW*hw + i = node NPW*hw + HPW*half + i, natural column order: position PL*lane + e is column
         // 32 (lane / 16) + 16 e + lane % 16 at d = 128 (a consumer wave's two fragments, interleaved), column lane at d = 64
@@ -830,21 +680,17 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
         BX_LGKM0();
         __syncthreads();
         tail_half(0, std::integral_constant<int, 1>{});              // (the other half of the sums is still in registers)
-        BX_STAMP(6);
         __syncthreads();
         dump_half(std::integral_constant<int, 1>{});
         BX_LGKM0();
         __syncthreads();
-        tail_half(1, std::integral_constant<int, GHF_BX_TGB>{});
-        BX_STAMP(7);
-        BX_STAMP_FLUSH();
+        tail_half(1, std::integral_constant<int, BX_TGB>{});
     } else {
         // =============================================== CONSUMERS ===============================================
         // B fragments (GHF_WLAYOUT_SPLIT2H): Wh[r][o/16][kk/32][piece][lane][8] fp16, then one float 2^-s per relation
         const uint32_t wsc_off = (uint32_t)((uint64_t)R * 2 * D * D * (NPL * 2));
         const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)Wsplit, 0, (int)wsc_off, 0x00020000);
         auto b_soff = [&](int r, int ph, int t) -> int {
-            if (GHF_BXEXP & 128) r = 0;                    // (timing experiment: one relation's weights, always hot in L2)
             return __builtin_amdgcn_readfirstlane((((r * NT + tw * NTW + t) * NKS + ph * KS) * NPL) * 1024);
         };
         const int lane16 = lane * 16;
@@ -854,7 +700,7 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             for (int t = 0; t < NTW; ++t)
 #pragma unroll
                 for (int pl = 0; pl < NPL; ++pl)
-                    b[j][t][pl] = __builtin_amdgcn_raw_buffer_load_b128(rsW, lane16 + pl * 1024, b_soff(r, ph, t) + j * (NPL * 1024), GHF_B_AUX);
+                    b[j][t][pl] = __builtin_amdgcn_raw_buffer_load_b128(rsW, lane16 + pl * 1024, b_soff(r, ph, t) + j * (NPL * 1024), 0);
         };
         f32x4 acc[MTC][NTW];
         const int arow = c16 * ROWB;
@@ -862,7 +708,7 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
         // (a uniform branch per (k-step, tile) position cost the MFMA stream a fetch bubble each)
         // (always_inline: with two call sites and little work per instance — d = 64 — hipcc otherwise makes the stage a real
         // function, called through s_swappc with its captures in scratch: 10x the time)
-        constexpr int AD = GHF_BX_AD;
+        constexpr int AD = BX_AD;
         static_assert(AD <= MTC - 2, "the prefetched positions are row tiles 0 .. AD-1 of the first k-step in every instance");
         i32x4 apre[AD][NPL];                               // the fragments of a stage's first AD positions, requested ahead of the stage
         auto lda_from = [&](const char* Abuf, int j, int m, i32x4 (&dst)[NPL]) __attribute__((always_inline)) {
@@ -875,7 +721,7 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             for (int p = 0; p < AD; ++p) lda_from(Abuf, 0, p, apre[p]);
         };
         auto compute_stage = [&](auto mt_c, auto pre_c, int ph, bool first, const char* Abuf, const int* meta, float wscale, int r_next, int ph_next,
-                                 const float (&bias_v)[NTW], auto&& between, auto&& after_k) __attribute__((always_inline)) {
+                                 const float (&bias_v)[NTW], auto&& after_k) __attribute__((always_inline)) {
             constexpr int MT = decltype(mt_c)::value;
             constexpr bool PRE = decltype(pre_c)::value;
             f32x4 part[MTC][NTW];
@@ -885,7 +731,7 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
                 for (int t = 0; t < NTW; ++t) part[m][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
             f32x4 sc[MTC];                                  // the rows' scales: read during the last k-step (short live range)
             // A fragments of (k-step, tile) positions p .. p + AD: with the helpers' DMA writes and fold reads on the LDS a read
-            // takes ~250 cycles, a position's six MFMAs 96 (tools/stamps_bx.py: two positions ahead left the stage
+            // takes ~250 cycles, a position's six MFMAs 96 (round 2's stamps: two positions ahead left the stage
             // latency-bound)
             i32x4 a[AD + 1][NPL];
             auto lda = [&](int j, int m, i32x4 (&dst)[NPL]) { lda_from(Abuf, j, m, dst); };
@@ -898,7 +744,6 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
                     lda(p / MT, p % MT, a[p]);
                 }
             }
-            BX_STAMP(4);
 #pragma unroll
             for (int j = 0; j < KS; ++j) {
                 if (j == KS - 1) {
@@ -909,32 +754,20 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
                 for (int m = 0; m < MT; ++m) {
                     const int p = j * MT + m, cur = p % (AD + 1);
                     if (p + AD < KS * MT) lda((p + AD) / MT, (p + AD) % MT, a[(p + AD) % (AD + 1)]);
-                    if (GHF_BXEXP & 4) {                                    // operands stay alive (no DCE of the loads)
 #pragma unroll
-                        for (int pl = 0; pl < NPL; ++pl) asm volatile("" ::"v"(a[cur][pl]));
-#pragma unroll
-                        for (int t = 0; t < NTW; ++t)
-#pragma unroll
-                            for (int pl = 0; pl < NPL; ++pl) asm volatile("" ::"v"(b[j][t][pl]));
-                    } else {
-#pragma unroll
-                        for (int t = 0; t < NTW; ++t) {
-                            auto fma = [&](int pa, int pb) {
-                                part[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a[cur][pa]),
-                                                                                    __builtin_bit_cast(f16x8, b[j][t][pb]),
-                                                                                    part[m][t], 0, 0, 0);
-                            };
-                            fma(1, 0); fma(0, 1);                               // lo*hi, hi*lo
-                            fma(0, 0);                                          // hi*hi
-                        }
+                    for (int t = 0; t < NTW; ++t) {
+                        auto fma = [&](int pa, int pb) {
+                            part[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a[cur][pa]),
+                                                                                __builtin_bit_cast(f16x8, b[j][t][pb]),
+                                                                                part[m][t], 0, 0, 0);
+                        };
+                        fma(1, 0); fma(0, 1);                               // lo*hi, hi*lo
+                        fma(0, 0);                                          // hi*hi
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                BX_STAMP(5);
-                between(j);
-                if (!(GHF_BXEXP & 1)) load_b_step(r_next, ph_next, j);
+                load_b_step(r_next, ph_next, j);
                 __builtin_amdgcn_sched_barrier(0);
-                BX_STAMP(7);
             }
             after_k();                                      // (hook: the next stage's first fragments, requested before the unscale)
 #pragma unroll
@@ -953,13 +786,13 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
                 for (int t = 0; t < NTW; ++t) acc[m][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
         };
         auto stage_for = [&](int mt, auto pre_c, int ph, bool first, const char* Abuf, const int* meta, float wscale, int r_next, int ph_next,
-                             const float (&bias_v)[NTW], auto&& between, auto&& after_k) __attribute__((always_inline)) {
+                             const float (&bias_v)[NTW], auto&& after_k) __attribute__((always_inline)) {
             // three instances: all tiles, one fewer, two fewer (shorter chunks — 7 % at C3 — run the last one: their dead
             // tiles cost MFMAs on stale rows that are never written)
             static_assert(MTC >= 3, "three compute_stage instances");
-            if (mt >= MTC) compute_stage(std::integral_constant<int, MTC>{}, pre_c, ph, first, Abuf, meta, wscale, r_next, ph_next, bias_v, between, after_k);
-            else if (mt == MTC - 1) compute_stage(std::integral_constant<int, MTC - 1>{}, pre_c, ph, first, Abuf, meta, wscale, r_next, ph_next, bias_v, between, after_k);
-            else compute_stage(std::integral_constant<int, MTC - 2>{}, pre_c, ph, first, Abuf, meta, wscale, r_next, ph_next, bias_v, between, after_k);
+            if (mt >= MTC) compute_stage(std::integral_constant<int, MTC>{}, pre_c, ph, first, Abuf, meta, wscale, r_next, ph_next, bias_v, after_k);
+            else if (mt == MTC - 1) compute_stage(std::integral_constant<int, MTC - 1>{}, pre_c, ph, first, Abuf, meta, wscale, r_next, ph_next, bias_v, after_k);
+            else compute_stage(std::integral_constant<int, MTC - 2>{}, pre_c, ph, first, Abuf, meta, wscale, r_next, ph_next, bias_v, after_k);
         };
         // a chunk's finished rows -> Y: lane (q, c16) holds rows 16m + 4q + s, positions 32tw + 2c16 + t (t = 0, 1) — with one
         // fragment per wave (d = 64), position 16tw + c16
@@ -982,25 +815,6 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             }
         };
 
-        // the same rows, slice j of KS (row tiles m = j, j + KS, ...; every tile, live or not: no branch — the helpers read the
-        // chunk's rows only)
-        auto write_rows_slice = [&](int j, unsigned ytile) __attribute__((always_inline)) {
-            const unsigned ybase = lds0 + ytile + yoff;
-#pragma unroll
-            for (int m = 0; m < MTC; ++m) {
-                if (m % KS != j) continue;
-                if (16 * m + 16 > CR && 16 * m + 4 * q >= CR) continue;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    if constexpr (NTW == 2)
-                        asm volatile("ds_write_b64 %0, %1 offset:%2" ::"v"(ybase), "v"((f32x2){acc[m][0][s], acc[m][NTW - 1][s]}),
-                                     "n"((16 * m + s) * (D * 4)) : "memory");
-                    else
-                        asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(ybase), "v"(acc[m][0][s]), "n"((16 * m + s) * (D * 4)) : "memory");
-                }
-            }
-        };
-        auto nothing = [](int) {};
         const int ph_first = (skip & 1) ? 1 : P0_HALF;      // the weights' half of a chunk's first live phase
         BxChunk ch{0, 0, 1};
         i32x2 dn{0, 0};
@@ -1011,7 +825,6 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             for (int t = 0; t < NTW; ++t) bv[t] = *bx_at<float>(bias, (uint32_t)(r * D + (tw * NTW + t) * 16 + c16) * 4u);
         };
         int mt_prev = 0;
-        static_assert(!(DEFER && YT), "GHF_BX_DEFER stages into the aliased tile");
         if (nchunks > 0) {
             ch = decode(load_desc(0));
             dn = load_desc(1);
@@ -1024,29 +837,22 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             const int mt = (ch.rows + 15) >> 4;
             const int* meta = (const int*)(smem + meta_off(k));
             __syncthreads();                               // ---- chunk k
-            BX_STAMP(0);
-            #ifndef GHF_BX_PRE0
-#define GHF_BX_PRE0 0          // 1: the first phase's first fragments requested right behind the barrier (round 4, LATE off: 2.86 vs 2.83 ms — not kept)
-#endif
-            constexpr bool PRE_OK = skip == 0 && !YT && (GHF_BX_LATE || GHF_BX_PRE0);     // (the source-row tile has landed before the barrier either way)
-            constexpr bool PRE0 = PRE_OK, PRE1 = false;        // first / second phase (the second phase's ahead of the unscale: 44 spilled registers)
-            using pre0_t = std::integral_constant<bool, PRE0>;
-            using pre1_t = std::integral_constant<bool, PRE1>;
-            if (PRE0) prefetch_a(smem + P0_OFF + (k & 1) * TILE);      // (chunk k's source rows landed before the barrier)
-            // GHF_BX_DEFER: the previous chunk's rows go to their staging tile (that chunk's destination-row tile) only now:
-            // behind the barrier every consumer wave is through with that tile, so there is no hand-shake among the consumers,
-            // and the accumulators are not needed before this chunk's first phase ends.  The helpers wait for the flag.
-            constexpr bool ILV = false;                         // (staging writes between the k-steps: measured slower, round 3)
-            if (DEFER && k > 0 && !ILV) {
-                if (!(GHF_BXEXP & 16)) write_rows(mt_prev, P1_OFF + ((k - 1) & 1) * TILE);
+            // DEFER: the previous chunk's rows go to their staging tile (that chunk's destination-row tile) only now: behind
+            // the barrier every consumer wave is through with that tile, so there is no hand-shake among the consumers, and
+            // the accumulators are not needed before this chunk's first phase ends.  The helpers wait for the flag.
+            // (Staging writes between the k-steps were measured slower: round 3.)
+            if (DEFER && k > 0) {
+                write_rows(mt_prev, P1_OFF + ((k - 1) & 1) * TILE);
                 BX_LGKM0();
                 if (lane == 0) lds_st_b32(lds0 + FLAG_OFF + 16 + 4 * tw, k);
-                BX_STAMP(3);
             }
             const BxChunk nx = decode(dn);
             // (a half whose weights the caller declared zero is not computed: the next live stage's weights are prefetched)
-            // behind the first phase's k-steps: this chunk's destination rows have landed (helpers' flags) -> the second phase's
-            // first fragments are requested before the first phase's unscale
+            // The stages' prefetch hooks are compiled out (pre_c false, PRE1 false: the second phase's first fragments requested
+            // ahead of the first phase's unscale spilled 44 registers; the first phase's behind the barrier measured no faster,
+            // round 4).  They stay because hipcc lays the whole kernel out differently without them — the schedule rewrite
+            // takes them out with the rest.
+            constexpr bool PRE1 = false;
             auto wait_landed = [&]() __attribute__((always_inline)) {
                 for (;;) {
                     i32x4 f;
@@ -1063,40 +869,24 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
                 }
             };
             auto no_after = []() {};
-            if (!(skip & 1)) {
-                if (ILV && k > 0) {
-                    const unsigned ytile = P1_OFF + ((k - 1) & 1) * TILE;
-                    stage_for(mt, pre0_t{}, P0_HALF, true, smem + P0_OFF + (k & 1) * TILE, meta, wscale, (skip & 2) ? nx.r : ch.r, (skip & 2) ? P0_HALF : 1, bias_v,
-                              [&](int j) __attribute__((always_inline)) { write_rows_slice(j, ytile); }, next_pre);
-                } else {
-                    stage_for(mt, pre0_t{}, P0_HALF, true, smem + P0_OFF + (k & 1) * TILE, meta, wscale, (skip & 2) ? nx.r : ch.r, (skip & 2) ? P0_HALF : 1, bias_v, nothing, next_pre);
-                }
-            }
-            if (ILV && k > 0) {                            // (the stage's unscale has not touched acc's OLD values before this point:
-                BX_LGKM0();                                //  compute_stage writes acc after its k-steps — the writes above read it before)
-                if (lane == 0) lds_st_b32(lds0 + FLAG_OFF + 16 + 4 * tw, k);
-            }
-            BX_STAMP(1);
+            if (!(skip & 1))
+                stage_for(mt, std::false_type{}, P0_HALF, true, smem + P0_OFF + (k & 1) * TILE, meta, wscale, (skip & 2) ? nx.r : ch.r, (skip & 2) ? P0_HALF : 1, bias_v, next_pre);
             dn = load_desc(k + 2);
             load_rel_words(nx.r, wscale_n, bias_n);
-            if (GHF_BX_LATE && !(skip & 2) && !YT && !PRE1) wait_landed();   // the destination-row tile of this chunk has landed (helpers' flags)
             if (skip & 1) {                                // no source phase ran: the destination phase adds to the bias
 #pragma unroll
                 for (int m = 0; m < MTC; ++m)
 #pragma unroll
                     for (int t = 0; t < NTW; ++t) acc[m][t] = (f32x4){bias_v[t], bias_v[t], bias_v[t], bias_v[t]};
             }
-            if (!(skip & 2)) stage_for(mt, pre1_t{}, 1, false, smem + P1_OFF + (k & 1) * TILE, meta, wscale, nx.r, ph_first, bias_v, nothing, no_after);
-            BX_STAMP(2);
-            // YT: the staging tile is free once every helper wave has folded the previous chunk's rows (flag = k + 1, set during
-            // this chunk); else the chunk's rows overwrite its destination-row tile once every consumer wave has read it
-            // the last chunk (and every chunk without GHF_BX_DEFER) stages its rows here, once all four consumer waves have read
-            // the tile they overwrite (flag words; YT: once every helper wave has folded the previous chunk's rows)
+            if (!(skip & 2)) stage_for(mt, std::false_type{}, 1, false, smem + P1_OFF + (k & 1) * TILE, meta, wscale, nx.r, ph_first, bias_v, no_after);
+            // the last chunk (and every chunk without DEFER) stages its rows here: they overwrite the chunk's destination-row tile
+            // once all four consumer waves have read it (flag words)
             const bool stage_now = !DEFER || k + 1 == nchunks;
             if (stage_now) {
-                const unsigned fw = DEFER ? FLAG_OFF + 48 : FLAG_OFF + (YT ? 0 : 16);      // (DEFER: words of their own)
+                const unsigned fw = DEFER ? FLAG_OFF + 48 : FLAG_OFF + 16;      // (DEFER: words of their own)
                 const int fv = DEFER ? 1 : k + 1;
-                if (!YT && lane == 0) lds_st_b32(lds0 + (DEFER ? FLAG_OFF + 48 : FLAG_OFF + 16) + 4 * tw, fv);
+                if (lane == 0) lds_st_b32(lds0 + fw + 4 * tw, fv);
                 for (;;) {
                     i32x4 f;
                     asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(f) : "v"(lds0 + fw) : "memory");
@@ -1104,30 +894,21 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
                     if (__builtin_amdgcn_readfirstlane(lo) >= fv) break;
                     __builtin_amdgcn_s_sleep(1);
                 }
-                if (!(GHF_BXEXP & 16)) write_rows(mt, YT ? Y_OFF : P1_OFF + (k & 1) * TILE);
+                write_rows(mt, P1_OFF + (k & 1) * TILE);
             }
-            if (GHF_BXEXP & 16)
-#pragma unroll
-                for (int m = 0; m < MTC; ++m)
-#pragma unroll
-                    for (int t = 0; t < NTW; ++t) asm volatile("" ::"v"(acc[m][t]));
             mt_prev = mt;
             ch = nx;
             wscale = wscale_n;
 #pragma unroll
             for (int t = 0; t < NTW; ++t) bias_v[t] = bias_n[t];
             BX_LGKM0();
-            BX_STAMP(3);
         }
         __syncthreads();                                   // epilogue stage
         for (int half = 0; half < 2; ++half) {
             __syncthreads();
             __syncthreads();
-            tail_half(half, std::integral_constant<int, GHF_BX_TGB>{});
-            if (half == 0) BX_STAMP(6);
+            tail_half(half, std::integral_constant<int, BX_TGB>{});
         }
-        BX_STAMP(6);
-        BX_STAMP_FLUSH();
     }
 }
 
@@ -1226,12 +1007,3 @@ int launch_message_bx(const MsgArgs& a, hipStream_t stream) {
 }
 
 }  // namespace ghf
-
-#ifdef GHF_STAMPS
-extern "C" int ghf_debug_read_stamps_bx(unsigned long long* host, size_t count) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(ghf::ghf_bx_stamp_buf), count * sizeof(unsigned long long));
-}
-extern "C" int ghf_debug_read_life_bx(unsigned long long* host, size_t count) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(ghf::ghf_bx_life_buf), count * sizeof(unsigned long long));
-}
-#endif

@@ -30,7 +30,6 @@
 // and a team scatters its chunks in order, so the sums stay bitwise reproducible.
 #include "common.h"
 
-#include <stdlib.h>
 #include <type_traits>
 
 namespace ghf {
@@ -50,24 +49,6 @@ template <class T>
 __device__ __forceinline__ const T* at(const void* base, uint32_t byte_off) {
     return (const T*)((const char*)base + byte_off);
 }
-
-// Diagnostic build only (-DGHF_STAMPS): per-wave s_memtime totals
-#ifdef GHF_STAMPS
-__device__ unsigned long long ghf_pp_stamp_buf[8192 * 8 * 8];
-#define PP_STAMP_DECL unsigned long long st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, st_last = 0
-#define PP_STAMP(i)                                                                            \
-    do {                                                                                       \
-        unsigned long long _t;                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t)::"memory");             \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
-        if ((i) >= 0) st_acc[(i) < 0 ? 0 : (i)] += _t - st_last;                               \
-        st_last = _t;                                                                          \
-    } while (0)
-#else
-#define PP_STAMP_DECL
-#define PP_STAMP(i)
-#endif
 
 template <int D> struct PpCfg;
 template <> struct PpCfg<128> { static constexpr int BN = 216, MTC = 3, WAVES_PER_SIMD = 2; };   // 162 KB LDS: 1 workgroup/CU
@@ -120,7 +101,6 @@ __global__ __launch_bounds__(512, PpCfg<D>::WAVES_PER_SIMD) void message_pp_kern
     for (int i = tid; i < (BN + 4) * D / 4; i += NWV * 64) ((f32x4*)acc_lds)[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int i = tid; i < 2 * CR; i += NWV * 64) s_meta[i] = ((BN + ((i >> 2) & 3)) * (D * 4)) | (i & 15);
 
-    PP_STAMP_DECL;
     int vzero;
     asm volatile("v_mov_b32 %0, 0" : "=v"(vzero));    // opaque 0: keeps the descriptor loads on the vector path
     const int c_begin = __builtin_amdgcn_readfirstlane(item[1]);
@@ -167,7 +147,6 @@ __global__ __launch_bounds__(512, PpCfg<D>::WAVES_PER_SIMD) void message_pp_kern
         int v[IPW];
 #pragma unroll
         for (int i = 0; i < IPW; ++i) v[i] = __shfl(word, (tw * IPW + i) * RPI + lane / CPR, 64);
-        PP_STAMP(5);                                    // prep: row words + shuffles
         const uint32_t nbase = ph == 0 ? 0u : (uint32_t)node0 - kbase;
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
@@ -175,7 +154,6 @@ __global__ __launch_bounds__(512, PpCfg<D>::WAVES_PER_SIMD) void message_pp_kern
             const uint32_t node = (ph == 0 ? (uint32_t)(v[i] & SRC_MASK) : (uint32_t)v[i]) + nbase;
             stg[i] = *at<f32x4>(h, node * (uint32_t)(D * 4) + (uint32_t)(((lane % CPR) ^ (rho & 15)) << 4));
         }
-        PP_STAMP(7);                                    // prep: gather issue
     };
     auto stage_commit = [&]() {
 #pragma unroll
@@ -321,7 +299,6 @@ __global__ __launch_bounds__(512, PpCfg<D>::WAVES_PER_SIMD) void message_pp_kern
             d_next = load_desc(kc + 2);
         }
         asm volatile("" ::: "memory");
-        PP_STAMP(2);                                    // prep: issue
         if (pend) {                                    // consumes registers and LDS only: nothing just requested
             i32x4 mq[MTC];
             load_row_words(mq);
@@ -331,11 +308,9 @@ __global__ __launch_bounds__(512, PpCfg<D>::WAVES_PER_SIMD) void message_pp_kern
             for (int t = 0; t < NTW; ++t) x2[MTC - 1][t] = acc[MTC - 1][t];
             deferred = pend == MTC;                    // a dead last tile carries zeros into dummy rows: skip it
         }
-        PP_STAMP(3);                                    // prep: scatter
         if (staged) stage_commit();
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_s_waitcnt(PP_WAIT_VMCNT0);     // everything landed before the barrier that hands it over
-        PP_STAMP(4);                                    // prep: wait for memory + LDS commit
     };
     // PREP before a phase-1 MFMA interval
     auto prep_ph1 = [&]() {
@@ -346,19 +321,15 @@ __global__ __launch_bounds__(512, PpCfg<D>::WAVES_PER_SIMD) void message_pp_kern
             ch_next = decode(d_next, kc + 2);          // loaded one PREP ago
             if (ch_next.rows) wd_next = load_words(ch_next);
         }
-        PP_STAMP(2);
         if (deferred) {
             scatter_tiles(std::integral_constant<int, MTC - 1>{}, std::integral_constant<int, MTC>{}, x2, mq2);
             deferred = 0;
         }
-        PP_STAMP(3);
         if (staged) stage_commit();
         __builtin_amdgcn_s_setprio(0);
         __builtin_amdgcn_s_waitcnt(PP_WAIT_VMCNT0);
-        PP_STAMP(4);
     };
     auto mfma_phase = [&](int ph) {
-        PP_STAMP(0);                                    // barrier wait
         if (!ch.rows) return;
         const int mt = (ch.rows + 15) >> 4;
         if (ph == 0) {
@@ -381,7 +352,6 @@ __global__ __launch_bounds__(512, PpCfg<D>::WAVES_PER_SIMD) void message_pp_kern
         // PREP, no MFMA stream to compete with); they land during my own PREP, which ends with vmcnt(0)
         if (ph == 0) load_b_head(ch.r, 1, b);
         else if (ch_next.rows) load_b_head(ch_next.r, 0, b);
-        PP_STAMP(1);                                    // mfma interval
     };
 
     if (ch.rows) {
@@ -389,7 +359,6 @@ __global__ __launch_bounds__(512, PpCfg<D>::WAVES_PER_SIMD) void message_pp_kern
         load_b_head(ch.r, 0, b);
     }
     __syncthreads();                                   // sums zeroed, row words initialised
-    PP_STAMP(-1);
 
     // Two static programs, one per team, offset by one barrier interval; both execute 4*iters + 1 barriers.
     //   interval:   4i        4i+1      4i+2      4i+3
@@ -400,15 +369,15 @@ __global__ __launch_bounds__(512, PpCfg<D>::WAVES_PER_SIMD) void message_pp_kern
         prep_ph0();
         for (int it = 0; it < iters; ++it) {
             __syncthreads();  mfma_phase(0);
-            __syncthreads();  PP_STAMP(0); prep_ph1();
+            __syncthreads(); prep_ph1();
             __syncthreads();  mfma_phase(1);
-            __syncthreads();  PP_STAMP(0); prep_ph0();
+            __syncthreads(); prep_ph0();
         }
     } else {
         for (int it = 0; it < iters; ++it) {
-            __syncthreads();  PP_STAMP(0); prep_ph0();
+            __syncthreads(); prep_ph0();
             __syncthreads();  mfma_phase(0);
-            __syncthreads();  PP_STAMP(0); prep_ph1();
+            __syncthreads(); prep_ph1();
             __syncthreads();  mfma_phase(1);
         }
     }
@@ -484,11 +453,6 @@ __global__ __launch_bounds__(512, PpCfg<D>::WAVES_PER_SIMD) void message_pp_kern
             }
         }
     }
-#ifdef GHF_STAMPS
-    PP_STAMP(6);                                        // drain + tail
-    if (lane == 0 && blockIdx.x < 8192)
-        for (int i = 0; i < 8; ++i) ghf_pp_stamp_buf[((size_t)blockIdx.x * 8 + w) * 8 + i] = st_acc[i];
-#endif
 }
 
 template <int D>
@@ -534,9 +498,3 @@ int launch_message_pp(const MsgArgs& a, hipStream_t stream) {
 }
 
 }  // namespace ghf
-
-#ifdef GHF_STAMPS
-extern "C" int ghf_debug_read_stamps_pp(unsigned long long* host, size_t count) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(ghf::ghf_pp_stamp_buf), count * sizeof(unsigned long long));
-}
-#endif

@@ -18,7 +18,6 @@
 // same k-permutation on both operands).
 #include "common.h"
 
-#include <stdlib.h>
 #include <type_traits>
 
 namespace ghf {
@@ -127,6 +126,8 @@ __global__ __launch_bounds__(256) void edge_transform_kernel(
 // buffered.  fp32 MFMA: 64 MFMAs x 32 cycles per 16 k; here 48 x 16 cycles per 32 k — 5.3 x less matrix time.
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+// Launched as <32, 1> only (d % 256 != 0; d % 256 == 0 runs edge_transform_h3_kernel below); <64, 1> and <32, 2> were
+// measured and retired (DESIGN_HISTORY.md).
 // KH = k per step: 32 (64-byte pieces of a row per visit; two workgroups per CU) or, for d % 256 == 0, 64 (whole 128-byte
 // lines, a half-row in four visits instead of eight; 129 KB of LDS, one workgroup per CU, the 16-byte granules of a row
 // XOR-swizzled by row & 7 so that a fragment read of 16 rows covers all banks).
@@ -134,9 +135,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // times 256 columns — waves 0-3 the first 128 columns, waves 4-7 the next, all eight reading the one A tile in LDS — so the
 // tile's rows are gathered once per 256 columns instead of once per 128: at d = 256 every gathered row is fetched once, not
 // twice (BASELINE config 5: 91 GB of 205 GB per layer were pass 1's fetches, profiles/r02_c5_kernel_pmc.json).
-#ifndef GHF_RSEXP
-#define GHF_RSEXP 0          // timing-only ablations of pass 1 (wrong results): 1 no MFMAs, 2 no global fetches, 4 no commits to LDS, 8 no fragment reads, 16 every gathered row one of 64 (L2-resident), 32 no barrier per step, 64 no result rows written
-#endif
 template <int KH, int NCT>
 __global__ __launch_bounds__(256 * NCT, KH == 32 ? 2 : 1) void edge_transform_h_kernel(
     const char* __restrict__ h_split, int64_t N, int d, const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
@@ -191,7 +189,6 @@ __global__ __launch_bounds__(256 * NCT, KH == 32 ? 2 : 1) void edge_transform_h_
     struct Stage { i32x4 a[2][GPA], b[2][GPT]; };          // [piece][i]
     Stage st[4];
     auto fetch = [&](int k0, Stage& S) {                   // k0: first contraction index of the step, in [0, 2d)
-        if ((GHF_RSEXP & 2) && k0 > 2 * RS_KH) return;
         const int half = k0 >= d;
         const int kk = half ? k0 - d : k0;
         const char* arow = half ? h_split + (size_t)sv * hrow : urow;
@@ -205,7 +202,6 @@ __global__ __launch_bounds__(256 * NCT, KH == 32 ? 2 : 1) void edge_transform_h_
         }
     };
     auto commit = [&](int buf, const Stage& S) {
-        if ((GHF_RSEXP & 4) && buf >= 0) { asm volatile("" :: "v"(S.a[0][0]), "v"(S.b[0][0]), "v"(S.a[1][0]), "v"(S.b[1][0])); return; }
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
 #pragma unroll
@@ -262,7 +258,6 @@ __global__ __launch_bounds__(256 * NCT, KH == 32 ? 2 : 1) void edge_transform_h_
                             // consecutive columns of ONE row — 16-byte stores of the results (one column of four rows:
                             // 4-byte stores, four times the store instructions)
                             auto fma = [&](int pa, int pb) {
-                                if (GHF_RSEXP & 1) { asm volatile("" :: "v"(b[c4][pb]), "v"(a[rt][pa])); return; }
                                 acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, b[c4][pb]),
                                                                                      __builtin_bit_cast(f16x8, a[rt][pa]), acc[rt][ct], 0, 0, 0);
                             };
@@ -312,17 +307,17 @@ __global__ __launch_bounds__(256 * NCT, KH == 32 ? 2 : 1) void edge_transform_h_
                 f32x4 o;
 #pragma unroll
                 for (int s = 0; s < 4; ++s) o[s] = fmaf(acc[rt][ct][s], fv, bv[ct][s] * n);
-                if (!(GHF_RSEXP & 64) || o[0] == 123.456f) *(f32x4*)(y + 16 * ct) = o;   // (64, timing: no result rows written)
+                *(f32x4*)(y + 16 * ct) = o;
             }
         }
     }
 }
 
 // ---- pass 1, round 4: the same contraction with the tiles gathered by LDS-DMA into a three-deep ring -------------------------
-// edge_transform_h_kernel<32, 2> stages its tiles through registers (96 of them) behind ONE barrier per k-step that all eight
-// waves reach in lockstep: per step every wave waits for its fragment reads, then every wave issues its MFMAs, then every wave
-// writes the next tile — the matrix pipe, the LDS and the vector-memory path take turns (ablations, tools/c5_shard_check.py with
-// GHF_VARIANT=rsexp<mask>: MFMAs, fetches and commits each cost ~0.7 of ~3.6 ms and add up).  Here (d % 256 == 0, 128 rows x
+// Round 3's edge_transform_h_kernel<32, 2> (retired; DESIGN_HISTORY.md) staged its tiles through registers (96 of them) behind
+// ONE barrier per k-step that all eight waves reached in lockstep: per step every wave waited for its fragment reads, then every
+// wave issued its MFMAs, then every wave wrote the next tile — the matrix pipe, the LDS and the vector-memory path took turns
+// (round 3's ablations: MFMAs, fetches and commits each cost ~0.7 of ~3.6 ms and added up).  Here (d % 256 == 0, 128 rows x
 // 256 columns per workgroup, k-steps of 32, eight waves as before):
 //   * tiles arrive by LDS-DMA (global_load_lds_dwordx4: per-lane 64-bit source address, 1 KiB per wave instruction, the granule
 //     swizzle applied on the source side), TWO steps ahead, into a ring of three buffers — no staging registers, no ds_write;
@@ -338,7 +333,7 @@ __global__ __launch_bounds__(256 * NCT, KH == 32 ? 2 : 1) void edge_transform_h_
 // The rest — operands, scales, the exact rescale between the row halves, the transposed product and the 16-byte stores — is
 // edge_transform_h_kernel's.
 // Measured (one GPU's share of C5, 27,118 tiles; tools/c5_shard_check.py under rocprofv3): 4.37 -> 3.95 ms per launch, the whole
-// C5 layer 41.3 -> 38.8 ms.  Ablations of THIS kernel (GHF_VARIANT=rsexp<mask>): without MFMAs 3.14, without the gathers 2.60,
+// C5 layer 41.3 -> 38.8 ms.  Ablations of THIS kernel (round 4): without MFMAs 3.14, without the gathers 2.60,
 // with every gathered row one of 64 L2-resident rows 3.21 — its matrix work alone is 1.09 ms at the dense fp16 peak.  What is left
 // (Second set, another box, 3.80 ms: no fragment reads 3.34, no barrier 3.68, no result rows 3.77, neither MFMAs nor fragment
 // reads 3.11 — a kernel that only moves its tiles into LDS still takes 82 % of the time.  The ring is a FIFO (loads return in
@@ -380,9 +375,8 @@ __global__ __launch_bounds__(512, 2) void edge_transform_h3_kernel(
     int64_t e = e0 + arow_i;
     if (e >= e1) e = e1 - 1;                               // rows past the tile's end repeat its last edge (never stored)
     const int64_t su = src[e], sv = dst[e];               // su < 0: row ~su of x_split (the sum of a run's source rows)
-    const char* __restrict__ urow = (GHF_RSEXP & 16) ? h_split + (size_t)(arow_i & 63) * hrow          // (timing: rows that stay in L2)
-                                    : su >= 0 ? h_split + (size_t)su * hrow : x_split + (size_t)(~su) * hrow;
-    const char* __restrict__ vrow = h_split + (size_t)((GHF_RSEXP & 16) ? (arow_i & 63) : sv) * hrow;
+    const char* __restrict__ urow = su >= 0 ? h_split + (size_t)su * hrow : x_split + (size_t)(~su) * hrow;
+    const char* __restrict__ vrow = h_split + (size_t)sv * hrow;
     const int ga = (slot ^ key(arow_i)) * 16;              // byte offset of my granule inside a 64-byte k-step of the row
     if (slot == 0) {
         const float n = row_cnt ? row_cnt[e] : 1.0f;
@@ -399,7 +393,6 @@ __global__ __launch_bounds__(512, 2) void edge_transform_h3_kernel(
     const size_t plane_b = (size_t)d * d * 2, half_b = (size_t)2 * d * d * 2;
     const int half_steps = d / KH, total = 2 * half_steps;
     auto dma = [&](int step) {                             // six 1 KiB pieces of step `step`'s tile into buffer step % 3
-        if (GHF_RSEXP & 2) return;
         const int st = step < total ? step : total - 1;    // (past the end: the last step again — the count stays six)
         const int half = st >= half_steps;
         const size_t kb = (size_t)(half ? st - half_steps : st) * KH * 2;
@@ -430,7 +423,6 @@ __global__ __launch_bounds__(512, 2) void edge_transform_h3_kernel(
     }
     i32x4 a[2][2], b0[4][2], b1[4][2];
     auto read_a = [&](unsigned buf) {
-        if (GHF_RSEXP & 8) return;                         // (timing: no fragment reads)
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt) {
             const unsigned ad = lds0 + buf + aoff[rt];
@@ -438,7 +430,6 @@ __global__ __launch_bounds__(512, 2) void edge_transform_h3_kernel(
         }
     };
     auto read_b = [&](unsigned buf, int ch, i32x4 (&b)[4][2]) {
-        if (GHF_RSEXP & 8) return;
 #pragma unroll
         for (int c4 = 0; c4 < 4; ++c4) {
             const unsigned ad = lds0 + buf + boff[4 * ch + c4];
@@ -457,7 +448,6 @@ __global__ __launch_bounds__(512, 2) void edge_transform_h3_kernel(
             for (int c4 = 0; c4 < 4; ++c4) {
                 const int ct = 4 * ch + c4;
                 auto fma = [&](int pa, int pb) {
-                    if (GHF_RSEXP & 1) { asm volatile("" :: "v"(b[c4][pb]), "v"(a[rt][pa])); return; }
                     acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, b[c4][pb]),
                                                                          __builtin_bit_cast(f16x8, a[rt][pa]), acc[rt][ct], 0, 0, 0);
                 };
@@ -496,7 +486,7 @@ __global__ __launch_bounds__(512, 2) void edge_transform_h3_kernel(
         // done; behind the barrier that holds for every wave
         asm volatile("s_waitcnt vmcnt(6)\n\ts_waitcnt lgkmcnt(0)" : "+v"(b1[0][0]), "+v"(b1[0][1]), "+v"(b1[1][0]), "+v"(b1[1][1]),
                      "+v"(b1[2][0]), "+v"(b1[2][1]), "+v"(b1[3][0]), "+v"(b1[3][1]) :: "memory");
-        if (!(GHF_RSEXP & 32)) __builtin_amdgcn_s_barrier();   // (32, timing: no barrier per step)
+        __builtin_amdgcn_s_barrier();
         i32x4 a_keep[2][2];
 #pragma unroll
         for (int rt = 0; rt < 2; ++rt)
@@ -513,7 +503,6 @@ __global__ __launch_bounds__(512, 2) void edge_transform_h3_kernel(
             for (int c4 = 0; c4 < 4; ++c4) {
                 const int ct = 4 + c4;
                 auto fma = [&](int pa, int pb) {
-                    if (GHF_RSEXP & 1) { asm volatile("" :: "v"(b1[c4][pb]), "v"(a_keep[rt][pa])); return; }
                     acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, b1[c4][pb]),
                                                                          __builtin_bit_cast(f16x8, a_keep[rt][pa]), acc[rt][ct], 0, 0, 0);
                 };
@@ -840,28 +829,14 @@ int launch_edge_transform_h(const void* h_split, int64_t N, int d, const int64_t
     // and share them in L2)
     GHF_REQUIRE(nslices * (d / RS_TN) < (1ll << 31), "edge_transform: too many tiles per launch");
     const unsigned grid = (unsigned)(nslices * (d / RS_TN));
-    // K-steps of 64 (whole 128-byte lines per visit, one workgroup per CU) measured 17.9 ms against 13.2 ms for K-steps of
-    // 32 (two workgroups per CU) on one GPU's share of C5: occupancy beats line efficiency here.  GHF_RS_K=64 for A/B.
-    static const bool k64 = getenv("GHF_RS_K") && atoi(getenv("GHF_RS_K")) == 64;
-    // d % 256 == 0: eight waves per workgroup, 256 columns per row tile (every gathered row fetched once per 256 columns);
-    // GHF_RS_NCT=1 keeps the four-wave workgroups for A/B
-    static const bool nct1 = getenv("GHF_RS_NCT") && atoi(getenv("GHF_RS_NCT")) == 1;
-    if ((d % 256) == 0 && k64) {
-        constexpr size_t lds = (size_t)2 * 2 * 2 * RS_TM * 64 * 2 + 3 * RS_TM * 4;
-        GHF_SET_MAX_LDS((edge_transform_h_kernel<64, 1>), lds);
-        edge_transform_h_kernel<64, 1><<<grid, 256, lds, stream>>>((const char*)h_split, N, d, src, dst, ypos, slice_tab,
-                                                                 (const char*)w2h, R, bias, (const char*)x_split, NX, row_cnt, Y);
-    } else if ((d % 256) == 0 && !nct1 && !(getenv("GHF_RS_P1") && atoi(getenv("GHF_RS_P1")) == 2)) {
-        // round 4: tiles by LDS-DMA into a three-deep ring (GHF_RS_P1=2 keeps round 3's register-staged kernel for A/B)
+    // d % 256 == 0: tiles by LDS-DMA into a three-deep ring, eight waves per workgroup, 256 columns per row tile (every
+    // gathered row fetched once per 256 columns).  K-steps of 64 (17.9 against 13.2 ms on one GPU's share of C5), four-wave
+    // workgroups at d % 256 == 0 and round 3's register-staged eight-wave kernel were measured and retired (DESIGN_HISTORY.md).
+    if ((d % 256) == 0) {
         constexpr size_t lds = (size_t)3 * (2 * RS_TM * 32 * 2 + 2 * 2 * RS_TN * 32 * 2) + 3 * RS_TM * 4;
         GHF_SET_MAX_LDS(edge_transform_h3_kernel, lds);
         edge_transform_h3_kernel<<<grid / 2, 512, lds, stream>>>((const char*)h_split, N, d, src, dst, ypos, slice_tab,
                                                                  (const char*)w2h, R, bias, (const char*)x_split, NX, row_cnt, Y);
-    } else if ((d % 256) == 0 && !nct1) {
-        constexpr size_t lds = (size_t)2 * 2 * 3 * RS_TM * 32 * 2 + 3 * RS_TM * 4;
-        GHF_SET_MAX_LDS((edge_transform_h_kernel<32, 2>), lds);
-        edge_transform_h_kernel<32, 2><<<grid / 2, 512, lds, stream>>>((const char*)h_split, N, d, src, dst, ypos, slice_tab,
-                                                                     (const char*)w2h, R, bias, (const char*)x_split, NX, row_cnt, Y);
     } else {
         constexpr size_t lds = (size_t)2 * 2 * 2 * RS_TM * 32 * 2 + 3 * RS_TM * 4;
         GHF_SET_MAX_LDS((edge_transform_h_kernel<32, 1>), lds);

@@ -19,7 +19,6 @@
 #include "common.h"
 
 #include <hipcub/hipcub.hpp>
-#include <stdlib.h>
 
 namespace ghf {
 
@@ -169,11 +168,9 @@ static int64_t num_segments(int64_t N, int R, int BN) { return BN == 1 ? N : cdi
 
 // The last round of workgroups: with NB blocks on `cus` compute units, NB % cus blocks remain for a last round that keeps
 // only as many CUs busy.  When that is less than half of them (and there is more than one round), each of these blocks
-// becomes floor(cus / remainder) <= 8 work items.  GHF_TAIL_SPLIT=0 turns it off.
+// becomes floor(cus / remainder) <= 8 work items.
 static int tail_split(int64_t NB, int64_t* tail0) {
     static const int cus = [] {
-        const char* e = getenv("GHF_TAIL_SPLIT");
-        if (e && atoi(e) == 0) return 0;
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
         return n;

@@ -20,10 +20,7 @@ namespace ghf {
 
 constexpr int WG_MAX_WIDTH = 1024;   // max(T, Hh) supported by the LDS ping-pong buffers
 constexpr int WG_UNROLL = 8;         // independent dot products per wave and step in the latency-bound small kernels
-#ifndef GHF_WG_HU
-#define GHF_WG_HU 8
-#endif
-constexpr int WG_HU = GHF_WG_HU;     // ... of wg_hidden_kernel (32 — a wave's whole share of a 128-unit layer at once — needs 264 registers: one workgroup per CU, 56 -> 130 us at config 3's 576 workgroups; 41 vs 43 us at config 2)
+constexpr int WG_HU = 8;             // ... of wg_hidden_kernel (32 — a wave's whole share of a 128-unit layer at once — needs 264 registers: one workgroup per CU, 56 -> 130 us at config 3's 576 workgroups; 41 vs 43 us at config 2)
 
 struct HeadPtrs {
     const float* w[3][8];     // [head][layer] weight

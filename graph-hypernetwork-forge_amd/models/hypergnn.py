@@ -19,7 +19,6 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
 
-import os
 
 import numpy as np
 import torch
@@ -384,7 +383,7 @@ class HyperGNN(nn.Module):
         # runs beside the message layers' gradient kernels instead of between them (C3: backward 35.2 -> 34.1 ms).  In the
         # forward the caller's stream waits for them at once: side by side with the input projection both got slower (forward
         # 13.45 -> 13.8 ms).  (With dropout the masks are drawn in the reference's order on one stream.)
-        side = (plan.E >= self.SIDE_STREAM_MIN_EDGES and not self._dropping() and os.environ.get("GHF_TRAIN_WG_SIDE", "1") != "0")
+        side = plan.E >= self.SIDE_STREAM_MIN_EDGES and not self._dropping()
         generated = []
         if side:
             main = torch.cuda.current_stream(device)
@@ -439,7 +438,7 @@ class HyperGNN(nn.Module):
         # all of them finish in the shadow of the input projection; in ONE side stream the later layers' kernels ran beside
         # the first message launch, which holds every CU's LDS — they trickled in as workgroups retired (0.3 ms each instead
         # of 0.05) and cost that launch 6 %
-        nside = max(1, int(os.environ.get("GHF_WG_STREAMS", str(self.num_layers))))
+        nside = max(1, self.num_layers)
         if self._wg_stream is None or self._wg_stream[0].device != dev or len(self._wg_stream) != nside:
             # (high-priority streams measured worse: 10.8 -> 11.6 ms per C3 forward)
             self._wg_stream = [torch.cuda.Stream(device=dev) for _ in range(nside)]
@@ -492,8 +491,8 @@ class HyperGNN(nn.Module):
             flag = _native.range_flag(device)
             flag.zero_()
             reader = _native.RangeFlagRead(flag)
-        early = reader is not None and os.environ.get("GHF_GUARD_EARLY", "1") != "0"           # (0: read at the end, for A/B)
-        out = self._forward_planned(x, plan, exchange, before_last=reader.arm if early else None, rows_per_layer=rows_per_layer)
+        out = self._forward_planned(x, plan, exchange, before_last=reader.arm if reader is not None else None,
+                                    rows_per_layer=rows_per_layer)
         if guard:
             bits = reader.value()
             self.last_range_flags = bits
@@ -523,10 +522,10 @@ class HyperGNN(nn.Module):
         # kernels took 0.4 + 0.3 ms and the first message launch waited for them (kernel-trace timeline, round 3: 0.76 ms
         # before the first message launch).  The later layers' generators run beside the projection on side streams as before.
         side = plan.E >= self.SIDE_STREAM_MIN_EDGES
-        batched = self.num_layers <= 8 and os.environ.get("GHF_GEN_BATCHED", "1") != "0"
+        batched = self.num_layers <= 8
         if batched:                                # all layers' generators in one launch sequence, first (round 3)
             weights, ready = self.generate_batched(text_embs, plan.wlayout), [None] * self.num_layers
-        w0 = self.weight_generators[0].generate(text_embs, plan.wlayout) if not batched and side and os.environ.get("GHF_GEN0_FIRST", "1") != "0" else None
+        w0 = self.weight_generators[0].generate(text_embs, plan.wlayout) if not batched and side else None
         h = _native.input_proj_fwd(x, self.input_proj.weight.detach(), self.input_proj.bias.detach(), h_split=hs,
                                    split_layout=plan.wlayout if split else 0)
         h_next = torch.empty_like(h)

@@ -189,8 +189,7 @@ def _slices(counts: List[int]) -> List[Tuple[int, int, int]]:
 def build_rs(plan: "GraphPlan", runs: Optional[bool] = None) -> RsPlan:
     """From a CSR plan (block_nodes == 1: edges sorted by key = dst * R + relation): the same edges grouped by relation.
     One device sort and a few host syncs per plan.  runs: rows = runs of equal (destination, relation) (None: when that
-    leaves at most RS_RUNS_MAX_SHARE of the rows — power-law graphs: a hub's edges repeat its relations; GHF_RS_RUNS=0/1
-    forces)."""
+    leaves at most RS_RUNS_MAX_SHARE of the rows — power-law graphs: a hub's edges repeat its relations)."""
     if plan.block_nodes != 1:
         raise ValueError("the relation-stationary layer runs on CSR plans (block_nodes == 1)")
     dev, R, N, E = plan.sorted_key.device, plan.R, plan.N, plan.E
@@ -200,8 +199,6 @@ def build_rs(plan: "GraphPlan", runs: Optional[bool] = None) -> RsPlan:
                       off=torch.zeros(N + 1, dtype=torch.int64, device=dev))
     key = plan.sorted_key[:E].to(torch.int64) & 0xFFFFFFFF
     src = plan.sorted_src[:E].to(torch.int64) & SRC_MASK
-    if os.environ.get("GHF_RS_RUNS") in ("0", "1"):
-        runs = os.environ["GHF_RS_RUNS"] == "1"
     if runs is None or runs:
         head = torch.ones(E, dtype=torch.bool, device=dev)
         head[1:] = key[1:] != key[:-1]

@@ -343,9 +343,8 @@ int ghf_group_outer(const float* A, const int64_t* ia, int da, const float* B, c
  * each relation.  workspace: nslices * (2*D*D + D) + 64 floats, D = min(d, 128).  Fixed summation order.  d = 64: exact fp32
  * (v_mfma_f32_16x16x4_f32); d % 128 == 0: two fp16 pieces per operand with ONE power-of-two scale per tensor (the largest
  * magnitude of h resp. G — found by the call — lifted into [2^13, 2^14)), three v_mfma_f32_16x16x32_f16 per product, fp32
- * accumulation: 22 significand bits relative to each tensor's largest entries.  N <= 0 (or GHF_EDGE_OUTER=exact in the
- * environment) keeps the exact fp32 chain at every d: what the host mirror passes when a training step fell back to the exact
- * kernels (range guard).
+ * accumulation: 22 significand bits relative to each tensor's largest entries.  N <= 0 keeps the exact fp32 chain at every d:
+ * what the host mirror passes when a training step fell back to the exact kernels (range guard).
  * order (or NULL = table order): a permutation of 0 .. nslices-1, the slice each workgroup of the launch takes, in launch
  * order.  It changes no bit of the result (a slice's partial sums land at the slice's index, the reduction runs in table order)
  * — only which slices are resident together: with destinations ascending inside a relation, the slices ordered by their
@@ -364,7 +363,7 @@ int ghf_edge_outer(const float* h, const float* G, const int64_t* src, const int
  * (a training step's G: the nodes the loss does not touch) and add 2^-15 of what the others add; when they are at least 7/8
  * of either tensor's nonzero rows — a few outlier rows set the scale and the bulk of the tensor would be cut short — the call
  * runs on the exact fp32 chain instead (the bits of N <= 0), decided on the device: both kernels are enqueued and the
- * workgroups of one return at once.  GHF_EO_GUARD=0 in the environment removes it.  The four counters (far-down rows, nonzero
+ * workgroups of one return at once.  The four counters (far-down rows, nonzero
  * rows; of h, of G) stay in the workspace behind the partial sums and the two maxima:
  * ints at float offset nslices * (2*D*D + D) + 2. */
 int ghf_edge_outer_scaled(const float* h, const float* G, const float* h_rowscale, const float* G_rowscale, const int64_t* src,

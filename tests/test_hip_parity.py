@@ -157,7 +157,7 @@ def test_input_projection_and_its_fused_split(N, F, d):
 def test_input_projection_on_two_fp16_pieces(N, F, d, monkeypatch):
     """Callers on the two-piece path (they ask for the SPLIT2H rows) get the projection on fp16 pieces too (round 3): within the
     fp32 tolerance of relu(x W^T + b) (reference hypergnn.py:261), its pieces = ghf_split_rows of its output bit for bit, rows
-    with a wide dynamic range raise the guard, and GHF_INPUT_PROJ=exact / callers without split rows keep the fp32 MFMAs."""
+    with a wide dynamic range raise the guard, and callers without split rows keep the fp32 MFMAs."""
     x = synth.normal(6, "x", (N, F))
     x[::7] *= 37.0                                                   # rows of different magnitudes: one power of two per row
     x[5] = 0.0
@@ -622,7 +622,7 @@ def test_side_output_and_zero_half_flags(N, E, R, kind):
             _native.message_layer_fwd(h_d, plan, Wz, None, bias, plan.wlayout, None, None, 0.0, fast, h_split=hs, flags=_native.GHF_FLAG_RAW_SUM | flag)
             assert torch.equal(fast, base), f"flag {flag}: max diff {float((fast - base).abs().max()):.3e}"
     # ... and the flags MEAN "that half must not be read" (ghf.h): ONE pack with both halves nonzero serves both passes, as the
-    # backward hands it over (autograd._ONE_PACK); each pass equals the pass on the pack whose other half is zero
+    # backward hands it over (autograd.layer_backward); each pass equals the pass on the pack whose other half is zero
     both = _native.weights_pack(t(Wm), t(Ws), True, R, d, plan.wlayout)
     for top, bottom, flag in ((None, Ws, _native.GHF_FLAG_ZERO_SRC), (Wm, None, _native.GHF_FLAG_ZERO_DST)):
         Wz = _native.weights_pack(None if top is None else t(top), None if bottom is None else t(bottom), True, R, d, plan.wlayout)
@@ -993,11 +993,10 @@ def test_input_projection_weight_gradient_through_edge_outer(d, monkeypatch):
         _grad_check(f"input_proj.bias (edge_outer {on})", grads[on][1], br.grad.numpy())
 
 
-def test_training_side_streams_change_no_bit(monkeypatch):
+def test_training_generator_side_stream_changes_no_bit(monkeypatch):
     """Large graphs train with the generators on a side stream (their backward then runs beside the message layers' gradient
-    kernels) and the layers' weight gradients beside the two gradient passes (autograd.py).  Forced on for a small graph, three
-    steps: output and every gradient bit for bit what the single-stream schedule computes."""
-    from graph_hypernetwork_forge_amd import autograd as A
+    kernels).  Forced on for a small graph, three steps: output and every gradient bit for bit what the single-stream schedule
+    computes."""
     cfg = cases.MODELS["c3"]
     g = synth.make_kg(1500, 16000, 9, cfg.node_feat_dim, seed=77, kind="powerlaw")
     ei, texts = torch.from_numpy(g.edge_index).to(DEV), g.edge_texts()
@@ -1005,7 +1004,6 @@ def test_training_side_streams_change_no_bit(monkeypatch):
 
     def run(side: bool):
         monkeypatch.setattr(HyperGNN, "SIDE_STREAM_MIN_EDGES", 0 if side else 1 << 60)
-        monkeypatch.setattr(A, "_EO_SIDE", side)
         model = make_model(cfg, cfg.params()).train()
         x = torch.from_numpy(g.node_features).to(DEV).requires_grad_(True)
         for _ in range(3):                                             # (the streams are reused from the second step on)

@@ -25,7 +25,7 @@ for i in range(runs):
     outs.append(o)
 ref = torch.stack(outs).median(dim=0).values
 BN = plan.block_nodes
-print("block_nodes", BN, "variant", os.environ.get("GHF_VARIANT"), "extra flags", extra)
+print("block_nodes", BN, "extra flags", extra)
 dst, src = ei[1], ei[0]
 item_tab = plan.item_tab.cpu().numpy().reshape(-1, 4)
 item_off = plan.blk_item_off.cpu().numpy()

@@ -1,5 +1,5 @@
 """ms per launch of ghf_edge_outer_scaled at C3's size (one layer's weight gradients), with the slices in table order and
-in the plan's launch order, and that the two give the same bits.  GHF_VARIANT picks the build."""
+in the plan's launch order, and that the two give the same bits."""
 import os, sys, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from graph_hypernetwork_forge_amd import _native, synth, autograd as A
@@ -27,6 +27,6 @@ for name, order in (("table order", None), ("launch order", tp.slice_order)):
         a.record(); f(); c.record()
     torch.cuda.synchronize()
     ms = [a.elapsed_time(c) for a, c in ev]
-    print(f"variant={os.environ.get('GHF_VARIANT', '-')} slices={tp.slice_tab.size(0)} {name}: {np.mean(ms):.3f} ms (min {min(ms):.3f})", flush=True)
+    print(f"slices={tp.slice_tab.size(0)} {name}: {np.mean(ms):.3f} ms (min {min(ms):.3f})", flush=True)
 a, b = res["table order"], res["launch order"]
 print("same bits:", bool(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])))

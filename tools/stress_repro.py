@@ -29,4 +29,4 @@ for i in range(runs):
     n = int((o != ref).any(dim=1).sum().item())
     if n:
         bad.append((i, n))
-print(f"variant {os.environ.get('GHF_VARIANT')} {kind} N={N} E={E} R={R} d={d} block_nodes {plan.block_nodes}: {len(bad)} of {runs} runs differ from the first", bad[:10])
+print(f"{kind} N={N} E={E} R={R} d={d} block_nodes {plan.block_nodes}: {len(bad)} of {runs} runs differ from the first", bad[:10])
