@@ -3,7 +3,7 @@
 __version__ = "0.2.0+mi355x.1"
 
 from .models.weight_generator import WeightGenerator
-from .models.hypergnn import HyperGNN, TextEncoder
+from .models.hypergnn import HyperGNN, TextEncoder, link_prediction_metrics
 from .data.knowledge_graph import ToyKnowledgeGraph
 
-__all__ = ["WeightGenerator", "HyperGNN", "TextEncoder", "ToyKnowledgeGraph"]
+__all__ = ["WeightGenerator", "HyperGNN", "TextEncoder", "ToyKnowledgeGraph", "link_prediction_metrics"]

@@ -95,6 +95,10 @@ SIGNATURES = {
     "ghf_transpose_batched": (_i32, [_vp, _i32, _i32, _i32, _vp, _vp]),
     "ghf_weights_pack": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "ghf_score_pairs_fwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp]),
+    "ghf_score_rank_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "ghf_score_rank": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _sz, _vp, _vp, _vp]),
+    "ghf_score_topk_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "ghf_score_topk": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _sz, _vp, _vp, _vp]),
     "ghf_rows_pack": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "ghf_rows_unpack": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "ghf_rows_accumulate": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp]),
@@ -513,6 +517,106 @@ def score_pairs_fwd(a: torch.Tensor, b: torch.Tensor, ia: Optional[torch.Tensor]
     _check(load().ghf_score_pairs_fwd(_ptr(a), _ptr(b), _ptr(ia), _ptr(ib), a.size(0), b.size(0), n, a.size(1), _ptr(out),
                                       _stream()), "ghf_score_pairs_fwd")
     return out
+
+
+# ---- link prediction against every node (include/ghf.h: ghf_score_rank / ghf_score_topk, csrc/rank.hip) ----------------
+def _rank_args(q: torch.Tensor, c: torch.Tensor, iq: Optional[torch.Tensor], filt_ptr: Optional[torch.Tensor],
+               filt_idx: Optional[torch.Tensor], what: str):
+    q = _req(q, torch.float32, "q")
+    c = _req(c, torch.float32, "c")
+    if q.dim() != 2 or c.dim() != 2 or q.size(1) != c.size(1) or q.size(0) == 0 or c.size(0) == 0:
+        raise ValueError(f"{what}: need two non-empty [rows, d] matrices of equal d, got {tuple(q.shape)} and {tuple(c.shape)}")
+    if q.device != c.device:
+        raise RuntimeError(f"{what}: q is on {q.device}, c on {c.device}")
+    iq = None if iq is None else _req(iq, torch.int64, "iq")
+    if iq is not None and iq.dim() != 1:
+        raise ValueError(f"{what}: iq must be 1-D")
+    B = iq.numel() if iq is not None else q.size(0)
+    if B == 0:
+        raise ValueError(f"{what}: no queries")
+    if (filt_ptr is None) != (filt_idx is None):
+        raise ValueError(f"{what}: filt_ptr and filt_idx come together")
+    nnz = 0
+    if filt_ptr is not None:
+        filt_ptr = _req(filt_ptr, torch.int64, "filt_ptr")
+        filt_idx = _req(filt_idx, torch.int64, "filt_idx")
+        if filt_ptr.dim() != 1 or filt_idx.dim() != 1 or filt_ptr.numel() != B + 1:
+            raise ValueError(f"{what}: filt_ptr must hold B + 1 = {B + 1} offsets, got {tuple(filt_ptr.shape)}")
+        nnz = filt_idx.numel()
+    for name, t in (("iq", iq), ("filt_ptr", filt_ptr), ("filt_idx", filt_idx)):
+        if t is not None and t.device != q.device:
+            raise RuntimeError(f"{what}: {name} is on {t.device}, the embeddings on {q.device}")
+    return q, c, iq, filt_ptr, filt_idx, B, nnz
+
+
+def _rank_workspace(workspace: Optional[torch.Tensor], need: int, device, what: str) -> torch.Tensor:
+    if workspace is None:
+        return torch.empty(need, dtype=torch.uint8, device=device)
+    workspace = _req(workspace, torch.uint8, "workspace")
+    if workspace.numel() < need:
+        raise ValueError(f"{what}: workspace of {workspace.numel()} bytes, need {need}")
+    return workspace
+
+
+def score_rank_workspace_bytes(B: int, N: int, d: int) -> int:
+    return int(load().ghf_score_rank_workspace_bytes(B, N, d))
+
+
+def score_topk_workspace_bytes(B: int, N: int, d: int, k: int) -> int:
+    return int(load().ghf_score_topk_workspace_bytes(B, N, d, k))
+
+
+def score_rank(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optional[torch.Tensor] = None,
+               filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+               workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """(greater, equal) int64 [B]: how many rows of c score above / the same as row target[i] against query q[iq[i]], the
+    target and the query's filter list (CSR, each list sorted ascending) left out.  Nothing of size B x N is stored.  With
+    `workspace` (uint8, score_rank_workspace_bytes) and `out` given the call allocates nothing (graph capture)."""
+    q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, "score_rank")
+    target = _req(target, torch.int64, "target")
+    if target.dim() != 1 or target.numel() != B or target.device != q.device:
+        raise ValueError(f"score_rank: target must be [B = {B}] on {q.device}, got {tuple(target.shape)} on {target.device}")
+    N, d = c.size(0), c.size(1)
+    need = score_rank_workspace_bytes(B, N, d)
+    if need == 0:
+        raise ValueError(f"score_rank: unsupported sizes B={B} N={N} d={d}")
+    ws = _rank_workspace(workspace, need, q.device, "score_rank")
+    if out is None:
+        greater = torch.empty(B, dtype=torch.int64, device=q.device)
+        equal = torch.empty(B, dtype=torch.int64, device=q.device)
+    else:
+        greater, equal = (_req(t, torch.int64, "out") for t in out)
+        if greater.numel() != B or equal.numel() != B or not (out[0].is_contiguous() and out[1].is_contiguous()):
+            raise ValueError(f"score_rank: out must be two contiguous int64 [{B}] tensors")
+    _check(load().ghf_score_rank(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d,
+                                 _ptr(ws), ws.numel(), _ptr(greater), _ptr(equal), _stream()), "ghf_score_rank")
+    return greater, equal
+
+
+def score_topk(q: torch.Tensor, c: torch.Tensor, k: int, iq: Optional[torch.Tensor] = None,
+               filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+               workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """(scores [B, k] fp32 descending, ids [B, k] int64): the k best rows of c for every query, ties towards the lower id,
+    (-inf, -1) where fewer than k candidates remain outside the query's filter list."""
+    q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, "score_topk")
+    k = int(k)
+    if not 1 <= k <= 128:
+        raise ValueError(f"score_topk: k = {k} outside 1..128")
+    N, d = c.size(0), c.size(1)
+    need = score_topk_workspace_bytes(B, N, d, k)
+    if need == 0:
+        raise ValueError(f"score_topk: unsupported sizes B={B} N={N} d={d} k={k}")
+    ws = _rank_workspace(workspace, need, q.device, "score_topk")
+    if out is None:
+        scores = torch.empty(B, k, dtype=torch.float32, device=q.device)
+        ids = torch.empty(B, k, dtype=torch.int64, device=q.device)
+    else:
+        scores, ids = _req(out[0], torch.float32, "out[0]"), _req(out[1], torch.int64, "out[1]")
+        if tuple(scores.shape) != (B, k) or tuple(ids.shape) != (B, k) or not (out[0].is_contiguous() and out[1].is_contiguous()):
+            raise ValueError(f"score_topk: out must be contiguous fp32 and int64 [{B}, {k}] tensors")
+    _check(load().ghf_score_topk(_ptr(q), _ptr(c), _ptr(iq), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d, k, _ptr(ws),
+                                 ws.numel(), _ptr(scores), _ptr(ids), _stream()), "ghf_score_topk")
+    return scores, ids
 
 
 # ---- wide hidden sizes: relation-stationary layer (include/ghf.h, csrc/message_rs.hip) ---------------------------

@@ -558,6 +558,30 @@ int ghf_score_pairs_fwd(const float* a, const float* b, const int64_t* ia, const
     return launch_score_pairs(a, b, ia, ib, rows_a, rows_b, n, d, scores, (hipStream_t)stream);
 }
 
+size_t ghf_score_rank_workspace_bytes(int64_t B, int64_t N, int d) { return score_rank_workspace_bytes(B, N, d); }
+
+int ghf_score_rank(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                   const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, void* workspace,
+                   size_t workspace_bytes, int64_t* greater, int64_t* equal, void* stream) {
+    GHF_REQUIRE(q && c && target && workspace && greater && equal, "score_rank: null pointer argument");
+    GHF_REQUIRE(nnz <= 0 || (filt_ptr && filt_idx), "score_rank: null filter list with nnz > 0");
+    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "score_rank: workspace not 256-byte aligned");
+    return launch_score_rank(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, workspace, workspace_bytes, greater, equal,
+                             (hipStream_t)stream);
+}
+
+size_t ghf_score_topk_workspace_bytes(int64_t B, int64_t N, int d, int k) { return score_topk_workspace_bytes(B, N, d, k); }
+
+int ghf_score_topk(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
+                   int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, void* workspace, size_t workspace_bytes,
+                   float* scores, int64_t* ids, void* stream) {
+    GHF_REQUIRE(q && c && workspace && scores && ids, "score_topk: null pointer argument");
+    GHF_REQUIRE(nnz <= 0 || (filt_ptr && filt_idx), "score_topk: null filter list with nnz > 0");
+    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "score_topk: workspace not 256-byte aligned");
+    return launch_score_topk(q, c, iq, filt_ptr, filt_idx, nnz, rows_q, N, B, d, k, workspace, workspace_bytes, scores, ids,
+                             (hipStream_t)stream);
+}
+
 int ghf_tail_fwd(const float* agg, const float* h, const float* ln_gamma, const float* ln_beta, float ln_eps,
                  int64_t row0, int64_t rows, int d, float* h_out, const float* drop, void* stream) {
     GHF_REQUIRE(agg && h && ln_gamma && ln_beta && h_out, "tail_fwd: null pointer argument");

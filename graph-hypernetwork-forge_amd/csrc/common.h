@@ -165,6 +165,15 @@ int launch_rows_pack(bool unpack, void* rows, int64_t row_bytes, void* extra, in
 int launch_rows_accumulate(const float* packed, const int64_t* idx, int64_t n, int64_t nrows, float* rows, int d, hipStream_t stream);
 int launch_score_pairs(const float* a, const float* b, const int64_t* ia, const int64_t* ib, int64_t rows_a, int64_t rows_b,
                        int64_t n, int d, float* scores, hipStream_t stream);
+// rank.hip
+size_t score_rank_workspace_bytes(int64_t B, int64_t N, int d);
+size_t score_topk_workspace_bytes(int64_t B, int64_t N, int d, int k);
+int launch_score_rank(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                      const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, void* ws,
+                      size_t ws_bytes, int64_t* greater, int64_t* equal, hipStream_t stream);
+int launch_score_topk(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
+                      int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, void* ws, size_t ws_bytes, float* scores,
+                      int64_t* ids, hipStream_t stream);
 int launch_text_encode(const int32_t* ids, const int32_t* lens, int U, int Lmax, const float* E, int V, int C,
                        const float* W, const float* b, int T, float* out, hipStream_t stream);
 int launch_input_proj(const float* x, const float* W_in, const float* b_in, int64_t N, int F, int d,

@@ -1,7 +1,7 @@
 """Host mirrors of the reference's modules (same constructors, attributes, state_dict keys and call signatures); every
 forward and backward runs in libghf_hip.so."""
 
-from .hypergnn import GraphedForward, HyperGNN, TextEncoder
+from .hypergnn import GraphedForward, HyperGNN, TextEncoder, link_prediction_metrics
 from .weight_generator import WeightGenerator
 
-__all__ = ("HyperGNN", "WeightGenerator", "TextEncoder", "GraphedForward")
+__all__ = ("HyperGNN", "WeightGenerator", "TextEncoder", "GraphedForward", "link_prediction_metrics")

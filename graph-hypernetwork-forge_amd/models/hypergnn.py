@@ -638,5 +638,116 @@ class HyperGNN(nn.Module):
             return ScoreEdgesFn.apply(embs, src, dst)
         return _native.score_pairs_fwd(embs, embs, src.to(torch.int64), dst.to(torch.int64))
 
+    # -- link prediction against every node (csrc/rank.hip; no counterpart in the reference, whose demo stops at the loss) --
+    @staticmethod
+    def _rank_ids(ids: torch.Tensor, rows: int, embs: torch.Tensor, name: str) -> torch.Tensor:
+        """1-D node ids checked as indexing checks them (IndexError), negative ids wrapped: int64 on embs' device."""
+        if not isinstance(ids, torch.Tensor) or ids.dim() != 1:
+            raise ValueError(f"{name} must be a 1-D tensor of node ids, got {getattr(ids, 'shape', type(ids))}")
+        if ids.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{name} must be int32 or int64, got {ids.dtype}")
+        if ids.numel():
+            lo, hi = (int(v) for v in torch.aminmax(ids))
+            if lo < -rows or hi >= rows:
+                raise IndexError(f"{name} holds ids outside [-{rows}, {rows}) (range {lo}..{hi})")
+        ids = ids.to(device=embs.device, dtype=torch.int64)
+        return torch.where(ids < 0, ids + rows, ids)
+
+    @classmethod
+    def _filter_lists(cls, embs: torch.Tensor, query: torch.Tensor, known, filt_ptr, filt_idx):
+        """Each query's filter list in the form the kernels take (CSR, every list sorted ascending), built on the device.
+        `known` = (src, dst) names true edges: query[i]'s list is every dst of an edge whose src is query[i] (pass the
+        edges in both directions for an undirected reading)."""
+        N, B = embs.size(0), query.numel()
+        if known is not None and (filt_ptr is not None or filt_idx is not None):
+            raise ValueError("pass either known=(src, dst) or filt_ptr / filt_idx, not both")
+        if known is not None:
+            src, dst = known
+            src = cls._rank_ids(src, N, embs, "known[0]")
+            dst = cls._rank_ids(dst, N, embs, "known[1]")
+            if src.numel() != dst.numel():
+                raise ValueError(f"known: {src.numel()} sources and {dst.numel()} destinations")
+            key = torch.unique(src * N + dst)                       # sorted by (src, dst), repeats gone
+            ks = torch.div(key, N, rounding_mode="floor")
+            lo = torch.searchsorted(ks, query)
+            lens = torch.searchsorted(ks, query, right=True) - lo
+            ptr = torch.zeros(B + 1, dtype=torch.int64, device=embs.device)
+            torch.cumsum(lens, 0, out=ptr[1:])
+            nnz = int(ptr[-1])
+            if nnz == 0:
+                return None, None
+            pos = torch.arange(nnz, device=embs.device) + torch.repeat_interleave(lo - ptr[:-1], lens, output_size=nnz)
+            return ptr, (key[pos] - ks[pos] * N).contiguous()
+        if filt_ptr is None and filt_idx is None:
+            return None, None
+        if filt_ptr is None or filt_idx is None:
+            raise ValueError("filt_ptr and filt_idx come together")
+        if filt_ptr.dim() != 1 or filt_ptr.numel() != B + 1 or filt_ptr.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"filt_ptr must hold B + 1 = {B + 1} integer offsets, got {tuple(filt_ptr.shape)} {filt_ptr.dtype}")
+        idx = cls._rank_ids(filt_idx, N, embs, "filt_idx")
+        ptr = filt_ptr.to(device=embs.device, dtype=torch.int64).contiguous()
+        lens = ptr[1:] - ptr[:-1]
+        nnz = idx.numel()
+        if int(ptr[0]) != 0 or int(ptr[-1]) != nnz or (nnz and int(lens.min()) < 0):
+            raise ValueError(f"filt_ptr must rise from 0 to filt_idx.numel() = {nnz}")
+        if nnz == 0:
+            return None, None
+        seg = torch.repeat_interleave(torch.arange(B, device=embs.device), lens, output_size=nnz)
+        key = torch.sort(seg * N + idx).values                      # every list ascending, the lists in place
+        return ptr, (key - seg * N).contiguous()
+
+    def rank_candidates(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, known=None,
+                        filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None):
+        """Where ``target[i]`` ranks among ALL nodes as a partner of ``query[i]`` under the dot-product score
+        (``score_triple``): ``(greater, equal)``, int64 ``[B]`` — the nodes scoring above / exactly as the target, the target
+        itself and the query's known partners (the "filtered" setting) left out.  ``known=(src, dst)`` names true edges
+        (the query's list = every ``dst`` whose ``src`` is the query); or pass CSR lists as ``filt_ptr`` / ``filt_idx``.
+        Feed the counts to ``link_prediction_metrics``.  One tiled ``q . c^T`` on the fp32 matrix cores with the comparison
+        in its epilogue (``ghf_score_rank``): the ``[B, N]`` scores are never stored.  The counts carry no autograd graph
+        (``embs`` is read as data)."""
+        if not embs.is_cuda:
+            raise RuntimeError(f"rank_candidates computes on an MI355X HIP device only (input is on {embs.device})")
+        if embs.dim() != 2:
+            raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        e = embs.detach().float()
+        q = self._rank_ids(query, e.size(0), e, "query")
+        t = self._rank_ids(target, e.size(0), e, "target")
+        if q.numel() != t.numel():
+            raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
+        ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx)
+        return _native.score_rank(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx)
+
+    def topk_candidates(self, embs: torch.Tensor, query: torch.Tensor, k: int, *, known=None,
+                        filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None):
+        """The ``k`` (1..128) best partners of every ``query[i]`` among ALL nodes outside its filter list (``known`` /
+        ``filt_ptr, filt_idx`` as in ``rank_candidates``): ``(scores [B, k]`` fp32 descending, ``ids [B, k]`` int64``)``, ties
+        towards the lower id, ``(-inf, -1)`` where fewer than k candidates remain.  The query node itself is a candidate
+        unless listed.  No autograd graph."""
+        if not embs.is_cuda:
+            raise RuntimeError(f"topk_candidates computes on an MI355X HIP device only (input is on {embs.device})")
+        if embs.dim() != 2:
+            raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        if not 1 <= int(k) <= 128:
+            raise ValueError(f"k = {k} outside 1..128")
+        e = embs.detach().float()
+        q = self._rank_ids(query, e.size(0), e, "query")
+        ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx)
+        return _native.score_topk(e, e, int(k), iq=q, filt_ptr=ptr, filt_idx=idx)
+
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
+
+
+def link_prediction_metrics(greater: torch.Tensor, equal: torch.Tensor, ks: Sequence[int] = (1, 3, 10)) -> Dict[str, float]:
+    """Filtered link-prediction metrics from ``HyperGNN.rank_candidates``' counts, with the realistic rank
+    ``1 + greater + equal / 2`` (a tie counts half): ``{"mrr", "mean_rank", "hits@k" for k in ks}``.  Queries whose counts
+    are negative (an id was out of range in a raw call) are an error."""
+    if greater.shape != equal.shape or greater.dim() != 1 or greater.numel() == 0:
+        raise ValueError(f"need two non-empty [B] count tensors, got {tuple(greater.shape)} and {tuple(equal.shape)}")
+    if bool((greater < 0).any()) or bool((equal < 0).any()):
+        raise ValueError("negative counts: a query had an id out of range")
+    rank = 1.0 + greater.to(torch.float64) + 0.5 * equal.to(torch.float64)
+    out = {"mrr": float((1.0 / rank).mean()), "mean_rank": float(rank.mean())}
+    for k in ks:
+        out[f"hits@{int(k)}"] = float((rank <= int(k)).to(torch.float64).mean())
+    return out

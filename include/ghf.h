@@ -416,6 +416,35 @@ int ghf_weights_pack(const float* top, const float* bottom, int transpose, int R
 int ghf_score_pairs_fwd(const float* a, const float* b, const int64_t* ia, const int64_t* ib,
                         int64_t rows_a, int64_t rows_b, int64_t n, int d, float* scores, void* stream);
 
+/* ---- link prediction against every node: rank counts and top-k (csrc/rank.hip) ----------------------
+ * The step after training (demo.py:79-101 trains on pair scores): score query rows against ALL N candidate rows,
+ *   s(i, j) = sum_k q[iq[i]][k] * c[j][k],  i < B, j < N   (fp32, accumulated in increasing k: the fmaf chain of
+ *   v_mfma_f32_32x32x2_f32, the same bits as ghf_score_pairs_fwd's products summed in that order),
+ * without ever storing the B x N scores.  q [rows_q, d], c [N, d] fp32 row-major (normally both the model's output);
+ * iq int64 [B] or NULL (= i, then B <= rows_q); d <= 256 (GHF_EUNSUPPORTED beyond), B and N below 2^31.
+ * Filter lists (the "filtered" setting: candidates known to be true, to be ignored) come in CSR form: filt_ptr int64
+ * [B+1] ascending from 0, filt_idx int64 [nnz], nnz = filt_ptr[B] passed on the host side; each query's list sorted
+ * ascending (an id may repeat: it is removed once).  nnz = 0 (both pointers may be NULL) means no lists.
+ * An iq / target / filter id outside its range does not fault: that query's counts and ids are -1 (its top-k scores
+ * NaN, as ghf_score_pairs_fwd).
+ *
+ * ghf_score_rank: with t_i = s(i, target[i]) and J_i = every row of c but target[i] and the rows in query i's list,
+ *   greater[i] = #{j in J_i : s(i,j) > t_i},   equal[i] = #{j in J_i : s(i,j) == t_i}      (int64 [B]; NaN counts in neither).
+ * Integer sums: bit-reproducible.  workspace: ghf_score_rank_workspace_bytes (0 = bad sizes), 256-byte aligned.
+ *
+ * ghf_score_topk: for 1 <= k <= 128 the k highest s(i, j) over j outside query i's list: scores [B, k] fp32 descending,
+ * ids [B, k] int64, ties towards the lower id, (-inf, -1) where fewer than k candidates remain.  NaN and -inf scores are
+ * never returned.  workspace: ghf_score_topk_workspace_bytes, 256-byte aligned (per query and candidate slab a list of
+ * k + 256 entries). */
+size_t ghf_score_rank_workspace_bytes(int64_t B, int64_t N, int d);
+int ghf_score_rank(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                   const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, void* workspace,
+                   size_t workspace_bytes, int64_t* greater, int64_t* equal, void* stream);
+size_t ghf_score_topk_workspace_bytes(int64_t B, int64_t N, int d, int k);
+int ghf_score_topk(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
+                   int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, void* workspace, size_t workspace_bytes,
+                   float* scores, int64_t* ids, void* stream);
+
 /* ---- the sparse row exchange of the multi-GPU forward (no counterpart in the single-process reference) ----
  * packed[i] = rows[idx[i]] (row_bytes, a multiple of 16) followed by extra[idx[i]] (extra_bytes, a multiple of 4; extra may be
  * NULL with extra_bytes = 0), i < n: the listed rows of a [nrows, row_bytes] table (and of a second table indexed alike — the

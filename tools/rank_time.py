@@ -1,0 +1,121 @@
+"""Link-prediction timing: HyperGNN.rank_candidates and topk_candidates(k = 10) against the formulation a user has without
+them — embs[q] @ embs.T in query chunks sized to 1 GB of scores, then compare-and-count (resp. torch.topk) — at the sizes of
+BASELINE configs 3 and 2.  Prints one JSON line.
+
+    python tools/rank_time.py [--configs c3,c2] [--batches 1024,16384] [--reps 5] [--no-torch]
+
+Per config and B in (1,024, 16,384): medians of device-event windows (ms, warm) of the two calls without filter lists, of
+the two calls with a filter list per query built from `known` edges (10 per query), and of the torch formulation; the ratio
+torch / ours; the achieved fraction of the fp32 matrix peak, 2 B N d / time / 157.3 TF.  The embeddings are LayerNorm-shaped
+random rows of the config's [N, d] (what the model's last layer emits): the time does not depend on their values beyond the
+insertion rate of the top-k lists, which random rows set at its expected k ln(N / k).  --no-torch leaves the torch
+formulation out (a counter collection of the kernels alone: tools/pmc.sh <prefix> rank_tile_kernel -- python tools/rank_time.py
+--configs c3 --batches 1024 --no-torch)."""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from graph_hypernetwork_forge_amd import HyperGNN  # noqa: E402
+
+CONFIGS = {"c3": dict(N=1_000_000, d=128, seed=1003), "c2": dict(N=100_000, d=64, seed=1002)}
+FP32_MATRIX_PEAK_TF = 157.3
+SCORE_BYTES = 1 << 30
+
+
+def timed(fn, reps):
+    """(median ms, last result) over `reps` device-event windows, after two warm-up calls."""
+    for _ in range(2):
+        out = fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return float(np.median(ts)), out
+
+
+def torch_rank(embs, q, t):
+    N = embs.size(0)
+    step = max(1, SCORE_BYTES // (4 * N))
+    greater, equal = [], []
+    for i in range(0, q.numel(), step):
+        s = embs[q[i:i + step]] @ embs.T
+        ti = s.gather(1, t[i:i + step, None])
+        greater.append((s > ti).sum(1))
+        equal.append((s == ti).sum(1) - 1)
+    return torch.cat(greater), torch.cat(equal)
+
+
+def torch_topk(embs, q, k):
+    N = embs.size(0)
+    step = max(1, SCORE_BYTES // (4 * N))
+    parts = [torch.topk(embs[q[i:i + step]] @ embs.T, k, dim=1) for i in range(0, q.numel(), step)]
+    return torch.cat([p.values for p in parts]), torch.cat([p.indices for p in parts])
+
+
+def run_config(name, reps, batches, with_torch):
+    cfg = CONFIGS[name]
+    dev = torch.device("cuda:0")
+    N, d = cfg["N"], cfg["d"]
+    gen = torch.Generator(device=dev).manual_seed(cfg["seed"])
+    embs = torch.nn.functional.layer_norm(torch.randn(N, d, device=dev, generator=gen), (d,),
+                                          1.0 + 0.1 * torch.randn(d, device=dev, generator=gen),
+                                          0.1 * torch.randn(d, device=dev, generator=gen))
+    model = HyperGNN(text_dim=16, node_feat_dim=8, hidden_dim=16, num_layers=1).to(dev).eval()
+    res = {}
+    for B in batches:
+        rng = np.random.default_rng(B)
+        q = torch.from_numpy(rng.integers(0, N, B)).to(dev)
+        t = torch.from_numpy(rng.integers(0, N, B)).to(dev)
+        known = (q.repeat(10), torch.from_numpy(rng.integers(0, N, 10 * B)).to(dev))
+        flops = 2.0 * B * N * d
+        r = {}
+        r["rank_ms"], ours = timed(lambda: model.rank_candidates(embs, q, t), reps)
+        r["rank_known_ms"], _ = timed(lambda: model.rank_candidates(embs, q, t, known=known), reps)
+        if with_torch:
+            r["torch_rank_ms"], ref = timed(lambda: torch_rank(embs, q, t), reps)
+            r["rank_greater_max_diff_vs_torch"] = int((ours[0] - ref[0]).abs().max())     # rocBLAS sums in another order
+            r["rank_speedup"] = r["torch_rank_ms"] / r["rank_ms"]
+        r["topk_ms"], ours = timed(lambda: model.topk_candidates(embs, q, 10), reps)
+        r["topk_known_ms"], _ = timed(lambda: model.topk_candidates(embs, q, 10, known=known), reps)
+        if with_torch:
+            r["torch_topk_ms"], ref = timed(lambda: torch_topk(embs, q, 10), reps)
+            r["topk_ids_equal_fraction"] = float((ours[1] == ref[1]).float().mean())
+            r["topk_speedup"] = r["torch_topk_ms"] / r["topk_ms"]
+        r["rank_fraction_of_fp32_matrix_peak"] = flops / (r["rank_ms"] * 1e-3) / (FP32_MATRIX_PEAK_TF * 1e12)
+        r["topk_fraction_of_fp32_matrix_peak"] = flops / (r["topk_ms"] * 1e-3) / (FP32_MATRIX_PEAK_TF * 1e12)
+        res[f"B{B}"] = r
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="c3,c2")
+    ap.add_argument("--batches", default="1024,16384")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-torch", action="store_true")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("rank_time.py measures on an MI355X; no HIP device here")
+    out = {"tool": "rank_time", "device": torch.cuda.get_device_name(0)}
+    for name in args.configs.split(","):
+        out[name] = run_config(name, args.reps, [int(b) for b in args.batches.split(",")], not args.no_torch)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
