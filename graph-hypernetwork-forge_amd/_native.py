@@ -387,6 +387,9 @@ def weightgen_fwd(text_emb: torch.Tensor, head_params: Sequence[torch.Tensor], l
     return (W_msg, W_self, bias, acts) if want_acts else (W_msg, W_self, bias)
 
 
+WG_BATCH_MAX = 8       # generators per ghf_weightgen_fwd_batched call: WG_MAX_L in csrc/weightgen.hip (kernel arguments below 4 KB)
+
+
 def weightgen_fwd_batched(text_emb: torch.Tensor, head_params: Sequence[Sequence[torch.Tensor]], log_scales: Sequence[Sequence[torch.Tensor]],
                           T: int, Hh: int, num_hidden: int, d_in: int, d_out: int, layout: int):
     """All L generators of a model in one launch sequence (include/ghf.h: ghf_weightgen_fwd_batched): head_params[g] /
@@ -987,12 +990,20 @@ def tail_fwd(agg: torch.Tensor, h: torch.Tensor, ln_gamma: torch.Tensor, ln_beta
     return h_out
 
 
+def _row_tables(tables):
+    """(rows, extra or None, row bytes, extra bytes) of the one or two tables ghf_rows_pack / ghf_rows_unpack take."""
+    if not 1 <= len(tables) <= 2:
+        raise ValueError(f"rows_pack / rows_unpack take one or two tables, got {len(tables)}")
+    rows = tables[0]
+    extra = tables[1] if len(tables) > 1 else None
+    return rows, extra, rows.size(1) * rows.element_size(), (extra.size(1) * extra.element_size() if extra is not None else 0)
+
+
 def rows_pack(tables, idx: torch.Tensor) -> torch.Tensor:
     """The rows `idx` (int64, device) of one or two row-indexed byte tables ([N, row_bytes] uint8 views of one allocation each)
     as one contiguous message [n, row_bytes (+ extra_bytes)] uint8 — ghf_rows_pack."""
-    rows = tables[0]
-    extra = tables[1] if len(tables) > 1 else None
-    rb, xb = rows.size(1) * rows.element_size(), (extra.size(1) * extra.element_size() if extra is not None else 0)
+    rows, extra, rb, xb = _row_tables(tables)
+    idx = _req(idx, torch.int64, "idx")
     out = torch.empty(idx.numel(), rb + xb, dtype=torch.uint8, device=rows.device)
     _check(load().ghf_rows_pack(_ptr(rows), rb, _ptr(extra), xb, _ptr(idx), idx.numel(), rows.size(0), _ptr(out), _stream()), "ghf_rows_pack")
     return out
@@ -1000,9 +1011,8 @@ def rows_pack(tables, idx: torch.Tensor) -> torch.Tensor:
 
 def rows_unpack(tables, idx: torch.Tensor, packed: torch.Tensor) -> None:
     """ghf_rows_unpack: a received message back to the rows' places in the same tables."""
-    rows = tables[0]
-    extra = tables[1] if len(tables) > 1 else None
-    rb, xb = rows.size(1) * rows.element_size(), (extra.size(1) * extra.element_size() if extra is not None else 0)
+    rows, extra, rb, xb = _row_tables(tables)
+    idx = _req(idx, torch.int64, "idx")
     if packed.numel() != idx.numel() * (rb + xb):
         raise ValueError(f"rows_unpack: message of {packed.numel()} bytes for {idx.numel()} rows of {rb + xb}")
     _check(load().ghf_rows_unpack(_ptr(packed), _ptr(idx), idx.numel(), rows.size(0), _ptr(rows), rb, _ptr(extra), xb, _stream()), "ghf_rows_unpack")

@@ -155,11 +155,9 @@ class NativeOps:
         _native.input_proj_fwd(x, model.input_proj.weight.detach(), model.input_proj.bias.detach(), out=out,
                                h_split=h_split, split_layout=plan.wlayout if h_split is not None else 0)
 
-    def all_weights(self, model, text_embs, plan, after=None):
-        """([weights of layer l], [event l] or None): every layer's generation on a side stream (HyperGNN.generate_all)."""
-        if model.num_layers <= 8:
-            return model.generate_batched(text_embs, plan.wlayout), None      # one launch sequence for all layers, on this stream
-        return model.generate_all(text_embs, plan.wlayout, side_stream=plan.E >= model.SIDE_STREAM_MIN_EDGES // 8, after=after)
+    def all_weights(self, model, text_embs, plan):
+        """[weights of layer l]: every layer's generation, batched, on this stream (HyperGNN.generate_batched)."""
+        return model.generate_batched(text_embs, plan.wlayout)
 
     def split_rows(self, plan, h):
         """What the message kernel gathers: h itself, or its rows cut into 16-bit pieces."""
@@ -374,131 +372,102 @@ class ShardedHyperGNN:
         for b in bufs:
             self._gather_chunk(b, spec, c)
 
-    def _gather_pairs(self, buf: torch.Tensor, spec: ShardSpec, c: int) -> None:
-        """Pairwise exchange of chunk c: my slot to every peer, every peer's slot from it (one batch of sends/receives).
-        Only real rows travel (slots are clipped to N), and slots may differ in size."""
-        nrows = buf.size(0)
-        a, b = spec.slot(c)
-        a, b = min(a, nrows), min(b, nrows)
-        bounce = buf.is_cuda and self.backend == "gloo"
-        mine = buf[a:b].cpu() if bounce else buf[a:b]
-        ops, recvs = [], []
-        for p in range(self.world):
-            if p == self.rank:
-                continue
-            lo, hi = spec.slot(c, p)
-            lo, hi = min(lo, nrows), min(hi, nrows)
-            if b > a:
-                ops.append(dist.P2POp(dist.isend, mine, p, group=self.group))
-            if hi > lo:
-                dst = torch.empty((hi - lo,) + tuple(buf.shape[1:]), dtype=buf.dtype) if bounce else buf[lo:hi]
-                ops.append(dist.P2POp(dist.irecv, dst, p, group=self.group))
-                recvs.append((lo, hi, dst))
-                self.stats["bytes_recv"] = self.stats.get("bytes_recv", 0.0) + dst.numel() * dst.element_size()
+    def _peers(self) -> List[int]:
+        return [p for p in range(self.world) if p != self.rank]
+
+    @staticmethod
+    def _slot_rows(buf: torch.Tensor, spec: ShardSpec, c: int, g: int) -> torch.Tensor:
+        """The rows of rank g's slot of chunk c in a row-indexed buffer (a view; clipped to the buffer's rows)."""
+        lo, hi = spec.slot(c, g)
+        return buf[min(lo, buf.size(0)): min(hi, buf.size(0))]
+
+    def _peer_exchange(self, sends: Dict[int, torch.Tensor], into: Dict[int, torch.Tensor], stat: Optional[str]) -> None:
+        """One batch of pairwise messages: sends[p] goes to peer p, peer p's message lands in into[p] (a view of the caller's
+        buffer is fine: RCCL then receives in place); empty tensors do not travel.  Peers in ascending rank order, the send
+        before the receive for each.  gloo moves host memory only, so device tensors bounce through host copies (this is
+        how the multi-rank GPU tests run several ranks on one card).  The received bytes are added to self.stats[stat]
+        ("bytes_recv" / "bytes_recv_bwd"; None: plan-time traffic, not counted)."""
+        bounce = self.backend == "gloo"
+        ops, keep, staged = [], [], []
+        for p in sorted(set(sends) | set(into)):
+            if p in sends and sends[p].numel():
+                t = sends[p].cpu() if bounce and sends[p].is_cuda else sends[p].contiguous()
+                keep.append(t)                                    # alive until the wait
+                ops.append(dist.P2POp(dist.isend, t, p, group=self.group))
+            if p in into and into[p].numel():
+                dst = into[p]
+                t = torch.empty(dst.shape, dtype=dst.dtype) if bounce and dst.is_cuda else dst
+                if t is not dst:
+                    staged.append((dst, t))
+                ops.append(dist.P2POp(dist.irecv, t, p, group=self.group))
+                if stat is not None:
+                    self.stats[stat] = self.stats.get(stat, 0.0) + dst.numel() * dst.element_size()
         if ops:
             for req in dist.batch_isend_irecv(ops):
                 req.wait()
-        if bounce:
-            for lo, hi, t in recvs:
-                buf[lo:hi].copy_(t)
+        for dst, t in staged:
+            dst.copy_(t)
+
+    def _gather_pairs(self, buf: torch.Tensor, spec: ShardSpec, c: int) -> None:
+        """Pairwise exchange of chunk c: my slot to every peer, every peer's slot from it, received in place.
+        Only real rows travel (slots are clipped to N), and slots may differ in size."""
+        mine = self._slot_rows(buf, spec, c, self.rank)
+        self._peer_exchange({p: mine for p in self._peers()}, {p: self._slot_rows(buf, spec, c, p) for p in self._peers()},
+                            "bytes_recv")
+
+    # the sparse exchanges' messages: rows `idx` of every table ([N, bytes] uint8 views), side by side — ops.pack_rows /
+    # ops.unpack_rows (csrc/exchange.hip) where the ops object has them and the tables are on the GPU, else torch indexing
+    # (the CPU rehearsal); the layout is the same
+    def _pack_rows(self, tables: List[torch.Tensor], idx: torch.Tensor) -> torch.Tensor:
+        if hasattr(self.ops, "pack_rows") and tables[0].is_cuda:
+            return self.ops.pack_rows(tables, idx)
+        return torch.cat([t.index_select(0, idx) for t in tables], dim=1)
+
+    def _unpack_rows(self, tables: List[torch.Tensor], idx: torch.Tensor, packed: torch.Tensor) -> None:
+        if hasattr(self.ops, "unpack_rows") and tables[0].is_cuda:
+            return self.ops.unpack_rows(tables, idx, packed)
+        for t, part in zip(tables, torch.split(packed, [t.size(1) for t in tables], dim=1)):
+            t.index_copy_(0, idx, part)
 
     def _gather_sparse(self, bufs: List[torch.Tensor], spec: ShardSpec, c: int) -> None:
         """Chunk c, needed rows only: to every peer the rows of my slot it asked for at plan time, from every peer the rows of
         its slot that my edges read, scattered to their places — ONE message per peer for all of `bufs` (the split form's
-        rows and their scales travel together): ops.pack_rows -> pairwise send/recv -> ops.unpack_rows.  Rows nobody on this
-        rank reads stay stale.  (ops without pack_rows — the CPU rehearsal's — go buffer by buffer through torch indexing.)"""
+        rows and their scales travel together).  Rows nobody on this rank reads stay stale."""
         send_idx, recv_idx = self._sparse["send"][c], self._sparse["recv"][c]
-        if not hasattr(self.ops, "pack_rows") or not bufs[0].is_cuda:
-            for buf in bufs:
-                self._gather_sparse_torch(buf, send_idx, recv_idx)
-            return
-        bounce = self.backend == "gloo"
-        ops, recvs, keep = [], [], []
-        row_bytes = sum(b.size(1) * b.element_size() for b in bufs)
-        for p in range(self.world):
-            if p == self.rank:
-                continue
-            if send_idx[p].numel():
-                packed = self.ops.pack_rows(bufs, send_idx[p])
-                packed = packed.cpu() if bounce else packed
-                keep.append(packed)
-                ops.append(dist.P2POp(dist.isend, packed, p, group=self.group))
-            if recv_idx[p].numel():
-                t = torch.empty(recv_idx[p].numel(), row_bytes, dtype=torch.uint8, device="cpu" if bounce else bufs[0].device)
-                ops.append(dist.P2POp(dist.irecv, t, p, group=self.group))
-                recvs.append((recv_idx[p], t))
-                self.stats["bytes_recv"] = self.stats.get("bytes_recv", 0.0) + t.numel()
-        if ops:
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
-        for idx, t in recvs:
-            self.ops.unpack_rows(bufs, idx, t.to(bufs[0].device) if bounce else t)
-
-    def _gather_sparse_torch(self, buf: torch.Tensor, send_idx, recv_idx) -> None:
-        bounce = buf.is_cuda and self.backend == "gloo"
-        ops, recvs, keep = [], [], []
-        for p in range(self.world):
-            if p == self.rank:
-                continue
-            if send_idx[p].numel():
-                packed = buf.index_select(0, send_idx[p])
-                packed = packed.cpu() if bounce else packed
-                keep.append(packed)
-                ops.append(dist.P2POp(dist.isend, packed, p, group=self.group))
-            if recv_idx[p].numel():
-                t = torch.empty((recv_idx[p].numel(),) + tuple(buf.shape[1:]), dtype=buf.dtype, device="cpu" if bounce else buf.device)
-                ops.append(dist.P2POp(dist.irecv, t, p, group=self.group))
-                recvs.append((recv_idx[p], t))
-                self.stats["bytes_recv"] = self.stats.get("bytes_recv", 0.0) + t.numel() * t.element_size()
-        if ops:
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
-        for idx, t in recvs:
-            buf.index_copy_(0, idx, t.to(buf.device) if bounce else t)
+        tables = [b.view(torch.uint8).view(b.size(0), -1) for b in bufs]
+        row_bytes = sum(t.size(1) for t in tables)
+        sends = {p: self._pack_rows(tables, send_idx[p]) for p in self._peers() if send_idx[p].numel()}
+        into = {p: torch.empty(recv_idx[p].numel(), row_bytes, dtype=torch.uint8, device=tables[0].device)
+                for p in self._peers() if recv_idx[p].numel()}
+        self._peer_exchange(sends, into, "bytes_recv")
+        for p, packed in into.items():
+            self._unpack_rows(tables, recv_idx[p], packed)
 
     def _plan_sparse(self, plan: GraphPlan, spec: ShardSpec, device) -> dict:
         """Who needs which rows: recv[c][p] = the rows of rank p's slot of chunk c that this rank's edges read (sorted row ids,
         on the device), send[c][q] = the rows of MY slot of chunk c that rank q reads.  One exchange of index lists per
-        plan (host tensors through the group: counts by all_gather, lists pairwise)."""
+        plan (counts by all_gather, lists pairwise)."""
         G, C, me = self.world, spec.chunks, self.rank
-        # the lists travel through the group on the backend's own memory: host tensors over gloo, device tensors over RCCL
-        comm = torch.device("cpu") if self.backend == "gloo" else torch.device(device)
         if plan.E > 0:
-            need = torch.unique(self.ops.plan_sources(plan))
-            slot = torch.bucketize(need, torch.tensor(spec.bounds[1:], dtype=torch.int64, device=need.device), right=True)
-            need, slot = need.to(comm), slot.to(comm)
+            need = torch.unique(self.ops.plan_sources(plan)).to(device)
+            slot = torch.bucketize(need, torch.tensor(spec.bounds[1:], dtype=torch.int64, device=device), right=True)
         else:
-            need = slot = torch.zeros(0, dtype=torch.int64, device=comm)
-        want = [[need[(slot == c * G + p)].contiguous() if p != me else need[:0] for p in range(G)] for c in range(C)]
-        cnt = torch.tensor([[want[c][p].numel() for p in range(G)] for c in range(C)], dtype=torch.int64, device=comm)
+            need = slot = torch.zeros(0, dtype=torch.int64, device=device)
+        recv = [[need[(slot == c * G + p)].contiguous() if p != me else need[:0] for p in range(G)] for c in range(C)]
+        # (the counts are a host tensor over gloo, which moves host memory only)
+        cnt = torch.tensor([[recv[c][p].numel() for p in range(G)] for c in range(C)], dtype=torch.int64,
+                           device="cpu" if self.backend == "gloo" else device)
         allc = [torch.zeros_like(cnt) for _ in range(G)]
         dist.all_gather(allc, cnt, group=self.group)                    # allc[q][c][p]: rows q needs from p in chunk c
         allc = [t.cpu() for t in allc]
-        ops, bufs, keep = [], {}, []
-        for p in range(G):
-            if p == me:
-                continue
-            out = torch.cat([want[c][p] for c in range(C)]) if C else need[:0]
-            if out.numel():
-                keep.append(out)
-                ops.append(dist.P2POp(dist.isend, out, p, group=self.group))
-            n_in = int(allc[p][:, me].sum())
-            if n_in:
-                bufs[p] = torch.empty(n_in, dtype=torch.int64, device=comm)
-                ops.append(dist.P2POp(dist.irecv, bufs[p], p, group=self.group))
-        if ops:
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
-        empty = torch.zeros(0, dtype=torch.int64, device=device)
-        send = [[empty] * G for _ in range(C)]
-        for p, t in bufs.items():
-            parts = torch.split(t, [int(allc[p][c, me]) for c in range(C)])
-            for c in range(C):
-                send[c][p] = parts[c].to(device)
-        recv = [[want[c][p].to(device) for p in range(G)] for c in range(C)]
-        cnt = cnt.cpu()
+        asked = {p: torch.empty(int(allc[p][:, me].sum()), dtype=torch.int64, device=device) for p in self._peers()}
+        self._peer_exchange({p: torch.cat([recv[c][p] for c in range(C)]) for p in self._peers()}, asked, None)
+        send = [[need[:0]] * G for _ in range(C)]
+        for p, t in asked.items():
+            for c, part in enumerate(torch.split(t, [int(allc[p][c, me]) for c in range(C)])):
+                send[c][p] = part
         owned = sum(hi - lo for lo, hi in spec.owned())
-        return {"send": send, "recv": recv, "rows_needed": int(cnt.sum()), "rows_other": int(spec.N - owned)}
+        return {"send": send, "recv": recv, "rows_needed": int(allc[me].sum()), "rows_other": int(spec.N - owned)}
 
     def _run_chunked(self, bufs, spec: ShardSpec, compute_rows, full_rows: bool = False) -> None:
         """compute_rows(lo, hi) fills my rows of a chunk in every buffer of `bufs`; the chunk's exchange overlaps the next
@@ -610,12 +579,7 @@ class ShardedHyperGNN:
         out = self._forward_on(node_features, plan)
         self.last_range_flags = 0
         if guard:
-            # every rank must take the same decision: the guard bits are OR-ed across the ranks (one small collective: MAX
-            # per bit — a MAX of the words would turn {1, 2} into 2)
-            word = flag.cpu() if self.backend == "gloo" else flag
-            bits = torch.stack([(word >> i) & 1 for i in range(3)]).flatten()
-            dist.all_reduce(bits, op=dist.ReduceOp.MAX, group=self.group)
-            word = sum(int(b) << i for i, b in enumerate(bits.tolist()))
+            word = self._reduce_guard(flag)                    # every rank must take the same decision
             self.last_range_flags = word
             if word:
                 # Some row of h or some relation's weights spans more dynamic range than two fp16 pieces hold (include/ghf.h:
@@ -639,13 +603,17 @@ class ShardedHyperGNN:
             return self._forward_split(node_features, plan, spec, text_embs, h, h_next)
         return self._forward_rows(node_features, plan, spec, text_embs, h, h_next)
 
+    def _all_weights(self, text_embs, plan) -> List:
+        """ops.all_weights' list.  The ops object is an injection seam: one written against the earlier interface returns
+        (list, events) — generated on the caller's stream, the events None — and keeps working: its list is taken."""
+        w = self.ops.all_weights(self.model, text_embs, plan)
+        return w[0] if isinstance(w, tuple) else w
+
     def _forward_rows(self, node_features, plan, spec, text_embs, h, h_next) -> torch.Tensor:
-        model, N, device = self.model, node_features.size(0), node_features.device
-        all_w, ready = self.ops.all_weights(model, text_embs, plan)
+        model, N = self.model, node_features.size(0)
+        all_w = self._all_weights(text_embs, plan)
         self.ops.input_proj(model, node_features, h[:N], None, plan)
         for l in range(model.num_layers):
-            if ready is not None and ready[l] is not None:
-                torch.cuda.current_stream(device).wait_event(ready[l])
             weights = all_w[l]
             src, dst = h, h_next
             self.ops.layer_begin(model, l, weights, src[:N], plan)
@@ -662,19 +630,10 @@ class ShardedHyperGNN:
         model, ops = self.model, self.ops
         N, d, device = node_features.size(0), model.hidden_dim, node_features.device
         hs, hs_next = ops.alloc_split(plan, N, d, device), ops.alloc_split(plan, N, d, device)
-
-        te_done = None
-        if node_features.is_cuda:
-            te_done = torch.cuda.Event()
-            te_done.record(torch.cuda.current_stream(device))
         ops.input_proj(model, node_features, h[:N], hs, plan)
-        # enqueued after the projection so that its kernel is not queued behind the generators' on a shared hardware
-        # queue; the side stream itself only waits for the text embeddings
-        all_w, ready = ops.all_weights(model, text_embs, plan, after=te_done)
+        all_w = self._all_weights(text_embs, plan)
         last = model.num_layers - 1
         for l in range(model.num_layers):
-            if ready is not None and ready[l] is not None:
-                torch.cuda.current_stream(device).wait_event(ready[l])
             weights = all_w[l]
             src, dst, src_split = h, h_next, hs
             out_split = None if l == last else hs_next
@@ -691,15 +650,13 @@ class ShardedHyperGNN:
         model, ops = self.model, self.ops
         N, d, device = node_features.size(0), model.hidden_dim, node_features.device
         G, S = self.world, spec.S
-        all_w, ready = ops.all_weights(model, text_embs, plan)
+        all_w = self._all_weights(text_embs, plan)
         ops.input_proj(model, node_features, h[:N], None, plan)
         partial = torch.empty(spec.padded_rows, d, dtype=torch.float32, device=device)
         if spec.padded_rows > N:
             partial[N:].zero_()
         lo, hi = spec.slot(0)
         for l in range(model.num_layers):
-            if ready is not None and ready[l] is not None:
-                torch.cuda.current_stream(device).wait_event(ready[l])
             weights = all_w[l]
             src_split = ops.split_rows(plan, h[:N])
             if self.profile != "exchange":
@@ -756,7 +713,8 @@ class ShardedHyperGNN:
         return out
 
     def _reduce_guard(self, flag: torch.Tensor) -> int:
-        """The range-guard bits OR-ed over the ranks (MAX per bit)."""
+        """The range-guard bits OR-ed over the ranks: one small collective, MAX per bit (a MAX of the words would turn
+        {1, 2} into 2)."""
         word = flag.cpu() if self.backend == "gloo" else flag
         bits = torch.stack([(word >> i) & 1 for i in range(3)]).flatten()
         dist.all_reduce(bits, op=dist.ReduceOp.MAX, group=self.group)
@@ -869,58 +827,23 @@ class ShardedHyperGNN:
     def _reduce_pairs(self, dh: torch.Tensor, spec: ShardSpec, c: int) -> None:
         """Adjoint of _gather_pairs: to every peer my rows of its slot of chunk c, from every peer its rows of my slot, added
         to mine in rank order (so the bits do not depend on arrival order)."""
-        N = dh.size(0)
-        a, b = (min(x, N) for x in spec.slot(c))
-        bounce = dh.is_cuda and self.backend == "gloo"
-        ops, recvs, keep = [], {}, []
-        for p in range(self.world):
-            if p == self.rank:
-                continue
-            lo, hi = (min(x, N) for x in spec.slot(c, p))
-            if hi > lo:
-                t = dh[lo:hi].cpu() if bounce else dh[lo:hi].contiguous()
-                keep.append(t)
-                ops.append(dist.P2POp(dist.isend, t, p, group=self.group))
-            if b > a:
-                r = torch.empty((b - a,) + tuple(dh.shape[1:]), dtype=dh.dtype, device="cpu" if bounce else dh.device)
-                ops.append(dist.P2POp(dist.irecv, r, p, group=self.group))
-                recvs[p] = r
-                self.stats["bytes_recv_bwd"] += r.numel() * r.element_size()
-        if ops:
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
-        for p in sorted(recvs):
-            self.ops.accumulate_rows(dh[a:b], None, recvs[p].to(dh.device) if bounce else recvs[p])
+        mine = self._slot_rows(dh, spec, c, self.rank)
+        into = {p: torch.empty_like(mine) for p in self._peers()}
+        self._peer_exchange({p: self._slot_rows(dh, spec, c, p) for p in self._peers()}, into, "bytes_recv_bwd")
+        if mine.size(0):
+            for p in sorted(into):
+                self.ops.accumulate_rows(mine, None, into[p])
 
     def _reduce_sparse(self, dh: torch.Tensor, sparse: dict, c: int) -> None:
         """Adjoint of _gather_sparse: to peer p the rows of its slot that my edges read (recv[c][p] — my only nonzero rows
         outside my slots), from peer q its rows of my slot that q read (send[c][q]), added at their places in rank order."""
         send_idx, recv_idx = sparse["send"][c], sparse["recv"][c]
-        bounce = dh.is_cuda and self.backend == "gloo"
-        native = hasattr(self.ops, "pack_rows") and dh.is_cuda
-        d = dh.size(1)
-        ops, recvs, keep = [], {}, []
-        for p in range(self.world):
-            if p == self.rank:
-                continue
-            if recv_idx[p].numel():
-                if native:
-                    t = self.ops.pack_rows([dh], recv_idx[p]).view(dh.dtype).view(-1, d)
-                else:
-                    t = dh.index_select(0, recv_idx[p])
-                t = t.cpu() if bounce else t
-                keep.append(t)
-                ops.append(dist.P2POp(dist.isend, t, p, group=self.group))
-            if send_idx[p].numel():
-                r = torch.empty(send_idx[p].numel(), d, dtype=dh.dtype, device="cpu" if bounce else dh.device)
-                ops.append(dist.P2POp(dist.irecv, r, p, group=self.group))
-                recvs[p] = r
-                self.stats["bytes_recv_bwd"] += r.numel() * r.element_size()
-        if ops:
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
-        for p in sorted(recvs):
-            self.ops.accumulate_rows(dh, send_idx[p], recvs[p].to(dh.device) if bounce else recvs[p])
+        d, table = dh.size(1), [dh.view(torch.uint8).view(dh.size(0), -1)]
+        sends = {p: self._pack_rows(table, recv_idx[p]).view(dh.dtype).view(-1, d) for p in self._peers() if recv_idx[p].numel()}
+        into = {p: torch.empty(send_idx[p].numel(), d, dtype=dh.dtype, device=dh.device) for p in self._peers() if send_idx[p].numel()}
+        self._peer_exchange(sends, into, "bytes_recv_bwd")
+        for p in sorted(into):
+            self.ops.accumulate_rows(dh, send_idx[p], into[p])
 
     __call__ = forward
 

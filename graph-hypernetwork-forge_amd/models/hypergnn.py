@@ -6,9 +6,9 @@ edge_index, edge_texts)`` signature and ``ValueError`` behaviour as
 forward is a sequence of C-ABI calls into ``libghf_hip.so``:
 
     plan (cached)            ghf_plan_build            replaces hypergnn.py:264-268 + edge order
+    weights per relation     ghf_weightgen_fwd_batched replaces :278 (weight_generator.py:137-141), all layers up front
     h0 = relu(x W_in^T + b)  ghf_input_proj_fwd        replaces :261
     per layer:
-      weights per relation   ghf_weightgen_fwd         replaces :278 (weight_generator.py:137-141)
       messages+mean+self+tail ghf_message_layer_fwd    replaces :281-296
 
 The per-edge weight gather of the reference (:281-283, O(E d^2) memory) does
@@ -191,14 +191,21 @@ class HyperGNN(nn.Module):
 
     def graphed(self, node_features: torch.Tensor, edge_index: torch.Tensor, edge_texts: List[str]) -> GraphedForward:
         """Capture ``forward`` for these inputs into a HIP graph (inference only); see GraphedForward."""
-        if edge_index.size(1) != len(edge_texts):
-            raise ValueError(f"edge_index has {edge_index.size(1)} edges but edge_texts has {len(edge_texts)} entries")
-        if node_features.dim() != 2 or node_features.size(1) != self.node_feat_dim:
-            raise ValueError(f"node_features must be [N, {self.node_feat_dim}], got {tuple(node_features.shape)}")
+        self._check_inputs(node_features, edge_index, edge_texts, "edge_texts")
         if not node_features.is_cuda:
             raise RuntimeError("HyperGNN computes on an MI355X HIP device only; there is no CPU path to capture")
         plan = self.plan_for(edge_index, edge_texts, node_features.size(0), node_features.device)
         return GraphedForward(self, node_features, plan)
+
+    def _check_inputs(self, node_features: torch.Tensor, edge_index: torch.Tensor, per_edge, name: str) -> None:
+        """Every entry point's input checks (reference :252-256): `per_edge` — the strings, or a 1-D tensor of relation ids —
+        holds one entry per edge, and the features are [N, node_feat_dim]."""
+        ids = isinstance(per_edge, torch.Tensor)
+        n = per_edge.numel() if ids else len(per_edge)
+        if (ids and per_edge.dim() != 1) or edge_index.size(1) != n:
+            raise ValueError(f"edge_index has {edge_index.size(1)} edges but {name} has {n} entries")
+        if node_features.dim() != 2 or node_features.size(1) != self.node_feat_dim:
+            raise ValueError(f"node_features must be [N, {self.node_feat_dim}], got {tuple(node_features.shape)}")
 
     def clear_plan_cache(self) -> None:
         self._plans.clear()
@@ -210,10 +217,7 @@ class HyperGNN(nn.Module):
         The reference's call form hands over one Python string per edge; mapping those to ids is pure host work
         (1.5 s at 10 M edges, reference hypergnn.py:264-268).  This overload skips it: the ids
         may live on the device, nothing O(E) runs on the host, and the plan is cached on the two tensors' identity."""
-        if edge_rel_ids.dim() != 1 or edge_index.size(1) != edge_rel_ids.numel():
-            raise ValueError(f"edge_index has {edge_index.size(1)} edges but edge_rel_ids has {edge_rel_ids.numel()} entries")
-        if node_features.dim() != 2 or node_features.size(1) != self.node_feat_dim:
-            raise ValueError(f"node_features must be [N, {self.node_feat_dim}], got {tuple(node_features.shape)}")
+        self._check_inputs(node_features, edge_index, edge_rel_ids, "edge_rel_ids")
         grad = wants_grad(self, node_features) or self._dropping()
         plan = self._ids_plan(edge_index, edge_rel_ids, relation_texts, node_features, grad)
         if grad:
@@ -237,11 +241,7 @@ class HyperGNN(nn.Module):
 
     # -- forward (reference :236-298) -----------------------------------------------------
     def forward(self, node_features: torch.Tensor, edge_index: torch.Tensor, edge_texts: List[str]) -> torch.Tensor:
-        if edge_index.size(1) != len(edge_texts):                     # reference :252-256
-            raise ValueError(f"edge_index has {edge_index.size(1)} edges but "
-                             f"edge_texts has {len(edge_texts)} entries")
-        if node_features.dim() != 2 or node_features.size(1) != self.node_feat_dim:
-            raise ValueError(f"node_features must be [N, {self.node_feat_dim}], got {tuple(node_features.shape)}")
+        self._check_inputs(node_features, edge_index, edge_texts, "edge_texts")
         grad = wants_grad(self, node_features) or self._dropping()
         device = node_features.device
         # The reference maps the strings to ids on every call (:264-268).  Here a cached plan is used at once and, when the
@@ -270,11 +270,7 @@ class HyperGNN(nn.Module):
         288-296), so the result is exact, not sampled.  `nodes`: a 1-D int32 / int64 tensor (device or CPU), duplicates and
         negative ids (as torch indexing) allowed.  Gradients reach the parameters and `node_features`; dropout masks in
         training mode are drawn over the subgraph's rows (random as in ``forward``, not the full forward's draws)."""
-        if edge_index.size(1) != len(edge_texts):                     # reference :252-256
-            raise ValueError(f"edge_index has {edge_index.size(1)} edges but "
-                             f"edge_texts has {len(edge_texts)} entries")
-        if node_features.dim() != 2 or node_features.size(1) != self.node_feat_dim:
-            raise ValueError(f"node_features must be [N, {self.node_feat_dim}], got {tuple(node_features.shape)}")
+        self._check_inputs(node_features, edge_index, edge_texts, "edge_texts")
         seeds = self._seed_ids(nodes, node_features)
         grad = wants_grad(self, node_features) or self._dropping()
         plan = self._plan_lookup(edge_index, edge_texts, node_features.size(0), node_features.device, training=grad)[0]
@@ -283,32 +279,20 @@ class HyperGNN(nn.Module):
     def forward_nodes_ids(self, node_features: torch.Tensor, edge_index: torch.Tensor, edge_rel_ids: torch.Tensor,
                           relation_texts: Sequence[str], nodes: torch.Tensor) -> torch.Tensor:
         """``forward_nodes`` for callers that already hold relation ids (see ``forward_ids``)."""
-        if edge_rel_ids.dim() != 1 or edge_index.size(1) != edge_rel_ids.numel():
-            raise ValueError(f"edge_index has {edge_index.size(1)} edges but edge_rel_ids has {edge_rel_ids.numel()} entries")
-        if node_features.dim() != 2 or node_features.size(1) != self.node_feat_dim:
-            raise ValueError(f"node_features must be [N, {self.node_feat_dim}], got {tuple(node_features.shape)}")
+        self._check_inputs(node_features, edge_index, edge_rel_ids, "edge_rel_ids")
         seeds = self._seed_ids(nodes, node_features)
         grad = wants_grad(self, node_features) or self._dropping()
         plan = self._ids_plan(edge_index, edge_rel_ids, relation_texts, node_features, grad)
         return self._forward_nodes(node_features, plan, seeds, grad, edge_index)
 
-    @staticmethod
-    def _seed_ids(nodes: torch.Tensor, node_features: torch.Tensor) -> torch.Tensor:
-        """`nodes` checked as torch indexing checks them, negative ids wrapped: int64 on node_features' device."""
-        if not isinstance(nodes, torch.Tensor) or nodes.dim() != 1:
-            raise ValueError(f"nodes must be a 1-D tensor of node ids, got {getattr(nodes, 'shape', type(nodes))}")
-        if nodes.dtype not in (torch.int32, torch.int64):
-            raise TypeError(f"nodes must be int32 or int64, got {nodes.dtype}")
+    @classmethod
+    def _seed_ids(cls, nodes: torch.Tensor, node_features: torch.Tensor) -> torch.Tensor:
+        """`nodes` through _rank_ids, for features that must already be on the device (forward_nodes has no CPU path)."""
+        ids = cls._rank_ids(nodes, node_features.size(0), node_features, "nodes")
         if not node_features.is_cuda:
             raise RuntimeError("HyperGNN computes on an MI355X HIP device only; node_features is on the CPU and there is "
                                "no CPU path")
-        N = node_features.size(0)
-        if nodes.numel():
-            lo, hi = (int(v) for v in torch.aminmax(nodes))
-            if lo < -N or hi >= N:
-                raise IndexError(f"nodes hold ids outside [-{N}, {N}) (range {lo}..{hi})")
-        ids = nodes.to(device=node_features.device, dtype=torch.int64)
-        return torch.where(ids < 0, ids + N, ids)
+        return ids
 
     def _forward_nodes(self, x: torch.Tensor, plan: GraphPlan, seeds: torch.Tensor, grad: bool,
                        edge_index: torch.Tensor) -> torch.Tensor:
@@ -387,9 +371,9 @@ class HyperGNN(nn.Module):
         generated = []
         if side:
             main = torch.cuda.current_stream(device)
-            if self._wg_stream is None or self._wg_stream[0].device != device:
-                self._wg_stream = [torch.cuda.Stream(device=device) for _ in range(self.num_layers)]
-            st = self._wg_stream[0]                        # one stream, one hand-over each way (a hop costs ~40 us)
+            if self._wg_stream is None or self._wg_stream.device != device:
+                self._wg_stream = torch.cuda.Stream(device=device)
+            st = self._wg_stream                           # one stream, one hand-over each way (a hop costs ~40 us)
             st.wait_stream(main)
             with torch.cuda.stream(st):
                 for gen in self.weight_generators:
@@ -418,57 +402,15 @@ class HyperGNN(nn.Module):
         """Every layer's (W_msg | Wfrag, W_self | None, bias) from ONE launch sequence (ghf_weightgen_fwd_batched: the layers'
         generators have identical shapes) — three kernels for all layers on the caller's stream: ~0.11 ms whatever the
         number of layers, where layer-by-layer generation cost that per layer (between the message launches of a small
-        graph: BASELINE config 2) or needed side streams and events to hide (config 3)."""
-        g0 = self.weight_generators[0]
-        return _native.weightgen_fwd_batched(text_embs, [g._head_params() for g in self.weight_generators],
-                                             [g._log_scale_vector() for g in self.weight_generators], g0.text_dim, g0.hidden_dim,
-                                             g0.num_hidden, g0.d_in, g0.d_out, layout)
-
-    def generate_all(self, text_embs: torch.Tensor, layout: int, side_stream: bool = True, after=None, first=None):
-        """([weights of layer l], [event l or None]): every layer's weight generation.  The generated weights depend on
-        the relation strings only, so on large graphs their ~0.13 ms of small latency-bound kernels per layer are
-        launched on a side stream and run in the shadow of the previous layers (C3: 13.0 -> 12.7 ms per forward); the
-        caller's stream waits for event l before layer l.  On small graphs the cross-stream events cost more than they
-        hide (C2: 0.66 -> 0.75 ms), so there the kernels stay in the caller's stream."""
-        if not side_stream:
-            return [gen.generate(text_embs, layout) for gen in self.weight_generators], [None] * self.num_layers
-        dev = text_embs.device
-        main = torch.cuda.current_stream(dev)
-        # one side stream per layer: the generators are independent chains of small latency-bound kernels, so side by side
-        # all of them finish in the shadow of the input projection; in ONE side stream the later layers' kernels ran beside
-        # the first message launch, which holds every CU's LDS — they trickled in as workgroups retired (0.3 ms each instead
-        # of 0.05) and cost that launch 6 %
-        nside = max(1, self.num_layers)
-        if self._wg_stream is None or self._wg_stream[0].device != dev or len(self._wg_stream) != nside:
-            # (high-priority streams measured worse: 10.8 -> 11.6 ms per C3 forward)
-            self._wg_stream = [torch.cuda.Stream(device=dev) for _ in range(nside)]
-        weights, ready = [], []
-        nfirst = 0 if first is None else 1
-        if nfirst:                                             # layer 0's weights: already generated on the caller's stream
-            weights.append(first)
-            ready.append(None)
-        try:
-            for l, gen in enumerate(self.weight_generators):
-                if l < nfirst:
-                    continue
-                side = self._wg_stream[l % nside]
-                if l < nside + nfirst:                         # a side stream's first use in this call
-                    if after is not None:
-                        side.wait_event(after)                            # an event recorded once text_embs was enqueued
-                    else:
-                        side.wait_stream(main)                            # text_embs, and the previous call's readers
-                torch.cuda.set_stream(side)
-                weights.append(gen.generate(text_embs, layout))
-                ev = torch.cuda.Event()
-                ev.record(side)
-                ready.append(ev)
-        finally:
-            torch.cuda.set_stream(main)
-        for ws in weights:
-            for t in ws:
-                if t is not None:
-                    t.record_stream(main)
-        return weights, ready
+        graph: BASELINE config 2).  A model deeper than one call takes (_native.WG_BATCH_MAX generators) gets one launch
+        sequence per group of consecutive layers."""
+        gens, g0, out = list(self.weight_generators), self.weight_generators[0], []
+        for i in range(0, len(gens), _native.WG_BATCH_MAX):
+            group = gens[i:i + _native.WG_BATCH_MAX]
+            out += _native.weightgen_fwd_batched(text_embs, [g._head_params() for g in group],
+                                                 [g._log_scale_vector() for g in group], g0.text_dim, g0.hidden_dim,
+                                                 g0.num_hidden, g0.d_in, g0.d_out, layout)
+        return out
 
     def forward_planned(self, node_features: torch.Tensor, plan: GraphPlan,
                         exchange=None, guard: bool = True, rows_per_layer: Optional[Sequence[int]] = None) -> torch.Tensor:
@@ -511,21 +453,12 @@ class HyperGNN(nn.Module):
         text_embs = self.text_encoder(plan.unique_texts, device)     # [U, text_dim]
         # the 16-bit-piece kernels gather rows already cut into pieces: the input projection emits them for the first
         # layer, every layer's tail for the next
-        main = torch.cuda.current_stream(device)
-        te_done = torch.cuda.Event()
-        te_done.record(main)
         split = plan.wlayout in _native.SPLIT_LAYOUTS
         hs = _native.alloc_split(x.size(0), self.hidden_dim, plan.wlayout, device) if split else None
         hs_next = torch.empty_like(hs) if split else None
-        # Only layer 0's weights are needed before the first message launch.  Its generator — five small latency-bound
-        # kernels, ~0.15 ms alone — runs FIRST, on this stream: beside the input projection, which saturates HBM, the same
-        # kernels took 0.4 + 0.3 ms and the first message launch waited for them (kernel-trace timeline, round 3: 0.76 ms
-        # before the first message launch).  The later layers' generators run beside the projection on side streams as before.
-        side = plan.E >= self.SIDE_STREAM_MIN_EDGES
-        batched = self.num_layers <= 8
-        if batched:                                # all layers' generators in one launch sequence, first (round 3)
-            weights, ready = self.generate_batched(text_embs, plan.wlayout), [None] * self.num_layers
-        w0 = self.weight_generators[0].generate(text_embs, plan.wlayout) if not batched and side else None
+        # All layers' generators first, on this stream: beside the input projection, which saturates HBM, the same small
+        # latency-bound kernels took several times as long and the first message launch waited for them.
+        weights = self.generate_batched(text_embs, plan.wlayout)
         h = _native.input_proj_fwd(x, self.input_proj.weight.detach(), self.input_proj.bias.detach(), h_split=hs,
                                    split_layout=plan.wlayout if split else 0)
         h_next = torch.empty_like(h)
@@ -536,14 +469,9 @@ class HyperGNN(nn.Module):
             h_next.zero_()
             if split:
                 hs_next.zero_()
-        # (enqueued after the input projection: streams can share a hardware queue, and packets queue in host order)
-        if not batched:
-            weights, ready = self.generate_all(text_embs, plan.wlayout, side_stream=side, after=te_done, first=w0)
         lo, hi = plan.row_lo, (plan.row_hi or plan.N)
         last = len(self.weight_generators) - 1
         for l, norm in enumerate(self.layer_norms):
-            if ready[l] is not None:
-                main.wait_event(ready[l])
             W, W_self, bias = weights[l]
             if l == last and before_last is not None:
                 before_last()
@@ -581,9 +509,9 @@ class HyperGNN(nn.Module):
         h_next = torch.empty_like(h)
         Y = rs.scratch(plan.E, self.hidden_dim, device)
         last = len(self.layer_norms) - 1
-        all_w = self.generate_batched(text_embs, _native.WLAYOUT_NATURAL) if self.num_layers <= 8 else None
-        for l, (gen, norm) in enumerate(zip(self.weight_generators, self.layer_norms)):
-            W_msg, W_self, bias = all_w[l] if all_w is not None else gen.generate(text_embs, _native.WLAYOUT_NATURAL)
+        all_w = self.generate_batched(text_embs, _native.WLAYOUT_NATURAL)
+        for l, norm in enumerate(self.layer_norms):
+            W_msg, W_self, bias = all_w[l]
             if plan.E > 0:
                 _native.edge_transform_fwd(h, rs, W_msg, W_self, bias, Y, h_split=hs, exact=exact)
             _native.segment_tail_fwd(Y, rs, h, norm.weight.detach(), norm.bias.detach(), norm.eps, h_next, row0=lo, rows=hi - lo,

@@ -59,10 +59,10 @@ class OracleOps:
         if h_split is not None:
             self.split_range(plan, out, h_split, 0, out.size(0))
 
-    def all_weights(self, model, text_embs, plan, after=None):
+    def all_weights(self, model, text_embs, plan):
         d = model.hidden_dim
         return [O.weight_generator(self._params(model), f"weight_generators.{l}.", text_embs, d, d)
-                for l in range(model.num_layers)], None
+                for l in range(model.num_layers)]
 
     def split_rows(self, plan, h):
         return None

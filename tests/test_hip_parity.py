@@ -4,6 +4,7 @@ All tests here need an MI355X.  Tolerance: allclose(rtol=1e-4, atol=1e-5) plus r
 L2 <= 1e-5 (tests/_util.py), the bar BASELINE.json states for this fp32 path.
 """
 
+import dataclasses
 import os
 
 import numpy as np
@@ -280,12 +281,15 @@ def test_weight_generator_module(golden_dir, c):
         assert_close(got, g[f"{c.name}/{k}"], f"{c.name}/{k}", atol=1e-7)
 
 
+@pytest.mark.parametrize("num_layers", [3, 9])
 @pytest.mark.parametrize("layout", ["natural", "split2h", "frag16"])
-def test_batched_generators_equal_the_single_calls(layout):
+def test_batched_generators_equal_the_single_calls(layout, num_layers):
     """ghf_weightgen_fwd_batched (round 3: all layers' generators in one launch sequence) gives, bit for bit, what one
     ghf_weightgen_fwd call per layer gives (reference: one WeightGenerator per layer, hypergnn.py:131-143, :278) — in the
-    natural layout (merged output kernel), in SPLIT2H (merged + batched packing) and in FRAG16 (per-head kernels in a loop)."""
-    cfg = cases.MODELS["c3"]
+    natural layout (merged output kernel), in SPLIT2H (merged + batched packing) and in FRAG16 (per-head kernels in a loop).
+    Nine layers: more generators than one call takes (_native.WG_BATCH_MAX), so generate_batched goes in groups."""
+    cfg = dataclasses.replace(cases.MODELS["c3"], num_layers=num_layers)
+    assert (num_layers > _native.WG_BATCH_MAX) == (num_layers == 9)
     model = make_model(cfg)
     kg = synth.make_kg(50, 400, 23, cfg.node_feat_dim, seed=5)
     unique, _ = relation_ids(kg.edge_texts())
@@ -295,7 +299,7 @@ def test_batched_generators_equal_the_single_calls(layout):
         batched = model.generate_batched(te, wl)
         single = [gen.generate(te, wl) for gen in model.weight_generators]
     torch.cuda.synchronize()
-    assert len(batched) == cfg.num_layers == 3
+    assert len(batched) == len(single) == num_layers
     for l in range(cfg.num_layers):
         for a, b in zip(batched[l], single[l]):
             assert (a is None) == (b is None)
@@ -303,6 +307,29 @@ def test_batched_generators_equal_the_single_calls(layout):
                 assert torch.equal(a, b), f"layer {l} {layout}"
     # different layers are different generators: the batched call must not have mixed them up
     assert not torch.equal(batched[0][2], batched[1][2])
+    assert not torch.equal(batched[0][2], batched[-1][2])
+
+
+def test_nine_layer_forward_groups_its_generators(monkeypatch):
+    """A model deeper than one batched generator call takes (nine layers: groups of 8 + 1), whole forward, on a small
+    block-kernel graph at d = 128 (BASELINE config 3's model with only the depth changed): (a) bit for bit the forward whose
+    generate_batched is one ghf_weightgen_fwd call per layer, and (b) the oracle's forward (reference hypergnn.py:236-298)
+    within the tolerance the goldens of up to three layers are held to (tests/_util.py)."""
+    cfg = dataclasses.replace(cases.MODELS["c3"], num_layers=9)
+    params = cfg.params()
+    model = make_model(cfg, params)
+    kg = synth.make_kg(1500, 6000, 16, cfg.node_feat_dim, seed=909)
+    x, ei, texts = torch.from_numpy(kg.node_features).to(DEV), torch.from_numpy(kg.edge_index).to(DEV), kg.edge_texts()
+    assert model.plan_for(ei, texts, x.size(0), DEV).block_nodes > 1
+    with torch.no_grad():
+        out = model(x, ei, texts)
+        monkeypatch.setattr(HyperGNN, "generate_batched",
+                            lambda self, te, layout: [gen.generate(te, layout) for gen in self.weight_generators])
+        looped = model(x, ei, texts)
+    assert model.last_range_flags == 0
+    assert torch.equal(out, looped)
+    ref = O.forward(params, kg.node_features, kg.edge_index, texts, variant="factorised")
+    assert_close(out.cpu().numpy(), ref.numpy(), "nine layers")
 
 
 def test_frag16_layout_is_a_permutation_of_natural():
