@@ -99,6 +99,10 @@ SIGNATURES = {
     "ghf_score_rank": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _sz, _vp, _vp, _vp]),
     "ghf_score_topk_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "ghf_score_topk": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _sz, _vp, _vp, _vp]),
+    "ghf_score_softmax_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "ghf_score_softmax_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _sz, _vp, _vp, _vp]),
+    "ghf_score_softmax_bwd_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "ghf_score_softmax_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ghf_rows_pack": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "ghf_rows_unpack": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "ghf_rows_accumulate": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp]),
@@ -620,6 +624,78 @@ def score_topk(q: torch.Tensor, c: torch.Tensor, k: int, iq: Optional[torch.Tens
     _check(load().ghf_score_topk(_ptr(q), _ptr(c), _ptr(iq), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d, k, _ptr(ws),
                                  ws.numel(), _ptr(scores), _ptr(ids), _stream()), "ghf_score_topk")
     return scores, ids
+
+
+# ---- 1-vs-all softmax loss against every node (include/ghf.h: ghf_score_softmax_fwd / _bwd, csrc/softmax.hip) ----------
+def score_softmax_workspace_bytes(B: int, N: int, d: int) -> int:
+    return int(load().ghf_score_softmax_workspace_bytes(B, N, d))
+
+
+def score_softmax_bwd_workspace_bytes(B: int, N: int, d: int) -> int:
+    return int(load().ghf_score_softmax_bwd_workspace_bytes(B, N, d))
+
+
+def _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, what: str):
+    q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, what)
+    target = _req(target, torch.int64, "target")
+    if target.dim() != 1 or target.numel() != B or target.device != q.device:
+        raise ValueError(f"{what}: target must be [B = {B}] on {q.device}, got {tuple(target.shape)} on {target.device}")
+    scale = float(scale)
+    if not (0.0 < scale < float("inf")):
+        raise ValueError(f"{what}: scale must be finite and positive, got {scale}")
+    return q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale
+
+
+def _f32_out(t: Optional[torch.Tensor], shape: Tuple[int, ...], device, what: str) -> torch.Tensor:
+    if t is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    r = _req(t, torch.float32, "out")
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what}: out must be contiguous fp32 tensors of shape {tuple(shape)}")
+    return r
+
+
+def score_softmax_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optional[torch.Tensor] = None,
+                      filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0,
+                      workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """(loss, lse) fp32 [B]: lse[i] = log sum_j exp(scale q[iq[i]] . c[j]) over every row j of c outside query i's filter
+    list (CSR, each list sorted ascending; the target always stays in), loss[i] = lse[i] - scale q[iq[i]] . c[target[i]].
+    Nothing of size B x N is stored.  With `workspace` (uint8, score_softmax_workspace_bytes) and `out` given the call
+    allocates nothing."""
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, "score_softmax_fwd")
+    N, d = c.size(0), c.size(1)
+    need = score_softmax_workspace_bytes(B, N, d)
+    if need == 0:
+        raise ValueError(f"score_softmax_fwd: unsupported sizes B={B} N={N} d={d}")
+    ws = _rank_workspace(workspace, need, q.device, "score_softmax_fwd")
+    loss = _f32_out(None if out is None else out[0], (B,), q.device, "score_softmax_fwd")
+    lse = _f32_out(None if out is None else out[1], (B,), q.device, "score_softmax_fwd")
+    _check(load().ghf_score_softmax_fwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
+                                        d, scale, _ptr(ws), ws.numel(), _ptr(loss), _ptr(lse), _stream()), "ghf_score_softmax_fwd")
+    return loss, lse
+
+
+def score_softmax_bwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, lse: torch.Tensor, grad_loss: torch.Tensor,
+                      iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
+                      filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0, workspace: Optional[torch.Tensor] = None,
+                      out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """(dq [B, d], dc [N, d]) fp32 of include/ghf.h: ghf_score_softmax_bwd — dq per query (not scattered through iq), every
+    row of dc written.  `lse` is the forward's."""
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, "score_softmax_bwd")
+    lse, grad_loss = _req(lse, torch.float32, "lse"), _req(grad_loss, torch.float32, "grad_loss")
+    if lse.numel() != B or grad_loss.numel() != B:
+        raise ValueError(f"score_softmax_bwd: lse and grad_loss must hold B = {B} values")
+    N, d = c.size(0), c.size(1)
+    need = score_softmax_bwd_workspace_bytes(B, N, d)
+    if need == 0:
+        raise ValueError(f"score_softmax_bwd: unsupported sizes B={B} N={N} d={d}")
+    ws = _rank_workspace(workspace, need, q.device, "score_softmax_bwd")
+    dq = _f32_out(None if out is None else out[0], (B, d), q.device, "score_softmax_bwd")
+    dc = _f32_out(None if out is None else out[1], (N, d), q.device, "score_softmax_bwd")
+    _check(load().ghf_score_softmax_bwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
+                                        d, scale, _ptr(lse), _ptr(grad_loss), _ptr(ws), ws.numel(), _ptr(dq), _ptr(dc), _stream()),
+           "ghf_score_softmax_bwd")
+    return dq, dc
 
 
 # ---- wide hidden sizes: relation-stationary layer (include/ghf.h, csrc/message_rs.hip) ---------------------------

@@ -20,7 +20,8 @@ gathers; kernels without that side output run GHF_FLAG_NO_TAIL plus ``ghf_tail_f
 
 The callers either side of the layer have their own Functions here: ``WeightGeneratorFn`` (three MLP heads and the
 learnable log-scales, reference weight_generator.py:120-143), ``InputProjFn`` (hypergnn.py:261), ``TextEncoderFn``
-(hypergnn.py:57-81), ``ScorePairsFn`` (hypergnn.py:304-318) and its fused form over index arrays ``ScoreEdgesFn``.  All of
+(hypergnn.py:57-81), ``ScorePairsFn`` (hypergnn.py:304-318), its fused form over index arrays ``ScoreEdgesFn`` and the 1-vs-all softmax loss
+against every node ``SoftmaxLossFn`` (no counterpart in the reference).  All of
 their contractions are ``A^T B`` over rows, i.e. ``ghf_group_outer`` again (``_native.matmul_tn``).
 """
 
@@ -403,6 +404,34 @@ class ScoreEdgesFn(torch.autograd.Function):
         partner = torch.cat([dst, src]).index_select(0, perm)
         pair = torch.remainder(perm, P)
         return _native.segment_axpy(g.contiguous().float(), pair, embs, partner, off), None, None
+
+
+class SoftmaxLossFn(torch.autograd.Function):
+    """loss_i = log sum_{j in J_i} exp(scale embs[query_i] . embs[j]) - scale embs[query_i] . embs[target_i] over ALL nodes j
+    outside query i's filter list (HyperGNN.softmax_loss; include/ghf.h: ghf_score_softmax_fwd).  The [B, N] logits exist
+    neither here nor in the backward, which recomputes them tile by tile from the saved lse (ghf_score_softmax_bwd with
+    q = c = embs): d embs = dc + the per-query rows dq summed into the rows `query` names — grouped by node
+    (ghf_group_edges, stable) and added per node in that order, as ScoreEdgesFn does: reproducible."""
+
+    @staticmethod
+    def forward(ctx, embs, query, target, ptr, idx, scale: float):
+        embs = embs.contiguous().float()
+        loss, lse = _native.score_softmax_fwd(embs, embs, target, iq=query, filt_ptr=ptr, filt_idx=idx, scale=scale)
+        ctx.save_for_backward(embs, lse, query, target, *(() if ptr is None else (ptr, idx)))
+        ctx.scale = scale
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        embs, lse, query, target, *lists = ctx.saved_tensors
+        ptr, idx = lists if lists else (None, None)
+        dq, dc = _native.score_softmax_bwd(embs, embs, target, lse, g.contiguous().float(), iq=query, filt_ptr=ptr, filt_idx=idx,
+                                           scale=ctx.scale)
+        B, N = query.numel(), embs.size(0)
+        perm, off = _native.group_edges(query, N)
+        folded = _native.segment_axpy(torch.ones(B, dtype=torch.float32, device=embs.device), perm, dq, perm, off)
+        return _native.add3(dc, folded, out=dc), None, None, None, None, None
 
 
 class ScorePairsFn(torch.autograd.Function):

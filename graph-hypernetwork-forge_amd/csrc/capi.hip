@@ -582,6 +582,33 @@ int ghf_score_topk(const float* q, const float* c, const int64_t* iq, const int6
                              (hipStream_t)stream);
 }
 
+size_t ghf_score_softmax_workspace_bytes(int64_t B, int64_t N, int d) { return score_softmax_workspace_bytes(B, N, d); }
+
+int ghf_score_softmax_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                          const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                          void* workspace, size_t workspace_bytes, float* loss, float* lse, void* stream) {
+    GHF_REQUIRE(q && c && target && workspace && loss && lse, "score_softmax_fwd: null pointer argument");
+    GHF_REQUIRE(nnz <= 0 || (filt_ptr && filt_idx), "score_softmax_fwd: null filter list with nnz > 0");
+    GHF_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, "score_softmax_fwd: scale must be finite and positive");
+    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "score_softmax_fwd: workspace not 256-byte aligned");
+    return launch_score_softmax_fwd(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, workspace, workspace_bytes,
+                                    loss, lse, (hipStream_t)stream);
+}
+
+size_t ghf_score_softmax_bwd_workspace_bytes(int64_t B, int64_t N, int d) { return score_softmax_bwd_workspace_bytes(B, N, d); }
+
+int ghf_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                          const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                          const float* lse, const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* dc,
+                          void* stream) {
+    GHF_REQUIRE(q && c && target && lse && grad_loss && workspace && dq && dc, "score_softmax_bwd: null pointer argument");
+    GHF_REQUIRE(nnz <= 0 || (filt_ptr && filt_idx), "score_softmax_bwd: null filter list with nnz > 0");
+    GHF_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, "score_softmax_bwd: scale must be finite and positive");
+    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "score_softmax_bwd: workspace not 256-byte aligned");
+    return launch_score_softmax_bwd(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, lse, grad_loss, workspace,
+                                    workspace_bytes, dq, dc, (hipStream_t)stream);
+}
+
 int ghf_tail_fwd(const float* agg, const float* h, const float* ln_gamma, const float* ln_beta, float ln_eps,
                  int64_t row0, int64_t rows, int d, float* h_out, const float* drop, void* stream) {
     GHF_REQUIRE(agg && h && ln_gamma && ln_beta && h_out, "tail_fwd: null pointer argument");

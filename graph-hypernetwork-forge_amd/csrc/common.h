@@ -174,6 +174,16 @@ int launch_score_rank(const float* q, const float* c, const int64_t* iq, const i
 int launch_score_topk(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
                       int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, void* ws, size_t ws_bytes, float* scores,
                       int64_t* ids, hipStream_t stream);
+// softmax.hip
+size_t score_softmax_workspace_bytes(int64_t B, int64_t N, int d);
+size_t score_softmax_bwd_workspace_bytes(int64_t B, int64_t N, int d);
+int launch_score_softmax_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                             const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                             void* ws, size_t ws_bytes, float* loss, float* lse, hipStream_t stream);
+int launch_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                             const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                             const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc,
+                             hipStream_t stream);
 int launch_text_encode(const int32_t* ids, const int32_t* lens, int U, int Lmax, const float* E, int V, int C,
                        const float* W, const float* b, int T, float* out, hipStream_t stream);
 int launch_input_proj(const float* x, const float* W_in, const float* b_in, int64_t N, int F, int d,

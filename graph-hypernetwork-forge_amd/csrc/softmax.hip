@@ -1,0 +1,467 @@
+// softmax.hip — the 1-vs-all softmax link-prediction loss against every node, forward and backward, the B x N logits never
+// stored (include/ghf.h: ghf_score_softmax_fwd / ghf_score_softmax_bwd).
+//
+//   lse[i] = log sum_{j in J_i} exp(scale s(i, j)),   loss[i] = lse[i] - scale s(i, target[i])
+//
+// with s(i, j) the sweep's fp32 chain (rank_sweep.h) and J_i every candidate outside query i's filter list, the target
+// always inside.
+//
+// Forward: rank_tile_kernel with its third epilogue.  A lane keeps a running (max, sum) per query column and folds a
+// finished candidate tile's 32 registers of that column into it; a listed candidate is masked BEFORE it enters the sum
+// (a query's known partners are the candidates that score highest: taking their terms out of a total afterwards cancels
+// catastrophically).  Lists are sorted and candidates arrive in ascending id, so a lane carries a cursor into its query's
+// list and only a tile whose id range holds a listed id looks ids up.  Partials merge in a fixed order: the half-waves and
+// waves of a workgroup through LDS, one (max, sum) per (query, slab) in the workspace, softmax_finish_kernel over the
+// slabs in slab order.  The slabs depend on N and d alone, so a query's loss has the same bits whatever batch it is in.
+//
+// Backward: softmax_bwd_kernel recomputes score tiles from the saved lse, as an attention backward does:
+//   G_ij = grad[i] scale (p_ij - [j = target[i]]),   p_ij = exp(scale s(i,j) - lse[i]) on J_i, 0 outside
+//   dq[i] = sum_j G_ij c[j]       a workgroup owns (query tile, candidate slab): candidates stream, one partial per slab,
+//                                  the partials summed in slab order (dq_reduce_kernel)
+//   dc[j] = sum_i G_ij q[iq[i]]   a workgroup owns a candidate tile, streams ALL query tiles in ascending order and
+//                                  writes its rows once
+// One kernel serves both: 256 threads, an owner tile (128 rows; 64 for d > 128) resident in LDS, streamed tiles of 64
+// whole-d rows in a second LDS buffer.  Per streamed tile: the score product (candidates the A operand, queries the B
+// operand, so a lane holds ONE query's lse / gradient / target for its accumulator column), G into LDS as [streamed k]
+// [owner row], then the second product out[owner, d] += G^T-or-G . Y on the same fp32 matrix instruction, the streamed
+// rows read across (the k permutation of their groups of 8 undone in the column index).  Sums run over streamed rows in
+// ascending order: no floating-point atomics, bit-reproducible.
+// Masking in the backward: the dq sweep uses the forward's cursor.  The dc sweep's queries change every step, so a
+// workgroup first collects the (query, candidate) pairs of all lists that fall
+// into ITS candidate tile (one coalesced pass over filt_idx) and zeroes those entries of G in LDS after each step's
+// epilogue; a tile that more than SB_HCAP pairs fall into (a hub listed by thousands of queries) looks every id up instead.
+#include "common.h"
+#include "rank_sweep.h"
+
+namespace ghf {
+
+constexpr int SM_SLABS = 128;                // forward: candidate slabs (fewer when N is small), whatever B is
+constexpr int SB_ST = 64;                    // backward: streamed rows per step
+constexpr int SB_NT = 256;                   // backward: threads
+constexpr int SB_HCAP = 1024;                // backward, dc: listed pairs a candidate tile keeps in LDS
+constexpr int SB_MIN_SLAB_TILES = 64;        // backward, dq: a slab is at least 4,096 candidates, so that the partials stay
+                                             // below 1/32 of a score matrix at d = 128
+static inline int sb_otile(int d) { return d <= 128 ? 128 : 64; }
+
+static inline bool softmax_geom(int64_t B, int64_t N, int d, RankGeom* g) {
+    if (B <= 0 || N <= 0 || N >= (int64_t)1 << 31 || B >= (int64_t)1 << 31) return false;
+    g->qtiles = cdiv(B, RK_TILE);
+    g->ctiles = cdiv(N, rank_ctile(d));
+    g->slab_tiles = cdiv(g->ctiles, SM_SLABS);
+    g->slabs = cdiv(g->ctiles, g->slab_tiles);
+    return g->qtiles * g->slabs < (int64_t)1 << 31;
+}
+
+// dq: two workgroups per CU over the call where the slabs' minimum length allows
+static inline bool softmax_bwd_geom(int64_t B, int64_t N, int d, RankGeom* g) {
+    if (B <= 0 || N <= 0 || N >= (int64_t)1 << 31 || B >= (int64_t)1 << 31) return false;
+    g->qtiles = cdiv(B, sb_otile(d));
+    g->ctiles = cdiv(N, SB_ST);
+    int64_t slabs = cdiv(2 * RK_CUS, g->qtiles);
+    if (slabs > g->ctiles / SB_MIN_SLAB_TILES) slabs = g->ctiles / SB_MIN_SLAB_TILES;
+    if (slabs < 1) slabs = 1;
+    g->slab_tiles = cdiv(g->ctiles, slabs);
+    g->slabs = cdiv(g->ctiles, g->slab_tiles);
+    return g->qtiles * g->slabs < (int64_t)1 << 31;
+}
+
+size_t score_softmax_workspace_bytes(int64_t B, int64_t N, int d) {
+    RankGeom g;
+    if (d <= 0 || d > RK_MAX_D || !softmax_geom(B, N, d, &g)) return 0;
+    // t [B] float, valid [B] int32, (max, sum) [B, slabs]
+    return 2 * rk_align((size_t)B * 4) + rk_align((size_t)B * (size_t)g.slabs * 8);
+}
+
+size_t score_softmax_bwd_workspace_bytes(int64_t B, int64_t N, int d) {
+    RankGeom g;
+    if (d <= 0 || d > RK_MAX_D || !softmax_bwd_geom(B, N, d, &g)) return 0;
+    return rk_align((size_t)g.slabs * (size_t)B * (size_t)d * 4);      // dq partials [slabs, B, d]
+}
+
+// ---- forward: the small kernels around the sweep --------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void softmax_prep_kernel(const float* __restrict__ q, const float* __restrict__ c,
+                                                           const int64_t* __restrict__ iq, const int64_t* __restrict__ target,
+                                                           int64_t rows_q, int64_t N, int64_t B, int d, float* __restrict__ t,
+                                                           int* __restrict__ valid) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B) return;
+    const int64_t r = iq ? iq[i] : i, tg = target[i];
+    const bool ok = r >= 0 && r < rows_q && tg >= 0 && tg < N;
+    t[i] = ok ? dot_chain(q + (size_t)r * d, c + (size_t)tg * d, d, rows_vec(q, d) && rows_vec(c, d)) : __int_as_float(0x7FC00000);
+    valid[i] = ok ? 1 : 0;
+}
+
+// one thread per filter entry: an id out of range marks the query whose list holds it
+__global__ __launch_bounds__(256) void softmax_filter_kernel(const int64_t* __restrict__ filt_ptr, const int64_t* __restrict__ filt_idx,
+                                                             int64_t nnz, int64_t N, int64_t B, int* valid) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= nnz) return;
+    const int64_t j = filt_idx[e];
+    if (j >= 0 && j < N) return;
+    int64_t lo = 0, hi = B;                          // last i with filt_ptr[i] <= e
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (filt_ptr[mid] <= e) lo = mid; else hi = mid;
+    }
+    if (filt_ptr[lo] <= e && filt_ptr[lo + 1] > e) valid[lo] = 0;
+}
+
+__global__ __launch_bounds__(256) void softmax_finish_kernel(const f32x2* __restrict__ ms, const float* __restrict__ t,
+                                                             const int* __restrict__ valid, int64_t B, int64_t slabs, float scale,
+                                                             float* __restrict__ loss, float* __restrict__ lse) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B) return;
+    f32x2 m = ms[(size_t)i * slabs];
+    for (int64_t s = 1; s < slabs; ++s) m = lse_merge(m, ms[(size_t)i * slabs + s]);
+    const float l = valid[i] ? m[0] + logf(m[1]) : __int_as_float(0x7FC00000);
+    lse[i] = l;
+    loss[i] = l - scale * t[i];
+}
+
+int launch_score_softmax_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                             const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                             void* ws, size_t ws_bytes, float* loss, float* lse, hipStream_t stream) {
+    RankGeom g;
+    GHF_REQUIRE(d > 0 && rows_q > 0 && N > 0 && B > 0 && nnz >= 0, "score_softmax_fwd: bad shape");
+    if (d > RK_MAX_D) return set_err(GHF_EUNSUPPORTED, "score_softmax_fwd: d = %d exceeds %d", d, RK_MAX_D);
+    GHF_REQUIRE(softmax_geom(B, N, d, &g), "score_softmax_fwd: B or N out of range");
+    GHF_REQUIRE(iq || B <= rows_q, "score_softmax_fwd: B exceeds the rows of q");
+    GHF_REQUIRE(ws_bytes >= score_softmax_workspace_bytes(B, N, d), "score_softmax_fwd: workspace of %zu bytes, need %zu", ws_bytes,
+                score_softmax_workspace_bytes(B, N, d));
+    float* t = (float*)ws;
+    int* valid = (int*)((char*)ws + rk_align((size_t)B * 4));
+    f32x2* ms = (f32x2*)((char*)ws + 2 * rk_align((size_t)B * 4));
+    const unsigned qb = (unsigned)cdiv(B, 256);
+    softmax_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, target, rows_q, N, B, d, t, valid);
+    GHF_LAUNCH_CHECK();
+    if (nnz > 0) {
+        softmax_filter_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(filt_ptr, filt_idx, nnz, N, B, valid);
+        GHF_LAUNCH_CHECK();
+    }
+    RankArgs a = {};
+    a.q = q; a.c = c; a.iq = iq; a.rows_q = rows_q; a.N = N; a.B = B; a.d = d;
+    a.qtiles = g.qtiles; a.slab_tiles = g.slab_tiles; a.slabs = g.slabs;
+    a.filt_ptr = nnz > 0 ? filt_ptr : nullptr; a.filt_idx = filt_idx; a.nnz = nnz;
+    a.target = target; a.scale = scale; a.ws_ms = ms;
+    const unsigned grid = (unsigned)(g.qtiles * g.slabs);
+    if (rank_ctile(d) == 256) {
+        const size_t lds = rank_lds_bytes(d, 32, 256);
+        GHF_SET_MAX_LDS((rank_tile_kernel<32, 256, RK_SOFTMAX>), lds);
+        rank_tile_kernel<32, 256, RK_SOFTMAX><<<grid, 512, lds, stream>>>(a);
+    } else {
+        const size_t lds = rank_lds_bytes(d, 16, 128);
+        GHF_SET_MAX_LDS((rank_tile_kernel<16, 128, RK_SOFTMAX>), lds);
+        rank_tile_kernel<16, 128, RK_SOFTMAX><<<grid, 256, lds, stream>>>(a);
+    }
+    GHF_LAUNCH_CHECK();
+    softmax_finish_kernel<<<qb, 256, 0, stream>>>(ms, t, valid, B, g.slabs, scale, loss, lse);
+    GHF_LAUNCH_CHECK();
+    return GHF_OK;
+}
+
+// ---- backward -------------------------------------------------------------------------------------------------------------
+struct SmBwdArgs {
+    const float* q; const float* c; const int64_t* iq; const int64_t* target;
+    const int64_t* filt_ptr; const int64_t* filt_idx; int64_t nnz;
+    int64_t rows_q, N, B;
+    int d;
+    float scale;
+    const float* lse; const float* grad;
+    int64_t qtiles, slab_tiles, slabs;       // dq
+    float* dq_part;                          // dq: [slabs, B, d]
+    float* dc;                               // dc: [N, d]
+};
+
+static inline size_t sb_lds_bytes(int d, int OT) {
+    const int dpad = (d + 31) & ~31;
+    return ((size_t)(OT + SB_ST) * (dpad + 4) + (size_t)SB_ST * (OT + 1)) * 4 + (size_t)SB_HCAP * 8 + 16;
+}
+
+// what a lane knows of the query in its accumulator column
+struct SmQuery {
+    float lse, gs;                           // lse NaN: the query takes no part; gs = grad * scale
+    int64_t tgt, f0, f1;                     // target, filter list [f0, f1)
+};
+
+template <int OT, int DMAX, bool DC>
+__global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr int ST = SB_ST, NT = SB_NT, LDG = OT + 1;
+    constexpr int QR = DC ? ST : OT, CR = DC ? OT : ST;             // query / candidate rows of a step's score tile
+    constexpr int QT = QR / 32, NTW = QT * (CR / 32) / 4;           // a wave: one query column tile, NTW candidate row tiles
+    constexpr int RT = OT / 32, NC = DMAX * RT / 128;               // second product: one owner row tile, NC column tiles of d
+    constexpr int NL = ST * (DMAX / 4) / NT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lr = lane & 31, lh = lane >> 5;
+    const int d = a.d, dpad = (d + 31) & ~31, LDX = dpad + 4, nf4 = dpad >> 2;
+    float* Xs = lds;                             // the owner tile, resident
+    float* Ys = Xs + OT * LDX;                   // the streamed tile
+    float* Gs = Ys + ST * LDX;                   // G of the step: [streamed row][owner row]
+    long long* hits = (long long*)(Gs + ST * LDG);
+    int* hcnt = (int*)(hits + SB_HCAP);
+    const bool vq = rows_vec(a.q, d), vc = rows_vec(a.c, d);
+
+    int64_t own0, tile0, tile1, slab = 0;
+    if (DC) {
+        own0 = (int64_t)blockIdx.x * OT;
+        tile0 = 0;
+        tile1 = (a.B + ST - 1) / ST;
+    } else {
+        int64_t wg = blockIdx.x;                 // as rank_tile_kernel: an XCD's workgroups are the query tiles of one slab
+        const int64_t per_xcd = gridDim.x / 8;
+        if (wg < per_xcd * 8) wg = (wg % 8) * per_xcd + wg / 8;
+        const int64_t qt = wg % a.qtiles, ctiles = (a.N + ST - 1) / ST;
+        slab = wg / a.qtiles;
+        own0 = qt * OT;
+        tile0 = slab * a.slab_tiles;
+        tile1 = tile0 + a.slab_tiles < ctiles ? tile0 + a.slab_tiles : ctiles;
+    }
+
+    auto qrow = [&](int64_t qi) -> const float* {
+        if (qi >= a.B) return nullptr;
+        const int64_t r = a.iq ? a.iq[qi] : qi;
+        return r >= 0 && r < a.rows_q ? a.q + (size_t)r * d : nullptr;
+    };
+    auto crow = [&](int64_t j) -> const float* { return j < a.N ? a.c + (size_t)j * d : nullptr; };
+    auto query = [&](int64_t qi) {
+        SmQuery m = {__int_as_float(0x7FC00000), 0.f, -1, 0, 0};
+        if (qi < a.B) {
+            const int64_t r = a.iq ? a.iq[qi] : qi;
+            const float l = a.lse[qi];
+            m.tgt = a.target[qi];
+            if (r >= 0 && r < a.rows_q && l == l) {
+                m.lse = l;
+                m.gs = a.grad[qi] * a.scale;
+            }
+            if (a.filt_ptr) {
+                int64_t lo = a.filt_ptr[qi], hi = a.filt_ptr[qi + 1];
+                lo = lo < 0 ? 0 : (lo > a.nnz ? a.nnz : lo);
+                hi = hi < lo ? lo : (hi > a.nnz ? a.nnz : hi);
+                m.f0 = lo;
+                m.f1 = hi;
+            }
+        }
+        return m;
+    };
+
+    for (int idx = tid; idx < OT * nf4; idx += NT) {
+        const int row = idx / nf4, c4 = idx - row * nf4;
+        const float* src = DC ? crow(own0 + row) : qrow(own0 + row);
+        store_perm(Xs + row * LDX, c4, load_k4(src, c4 * 4, d, DC ? vc : vq));
+    }
+
+    // dc: the listed (query, candidate) pairs inside this candidate tile, the targets' own left out
+    if (DC) {
+        if (tid == 0) *hcnt = 0;
+        __syncthreads();
+        if (a.filt_ptr) {
+            for (int64_t e = tid; e < a.nnz; e += NT) {
+                const int64_t j = a.filt_idx[e];
+                if (j < own0 || j >= own0 + OT) continue;
+                int64_t lo = 0, hi = a.B;                            // last i with filt_ptr[i] <= e
+                while (hi - lo > 1) {
+                    const int64_t mid = (lo + hi) >> 1;
+                    if (a.filt_ptr[mid] <= e) lo = mid; else hi = mid;
+                }
+                if (a.filt_ptr[lo] > e || a.filt_ptr[lo + 1] <= e || a.target[lo] == j) continue;
+                const int pos = atomicAdd(hcnt, 1);
+                if (pos < SB_HCAP) hits[pos] = (long long)(lo * 256 + (j - own0));
+            }
+        }
+    }
+
+    const int ct = wave % QT, rt0 = (wave / QT) * NTW;          // score tiles of this wave
+    const int rt2 = wave % RT, cb = (wave / RT) * NC;           // output tiles of this wave
+    const int ql = ct * 32 + lr;                                // the lane's query row inside the step's query rows
+    const int pl = (lr & ~7) + 4 * (lr & 1) + ((lr >> 1) & 3);  // where store_perm put column lr of a group of 32
+
+    SmQuery cur = query(DC ? tile0 * ST + ql : own0 + ql), nxtq = cur;
+    int64_t nxt = INT64_MAX;                                    // dq: the first listed id not yet behind the sweep
+    if (!DC) {
+        cur.f0 = filter_lower_bound(a.filt_idx, cur.f0, cur.f1, tile0 * ST);
+        if (cur.f0 < cur.f1) nxt = a.filt_idx[cur.f0];
+    }
+
+    f32x4 pre[NL];
+    auto fetch = [&](int64_t tile) {
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            const int idx = tid + NT * i;
+            if (idx < ST * nf4) {
+                const int row = idx / nf4, c4 = idx - row * nf4;
+                const float* src = DC ? qrow(tile * ST + row) : crow(tile * ST + row);
+                pre[i] = load_k4(src, c4 * 4, d, DC ? vq : vc);
+            }
+        }
+    };
+    auto stash = [&]() {
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            const int idx = tid + NT * i;
+            if (idx < ST * nf4) {
+                const int row = idx / nf4, c4 = idx - row * nf4;
+                store_perm(Ys + row * LDX, c4, pre[i]);
+            }
+        }
+    };
+
+    f32x16 out[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) out[c][r] = 0.f;
+
+    fetch(tile0);
+    stash();
+    __syncthreads();
+    const int nh = DC ? (*hcnt < SB_HCAP ? *hcnt : SB_HCAP) : 0;
+    const bool over = DC && *hcnt > SB_HCAP;
+
+    for (int64_t tile = tile0; tile < tile1; ++tile) {
+        const bool more = tile + 1 < tile1;
+        if (more) {
+            fetch(tile + 1);
+            if (DC) nxtq = query((tile + 1) * ST + ql);
+        }
+
+        // scores of the step: candidates x queries, the chain of the forward
+        f32x16 s[NTW];
+#pragma unroll
+        for (int t = 0; t < NTW; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s[t][r] = 0.f;
+        const float* cA = (DC ? Xs : Ys) + (rt0 * 32 + lr) * LDX + 4 * lh;
+        const float* qB = (DC ? Ys : Xs) + ql * LDX + 4 * lh;
+        for (int g = 0; g < (dpad >> 3); ++g) {
+            const f32x4 b = *(const f32x4*)(qB + 8 * g);
+            f32x4 av[NTW];
+#pragma unroll
+            for (int t = 0; t < NTW; ++t) av[t] = *(const f32x4*)(cA + t * 32 * LDX + 8 * g);
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int t = 0; t < NTW; ++t) s[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[t][m], b[m], s[t], 0, 0, 0);
+        }
+
+        // G of the step, into LDS
+        const int64_t cand0 = DC ? own0 : tile * ST;
+        const bool live = cur.lse == cur.lse;
+        bool look;                                   // whether one of the query's listed ids can be among the step's candidates
+        if (DC) {
+            look = false;
+            if (over && live) {
+                const int64_t lb = filter_lower_bound(a.filt_idx, cur.f0, cur.f1, cand0);
+                look = lb < cur.f1 && a.filt_idx[lb] < cand0 + CR;
+            }
+        } else {
+            look = nxt < cand0 + CR;
+        }
+#pragma unroll
+        for (int t = 0; t < NTW; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int cl = (rt0 + t) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                const int64_t cand = cand0 + cl;
+                float gv = 0.f;
+                if (live && cand < a.N) {
+                    const bool masked = look && cand != cur.tgt && in_filter(a.filt_idx, cur.f0, cur.f1, cand);
+                    const float p = masked ? 0.f : __expf(fmaf(a.scale, s[t][r], -cur.lse));
+                    gv = cur.gs * (p - (cand == cur.tgt ? 1.f : 0.f));
+                }
+                Gs[DC ? ql * LDG + cl : cl * LDG + ql] = gv;
+            }
+        if (!DC) {
+            while (nxt < cand0 + CR) {
+                ++cur.f0;
+                nxt = cur.f0 < cur.f1 ? a.filt_idx[cur.f0] : INT64_MAX;
+            }
+        }
+        __syncthreads();
+        if (DC && nh > 0) {                          // the listed pairs of this candidate tile whose query is in the step
+            for (int h = tid; h < nh; h += NT) {
+                const int64_t qi = hits[h] >> 8;
+                if (qi >= tile * ST && qi < tile * ST + ST) Gs[(int)(qi - tile * ST) * LDG + (int)(hits[h] & 255)] = 0.f;
+            }
+            __syncthreads();
+        }
+
+        // out[owner rows, d] += G . (streamed rows): k = the streamed row, ascending
+        const float* gA = Gs + lh * LDG + rt2 * 32 + lr;
+        const float* yB = Ys + lh * LDX + pl;
+#pragma unroll 4
+        for (int k = 0; k < ST; k += 2) {
+            const float av = gA[k * LDG];
+#pragma unroll
+            for (int c = 0; c < NC; ++c)
+                if ((cb + c) * 32 < d) out[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, yB[k * LDX + (cb + c) * 32], out[c], 0, 0, 0);
+        }
+        __syncthreads();
+        if (more) {
+            stash();
+            if (DC) cur = nxtq;
+        }
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const int col = (cb + c) * 32 + lr;
+        if (col < d) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int64_t row = own0 + rt2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                if (DC) {
+                    if (row < a.N) a.dc[(size_t)row * d + col] = out[c][r];
+                } else {
+                    if (row < a.B) a.dq_part[((size_t)slab * a.B + row) * d + col] = out[c][r];
+                }
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void dq_reduce_kernel(const float* __restrict__ part, int64_t n, int64_t slabs, float* __restrict__ dq) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s = part[i];
+    for (int64_t sl = 1; sl < slabs; ++sl) s += part[(size_t)sl * n + i];
+    dq[i] = s;
+}
+
+template <int OT, int DMAX>
+static int launch_bwd_tiles(const SmBwdArgs& a, hipStream_t stream) {
+    const size_t lds = sb_lds_bytes(a.d, OT);
+    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, false>), lds);
+    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, true>), lds);
+    softmax_bwd_kernel<OT, DMAX, false><<<(unsigned)(a.qtiles * a.slabs), SB_NT, lds, stream>>>(a);
+    GHF_LAUNCH_CHECK();
+    softmax_bwd_kernel<OT, DMAX, true><<<(unsigned)cdiv(a.N, OT), SB_NT, lds, stream>>>(a);
+    GHF_LAUNCH_CHECK();
+    return GHF_OK;
+}
+
+int launch_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                             const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                             const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc,
+                             hipStream_t stream) {
+    RankGeom g;
+    GHF_REQUIRE(d > 0 && rows_q > 0 && N > 0 && B > 0 && nnz >= 0, "score_softmax_bwd: bad shape");
+    if (d > RK_MAX_D) return set_err(GHF_EUNSUPPORTED, "score_softmax_bwd: d = %d exceeds %d", d, RK_MAX_D);
+    GHF_REQUIRE(softmax_bwd_geom(B, N, d, &g), "score_softmax_bwd: B or N out of range");
+    GHF_REQUIRE(iq || B <= rows_q, "score_softmax_bwd: B exceeds the rows of q");
+    GHF_REQUIRE(ws_bytes >= score_softmax_bwd_workspace_bytes(B, N, d), "score_softmax_bwd: workspace of %zu bytes, need %zu",
+                ws_bytes, score_softmax_bwd_workspace_bytes(B, N, d));
+    SmBwdArgs a = {};
+    a.q = q; a.c = c; a.iq = iq; a.target = target;
+    a.filt_ptr = nnz > 0 ? filt_ptr : nullptr; a.filt_idx = filt_idx; a.nnz = nnz;
+    a.rows_q = rows_q; a.N = N; a.B = B; a.d = d; a.scale = scale; a.lse = lse; a.grad = grad_loss;
+    a.qtiles = g.qtiles; a.slab_tiles = g.slab_tiles; a.slabs = g.slabs;
+    a.dq_part = (float*)ws; a.dc = dc;
+    const int rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128>(a, stream) : launch_bwd_tiles<64, 256>(a, stream);
+    if (rc != GHF_OK) return rc;
+    const int64_t n = B * (int64_t)d;
+    dq_reduce_kernel<<<(unsigned)cdiv(n, 256), 256, 0, stream>>>(a.dq_part, n, g.slabs, dq);
+    GHF_LAUNCH_CHECK();
+    return GHF_OK;
+}
+
+}  // namespace ghf

@@ -662,6 +662,33 @@ class HyperGNN(nn.Module):
         ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx)
         return _native.score_topk(e, e, int(k), iq=q, filt_ptr=ptr, filt_idx=idx)
 
+    def softmax_loss(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, scale: float = 1.0, known=None,
+                     filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The 1-vs-all softmax cross-entropy that ``rank_candidates``' filtered metrics measure, fp32 ``[B]``:
+        ``loss[i] = logsumexp_j(scale * embs[query[i]] . embs[j]) - scale * embs[query[i]] . embs[target[i]]`` over ALL nodes
+        ``j`` except ``query[i]``'s known partners (``known`` / ``filt_ptr, filt_idx`` as in ``rank_candidates``; the target
+        itself always stays in the sum).  ``F.cross_entropy(scale * embs[query] @ embs.T, target)`` without the ``[B, N]``
+        logits, forward or backward: one sweep on the fp32 matrix cores with an online softmax in its epilogue
+        (``ghf_score_softmax_fwd``), and a backward that recomputes the scores from the saved log-sum (``ghf_score_softmax_bwd``,
+        ``autograd.SoftmaxLossFn``).  Bit-reproducible.  Recorded for autograd when grad mode is on and ``embs`` requires grad."""
+        if embs.dim() != 2:
+            raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        scale = float(scale)
+        if not (0.0 < scale < float("inf")):
+            raise ValueError(f"scale must be finite and positive, got {scale}")
+        q = self._rank_ids(query, embs.size(0), embs, "query")
+        t = self._rank_ids(target, embs.size(0), embs, "target")
+        if q.numel() != t.numel():
+            raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
+        if not embs.is_cuda:
+            raise RuntimeError(f"softmax_loss computes on an MI355X HIP device only (input is on {embs.device})")
+        ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx)
+        if torch.is_grad_enabled() and embs.requires_grad:
+            from ..autograd import SoftmaxLossFn
+            return SoftmaxLossFn.apply(embs, q, t, ptr, idx, scale)
+        e = embs.detach().float()
+        return _native.score_softmax_fwd(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, scale=scale)[0]
+
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)
 

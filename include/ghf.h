@@ -445,6 +445,33 @@ int ghf_score_topk(const float* q, const float* c, const int64_t* iq, const int6
                    int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, void* workspace, size_t workspace_bytes,
                    float* scores, int64_t* ids, void* stream);
 
+/* ---- 1-vs-all softmax link-prediction loss against every node (csrc/softmax.hip) ---------------------
+ * The differentiable counterpart of ghf_score_rank: the objective its filtered metrics measure.  q, c, iq, target and the
+ * filter lists exactly as above, s(i, j) the same chain.  scale: a finite float > 0 (GHF_EINVAL otherwise).  With
+ *   t_i = s(i, target[i]),   J_i = every row of c except the rows in query i's list — the target ALWAYS stays in J_i, even
+ *   if it is listed; a repeated id in a list changes nothing —
+ *   lse[i]  = log sum_{j in J_i} exp(scale s(i, j)),      loss[i] = lse[i] - scale t_i          (fp32 [B] each).
+ * A listed candidate never enters the sum (it is not subtracted afterwards).  The B x N logits are never stored.
+ * ghf_score_softmax_bwd: given grad_loss [B] and the forward's lse, with p_ij = exp(scale s(i,j) - lse[i]) for j in J_i
+ * and 0 otherwise, and G_ij = grad_loss[i] scale (p_ij - [j = target[i]]):
+ *   dq[i][:] = sum_j G_ij c[j][:]         [B, d], per query (NOT scattered through iq)
+ *   dc[j][:] = sum_i G_ij q[iq[i]][:]     [N, d], every row written (zeros included: the caller does not clear it)
+ * Limits as ghf_score_rank (d <= 256, GHF_EUNSUPPORTED beyond; B, N below 2^31).  An iq / target / filter id out of
+ * range does not fault: that query's loss and lse are NaN and it contributes nothing to dq / dc (the backward takes a
+ * NaN lse as "this query takes no part").  All sums run in a fixed order and there are no floating-point atomics: loss,
+ * lse, dq and dc are bit-reproducible, and a query's loss and lse do not depend on the other queries of the call.
+ * workspace: the matching _workspace_bytes query (0 = bad sizes), 256-byte aligned; O(B) plus 8 bytes per (query, candidate
+ * slab) forward, one [B, d] partial of dq per candidate slab backward.  Nothing allocates or synchronises. */
+size_t ghf_score_softmax_workspace_bytes(int64_t B, int64_t N, int d);
+int ghf_score_softmax_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                          const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                          void* workspace, size_t workspace_bytes, float* loss, float* lse, void* stream);
+size_t ghf_score_softmax_bwd_workspace_bytes(int64_t B, int64_t N, int d);
+int ghf_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                          const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                          const float* lse, const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* dc,
+                          void* stream);
+
 /* ---- the sparse row exchange of the multi-GPU forward (no counterpart in the single-process reference) ----
  * packed[i] = rows[idx[i]] (row_bytes, a multiple of 16) followed by extra[idx[i]] (extra_bytes, a multiple of 4; extra may be
  * NULL with extra_bytes = 0), i < n: the listed rows of a [nrows, row_bytes] table (and of a second table indexed alike — the

@@ -1,0 +1,147 @@
+"""1-vs-all softmax loss timing: HyperGNN.softmax_loss forward alone and forward + backward, against the formulation a user
+has without it — embs[q] @ embs.T in query chunks sized to 1 GB of scores, masked, logsumexp, autograd backward chunk by
+chunk — at the sizes of BASELINE configs 3 and 2, with rank_candidates' time on the same box beside them.  Prints one JSON
+line.
+
+    python tools/softmax_time.py [--configs c3,c2] [--batches 1024,16384] [--reps 5] [--no-torch]
+
+Per config and B in (1,024, 16,384): medians of device-event windows (ms, warm) of the forward (no autograd graph), of the
+forward plus backward down to d embs (both with a filter list per query built from `known` edges, 10 per query, and the
+forward also without lists), and of the torch formulation; the peak memory each allocates beyond the embeddings
+(torch.cuda.max_memory_allocated); the achieved fraction of the fp32 matrix peak, counting one B x N x d product forward
+and four backward.  The torch formulation reports "does not fit" where it raises an out-of-memory error.  --no-torch leaves
+it out (a counter collection of the kernels alone: tools/pmc.sh <prefix> softmax_bwd_kernel -- python tools/softmax_time.py
+--configs c3 --batches 1024 --no-torch)."""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from graph_hypernetwork_forge_amd import HyperGNN  # noqa: E402
+
+CONFIGS = {"c3": dict(N=1_000_000, d=128, seed=1003), "c2": dict(N=100_000, d=64, seed=1002)}
+FP32_MATRIX_PEAK_TF = 157.3
+SCORE_BYTES = 1 << 30
+
+
+def timed(fn, reps):
+    """(median ms, peak bytes allocated above the starting level, last result) over `reps` device-event windows, after two
+    warm-up calls."""
+    for _ in range(2):
+        out = fn()
+    del out
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        b.synchronize()
+        ts.append(a.elapsed_time(b))
+    return float(np.median(ts)), int(torch.cuda.max_memory_allocated() - base), out
+
+
+def torch_loss(embs, q, t, ptr, idx, scale, backward):
+    """The loss per query, chunk by chunk; with `backward` the gradient of its mean as well, accumulated chunk by chunk so
+    that only one chunk's scores are alive at a time."""
+    N, B = embs.size(0), q.numel()
+    step = max(1, SCORE_BYTES // (4 * N))
+    e = embs.detach().requires_grad_(backward)
+    out = []
+    for i in range(0, B, step):
+        qi, ti = q[i:i + step], t[i:i + step]
+        s = scale * (e[qi] @ e.T)
+        tsc = s.gather(1, ti[:, None])[:, 0]
+        lens = ptr[i + 1:i + 1 + qi.numel()] - ptr[i:i + qi.numel()]
+        rows = torch.repeat_interleave(torch.arange(qi.numel(), device=e.device), lens)
+        cols = idx[int(ptr[i]):int(ptr[i + qi.numel()])]
+        keep = cols != ti[rows]                                             # the target always stays
+        s = s.index_put((rows[keep], cols[keep]), torch.tensor(float("-inf"), device=e.device))
+        loss = torch.logsumexp(s, 1) - tsc
+        if backward:
+            (loss.sum() / B).backward()
+        out.append(loss.detach())
+    return torch.cat(out), e.grad
+
+
+def run_config(name, reps, batches, with_torch):
+    cfg = CONFIGS[name]
+    dev = torch.device("cuda:0")
+    N, d = cfg["N"], cfg["d"]
+    gen = torch.Generator(device=dev).manual_seed(cfg["seed"])
+    embs = torch.nn.functional.layer_norm(torch.randn(N, d, device=dev, generator=gen), (d,),
+                                          1.0 + 0.1 * torch.randn(d, device=dev, generator=gen),
+                                          0.1 * torch.randn(d, device=dev, generator=gen))
+    model = HyperGNN(text_dim=16, node_feat_dim=8, hidden_dim=16, num_layers=1).to(dev).eval()
+    scale = d ** -0.5
+    res = {}
+    for B in batches:
+        rng = np.random.default_rng(B)
+        q = torch.from_numpy(rng.integers(0, N, B)).to(dev)
+        t = torch.from_numpy(rng.integers(0, N, B)).to(dev)
+        known = (q.repeat(10), torch.from_numpy(rng.integers(0, N, 10 * B)).to(dev))
+        ptr, idx = model._filter_lists(embs, q, known, None, None)
+        flops = 2.0 * B * N * d
+        r = {}
+        r["rank_known_ms"], _, _ = timed(lambda: model.rank_candidates(embs, q, t, filt_ptr=ptr, filt_idx=idx), reps)
+        r["fwd_ms"], _, _ = timed(lambda: model.softmax_loss(embs, q, t, scale=scale), reps)
+        r["fwd_known_ms"], r["fwd_peak_bytes"], ours = timed(
+            lambda: model.softmax_loss(embs, q, t, scale=scale, filt_ptr=ptr, filt_idx=idx), reps)
+
+        def step():
+            e = embs.detach().requires_grad_(True)
+            loss = model.softmax_loss(e, q, t, scale=scale, filt_ptr=ptr, filt_idx=idx)
+            loss.mean().backward()
+            return loss.detach(), e.grad
+
+        r["fwd_bwd_known_ms"], r["fwd_bwd_peak_bytes"], (_, grad) = timed(step, reps)
+        r["fwd_fraction_of_fp32_matrix_peak"] = flops / (r["fwd_known_ms"] * 1e-3) / (FP32_MATRIX_PEAK_TF * 1e12)
+        r["bwd_fraction_of_fp32_matrix_peak"] = (4 * flops / ((r["fwd_bwd_known_ms"] - r["fwd_known_ms"]) * 1e-3)
+                                                 / (FP32_MATRIX_PEAK_TF * 1e12))
+        if with_torch:
+            for key, backward in (("torch_fwd", False), ("torch_fwd_bwd", True)):
+                try:
+                    r[key + "_ms"], r[key + "_peak_bytes"], ref = timed(lambda: torch_loss(embs, q, t, ptr, idx, scale, backward), reps)
+                    r[key + "_loss_max_abs_diff"] = float((ref[0] - ours).abs().max())
+                    if backward:
+                        r["torch_grad_rel_l2_diff"] = float((ref[1] - grad).norm() / ref[1].norm())
+                        r["fwd_bwd_speedup"] = r["torch_fwd_bwd_ms"] / r["fwd_bwd_known_ms"]
+                    else:
+                        r["fwd_speedup"] = r["torch_fwd_ms"] / r["fwd_known_ms"]
+                    del ref
+                except torch.cuda.OutOfMemoryError:
+                    r[key + "_ms"] = "does not fit"
+                    torch.cuda.empty_cache()
+        res[f"B{B}"] = r
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="c3,c2")
+    ap.add_argument("--batches", default="1024,16384")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-torch", action="store_true")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("softmax_time.py measures on an MI355X; no HIP device here")
+    out = {"tool": "softmax_time", "device": torch.cuda.get_device_name(0)}
+    for name in args.configs.split(","):
+        out[name] = run_config(name, args.reps, [int(b) for b in args.batches.split(",")], not args.no_torch)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
