@@ -50,6 +50,10 @@ SIGNATURES = {
     "ghf_subgraph_hops": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _sz, _vp, _vp]),
     "ghf_subgraph_nodes": (_i32, [_vp, _i64, _i32, _vp, _sz, _vp, _vp, _vp, _vp]),
     "ghf_subgraph_edges": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "ghf_subgraph_sample_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "ghf_subgraph_sample_hops": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _i32, C.POINTER(_i32), C.c_uint64, _vp, _sz,
+                                        _vp, _vp, C.POINTER(_i64), _vp]),
+    "ghf_subgraph_sample_edges": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "ghf_weightgen_fwd": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _vp]),
     "ghf_weightgen_fwd_batched": (_i32, [_i32, _vp, C.POINTER(_vp), C.POINTER(_vp), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
@@ -314,6 +318,45 @@ def subgraph(plan, seeds: torch.Tensor, k: int) -> dict:
     m, E_sub = c[:k + 1], c[k + 1]
     return dict(dist=dist, node_list=node_list[:m[k]], new_id=new_id, m=m,
                 edge_index=edge_out[:, :E_sub] if E else edge_out[:, :0], rel=rel_out[:E_sub])
+
+
+def subgraph_sample(plan, seeds: torch.Tensor, fanout: Sequence[int], seed: int) -> dict:
+    """`subgraph` with per-hop fanout caps (include/ghf.h: ghf_subgraph_sample_*): k = len(fanout) hops, hop j keeping at most
+    fanout[j] in-edges (-1: all) of each node first reached at sampled distance j — the ones with the smallest
+    (priority(seed, plan position), plan position).  The keys of `subgraph`, plus host_reads: the words read back inside the
+    hops stage (at most one per capped hop); one more host sync for the counts."""
+    lib = load()
+    seeds = _req(seeds, torch.int64, "seeds")
+    fanout = [int(f) for f in fanout]
+    k = len(fanout)
+    if not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"subgraph_sample: seed {seed} is not a 64-bit unsigned integer")
+    dev, N, E = seeds.device, plan.N, plan.E
+    ws_bytes = lib.ghf_subgraph_sample_workspace_bytes(N, E, k)
+    if ws_bytes == 0:
+        raise ValueError(f"subgraph_sample: bad sizes N={N} E={E} k={k}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    dist = torch.empty(N, dtype=torch.int32, device=dev)
+    keep = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
+    node_list = torch.empty(N, dtype=torch.int64, device=dev)
+    new_id = torch.empty(N, dtype=torch.int64, device=dev)
+    counts = torch.empty(k + 2, dtype=torch.int64, device=dev)           # m_0 .. m_k, E'
+    edge_out = torch.empty((2, max(E, 1)), dtype=torch.int64, device=dev)
+    rel_out = torch.empty(max(E, 1), dtype=torch.int64, device=dev)
+    key, src, st = _ptr(plan.sorted_key), _ptr(plan.sorted_src), _stream()
+    reads = _i64(0)
+    _check(lib.ghf_subgraph_sample_hops(key, src, N, E, plan.R, plan.block_nodes, _ptr(seeds), seeds.numel(), k,
+                                        (_i32 * k)(*fanout), int(seed), _ptr(ws), ws_bytes, _ptr(dist), _ptr(keep),
+                                        C.byref(reads), st), "ghf_subgraph_sample_hops")
+    _check(lib.ghf_subgraph_nodes(_ptr(dist), N, k, _ptr(ws), ws_bytes, _ptr(node_list), _ptr(new_id), _ptr(counts), st),
+           "ghf_subgraph_nodes")
+    _check(lib.ghf_subgraph_sample_edges(key, src, N, E, plan.R, plan.block_nodes, _ptr(keep), _ptr(new_id), _ptr(ws), ws_bytes,
+                                         _ptr(edge_out), _ptr(rel_out), counts.data_ptr() + 8 * (k + 1), st),
+           "ghf_subgraph_sample_edges")
+    c = counts.cpu().tolist()
+    m, E_sub = c[:k + 1], c[k + 1]
+    return dict(dist=dist, node_list=node_list[:m[k]], new_id=new_id, m=m,
+                edge_index=edge_out[:, :E_sub] if E else edge_out[:, :0], rel=rel_out[:E_sub], host_reads=reads.value)
 
 
 def exact_config(d: int) -> Tuple[int, int, int, int]:

@@ -552,6 +552,27 @@ int ghf_subgraph_edges(const uint32_t* sorted_key, const int32_t* sorted_src, in
                                  edge_out, rel_out, num_edges, (hipStream_t)stream);
 }
 
+size_t ghf_subgraph_sample_workspace_bytes(int64_t N, int64_t E, int k) { return subgraph_sample_workspace_bytes(N, E, k); }
+
+int ghf_subgraph_sample_hops(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
+                             const int64_t* seeds, int64_t S, int k, const int* fanout, uint64_t seed, void* workspace,
+                             size_t workspace_bytes, int32_t* dist, int32_t* keep, int64_t* host_reads, void* stream) {
+    GHF_REQUIRE(workspace && dist && fanout && (seeds || S == 0) && ((sorted_key && sorted_src && keep) || E == 0),
+                "subgraph_sample_hops: null pointer argument");
+    GHF_REQUIRE(k >= 1, "subgraph_sample_hops: k must be positive");
+    return launch_subgraph_sample_hops(sorted_key, sorted_src, N, E, R, block_nodes, seeds, S, k, fanout, seed, workspace,
+                                       workspace_bytes, dist, keep, host_reads, (hipStream_t)stream);
+}
+
+int ghf_subgraph_sample_edges(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
+                              const int32_t* keep, const int64_t* new_id, void* workspace, size_t workspace_bytes,
+                              int64_t* edge_out, int64_t* rel_out, int64_t* num_edges, void* stream) {
+    GHF_REQUIRE(new_id && workspace && num_edges && ((sorted_key && sorted_src && keep && edge_out && rel_out) || E == 0),
+                "subgraph_sample_edges: null pointer argument");
+    return launch_subgraph_sample_edges(sorted_key, sorted_src, N, E, R, block_nodes, keep, new_id, workspace, workspace_bytes,
+                                        edge_out, rel_out, num_edges, (hipStream_t)stream);
+}
+
 int ghf_score_pairs_fwd(const float* a, const float* b, const int64_t* ia, const int64_t* ib, int64_t rows_a, int64_t rows_b,
                         int64_t n, int d, float* scores, void* stream) {
     GHF_REQUIRE(a && b && (scores || n == 0), "score_pairs_fwd: null pointer argument");

@@ -222,6 +222,13 @@ int launch_subgraph_nodes(const int32_t* dist, int64_t N, int k, void* ws, size_
 int launch_subgraph_edges(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
                           const int32_t* dist, const int64_t* new_id, int k, void* ws, size_t ws_bytes, int64_t* edge_out,
                           int64_t* rel_out, int64_t* num_edges, hipStream_t stream);
+size_t subgraph_sample_workspace_bytes(int64_t N, int64_t E, int k);
+int launch_subgraph_sample_hops(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
+                                const int64_t* seeds, int64_t S, int k, const int* fanout, uint64_t seed, void* ws,
+                                size_t ws_bytes, int32_t* dist, int32_t* keep, int64_t* host_reads, hipStream_t stream);
+int launch_subgraph_sample_edges(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
+                                 const int32_t* keep, const int64_t* new_id, void* ws, size_t ws_bytes, int64_t* edge_out,
+                                 int64_t* rel_out, int64_t* num_edges, hipStream_t stream);
 // backward.hip
 int launch_tail_bwd(const float* g_out, const float* agg, const float* h, const float* gamma, float eps, const int32_t* indeg,
                     int64_t N, int d, float* dpre, float* G, void* G_split, float* dgb, float* workspace, const float* drop,

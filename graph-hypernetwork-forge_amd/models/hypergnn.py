@@ -17,6 +17,7 @@ not exist here: kernels index W[r] in place.
 
 from __future__ import annotations
 
+import operator
 from typing import Dict, List, Optional, Sequence, Tuple
 
 
@@ -264,26 +265,68 @@ class HyperGNN(nn.Module):
 
     # -- node batches: the rows of a few nodes from their k-hop subgraph (include/ghf.h: ghf_subgraph_*) ---------------
     def forward_nodes(self, node_features: torch.Tensor, edge_index: torch.Tensor, edge_texts: List[str],
-                      nodes: torch.Tensor) -> torch.Tensor:
+                      nodes: torch.Tensor, fanout=None, seed: Optional[int] = None) -> torch.Tensor:
         """``forward(node_features, edge_index, edge_texts)[nodes]`` computed on the nodes' ``num_layers``-hop
         in-neighbourhood only: an L-layer row depends on the rows within L hops upstream of it (reference hypergnn.py:190-230,
         288-296), so the result is exact, not sampled.  `nodes`: a 1-D int32 / int64 tensor (device or CPU), duplicates and
         negative ids (as torch indexing) allowed.  Gradients reach the parameters and `node_features`; dropout masks in
-        training mode are drawn over the subgraph's rows (random as in ``forward``, not the full forward's draws)."""
+        training mode are drawn over the subgraph's rows (random as in ``forward``, not the full forward's draws).
+
+        `fanout` (None: the exact call above) samples the neighbourhood as GraphSAGE / NeighborLoader do: an int, or
+        ``num_layers`` ints, each >= 1 or -1 (no cap); hop j keeps at most ``fanout[j]`` in-edges, drawn uniformly without
+        replacement, of every node first reached at hop j — ``fanout[0]`` caps the seeds' own in-edges, which the last layer
+        consumes.  The layer aggregates by mean, so each sampled aggregate is an unbiased estimate.  `seed` (an int in
+        [0, 2**63); None: drawn from torch's default CPU generator, so ``torch.manual_seed`` reproduces a run) fixes the
+        draw, which is a pure function of (plan, nodes, fanout, seed) (include/ghf.h).  The plan's geometry depends on the
+        hidden size and on whether gradients are recorded, so one seed may pick different edges in ``train()`` and
+        ``eval()``.  ``last_subgraph`` records `fanout` (a tuple) and the seed used."""
         self._check_inputs(node_features, edge_index, edge_texts, "edge_texts")
+        sample = self._sample_args(fanout, seed)
         seeds = self._seed_ids(nodes, node_features)
         grad = wants_grad(self, node_features) or self._dropping()
         plan = self._plan_lookup(edge_index, edge_texts, node_features.size(0), node_features.device, training=grad)[0]
-        return self._forward_nodes(node_features, plan, seeds, grad, edge_index)
+        return self._forward_nodes(node_features, plan, seeds, grad, edge_index, sample)
 
     def forward_nodes_ids(self, node_features: torch.Tensor, edge_index: torch.Tensor, edge_rel_ids: torch.Tensor,
-                          relation_texts: Sequence[str], nodes: torch.Tensor) -> torch.Tensor:
+                          relation_texts: Sequence[str], nodes: torch.Tensor, fanout=None,
+                          seed: Optional[int] = None) -> torch.Tensor:
         """``forward_nodes`` for callers that already hold relation ids (see ``forward_ids``)."""
         self._check_inputs(node_features, edge_index, edge_rel_ids, "edge_rel_ids")
+        sample = self._sample_args(fanout, seed)
         seeds = self._seed_ids(nodes, node_features)
         grad = wants_grad(self, node_features) or self._dropping()
         plan = self._ids_plan(edge_index, edge_rel_ids, relation_texts, node_features, grad)
-        return self._forward_nodes(node_features, plan, seeds, grad, edge_index)
+        return self._forward_nodes(node_features, plan, seeds, grad, edge_index, sample)
+
+    def _sample_args(self, fanout, seed):
+        """forward_nodes' `fanout` / `seed` checked on the host: None (the exact call), or (fanout tuple of num_layers ints,
+        seed) — a seed of None drawn from torch's default CPU generator."""
+        def integer(v, what):
+            if isinstance(v, bool) or not hasattr(v, "__index__") or isinstance(v, torch.Tensor):
+                raise TypeError(f"{what} must be an integer, got {type(v).__name__}")
+            return operator.index(v)
+
+        if fanout is None:
+            if seed is not None:
+                raise ValueError("seed given without fanout: the exact forward_nodes draws nothing")
+            return None
+        if isinstance(fanout, (str, bytes)) or (not hasattr(fanout, "__index__") and not hasattr(fanout, "__iter__")):
+            raise TypeError(f"fanout must be an int or a sequence of {self.num_layers} ints, got {type(fanout).__name__}")
+        if hasattr(fanout, "__iter__") and not isinstance(fanout, torch.Tensor):
+            fan = tuple(integer(f, "fanout entries") for f in fanout)
+            if len(fan) != self.num_layers:
+                raise ValueError(f"fanout has {len(fan)} entries, the model has {self.num_layers} layers")
+        else:
+            fan = (integer(fanout, "fanout"),) * self.num_layers
+        if any(f == 0 or f < -1 or f >= 1 << 31 for f in fan):
+            raise ValueError(f"fanout entries must be >= 1, or -1 for no cap: got {fan}")
+        if seed is None:
+            seed = int(torch.randint(0, (1 << 63) - 1, (1,), dtype=torch.int64).item())
+        else:
+            seed = integer(seed, "seed")
+            if not 0 <= seed < 1 << 63:
+                raise ValueError(f"seed must be in [0, 2**63), got {seed}")
+        return fan, seed
 
     @classmethod
     def _seed_ids(cls, nodes: torch.Tensor, node_features: torch.Tensor) -> torch.Tensor:
@@ -295,26 +338,30 @@ class HyperGNN(nn.Module):
         return ids
 
     def _forward_nodes(self, x: torch.Tensor, plan: GraphPlan, seeds: torch.Tensor, grad: bool,
-                       edge_index: torch.Tensor) -> torch.Tensor:
+                       edge_index: torch.Tensor, sample=None) -> torch.Tensor:
         """The rows `seeds` (int64, in range) of the forward on `plan`'s graph, from the seeds' k-hop subgraph: its nodes
         ordered by (hop distance, id), so that the rows within j hops are a prefix; inference layer l (0-based) then computes
-        the first m_{k-1-l} rows only (the last layer: the seeds).  The sub-plan is built per call and not cached."""
+        the first m_{k-1-l} rows only (the last layer: the seeds).  The sub-plan is built per call and not cached.
+        `sample` = (fanout, seed): the sampled subgraph instead (_native.subgraph_sample), which keeps the prefix property."""
         k, d, device = self.num_layers, self.hidden_dim, x.device
         if seeds.numel() == 0:
             return x.new_zeros((0, d), dtype=torch.float32)
-        sub = _native.subgraph(plan, seeds, k)
+        if sample is None:
+            sub, drawn = _native.subgraph(plan, seeds, k), {}
+        else:
+            sub, drawn = _native.subgraph_sample(plan, seeds, *sample), dict(fanout=sample[0], seed=sample[1])
         m, n = sub["m"], sub["m"][k]
         xs = x.index_select(0, sub["node_list"])                     # differentiable: gradients reach node_features
         rows = sub["new_id"].index_select(0, seeds)
         config = CSR_CONFIG if plan.block_nodes == 1 else None        # (the full plan's kernel family: wide rows stay wide)
         if sub["edge_index"].size(1) == 0:
             if grad:                                                  # (no edge to train through: the full recorded forward)
-                self.last_subgraph = dict(m=m, edges=0, block_nodes=plan.block_nodes, wlayout=plan.wlayout)
+                self.last_subgraph = dict(m=m, edges=0, block_nodes=plan.block_nodes, wlayout=plan.wlayout, **drawn)
                 return self._forward_recorded(x, plan, edge_index).index_select(0, seeds)
             sub_plan = empty_plan(n, plan.unique_texts, config or plan_config(d, 0, n), device)
         else:
             sub_plan = build_plan(sub["edge_index"], sub["rel"], plan.unique_texts, n, d, device, force_generic=config is not None)
-        self.last_subgraph = dict(m=m, edges=sub_plan.E, block_nodes=sub_plan.block_nodes, wlayout=sub_plan.wlayout)
+        self.last_subgraph = dict(m=m, edges=sub_plan.E, block_nodes=sub_plan.block_nodes, wlayout=sub_plan.wlayout, **drawn)
         if grad:
             out = self._forward_recorded(xs, sub_plan, sub["edge_index"])
         else:

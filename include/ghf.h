@@ -140,6 +140,50 @@ int ghf_subgraph_edges(const uint32_t* sorted_key, const int32_t* sorted_src, in
                        const int32_t* dist, const int64_t* new_id, int k, void* workspace, size_t workspace_bytes,
                        int64_t* edge_out /* [2, E] */, int64_t* rel_out /* [E] */, int64_t* num_edges /* [1] */, void* stream);
 
+/* ---- sampled node-batch subgraph: per-hop fanout caps (HyperGNN.forward_nodes(..., fanout, seed)) ------------------
+ * The layer aggregates by mean, so a uniform sample without replacement of a row's in-edges is an unbiased estimate of that
+ * row's aggregate.  Inputs: fanout [k] (HOST array of ints, each -1 or >= 1) and a 64-bit seed.  Hop j (0 <= j < k) expands
+ * the nodes first reached at sampled distance j (the seeds are distance 0).  For such a node t:
+ *   fanout[j] == -1, or t has at most fanout[j] in-edges: every in-edge of t is kept;
+ *   otherwise exactly fanout[j] are kept: those with the smallest (priority(e), position(e)).
+ * position(e) is the edge's index in the plan's sorted order (its index in sorted_key / sorted_src) and, in uint64
+ * arithmetic modulo 2^64 (splitmix64: Steele, Lea & Flood 2014, with Vigna's constants),
+ *   z = seed + (position(e) + 1) * 0x9E3779B97F4A7C15
+ *   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *   z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *   z =  z ^ (z >> 31)
+ *   priority(e) = z >> 32                                   (a 32-bit integer)
+ * Sources of kept edges that have no distance yet get distance j + 1.  A node is expanded once, at the hop that first
+ * reached it; nodes at distance k are not expanded; parallel edges are separate edges.  So every destination at distance
+ * j <= k - 1 has at most fanout[j] kept in-edges, their sources are at distance <= j + 1, and node_list ordered by
+ * (dist, id) keeps the "rows within j hops are a prefix" property.  The result is a pure function of (plan, seeds, fanout,
+ * seed): no value written depends on which thread lands first.  It depends on the PLAN's order: plans of the same graph
+ * with another geometry (hidden size, recorded or not) number the edges differently, and the same seed then picks other
+ * edges.  With every fanout[j] == -1 or >= the largest in-degree the outputs equal ghf_subgraph_*'s bit for bit.
+ *   ghf_subgraph_sample_workspace_bytes: the workspace of the three stages (256-byte aligned), 0 for bad sizes: the scan
+ *                       arrays of ghf_subgraph_workspace_bytes plus, per edge, two 64-bit sort keys and two 32-bit values.
+ *   ghf_subgraph_sample_hops: dist [N] int32 (sampled distance, k + 1 when not reached) and keep [E] int32 (1: the edge at
+ *                       that plan position is kept).  A capped hop: flags, a scan, a compaction into keys (dst << 32 |
+ *                       priority) with the position as value, one stable radix sort, one selection pass; a hop with
+ *                       fanout -1: one pass over the edges, no sort.  UNLIKE every other call, a capped hop reads ONE word
+ *                       back on the host (the number of candidate edges: the sort's length) and waits for `stream`: the call
+ *                       is not graph-capturable.  At most k reads, none for a hop with fanout -1; the first capped hop that
+ *                       reads a count of zero ends the stage (the later hops are skipped).  The host does not learn of an
+ *                       uncapped hop that reached nobody before the next capped hop's read.  host_reads (HOST pointer, may
+ *                       be NULL) receives their number.
+ *   ghf_subgraph_nodes: as above, on dist, with this workspace.
+ *   ghf_subgraph_sample_edges: the kept edges in the plan's sorted order (a stable compaction), renumbered by new_id, with
+ *                       the plan's relation ids: edge_out / rel_out / num_edges as ghf_subgraph_edges.
+ * Requires what ghf_subgraph_* requires. */
+size_t ghf_subgraph_sample_workspace_bytes(int64_t N, int64_t E, int k);
+int ghf_subgraph_sample_hops(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
+                             const int64_t* seeds, int64_t S, int k, const int* fanout /* HOST [k] */, uint64_t seed,
+                             void* workspace, size_t workspace_bytes, int32_t* dist, int32_t* keep /* [E] */,
+                             int64_t* host_reads /* HOST [1] or NULL */, void* stream);
+int ghf_subgraph_sample_edges(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
+                              const int32_t* keep, const int64_t* new_id, void* workspace, size_t workspace_bytes,
+                              int64_t* edge_out /* [2, E] */, int64_t* rel_out /* [E] */, int64_t* num_edges /* [1] */, void* stream);
+
 /* ---- K1: weight generation ------------------------------------------------------
  * Replaces models/weight_generator.py:137-141 (three nn.Sequential heads, reshape,
  * * exp(log_scale)) for B = R relation embeddings at once.

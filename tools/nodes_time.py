@@ -1,13 +1,18 @@
 """Node-batch forward timing: HyperGNN.forward_nodes against the full forward, on BASELINE configs 3 and 2 (the bench's
 synthetic graphs and seeds), with a breakdown of where a call's time goes.  Prints one JSON line.
 
-    python tools/nodes_time.py [--configs c3,c2] [--reps 5]
+    python tools/nodes_time.py [--configs c3,c2] [--reps 5] [--kind uniform|powerlaw] [--fanout 5,5,5[;10,10,10]]
 
 Per config: the full inference forward; forward_nodes (eval) at 1,024 and 16,384 random seeds, split into the subgraph
 extraction (ghf_subgraph_*, with its one host sync for the counts), the sub-plan build (build_plan: a device sort and
 its host syncs), the input projection over all subgraph rows (with the feature gather) and the shrunk layers; one training
 step (forward_nodes in train mode + backward) on 1,024 seeds against the same step through forward, with the per-call reversed-plan / grouping cost
-(build_train_plan) on its own.  Times are medians of device-event windows (ms), warm (plans of the full graph cached)."""
+(build_train_plan) on its own.  Times are medians of device-event windows (ms), warm (plans of the full graph cached).
+
+--fanout adds, per cap list (the first num_layers entries of each are used) and per seed count, the sampled call beside
+the exact one: m, the sampled edges, the sampled extraction (ghf_subgraph_sample_*: its hop passes, sorts and host reads
+together — split them with a kernel trace), the whole inference call and the training step, each with its exact
+counterpart from the same process."""
 
 from __future__ import annotations
 
@@ -46,17 +51,61 @@ def timed(fn, reps):
     return float(np.median(ts)), out
 
 
-def run_config(name, reps):
+def setup(name, kind):
+    """The config's synthetic graph (the bench's seeds), features and model on the device."""
     cfg = CONFIGS[name]
     dev = torch.device("cuda:0")
     N, E, R, d, L, T = (cfg[k] for k in ("N", "E", "R", "d", "L", "T"))
-    ei_np, rel_np = synth.make_graph_arrays(N, E, R, cfg["seed"], "uniform")
+    ei_np, rel_np = synth.make_graph_arrays(N, E, R, cfg["seed"], kind)
     names = synth.relation_names(R)
     texts = [names[i] for i in rel_np.tolist()]
     ei = torch.from_numpy(ei_np).to(dev)
     x = torch.randn(N, d, generator=torch.Generator(device=dev).manual_seed(cfg["seed"]), device=dev)
     torch.manual_seed(0)
     model = HyperGNN(text_dim=T, node_feat_dim=d, hidden_dim=d, num_layers=L).to(dev).eval()
+    return model, x, ei, texts, N, d, L, dev
+
+
+def run_sampled(name, reps, kind, fanouts):
+    """Per cap list and seed count: the sampled forward_nodes beside the exact one (inference call, extraction, training step)."""
+    model, x, ei, texts, N, d, L, dev = setup(name, kind)
+    res = {}
+    for S in (1024, 16384):
+        seeds = torch.from_numpy(np.random.default_rng(S).choice(N, S, replace=False)).to(dev)
+        g = torch.randn(S, d, device=dev, generator=torch.Generator(device=dev).manual_seed(5))
+
+        def measure(fan):
+            kw = {} if fan is None else dict(fanout=fan, seed=12345)
+            out = {}
+            model.eval()
+            with torch.no_grad():
+                plan = model.plan_for(ei, texts, N, dev)
+                out["ms"], _ = timed(lambda: model.forward_nodes(x, ei, texts, seeds, **kw), reps)
+                if fan is None:
+                    out["extract_ms"], sub = timed(lambda: _native.subgraph(plan, seeds, L), reps)
+                else:
+                    out["extract_ms"], sub = timed(lambda: _native.subgraph_sample(plan, seeds, fan, 12345), reps)
+                    out["host_reads"] = sub["host_reads"]
+                out["m"], out["edges"] = sub["m"], int(sub["edge_index"].size(1))
+            model.train()
+
+            def step():
+                model.zero_grad(set_to_none=True)
+                (model.forward_nodes(x, ei, texts, seeds, **kw) * g).sum().backward()
+
+            out["step_ms"], _ = timed(step, reps)
+            out["train_m"], out["train_edges"] = model.last_subgraph["m"], model.last_subgraph["edges"]
+            model.eval()
+            return out
+
+        res[f"nodes{S}"] = {"exact": measure(None)}
+        for fan in fanouts:
+            res[f"nodes{S}"]["fanout " + ",".join(map(str, fan[:L]))] = measure(tuple(fan[:L]))
+    return res
+
+
+def run_config(name, reps, kind="uniform"):
+    model, x, ei, texts, N, d, L, dev = setup(name, kind)
     res = {}
     with torch.no_grad():
         res["forward_ms"], full = timed(lambda: model(x, ei, texts), reps)
@@ -106,12 +155,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="c3,c2")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--kind", default="uniform", choices=["uniform", "powerlaw"], help="the synthetic graph's degree law")
+    ap.add_argument("--fanout", default="", help="per-hop caps, e.g. 5,5,5 (several lists: separate with ';'; -1 = no cap): "
+                    "time the sampled forward_nodes beside the exact one instead of the exact call's breakdown")
     args = ap.parse_args()
+    fanouts = [[int(f) for f in part.split(",")] for part in args.fanout.split(";") if part.strip()]
+    for name in args.configs.split(","):
+        if any(len(f) < CONFIGS[name]["L"] for f in fanouts):
+            raise SystemExit(f"--fanout needs {CONFIGS[name]['L']} caps per list for {name}")
     if not torch.cuda.is_available():
         raise SystemExit("nodes_time.py measures on an MI355X; no HIP device here")
-    out = {"tool": "nodes_time", "device": torch.cuda.get_device_name(0)}
+    out = {"tool": "nodes_time", "device": torch.cuda.get_device_name(0), "kind": args.kind}
     for name in args.configs.split(","):
-        out[name] = run_config(name, args.reps)
+        out[name] = run_sampled(name, args.reps, args.kind, fanouts) if fanouts else run_config(name, args.reps, args.kind)
     print(json.dumps(out))
 
 
