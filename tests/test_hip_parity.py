@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import cases
+from _hyper_cases import frag16_of as _to_frag16, split2h_np as _split2h_np, split2h_of as _to_split2h
 from _util import assert_close
 from graph_hypernetwork_forge_amd import HyperGNN, WeightGenerator, ToyKnowledgeGraph, _native, synth
 from graph_hypernetwork_forge_amd.plan import build_plan, relation_ids
@@ -350,29 +351,6 @@ def test_frag16_layout_is_a_permutation_of_natural():
     assert torch.equal(back, cat)
 
 
-def _split2h_np(x, axis_groups):
-    """SPLIT2H pieces of x: per group (all axes but the first `axis_groups`) s = 13 - floor(log2(max |x|)) clamped to
-    +-100; hi = fp16(x 2^s), lo = fp16(x 2^s - hi).  Returns (hi, lo as float16, 2^-s as float32 per group)."""
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    mx = np.abs(x).reshape(x.shape[:axis_groups] + (-1,)).max(axis=-1)
-    e = ((mx.view(np.uint32) >> 23) & 255).astype(np.int32) - 127                        # exponent field, as the device
-    sh = np.clip(13 - e, -100, 100)
-    up = np.ldexp(np.float32(1), sh).astype(np.float32).reshape(sh.shape + (1,) * (x.ndim - axis_groups))
-    xs = x * up
-    hi = xs.astype(np.float16)
-    lo = (xs - hi.astype(np.float32)).astype(np.float16)
-    return hi, lo, np.ldexp(np.float32(1), -sh).astype(np.float32)
-
-
-def _to_split2h(Wm, Ws):
-    """Wh[r][o/16][kk/32][piece][lane = ((kk%32)/8)*16 + o%16][kk%8] fp16 + float 2^-s [R], as an opaque float32 buffer."""
-    R, d, _ = Wm.shape
-    hi, lo, down = _split2h_np(np.concatenate([Wm, Ws], axis=1), 1)                       # [R, 2d, d]
-    pc = np.stack([hi, lo]).reshape(2, R, 2 * d // 32, 4, 8, d // 16, 16)                 # piece, r, ks, q, e, ct, c16
-    frag = np.ascontiguousarray(pc.transpose(1, 5, 2, 0, 3, 6, 4)).reshape(-1)            # r, ct, ks, piece, q, c16, e
-    return np.concatenate([frag.view(np.float32), down])
-
-
 def _rows_split2h(h):
     """What ghf_split_rows(SPLIT2H) writes: [N][2][d] fp16 then float 2^-s [N], as int16."""
     hi, lo, down = _split2h_np(h, 1)
@@ -547,12 +525,6 @@ def _layer_inputs(N, E, R, d, seed, kind):
     gamma = (1.0 + 0.2 * synth.normal(seed, "g", (d,))).astype(np.float32)
     beta = (0.2 * synth.normal(seed, "bt", (d,))).astype(np.float32)
     return ei, rel, h, Wm, Ws, b, gamma, beta
-
-
-def _to_frag16(Wm, Ws):
-    R, d, _ = Wm.shape
-    cat = np.concatenate([Wm, Ws], axis=1).reshape(R, 2 * d // 16, 4, 4, d // 16, 16)     # r, j, q, s, nt, c16
-    return np.ascontiguousarray(cat.transpose(0, 4, 1, 2, 5, 3)).reshape(-1)             # r, nt, j, q, c16, s
 
 
 @pytest.mark.parametrize("d,N,E,R,kind", [
