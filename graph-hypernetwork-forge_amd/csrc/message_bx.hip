@@ -111,6 +111,14 @@ __device__ __forceinline__ int opaque_lane(int lane) {
     return lane + z;
 }
 
+// The lane id counted anew (mbcnt over a mask of all ones: the number of lanes below this one, whatever EXEC holds), behind an
+// asm the optimiser cannot see through: no register holds it between its uses.
+__device__ __forceinline__ int fresh_lane() {
+    int z;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+    return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, (unsigned)z));
+}
+
 // the tail's loads of h and its stores are non-temporal (each line is touched once per launch: 2.94 -> 2.92 ms per C3 launch)
 template <class T> __device__ __forceinline__ T bx_tail_ld(const T* p) { return __builtin_nontemporal_load(p); }
 template <class T> __device__ __forceinline__ void bx_tail_st(T* p, T v) { __builtin_nontemporal_store(v, p); }
@@ -156,6 +164,18 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define BX_PIN_64(s) "+{v[64:79]}"(s[0]), "+{v[80:95]}"(s[1]), "+{v[96:111]}"(s[2])        // (BxCfg<64>::NPW = 48)
 
 struct BxChunk { int r; int e0; int rows; };
+
+// hidden 128: the fused tail's operands from memory for GB_ four-row groups of a wave (residual rows, in-degrees, the LayerNorm
+// parameters of the lane's columns): requested in one place (tail_issue), used in another (tail_rows), workgroup barriers in between
+template <int GB_, int NV_> struct BxTailSt {
+    static constexpr int GB = GB_, NV = NV_;
+    f32x4 x[GB_][NV_];
+    int deg[GB_];
+    float gm[4 * NV_], bt[4 * NV_];
+};
+// hidden 128: of a half's twelve four-row groups per (consumer wave, helper wave) pair, the consumer's share.  The consumers'
+// operands arrive while the helpers dump; the helpers request theirs behind their dump and wait for them once.
+constexpr int BX_TCG = 8;
 
 // SKIP: bit 0 = the source half of the weights is zero (GHF_FLAG_ZERO_SRC), bit 1 = the destination half: that half's gathers
 // and products are compiled out (a run-time switch cost the consumers' loop a spilled weight fragment)
@@ -252,6 +272,9 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
     // 16 lanes per row (a wave works on four rows at a time), CPL = d / 16 adjacent columns per lane: every load and store is
     // 16 bytes per lane, and a row reduction is four DPP steps inside its 16-lane row — for four rows at once.  (One wave
     // per row, two columns per lane, took 1,800 cycles per row: ~110 dependent instructions, 2- and 4-byte stores.)
+    // (tail_rows below repeats this lambda's per-row arithmetic for hidden 128 — row_sum / row_max, the mean, ReLU, LayerNorm,
+    // the split and the range guard — operation for operation: a change to either goes into both.  They are two copies because
+    // a helper shared with hidden 64 moved that instance's register assignment: DESIGN_HISTORY.md §12.)
     auto tail_half = [&](int half, auto gb_c) __attribute__((always_inline)) {          // gb_c: four-row groups in flight per wave
         const float* acc_lds = (const float*)smem;       // dump rows, natural column order
         // a lane's CPL columns: 4 (lane mod 16) + 64 i + (0..3), i < NV — every 16-byte load / store of a row's 16 lanes is one
@@ -391,6 +414,160 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             }
         }
     };
+
+    // ---- hidden 128: the same tail with its memory operands requested apart from their use ----
+    // A wave asks for the residual rows, in-degrees and LayerNorm parameters of ALL its four-row groups of a half at once
+    // (tail_issue) and turns them into rows behind the barriers (tail_rows).  Its groups are gfirst, gfirst + 4, .. below gend.
+    // The requests are buffer loads without a branch around them — hipcc waits for a load at the join of such a branch — an
+    // empty descriptor standing for "no residual" / "no LayerNorm" (zeros, no memory access).
+    auto tail_issue = [&](int half, auto& st, int gfirst, auto gend_c) __attribute__((always_inline)) {
+        using St = typename std::remove_reference<decltype(st)>::type;
+        constexpr int GB = St::GB, NV = St::NV, CS = 64;
+        static_assert(NV * 4 == CPL && 4 * GB <= decltype(gend_c)::value, "one batch holds all of the wave's groups");
+        if (slot >= 0) return;                            // (a split block's item copies raw sums: tail_rows)
+        const int tl = fresh_lane(), sub = tl >> 4, c0 = 4 * (tl & 15);
+        const bool no_x = no_tail && !(no_tail & GHF_FLAG_ADD_H);
+        const __amdgpu_buffer_rsrc_t rsG = __builtin_amdgcn_make_buffer_rsrc((void*)gamma, 0, no_tail ? 0 : D * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)beta, 0, no_tail ? 0 : D * 4, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(     // (N * 4 d bytes are below 4 GiB: launch_bx_for)
+            (void*)h, 0, no_x ? 0 : (int)(uint32_t)((uint64_t)N * D * 4), 0x00020000);
+#pragma unroll
+        for (int c = 0; c < CPL; ++c) {
+            st.gm[c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsG, (c0 + CS * (c >> 2) + (c & 3)) * 4, 0, 0));
+            st.bt[c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsB, (c0 + CS * (c >> 2) + (c & 3)) * 4, 0, 0));
+        }
+#pragma unroll
+        for (int gb = 0; gb < GB; ++gb) {
+            const int v = 4 * (gfirst + 4 * gb) + sub;
+            const int nl = (v / HPW) * NPW + half * HPW + (v % HPW);
+            const int64_t node = node0 + (nl < nrows ? nl : nrows - 1);
+            st.deg[gb] = indeg[node];
+#pragma unroll
+            for (int i = 0; i < NV; ++i)                  // (GHF_FLAG_ADD_H: the residual operand also without the tail)
+                st.x[gb][i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                    rsX, (int)(((uint32_t)node * D + c0 + CS * i) * 4u), 0, 2 /*nt*/));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // (from `float inv` on this is tail_half's per-row arithmetic, operation for operation, on operands held in `st`: the results
+    // are bit-equal to tail_half's only while the two stay so — a change to either goes into both)
+    auto tail_rows = [&](int half, auto& st, int gfirst, auto gend_c) __attribute__((always_inline)) {
+        using St = typename std::remove_reference<decltype(st)>::type;
+        constexpr int GB = St::GB, NV = St::NV, gend = decltype(gend_c)::value, CS = 64;
+        // The batch is waited for as a whole, here.  The rows' stores are conditional, so hipcc counts none of them: a counted
+        // wait for the batch's last rows further down would be vmcnt(0) — behind the stores of every group before; and the
+        // requests, being buffer loads, are hoisted over tail_issue's branch: left pending on a split block's path they become
+        // a vmcnt(0) in front of the next batch's requests — behind this batch's stores.
+        __builtin_amdgcn_s_waitcnt(0x0F70);               // vmcnt(0) alone
+        const float* acc_lds = (const float*)smem;        // dump rows, natural column order
+        const int tl = fresh_lane(), sub = tl >> 4, c0 = 4 * (tl & 15);
+        auto node_of = [&](int v) -> int { return (v / HPW) * NPW + half * HPW + (v % HPW); };   // block-local node of dump row v
+        auto row_sum = [&](float v) -> float {            // over the 16 lanes of a row, result in each of them
+            v += dpp_take<0xB1, 0xF>(v);
+            v += dpp_take<0x4E, 0xF>(v);
+            v += dpp_take<0x141, 0xF>(v);
+            v += dpp_take<0x140, 0xF>(v);
+            return v;
+        };
+        auto row_max = [&](float v) -> float {            // non-negative values
+            v = fmaxf(v, dpp_take<0xB1, 0xF>(v));
+            v = fmaxf(v, dpp_take<0x4E, 0xF>(v));
+            v = fmaxf(v, dpp_take<0x141, 0xF>(v));
+            v = fmaxf(v, dpp_take<0x140, 0xF>(v));
+            return v;
+        };
+        if (slot >= 0) {                                  // one item of a split block: raw sums to my slot
+            float* __restrict__ ps = partial + (size_t)slot * BN * D;
+            for (int g = gfirst; g < gend; g += 4) {
+                const int v = 4 * g + sub;
+                float* __restrict__ o = ps + (size_t)node_of(v) * D + c0;
+#pragma unroll
+                for (int i = 0; i < NV; ++i) *(f32x4*)(o + CS * i) = *(const f32x4*)(acc_lds + v * D + c0 + CS * i);
+            }
+            return;
+        }
+        float inv[GB];
+#pragma unroll
+        for (int gb = 0; gb < GB; ++gb) inv[gb] = (no_tail & GHF_FLAG_RAW_SUM) ? 1.0f : 1.0f / (float)(st.deg[gb] > 1 ? st.deg[gb] : 1);
+#pragma unroll
+        for (int gb = 0; gb < GB; ++gb) {
+            const int v = 4 * (gfirst + 4 * gb) + sub;
+            const int nl = node_of(v);
+            const bool live = nl < nrows;
+            f32x4 a[NV];
+#pragma unroll
+            for (int i = 0; i < NV; ++i) a[i] = *(const f32x4*)(acc_lds + v * D + c0 + CS * i);
+            if (agg_out && live) {                       // side output: the mean before the tail (what the backward keeps)
+                float* __restrict__ o = agg_out + (size_t)(node0 + nl) * D + c0;
+#pragma unroll
+                for (int i = 0; i < NV; ++i) bx_tail_st((f32x4*)(o + CS * i), a[i] * inv[gb]);
+            }
+            float y[CPL];
+            float s = 0.f;
+#pragma unroll
+            for (int c = 0; c < CPL; ++c) {
+                const float av = a[c >> 2][c & 3] * inv[gb];
+                y[c] = no_tail ? av + st.x[gb][c >> 2][c & 3] : fmaxf(av + st.x[gb][c >> 2][c & 3], 0.f);      // (x = 0 without ADD_H)
+                s += y[c];
+            }
+            if (!no_tail) {
+                const float mean = row_sum(s) * (1.0f / D);
+                float var = 0.f;
+#pragma unroll
+                for (int c = 0; c < CPL; ++c) { const float t = y[c] - mean; var += t * t; }
+                const float rstd = 1.0f / sqrtf(row_sum(var) * (1.0f / D) + eps);
+#pragma unroll
+                for (int c = 0; c < CPL; ++c) y[c] = (y[c] - mean) * rstd * st.gm[c] + st.bt[c];
+            }
+            float up = 1.f;
+            if (h_split_out) {                           // the same row cut into fp16 pieces, for the next layer's gathers
+                float mx = 0.f;
+#pragma unroll
+                for (int c = 0; c < CPL; ++c) mx = fmaxf(mx, fabsf(y[c]));
+                const int sh = split2h_shift(row_max(mx));
+                up = pow2f(sh);
+                if ((tl & 15) == 0 && live) *(float*)((char*)h_split_out + (size_t)hsc_off + (size_t)(node0 + nl) * 4) = pow2f(-sh);
+            }
+            if (live) {
+                float* __restrict__ o = h_out + (size_t)(node0 + nl) * D + c0;
+#pragma unroll
+                for (int i = 0; i < NV; ++i) bx_tail_st((f32x4*)(o + CS * i), (f32x4){y[4 * i], y[4 * i + 1], y[4 * i + 2], y[4 * i + 3]});
+                if (h_split_out) {
+                    _Float16* __restrict__ sp = (_Float16*)h_split_out + (size_t)(node0 + nl) * (NPL * D) + c0;
+                    _Float16 hi[CPL], lo[CPL];
+#pragma unroll
+                    for (int c = 0; c < CPL; ++c) split2h(y[c] * up, hi[c], lo[c]);
+#pragma unroll
+                    for (int i = 0; i < NV; ++i) {
+                        bx_tail_st((f16x4*)(sp + CS * i), (f16x4){hi[4 * i], hi[4 * i + 1], hi[4 * i + 2], hi[4 * i + 3]});
+                        bx_tail_st((f16x4*)(sp + D + CS * i), (f16x4){lo[4 * i], lo[4 * i + 1], lo[4 * i + 2], lo[4 * i + 3]});
+                    }
+                }
+            }
+            if (h_split_out) {                           // range guard (common.h): rows with many entries far below their largest
+                int tiny = 0, nz = 0;
+#pragma unroll
+                for (int c = 0; c < CPL; ++c) { tiny += range_tiny(y[c] * up); nz += y[c] != 0.f; }
+                if (__ballot(tiny != 0)) {               // (rare)
+                    tiny = (int)row_sum((float)tiny);
+                    nz = (int)row_sum((float)nz);
+                    if ((tl & 15) == 0 && live) range_raise(range_flag, GHF_RANGE_ROWS, tiny, nz);
+                }
+            }
+        }
+    };
+    // a barrier of that epilogue: it leaves the requests in flight (__syncthreads() waits for them: vmcnt(0))
+    auto tail_barrier = [&]() __attribute__((always_inline)) {
+        BX_LGKM0();
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+    };
+    constexpr int TNG = BN / 2 / 4;                           // four-row groups per half
+    constexpr int TCG = BX_TCG, THG = TNG / 4 - TCG;          // of them per consumer wave, per helper wave (hidden 128)
+    static_assert(D != 128 || (TNG % 4 == 0 && TCG >= 1 && THG >= 1 && 9 * THG + 2 * CPL <= 96),
+                  "the helpers' operands of a half fit the registers its dump freed");
+    std::integral_constant<int, TNG> c_tng;
+    std::integral_constant<int, 4 * TCG> c_cend;
 
     if (helper) {
         typename std::conditional<D == 128, f32x32, f32x16>::type sm[NSV];   // the block sums (see header): register PL*n + e = position
@@ -677,14 +854,31 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
         };
         __syncthreads();
         dump_half(std::integral_constant<int, 0>{});
-        BX_LGKM0();
-        __syncthreads();
-        tail_half(0, std::integral_constant<int, 1>{});              // (the other half of the sums is still in registers)
-        __syncthreads();
-        dump_half(std::integral_constant<int, 1>{});
-        BX_LGKM0();
-        __syncthreads();
-        tail_half(1, std::integral_constant<int, BX_TGB>{});
+        if constexpr (D == 128) {
+            // The wave's groups of a half are requested in one batch, once: the first half's behind its dump, into the
+            // registers that dump freed; the second half's right behind the first half's rows — still before the second dump,
+            // whose registers they do not need — so that they land during the barrier and that dump.  The consumers, idle while
+            // the helpers dump, take TCG of a pair's twelve groups and have their operands by the time the dump is visible.
+            const int gf = 4 * TCG + hw;
+            BxTailSt<THG, CPL / 4> st;
+            tail_issue(0, st, gf, c_tng);
+            tail_barrier();
+            tail_rows(0, st, gf, c_tng);
+            tail_issue(1, st, gf, c_tng);
+            tail_barrier();
+            dump_half(std::integral_constant<int, 1>{});
+            tail_barrier();
+            tail_rows(1, st, gf, c_tng);
+        } else {
+            BX_LGKM0();
+            __syncthreads();
+            tail_half(0, std::integral_constant<int, 1>{});              // (the other half of the sums is still in registers)
+            __syncthreads();
+            dump_half(std::integral_constant<int, 1>{});
+            BX_LGKM0();
+            __syncthreads();
+            tail_half(1, std::integral_constant<int, BX_TGB>{});
+        }
     } else {
         // =============================================== CONSUMERS ===============================================
         // B fragments (GHF_WLAYOUT_SPLIT2H): Wh[r][o/16][kk/32][piece][lane][8] fp16, then one float 2^-s per relation
@@ -904,10 +1098,24 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             BX_LGKM0();
         }
         __syncthreads();                                   // epilogue stage
-        for (int half = 0; half < 2; ++half) {
-            __syncthreads();
-            __syncthreads();
-            tail_half(half, std::integral_constant<int, BX_TGB>{});
+        if constexpr (D == 128) {
+            // (see the helpers' epilogue) the accumulators and the weight ring are dead: a half's operands are requested before
+            // the helpers dump it, the next half's behind this half's rows
+            BxTailSt<TCG, CPL / 4> st;
+            tail_issue(0, st, tw, c_cend);
+            tail_barrier();
+            tail_barrier();
+            tail_rows(0, st, tw, c_cend);
+            tail_issue(1, st, tw, c_cend);
+            tail_barrier();
+            tail_barrier();
+            tail_rows(1, st, tw, c_cend);
+        } else {
+            for (int half = 0; half < 2; ++half) {
+                __syncthreads();
+                __syncthreads();
+                tail_half(half, std::integral_constant<int, BX_TGB>{});
+            }
         }
     }
 }
