@@ -4,8 +4,9 @@
 // k in {W_msg, W_self, bias}:  flat_k = Lin_last(ReLU(Lin(...ReLU(Lin_0(x)))))
 // (nn.Linear: y = x W^T + b, W stored [out,in]), out_k = flat_k * exp(log_scale_k).
 //
-//  wg_hidden_kernel : the num_hidden small Linear+ReLU layers, one workgroup per
-//                     (relation, head), activations ping-ponged in LDS.
+//  wg_hidden_rb_kernel: the num_hidden small Linear+ReLU layers, one workgroup per
+//                     (WG_RB relations, head, generator), activations ping-ponged in LDS
+//                     (wg_hidden_kernel, one relation per workgroup: ghf_weightgen_acts).
 //  wg_out_mfma_kernel: the last layer [R,Hl] x [Hl, n_out] as an fp32 MFMA GEMM
 //                     (v_mfma_f32_16x16x4_f32: exact fp32 fma chain), transposed so that the
 //                     output-element index is the MFMA row and the relation the
@@ -79,6 +80,89 @@ __global__ __launch_bounds__(256) void wg_hidden_kernel(const float* __restrict_
     if (!hidden_ws) return;
     float* out = hidden_ws + ((size_t)head * R + r) * in_dim;
     for (int k = threadIdx.x; k < in_dim; k += blockDim.x) out[k] = buf[cur][k];
+}
+
+// The same layers with WG_RB relations of one (head, generator) per workgroup: grid (ceil(R / WG_RB), 3, generators), block
+// WG_HT.  One workgroup per relation had the R workgroups of a (head, generator) pull the same weights from L2, each for a
+// single input vector, and each of its four waves walk Hh / 32 steps per layer — a step being an exposed L2 round trip with
+// eight FMAs per lane behind it, then eight wave reductions.  Here a lane's weight values are loaded once into registers and
+// used for each relation's activation (WG_RB times the independent FMAs and reductions per load, 1 / WG_RB of the L2 requests),
+// and sixteen waves take Hh = 128 in ONE step per layer: the steps per wave decide (config 3, R = 64: 56 us at (1, 256),
+// 21 at (1, 1024), 18 at (2, 1024), 13.4 at (4, 1024), 25 at (8, 512) and (8, 1024), which spills; config 2, R = 32: 50,
+// 8.2, 9.4, 12.4, 23 — DESIGN.md section 3, K1).  Every output unit keeps its order — lane l accumulates k = l, l + 64, ...
+// with fmaf, then wave_sum, bias, ReLU, the dropout multiply — so the values are wg_hidden_kernel's bit for bit.
+constexpr int WG_RB = 4;             // relations per workgroup (WG_RB * WG_HU <= 64: a lane per (relation, unit) finishes a step)
+constexpr int WG_HT = 1024;          // threads per workgroup
+__global__ __launch_bounds__(WG_HT) void wg_hidden_rb_kernel(const float* __restrict__ text_emb, HeadPtrsL PL,
+                                                             int R, int T, int Hh, int num_hidden, int width,
+                                                             float* __restrict__ hidden_ws, float* __restrict__ acts,
+                                                             const float* __restrict__ drop /* acts' layout, or NULL */) {
+    extern __shared__ float hbuf[];                      // [2][WG_RB][width], width >= max(T, Hh)
+    const int r0 = blockIdx.x * WG_RB, head = blockIdx.y;
+    const int nr = R - r0 < WG_RB ? R - r0 : WG_RB;      // relations of this workgroup (the others' slots hold zeros)
+    const HeadPtrs& P = PL.p[blockIdx.z];
+    if (hidden_ws) hidden_ws += (size_t)blockIdx.z * 3 * R * (num_hidden ? Hh : T);
+    float* cur = hbuf;
+    float* nxt = hbuf + (size_t)WG_RB * width;
+    for (int i = threadIdx.x; i < WG_RB * T; i += blockDim.x) {
+        const int rr = i / T, k = i - rr * T;
+        cur[rr * width + k] = rr < nr ? text_emb[(size_t)(r0 + rr) * T + k] : 0.f;
+    }
+    __syncthreads();
+    int in_dim = T;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int lr = lane / WG_HU, lu = lane % WG_HU;      // the (relation, unit) this lane finishes in every step
+    for (int li = 0; li < num_hidden; ++li) {
+        const float* __restrict__ W = P.w[head][li];
+        const float* __restrict__ B = P.b[head][li];
+        for (int j0 = wv * WG_HU; j0 < Hh; j0 += nw * WG_HU) {
+            float s[WG_RB][WG_HU];
+#pragma unroll
+            for (int rr = 0; rr < WG_RB; ++rr)
+#pragma unroll
+                for (int u = 0; u < WG_HU; ++u) s[rr][u] = 0.f;
+            for (int k = lane; k < in_dim; k += 64) {
+                float w[WG_HU];
+#pragma unroll
+                for (int u = 0; u < WG_HU; ++u) {         // units past Hh read the last unit's row: no branch around a load
+                    const int j = j0 + u < Hh ? j0 + u : Hh - 1;
+                    w[u] = W[(size_t)j * in_dim + k];
+                }
+#pragma unroll
+                for (int rr = 0; rr < WG_RB; ++rr) {
+                    const float xk = cur[rr * width + k];
+#pragma unroll
+                    for (int u = 0; u < WG_HU; ++u) s[rr][u] = fmaf(xk, w[u], s[rr][u]);
+                }
+            }
+            float t = 0.f;
+#pragma unroll
+            for (int rr = 0; rr < WG_RB; ++rr)
+#pragma unroll
+                for (int u = 0; u < WG_HU; ++u) {
+                    const float tu = wave_sum(s[rr][u]);      // (a scalar) -> the lane that finishes this (relation, unit)
+                    asm("v_writelane_b32 %0, %1, %2" : "+v"(t) : "s"(tu), "n"(rr * WG_HU + u));
+                }
+            const int j = j0 + lu;
+            if (lane < WG_RB * WG_HU && lr < nr && j < Hh) {     // Linear -> ReLU -> Dropout (reference weight_generator.py:96-107)
+                const float a = fmaxf(t + B[j], 0.f);
+                nxt[lr * width + j] = drop ? a * drop[(((size_t)head * num_hidden + li) * R + r0 + lr) * Hh + j] : a;
+            }
+        }
+        __syncthreads();
+        float* sw = cur; cur = nxt; nxt = sw;
+        in_dim = Hh;
+        if (acts)
+            for (int i = threadIdx.x; i < nr * Hh; i += blockDim.x) {
+                const int rr = i / Hh, k = i - rr * Hh;
+                acts[(((size_t)head * num_hidden + li) * R + r0 + rr) * Hh + k] = cur[rr * width + k];
+            }
+    }
+    if (!hidden_ws) return;
+    for (int i = threadIdx.x; i < nr * in_dim; i += blockDim.x) {
+        const int rr = i / in_dim, k = i - rr * in_dim;
+        hidden_ws[((size_t)head * R + r0 + rr) * in_dim + k] = cur[rr * width + k];
+    }
 }
 
 // Destination index of element (r, kk, o) of the combined [W_msg; W_self] matrix of relation r
@@ -465,7 +549,12 @@ int launch_weightgen_batched(int L, const float* text_emb, const float* const* h
                 PL.p[g].b[h][l] = head_params[((size_t)(g * 3 + h) * nl + l) * 2 + 1];
                 GHF_REQUIRE(PL.p[g].w[h][l] && PL.p[g].b[h][l], "weightgen: null parameter pointer (generator %d head %d layer %d)", g, h, l);
             }
-    wg_hidden_kernel<<<dim3(R, 3, L), 256, 0, stream>>>(text_emb, PL, R, T, Hh, num_hidden, hidden_ws, acts, hidden_drop);
+    {
+        const int width = T > Hh ? T : Hh;
+        const size_t lds = (size_t)2 * WG_RB * width * sizeof(float);     // 32 KB at WG_MAX_WIDTH
+        wg_hidden_rb_kernel<<<dim3((R + WG_RB - 1) / WG_RB, 3, L), WG_HT, lds, stream>>>(text_emb, PL, R, T, Hh, num_hidden, width,
+                                                                                    hidden_ws, acts, hidden_drop);
+    }
     GHF_LAUNCH_CHECK();
 
     const int Hl = num_hidden ? Hh : T;
