@@ -107,6 +107,8 @@ SIGNATURES = {
     "ghf_score_softmax_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _sz, _vp, _vp, _vp]),
     "ghf_score_softmax_bwd_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "ghf_score_softmax_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "ghf_relation_rows_workspace_bytes": (_sz, [_i64, _i32]),
+    "ghf_relation_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
     "ghf_rows_pack": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "ghf_rows_unpack": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "ghf_rows_accumulate": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp]),
@@ -739,6 +741,56 @@ def score_softmax_bwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, ls
                                         d, scale, _ptr(lse), _ptr(grad_loss), _ptr(ws), ws.numel(), _ptr(dq), _ptr(dc), _stream()),
            "ghf_score_softmax_bwd")
     return dq, dc
+
+
+# ---- relation-typed query rows (include/ghf.h: ghf_relation_rows, csrc/relation.hip) ------------------------------------
+GHF_REL_ADD_X = 1
+GHF_REL_TRANSPOSE = 2
+
+
+def relation_rows_workspace_bytes(B: int, R: int) -> int:
+    return int(load().ghf_relation_rows_workspace_bytes(B, R))
+
+
+def relation_rows(x: torch.Tensor, rel: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                  ix: Optional[torch.Tensor] = None, add_x: bool = True, transpose: bool = False,
+                  group: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, workspace: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i] = [x[ix[i]]] + x[ix[i]] @ op(W[rel[i]]) + [bias[rel[i]]], fp32 [B, d], with no matrix gathered per query.
+    x [rows_x, d]; rel int64 [B]; W [R, d, d] natural; bias [R, d] or None; ix int64 [B] or None (= the rows in order);
+    transpose: multiply by W[r]^T.  group = group_edges(rel, R) when the caller has it (the backward reuses the forward's).
+    An id out of range gives a NaN row.  With `group`, `workspace` (uint8, relation_rows_workspace_bytes) and `out` given
+    the call allocates nothing."""
+    x = _req(x, torch.float32, "x")
+    W = _req(W, torch.float32, "W")
+    rel = _req(rel, torch.int64, "rel")
+    if x.dim() != 2 or W.dim() != 3 or W.size(1) != x.size(1) or W.size(2) != x.size(1) or rel.dim() != 1:
+        raise ValueError(f"relation_rows: need x [rows, d], W [R, d, d] and rel [B], got {tuple(x.shape)}, {tuple(W.shape)}, "
+                         f"{tuple(rel.shape)}")
+    (rows_x, d), R = x.shape, W.size(0)
+    ix = None if ix is None else _req(ix, torch.int64, "ix")
+    B = rel.numel()
+    if ix is not None and (ix.dim() != 1 or ix.numel() != B):
+        raise ValueError(f"relation_rows: ix must name one row per entry of rel ({B}), got {tuple(ix.shape)}")
+    if bias is not None:
+        bias = _req(bias, torch.float32, "bias")
+        if tuple(bias.shape) != (R, d):
+            raise ValueError(f"relation_rows: bias must be [{R}, {d}], got {tuple(bias.shape)}")
+    for name, t in (("W", W), ("rel", rel), ("ix", ix), ("bias", bias)):
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"relation_rows: {name} is on {t.device}, x on {x.device}")
+    need = relation_rows_workspace_bytes(B, R)
+    if need == 0 or rows_x == 0 or d == 0:
+        raise ValueError(f"relation_rows: unsupported sizes B={B} R={R} rows={rows_x} d={d}")
+    perm, goff = group_edges(rel, R) if group is None else (_req(group[0], torch.int64, "perm"), _req(group[1], torch.int64, "goff"))
+    if perm.numel() != B or goff.numel() != R + 1:
+        raise ValueError(f"relation_rows: group must be (perm [{B}], goff [{R + 1}])")
+    ws = _rank_workspace(workspace, need, x.device, "relation_rows")
+    out = _f32_out(out, (B, d), x.device, "relation_rows")
+    flags = (GHF_REL_ADD_X if add_x else 0) | (GHF_REL_TRANSPOSE if transpose else 0)
+    _check(load().ghf_relation_rows(_ptr(x), _ptr(ix), _ptr(rel), _ptr(W), _ptr(bias), _ptr(perm), _ptr(goff), rows_x, B, R, d,
+                                    flags, _ptr(ws), ws.numel(), _ptr(out), _stream()), "ghf_relation_rows")
+    return out
 
 
 # ---- wide hidden sizes: relation-stationary layer (include/ghf.h, csrc/message_rs.hip) ---------------------------

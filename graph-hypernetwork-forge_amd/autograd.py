@@ -449,3 +449,95 @@ class ScorePairsFn(torch.autograd.Function):
         g = g.contiguous().float()
         return (_native.rowscale(b, g) if ctx.needs_input_grad[0] else None,
                 _native.rowscale(a, g) if ctx.needs_input_grad[1] else None)
+
+
+# ---- relation-typed scoring (models/relation_decoder.py; include/ghf.h: ghf_relation_rows) -----------------------------
+def _fold_rows(rows: torch.Tensor, ids: torch.Tensor, n: int) -> torch.Tensor:
+    """out[v] = sum_{i: ids[i] = v} rows[i], [n, d]: grouped by v (ghf_group_edges, stable) and added in that order."""
+    perm, off = _native.group_edges(ids, n)
+    return _native.segment_axpy(torch.ones(ids.numel(), dtype=torch.float32, device=rows.device), perm, rows, perm, off)
+
+
+class RelationRowsFn(torch.autograd.Function):
+    """out_i = x[ix_i] + x[ix_i] @ A[rel_i] + b[rel_i] (ghf_relation_rows), A [R, d, d] and b [R, d] normally a
+    WeightGenerator's heads.  The queries are grouped by relation once; the backward reuses the grouping:
+        dx_rows_i = g_i + g_i @ A[rel_i]^T      the same call with GHF_REL_TRANSPOSE, no bias
+        dx[v]     = sum_{i: ix_i = v} dx_rows_i   grouped by node, added in a fixed order (ghf_segment_axpy)
+        dA[r]     = sum_{i in r} x[ix_i]^T g_i    db[r] = sum_{i in r} g_i      (ghf_group_outer over the relation groups)
+    No [B, d, d] tensor, no atomics: reproducible."""
+
+    @staticmethod
+    def forward(ctx, x, ix, rel, A, b):
+        x, A = x.contiguous().float(), A.contiguous().float()
+        b = None if b is None else b.contiguous().float()
+        group = _native.group_edges(rel, A.size(0))
+        ctx.save_for_backward(x, A, rel, *group, *(() if ix is None else (ix,)))
+        ctx.has_bias = b is not None
+        return _native.relation_rows(x, rel, A, b, ix=ix, add_x=True, group=group)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, A, rel, perm, goff, *rest = ctx.saved_tensors
+        ix = rest[0] if rest else None
+        g = g.contiguous().float()
+        B, rows = rel.numel(), x.size(0)
+        dx = dA = db = None
+        if ctx.needs_input_grad[0]:
+            dx = _native.relation_rows(g, rel, A, None, add_x=True, transpose=True, group=(perm, goff))
+            if ix is not None:
+                dx = _fold_rows(dx, ix, rows)
+            elif rows > B:                                   # rows beyond the B queries took no part
+                dx = torch.cat([dx, dx.new_zeros(rows - B, dx.size(1))])
+        if ctx.needs_input_grad[3]:
+            dA = _native.group_outer(x, perm if ix is None else ix.index_select(0, perm), g, perm, goff)
+        if ctx.has_bias and ctx.needs_input_grad[4]:
+            db = _native.group_outer(None, None, g, perm, goff).reshape(A.size(0), -1)
+        return dx, None, None, dA, db
+
+
+class ScoreRowsFn(torch.autograd.Function):
+    """s_i = Q_i . embs[tail_i] (RelationDecoder.score).  dQ_i = g_i embs[tail_i]; d embs[v] = sum_{i: tail_i = v} g_i Q_i,
+    grouped by node and summed in a fixed order as ScoreEdgesFn does."""
+
+    @staticmethod
+    def forward(ctx, Q, embs, tail):
+        Q, embs = Q.contiguous().float(), embs.contiguous().float()
+        ctx.save_for_backward(Q, embs, tail)
+        return _native.score_pairs_fwd(Q, embs, None, tail)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        Q, embs, tail = ctx.saved_tensors
+        g = g.contiguous().float()
+        dQ = dE = None
+        if ctx.needs_input_grad[0]:
+            dQ = _native.rowscale(embs.index_select(0, tail), g)
+        if ctx.needs_input_grad[1]:
+            perm, off = _native.group_edges(tail, embs.size(0))
+            dE = _native.segment_axpy(g, perm, Q, perm, off)
+        return dQ, dE, None
+
+
+class SoftmaxRowsLossFn(torch.autograd.Function):
+    """SoftmaxLossFn with the query rows given (``softmax_loss(..., query_rows=Q)``): q = Q, c = embs.
+    ghf_score_softmax_bwd returns dq per query and dc per candidate: the gradients of Q and of embs as they are, with no
+    fold through the query ids."""
+
+    @staticmethod
+    def forward(ctx, embs, rows, target, ptr, idx, scale: float):
+        embs, rows = embs.contiguous().float(), rows.contiguous().float()
+        loss, lse = _native.score_softmax_fwd(rows, embs, target, filt_ptr=ptr, filt_idx=idx, scale=scale)
+        ctx.save_for_backward(embs, rows, lse, target, *(() if ptr is None else (ptr, idx)))
+        ctx.scale = scale
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        embs, rows, lse, target, *lists = ctx.saved_tensors
+        ptr, idx = lists if lists else (None, None)
+        dq, dc = _native.score_softmax_bwd(rows, embs, target, lse, g.contiguous().float(), filt_ptr=ptr, filt_idx=idx,
+                                           scale=ctx.scale)
+        return (dc if ctx.needs_input_grad[0] else None), (dq if ctx.needs_input_grad[1] else None), None, None, None, None

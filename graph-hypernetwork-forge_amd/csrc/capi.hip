@@ -630,6 +630,17 @@ int ghf_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, con
                                     workspace_bytes, dq, dc, (hipStream_t)stream);
 }
 
+size_t ghf_relation_rows_workspace_bytes(int64_t B, int R) { return relation_rows_workspace_bytes(B, R); }
+
+int ghf_relation_rows(const float* x, const int64_t* ix, const int64_t* rel, const float* W, const float* bias,
+                      const int64_t* perm, const int64_t* goff, int64_t rows_x, int64_t B, int R, int d, int flags,
+                      void* workspace, size_t workspace_bytes, float* out, void* stream) {
+    GHF_REQUIRE(x && rel && W && perm && goff && workspace && out, "relation_rows: null pointer argument");
+    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "relation_rows: workspace not 256-byte aligned");
+    return launch_relation_rows(x, ix, rel, W, bias, perm, goff, rows_x, B, R, d, flags, workspace, workspace_bytes, out,
+                                (hipStream_t)stream);
+}
+
 int ghf_tail_fwd(const float* agg, const float* h, const float* ln_gamma, const float* ln_beta, float ln_eps,
                  int64_t row0, int64_t rows, int d, float* h_out, const float* drop, void* stream) {
     GHF_REQUIRE(agg && h && ln_gamma && ln_beta && h_out, "tail_fwd: null pointer argument");

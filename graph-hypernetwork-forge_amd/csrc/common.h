@@ -184,6 +184,11 @@ int launch_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, 
                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                              const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc,
                              hipStream_t stream);
+// relation.hip
+size_t relation_rows_workspace_bytes(int64_t B, int R);
+int launch_relation_rows(const float* x, const int64_t* ix, const int64_t* rel, const float* W, const float* bias,
+                         const int64_t* perm, const int64_t* goff, int64_t rows_x, int64_t B, int R, int d, int flags,
+                         void* ws, size_t ws_bytes, float* out, hipStream_t stream);
 int launch_text_encode(const int32_t* ids, const int32_t* lens, int U, int Lmax, const float* E, int V, int C,
                        const float* W, const float* b, int T, float* out, hipStream_t stream);
 int launch_input_proj(const float* x, const float* W_in, const float* b_in, int64_t N, int F, int d,

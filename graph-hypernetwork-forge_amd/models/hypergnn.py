@@ -628,24 +628,70 @@ class HyperGNN(nn.Module):
         ids = ids.to(device=embs.device, dtype=torch.int64)
         return torch.where(ids < 0, ids + rows, ids)
 
+    @staticmethod
+    def _rel_ids(ids: torch.Tensor, n: int, embs: torch.Tensor, name: str) -> torch.Tensor:
+        """1-D relation ids, one per entry: int64 on embs' device.  The id space is the caller's (``plan.rel_ids``, the ids
+        passed to ``forward_ids``); relation ids do not wrap: a negative one is a ValueError."""
+        if not isinstance(ids, torch.Tensor) or ids.dim() != 1:
+            raise ValueError(f"{name} must be a 1-D tensor of relation ids, got {getattr(ids, 'shape', type(ids))}")
+        if ids.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"{name} must be int32 or int64, got {ids.dtype}")
+        if ids.numel() != n:
+            raise ValueError(f"{name} holds {ids.numel()} relation ids, expected {n}")
+        if ids.numel() and int(ids.min()) < 0:
+            raise ValueError(f"{name} holds a negative relation id (relation ids do not wrap)")
+        return ids.to(device=embs.device, dtype=torch.int64)
+
+    @staticmethod
+    def _query_rows(embs: torch.Tensor, query: torch.Tensor, query_rows: Optional[torch.Tensor], what: str) -> None:
+        """``query_rows`` ([B, d] fp32, one row per query, on embs' device) stands in for the gathered rows ``embs[query]``."""
+        if query_rows is None:
+            return
+        B = query.numel() if isinstance(query, torch.Tensor) else -1
+        if not isinstance(query_rows, torch.Tensor) or query_rows.dim() != 2 or tuple(query_rows.shape) != (B, embs.size(1)):
+            raise ValueError(f"{what}: query_rows must be [B = {B}, d = {embs.size(1)}], one row per query, got "
+                             f"{getattr(query_rows, 'shape', type(query_rows))}")
+        if query_rows.dtype != torch.float32:
+            raise TypeError(f"{what}: query_rows must be float32, got {query_rows.dtype}")
+        if not query_rows.is_cuda or query_rows.device != embs.device:
+            raise RuntimeError(f"{what} computes on an MI355X HIP device only (query_rows is on {query_rows.device}, embs on "
+                               f"{embs.device})")
+
     @classmethod
-    def _filter_lists(cls, embs: torch.Tensor, query: torch.Tensor, known, filt_ptr, filt_idx):
+    def _filter_lists(cls, embs: torch.Tensor, query: torch.Tensor, known, filt_ptr, filt_idx, query_rel=None):
         """Each query's filter list in the form the kernels take (CSR, every list sorted ascending), built on the device.
         `known` = (src, dst) names true edges: query[i]'s list is every dst of an edge whose src is query[i] (pass the
-        edges in both directions for an undirected reading)."""
+        edges in both directions for an undirected reading).  `known` = (src, dst, rel) with `query_rel` [B] is the typed
+        form: query[i]'s list is every dst of an edge with src == query[i] AND rel == query_rel[i] (for (?, r, t) queries
+        pass known=(dst, src, rel))."""
         N, B = embs.size(0), query.numel()
         if known is not None and (filt_ptr is not None or filt_idx is not None):
             raise ValueError("pass either known=(src, dst) or filt_ptr / filt_idx, not both")
+        typed = known is not None and len(known) == 3
+        if query_rel is not None and not typed:
+            raise ValueError("query_rel needs the typed known=(src, dst, rel)")
+        if typed and query_rel is None:
+            raise ValueError("known=(src, dst, rel) needs query_rel: the relation of every query")
         if known is not None:
-            src, dst = known
+            if len(known) not in (2, 3):
+                raise ValueError(f"known must be (src, dst) or (src, dst, rel), got {len(known)} members")
+            src, dst = known[0], known[1]
             src = cls._rank_ids(src, N, embs, "known[0]")
             dst = cls._rank_ids(dst, N, embs, "known[1]")
             if src.numel() != dst.numel():
                 raise ValueError(f"known: {src.numel()} sources and {dst.numel()} destinations")
-            key = torch.unique(src * N + dst)                       # sorted by (src, dst), repeats gone
+            qkey = query
+            if typed:
+                rel = cls._rel_ids(known[2], src.numel(), embs, "known[2]")
+                qrel = cls._rel_ids(query_rel, B, embs, "query_rel")
+                R = 1 + max(int(rel.max()) if rel.numel() else 0, int(qrel.max()) if B else 0)
+                if (N * R + R) * N >= 1 << 63:
+                    raise ValueError(f"known: {N} nodes x {R} relations do not fit the 64-bit (src, rel, dst) keys")
+                src, qkey = src * R + rel, query * R + qrel
+            key = torch.unique(src * N + dst)                       # sorted by (src[, rel], dst), repeats gone
             ks = torch.div(key, N, rounding_mode="floor")
-            lo = torch.searchsorted(ks, query)
-            lens = torch.searchsorted(ks, query, right=True) - lo
+            lo = torch.searchsorted(ks, qkey)
+            lens = torch.searchsorted(ks, qkey, right=True) - lo
             ptr = torch.zeros(B + 1, dtype=torch.int64, device=embs.device)
             torch.cumsum(lens, 0, out=ptr[1:])
             nnz = int(ptr[-1])
@@ -672,54 +718,75 @@ class HyperGNN(nn.Module):
         return ptr, (key - seg * N).contiguous()
 
     def rank_candidates(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, known=None,
-                        filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None):
+                        filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+                        query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None):
         """Where ``target[i]`` ranks among ALL nodes as a partner of ``query[i]`` under the dot-product score
         (``score_triple``): ``(greater, equal)``, int64 ``[B]`` — the nodes scoring above / exactly as the target, the target
         itself and the query's known partners (the "filtered" setting) left out.  ``known=(src, dst)`` names true edges
         (the query's list = every ``dst`` whose ``src`` is the query); or pass CSR lists as ``filt_ptr`` / ``filt_idx``.
         Feed the counts to ``link_prediction_metrics``.  One tiled ``q . c^T`` on the fp32 matrix cores with the comparison
         in its epilogue (``ghf_score_rank``): the ``[B, N]`` scores are never stored.  The counts carry no autograd graph
-        (``embs`` is read as data)."""
+        (``embs`` is read as data).
+
+        Relation-typed queries ``(head, relation, ?)``: ``query_rows`` (``[B, d]`` fp32, ``RelationDecoder``'s output) replaces
+        the gathered rows ``embs[query]`` as the sweep's query matrix; ``query`` still names the node each row stands for and
+        is used only to build the filter lists.  ``known=(src, dst, rel)`` with ``query_rel`` (``[B]`` relation ids, in the
+        caller's id space, e.g. ``plan.rel_ids``) lists for query ``i`` every ``dst`` of a known edge with ``src == query[i]``
+        and ``rel == query_rel[i]``.  For ``(?, relation, tail)`` queries (``direction="head"``) pass ``known=(dst, src, rel)``.
+        With both ``None`` the call is the untyped one."""
         if not embs.is_cuda:
             raise RuntimeError(f"rank_candidates computes on an MI355X HIP device only (input is on {embs.device})")
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        self._query_rows(embs, query, query_rows, "rank_candidates")
         e = embs.detach().float()
         q = self._rank_ids(query, e.size(0), e, "query")
         t = self._rank_ids(target, e.size(0), e, "target")
         if q.numel() != t.numel():
             raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
-        ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx)
+        ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx, query_rel)
+        if query_rows is not None:
+            return _native.score_rank(query_rows.detach(), e, t, filt_ptr=ptr, filt_idx=idx)
         return _native.score_rank(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx)
 
     def topk_candidates(self, embs: torch.Tensor, query: torch.Tensor, k: int, *, known=None,
-                        filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None):
+                        filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+                        query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None):
         """The ``k`` (1..128) best partners of every ``query[i]`` among ALL nodes outside its filter list (``known`` /
         ``filt_ptr, filt_idx`` as in ``rank_candidates``): ``(scores [B, k]`` fp32 descending, ``ids [B, k]`` int64``)``, ties
         towards the lower id, ``(-inf, -1)`` where fewer than k candidates remain.  The query node itself is a candidate
-        unless listed.  No autograd graph."""
+        unless listed.  No autograd graph.  ``query_rows`` / ``known=(src, dst, rel)`` with ``query_rel``: relation-typed
+        queries, as in ``rank_candidates``."""
         if not embs.is_cuda:
             raise RuntimeError(f"topk_candidates computes on an MI355X HIP device only (input is on {embs.device})")
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        self._query_rows(embs, query, query_rows, "topk_candidates")
         if not 1 <= int(k) <= 128:
             raise ValueError(f"k = {k} outside 1..128")
         e = embs.detach().float()
         q = self._rank_ids(query, e.size(0), e, "query")
-        ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx)
+        ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx, query_rel)
+        if query_rows is not None:
+            return _native.score_topk(query_rows.detach(), e, int(k), filt_ptr=ptr, filt_idx=idx)
         return _native.score_topk(e, e, int(k), iq=q, filt_ptr=ptr, filt_idx=idx)
 
     def softmax_loss(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, scale: float = 1.0, known=None,
-                     filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+                     query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The 1-vs-all softmax cross-entropy that ``rank_candidates``' filtered metrics measure, fp32 ``[B]``:
         ``loss[i] = logsumexp_j(scale * embs[query[i]] . embs[j]) - scale * embs[query[i]] . embs[target[i]]`` over ALL nodes
         ``j`` except ``query[i]``'s known partners (``known`` / ``filt_ptr, filt_idx`` as in ``rank_candidates``; the target
         itself always stays in the sum).  ``F.cross_entropy(scale * embs[query] @ embs.T, target)`` without the ``[B, N]``
         logits, forward or backward: one sweep on the fp32 matrix cores with an online softmax in its epilogue
         (``ghf_score_softmax_fwd``), and a backward that recomputes the scores from the saved log-sum (``ghf_score_softmax_bwd``,
-        ``autograd.SoftmaxLossFn``).  Bit-reproducible.  Recorded for autograd when grad mode is on and ``embs`` requires grad."""
+        ``autograd.SoftmaxLossFn``).  Bit-reproducible.  Recorded for autograd when grad mode is on and ``embs`` requires grad.
+        ``query_rows`` / ``known=(src, dst, rel)`` with ``query_rel``: relation-typed queries, as in ``rank_candidates``; the
+        loss is then recorded when ``embs`` or ``query_rows`` requires grad (``autograd.SoftmaxRowsLossFn``: the per-query
+        gradient is ``query_rows``' own, the per-candidate one ``embs``')."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        self._query_rows(embs, query, query_rows, "softmax_loss")
         scale = float(scale)
         if not (0.0 < scale < float("inf")):
             raise ValueError(f"scale must be finite and positive, got {scale}")
@@ -729,7 +796,13 @@ class HyperGNN(nn.Module):
             raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
         if not embs.is_cuda:
             raise RuntimeError(f"softmax_loss computes on an MI355X HIP device only (input is on {embs.device})")
-        ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx)
+        ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
+        if query_rows is not None:
+            if torch.is_grad_enabled() and (embs.requires_grad or query_rows.requires_grad):
+                from ..autograd import SoftmaxRowsLossFn
+                return SoftmaxRowsLossFn.apply(embs, query_rows, t, ptr, idx, scale)
+            return _native.score_softmax_fwd(query_rows.detach(), embs.detach().float(), t, filt_ptr=ptr, filt_idx=idx,
+                                             scale=scale)[0]
         if torch.is_grad_enabled() and embs.requires_grad:
             from ..autograd import SoftmaxLossFn
             return SoftmaxLossFn.apply(embs, q, t, ptr, idx, scale)

@@ -516,6 +516,34 @@ int ghf_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, con
                           const float* lse, const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* dc,
                           void* stream);
 
+/* ---- relation-typed query rows (csrc/relation.hip) ----------------------------------------------------
+ * No counterpart in the reference, whose score_triple (models/hypergnn.py:304-318) ignores the relation.  The query side of
+ * a (head, relation, ?) score: every query row multiplied by ITS relation's matrix, without gathering a matrix per query
+ * (the [B, d, d] operand of torch.bmm(x[ix].unsqueeze(1), W[rel])):
+ *   out[i][:] = [GHF_REL_ADD_X] x[ix[i]][:]  +  x[ix[i]][:] @ op(W[rel[i]])  +  [bias != NULL] bias[rel[i]][:],     i < B
+ * x [rows_x, d] fp32 row-major; ix int64 [B] or NULL (= i, then B <= rows_x); rel int64 [B]; W [R, d, d] natural
+ * (W[r][k][l]: input k, output l); op = identity, or the transpose with GHF_REL_TRANSPOSE (out[l] = sum_k x[k] W[r][l][k]:
+ * the gradient with respect to the rows, dx = g + g @ W[r]^T, is this same call); bias [R, d] or NULL; out [B, d].
+ * 1 <= d <= 256 (the range of the rank calls; GHF_EUNSUPPORTED beyond), 0 < B < 2^31, 0 < R < 2^23.
+ * perm [B] / goff [R + 1]: the queries grouped by relation, exactly what ghf_group_edges gives for (rel, B, R).  They are
+ * PASSED IN, not computed here: the caller's backward needs the same grouping (ghf_group_outer over the relation groups),
+ * so one sort serves the forward and both gradient calls.  A row that perm does not list is not written.
+ * workspace: ghf_relation_rows_workspace_bytes(B, R) bytes (0 = bad sizes), 256-byte aligned: the table of (relation, tile
+ * of <= 64 grouped rows) work items, cut from goff on the device; the launch is sized by its bound ceil(B/64) + R on the
+ * host.  Nothing allocates, reads back or synchronises: the call is capturable.
+ * An ix[i] or rel[i] out of range does not fault: that row of out is NaN and no other row is touched by it (goff and perm
+ * are clamped as well: a malformed grouping cannot make the kernels read or write out of bounds).
+ * Numerics: out[i][l] = (x[l] + s) + bias[l] with s the fp32 chain s = fmaf(x[k], op(W)[k][l], s), k = 0 .. d-1, from 0 —
+ * v_mfma_f32_16x16x4_f32, the tail of k padded with zeros.  A row of out depends on its own x row, W[r] and bias[r] only,
+ * bit for bit: never on the other queries of the call or on its place among them.  No atomics. */
+#define GHF_REL_ADD_X     1   /* add the row itself (the residual) */
+#define GHF_REL_TRANSPOSE 2   /* multiply by W[r]^T */
+size_t ghf_relation_rows_workspace_bytes(int64_t B, int R);
+int ghf_relation_rows(const float* x, const int64_t* ix /* [B] or NULL */, const int64_t* rel /* [B] */, const float* W /* [R,d,d] */,
+                      const float* bias /* [R,d] or NULL */, const int64_t* perm /* [B] */, const int64_t* goff /* [R+1] */,
+                      int64_t rows_x, int64_t B, int R, int d, int flags, void* workspace, size_t workspace_bytes,
+                      float* out /* [B,d] */, void* stream);
+
 /* ---- the sparse row exchange of the multi-GPU forward (no counterpart in the single-process reference) ----
  * packed[i] = rows[idx[i]] (row_bytes, a multiple of 16) followed by extra[idx[i]] (extra_bytes, a multiple of 4; extra may be
  * NULL with extra_bytes = 0), i < n: the listed rows of a [nrows, row_bytes] table (and of a second table indexed alike — the
