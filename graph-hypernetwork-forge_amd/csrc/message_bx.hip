@@ -24,16 +24,24 @@
 //     instruction, the XOR swizzle applied on the source side): no staging registers, no ds_write;
 //   * the fused tail runs from LDS after the helpers have dumped their registers there (two halves of the block).
 //
-// LDS: P0[2] (source-row tiles), P1[2] (destination-row tiles), CR * 4d bytes each; four chunk descriptors ("meta": the
-// rows' scales and node ids); a KiB for DMA pieces past a tile, a row of zeros, sixteen flag words.
+// LDS: a ring of four A tiles T[0..3], CR * 4d bytes each; four chunk descriptors ("meta": the rows' scales and node ids); a
+// KiB for DMA pieces past a tile, a row of zeros, sixteen flag words.  With T[j] = tile j & 3, chunk j keeps its source rows
+// S(j) in T[j], its destination rows D(j) in T[j-1] and its staged rows Y(j) in T[j-1] too (over its own destination rows, once
+// read).  The four tiles live during chunk k are distinct: S(k) = T[k], D(k) = T[k-1], Y(k-1) = T[k-2], S(k+1) = T[k+1].
 // ONE workgroup barrier per chunk.  During chunk k (between barriers k and k + 1):
-//   consumers: stage Y(k-1) into P1[(k-1)&1] (behind the barrier every consumer is through with that tile; flag "staged");
-//              phase 0 (h_src x W_msg) from P0[k&1]; phase 1 (h_dst x W_self) from P1[k&1]; the accumulators keep Y(k)
-//              until the next barrier
-//   helpers:   DMA P0[(k+1)&1] <- source rows of chunk k+1 (HBM: a whole chunk to land); wait for "staged", fold Y(k-1) out
-//              of P1[(k-1)&1]; once all four have folded (flag words), DMA that tile <- destination rows of chunk k+1 (L2);
-//              the descriptor pipeline (chunk_tab entry k+5, edge words k+4, row scales k+3, publish k+2); vmcnt(0): both
-//              tiles of chunk k+1 are in before the barrier
+//   consumers: stage Y(k-1) into T[k-2] (behind the barrier every consumer is through with that tile; flag "staged");
+//              phase 0 (h_src x W_msg) from T[k], then flag "phase 0 of chunk k read"; phase 1 (h_dst x W_self) from T[k-1];
+//              the accumulators keep Y(k) until the next barrier
+//   helpers:   DMA T[k+1] <- source rows of chunk k+1 (HBM: a whole chunk to land; the tile Y(k-2) was folded out of during
+//              chunk k-1); wait for "staged", fold Y(k-1) out of T[k-2]; wait for "phase 0 of chunk k read", DMA T[k] <-
+//              destination rows of chunk k+1 (L2) — no helper waits for another's fold: T[k-2] is next written by S(k+2),
+//              behind barrier k+1; the descriptor pipeline (chunk_tab entry k+5, edge words k+4, row scales k+3, publish k+2:
+//              each wave its rows, then its flag word "published" — the four words are waited for, in the round trip of the
+//              phase-0 flag, before the source ids of chunk k+2 are read by DMA pieces at the chunk's end);
+//              vmcnt(0): both tiles of chunk k+1 are in before the barrier
+// One-phase instances (SKIP 1 / 2) use S and Y only.  Hidden 64 (no deferred staging) stages Y(k) at the end of chunk k, into
+// the same T[k-1].  (Fixed tile pairs P0[2] / P1[2] — the staged rows where the next destination rows go — made that DMA wait
+// for every helper wave's fold: see DESIGN.md §3.)
 // The indexing mode's switch (round 4: the cause of round 3's "unexplained hazard").  s_set_gpr_idx_on writes MODE.gpr_idx_en; a
 // VALU instruction issued in the very next slot is not guaranteed to see it — the same class as the ISA's "s_setreg of MODE ->
 // vector instruction" rule, which the assembler's and hipcc's hazard handling do not apply to this instruction.  With one helper
@@ -191,14 +199,14 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
     int32_t* __restrict__ range_flag, float* __restrict__ agg_out) {
     using C = BxCfg<D>;
     // ZERO_SRC (SKIP = 1, the backward's pass over the forward plan) runs as the one-phase kernel of ZERO_DST does — its rows
-    // gathered a whole chunk ahead into the P0 tiles, no hand-shake for a late tile — with the destination ids, the
+    // gathered a whole chunk ahead into the source-row tiles S(k) of the ring, no hand-shake for a late tile — with the destination ids, the
     // destination half of the weights and the destination rows' scales in that phase: as a second phase without a first one
     // its gathers were issued behind the fold and waited for at the next chunk's start (2.41 -> 2.34 ms per C3 launch, same box;
     // the 4.8 ms of round 2's training profile was this launch beside the weight gradients' kernel on a second stream)
     constexpr bool SWAP1 = SKIP == 1;
     constexpr int skip = SWAP1 ? 2 : SKIP;
-    constexpr int P0_IDS = SWAP1 ? 3 : 2;          // which ids the P0 tiles' rows follow (2: source, 3: destination)
-    constexpr int P0_HALF = SWAP1 ? 1 : 0;         // the half of the weights (and the row scales) of the P0 phase
+    constexpr int P0_IDS = SWAP1 ? 3 : 2;          // which ids the rows of the S tiles follow (2: source, 3: destination)
+    constexpr int P0_HALF = SWAP1 ? 1 : 0;         // the half of the weights (and the row scales) of the phase that reads S
     constexpr int BN = C::BN, MTC = C::MTC, CR = C::CR, NPW = C::NPW;
     constexpr bool DEFER = C::DEFER;
     constexpr int NWV = 8, TW = 4;            // waves per workgroup, per role
@@ -228,12 +236,14 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
     // two rows share a 256-byte bank line, so the key is (row / 2) mod 8 — either way the 16 rows of a fragment read hit every
     // bank once
     auto akey = [](int row) -> int { return D == 128 ? (row & 15) : ((row >> 1) & 7); };
-    // P0[2] source-row tiles, P1[2] destination-row tiles; a chunk's staged rows Y overwrite its own P1 tile
-    constexpr unsigned P0_OFF = 0, P1_OFF = 2 * TILE, META_OFF = 4 * TILE,
+    // a ring of four A tiles, T[j] = tile j & 3: chunk j's source rows in T[j], its destination rows in T[j-1], its staged rows
+    // Y(j) over its own destination rows (see the header)
+    constexpr unsigned META_OFF = 4 * TILE,
                        DUMMY_OFF = META_OFF + 4 * MSTR * 4, ZERO_OFF = DUMMY_OFF + 1024,       // ZERO: a staged row of zeros (512 bytes)
-                       FLAG_OFF = ZERO_OFF + 512;         // FLAG: 4 helper words (chunks folded), 4 consumer words (chunks whose tiles are read),
-                                                          // 4 unused words, 4 consumer words (the last chunk's hand-shake when staging
-                                                          // is deferred)
+                       FLAG_OFF = ZERO_OFF + 512;         // FLAG: 4 helper words (descriptors published), 4 consumer words (chunks staged), 4 consumer words
+                                                          // (chunks whose first phase has read its tile), 4 consumer words (the last
+                                                          // chunk's hand-shake when staging is deferred)
+    auto tile_of = [](int j) -> unsigned { return (unsigned)(j & 3) * (unsigned)TILE; };       // T[j]
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned lds0 = (unsigned)(size_t)(lptr_t)smem;       // LDS byte address of smem (0 unless static LDS exists)
@@ -668,7 +678,7 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             return FoldPlan{n0, n1, ra, cnt};
         };
         auto fold_rows = [&](int j, const FoldPlan& fp, int lane) __attribute__((always_inline)) {
-            const unsigned Y = lds0 + (P1_OFF + (unsigned)(j & 1) * TILE);
+            const unsigned Y = lds0 + tile_of(j - 1);
             const int ra = fp.ra, cnt = fp.cnt;
             const unsigned zrow = lds0 + ZERO_OFF + (unsigned)(PL * 4 * lane), lb = (unsigned)(PL * 4 * lane);
             typedef typename std::conditional<D == 128, f32x2, float>::type yv_t;
@@ -742,13 +752,23 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
                 __builtin_amdgcn_s_sleep(1);
             }
         };
+        // the same for two flag groups in one LDS round trip
+        auto wait_flags2 = [&](unsigned fa, unsigned fb, int v) {
+            for (;;) {
+                i32x4 f, g;
+                asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)" : "=&v"(f), "=&v"(g) : "v"(fa), "v"(fb) : "memory");
+                const int lo = min(min(min(f[0], f[1]), min(f[2], f[3])), min(min(g[0], g[1]), min(g[2], g[3])));
+                if (__builtin_amdgcn_readfirstlane(lo) >= v) break;
+                __builtin_amdgcn_s_sleep(1);
+            }
+        };
 
-        // ---- one workgroup barrier per chunk.  During chunk k (between barriers k and k + 1):
-        //   consumers: phase 0 from P0[k&1], phase 1 from P1[k&1]; once all four have read that tile, the chunk's rows Y(k)
-        //              overwrite it
-        //   helpers:   DMA P0[(k+1)&1] <- source rows of chunk k+1 (HBM: a whole chunk to land); fold Y(k-1) out of
-        //              P1[(k-1)&1]; once all four have folded, DMA that tile <- destination rows of chunk k+1 (L2); table of
-        //              chunk k; descriptor of chunk k+2
+        // ---- one workgroup barrier per chunk.  During chunk k (between barriers k and k + 1), T[j] = tile j & 3:
+        //   consumers: phase 0 from T[k] (then the flag "phase 0 read"), phase 1 from T[k-1]; once all four have read that
+        //              tile, the chunk's rows Y(k) overwrite it (deferred staging: behind the next barrier)
+        //   helpers:   DMA T[k+1] <- source rows of chunk k+1 (HBM: a whole chunk to land); fold Y(k-1) out of T[k-2]; once the
+        //              consumers have read phase 0's tile, DMA T[k] <- destination rows of chunk k+1 (L2); table of chunk k;
+        //              descriptor of chunk k+2
         // Descriptor pipeline of chunk j: chunk_tab entry requested during chunk j-5, words (source id, key) j-4, the rows'
         // scales j-3, published j-2.  Values move up one place at the START of a chunk, when they have long arrived (a
         // register copy of a value still in flight waits for it, and for every DMA issued before it).
@@ -783,8 +803,8 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
         __builtin_amdgcn_s_barrier();                      // barrier A: descriptors 0 and 1 visible to all helper waves
         // (raw barriers in this role: __syncthreads() drains every LDS-DMA in flight — vmcnt(0) — before it)
         if (nchunks > 0) {
-            if (!(skip & 1)) dma_tile(P0_OFF, 0, P0_IDS, ch[0], lane);
-            if (!(skip & 2)) dma_tile(P1_OFF, 0, 3, ch[0], lane);
+            if (!(skip & 1)) dma_tile(tile_of(0), 0, P0_IDS, ch[0], lane);
+            if (!(skip & 2)) dma_tile(tile_of(-1), 0, 3, ch[0], lane);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         int sid[6] = {0, 0, 0, 0, 0, 0};                     // source ids of the NEXT chunk's rows (read at the end of a chunk)
@@ -802,19 +822,27 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
                 asm volatile("" : "+v"(wdP.src), "+v"(wdP.key), "+v"(scP.u), "+v"(scP.v), "+v"(wdN.src), "+v"(wdN.key));
             }
             publish(k + 2, ch[2], wdP, scP, l0);
-            if (!(skip & 1)) dma_issue(P0_OFF + ((k + 1) & 1) * TILE, ch[1].rows, l0, sid);
+            if (!(skip & 1)) dma_issue(tile_of(k + 1), ch[1].rows, l0, sid);
+            // descriptor k+2 is cut by rows among the helper waves and its ids are read by pieces (dma_ids at this chunk's end):
+            // this wave's part is in LDS (the writes have had the DMA's issue to complete) — say so
+            BX_LGKM0();
+            if (lane == 0) lds_st_b32(lds0 + FLAG_OFF + 4 * hw, k + 1);
             if (k > 0) {
                 const FoldPlan fp = fold_plan(k - 1, prev_rows, l0);
                 if (DEFER) wait_flags(lds0 + FLAG_OFF + 16, k);   // all four consumer waves have staged Y(k-1)
                 fold_rows(k - 1, fp, l0);
             }
-            BX_LGKM0();
-            if (lane == 0) lds_st_b32(lds0 + FLAG_OFF + 4 * hw, k + 1);   // this wave is through with Y(k-1)
-            // the destination ids of chunk k+1's rows (its tile's DMA): one round trip taken while the other helper waves catch up
+            // the destination ids of chunk k+1's rows (published two chunks ago), then its tile: T[k], this chunk's source rows —
+            // free once all four consumer waves are through with their first phase.  (No helper waits for another's FOLD: the
+            // tile Y(k-1) was folded out of is next written behind barrier k+1.)  The same round trip takes the helpers'
+            // "descriptor k+2 published" words, written at this chunk's start: the ids read at its end come from all four waves.
             int did[6];
-            if (!(skip & 2)) dma_ids(k + 1, 3, opaque_lane(lane), did);
-            // the staged rows sit where the next destination rows go: every helper wave must have folded them first
-            wait_flags(lds0 + FLAG_OFF, k + 1);
+            if (!(skip & 2)) {
+                dma_ids(k + 1, 3, opaque_lane(lane), did);
+                wait_flags2(lds0 + FLAG_OFF, lds0 + FLAG_OFF + 32, k + 1);
+            } else {
+                wait_flags(lds0 + FLAG_OFF, k + 1);
+            }
             const int l1 = opaque_lane(lane);
             // the next requests of the descriptor pipeline: behind the loops above (a load in flight across a loop makes hipcc
             // wait for everything — the source-row DMA included — at the loop), ahead of the rest of the chunk (requested
@@ -822,9 +850,9 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             scN = load_scales(ch[3], wdN);
             wdL = load_words(ch[4], l1);
             d5 = load_desc(k + 5);
-            if (!(skip & 2)) dma_issue(P1_OFF + ((k + 1) & 1) * TILE, ch[1].rows, l1, did);
+            if (!(skip & 2)) dma_issue(tile_of(k), ch[1].rows, l1, did);
             prev_rows = ch[0].rows;
-            if (!(skip & 1)) dma_ids(k + 2, P0_IDS, l1, sid);     // (published at this chunk's start by every helper wave; all are past their flag)
+            if (!(skip & 1)) dma_ids(k + 2, P0_IDS, l1, sid);     // (published at this chunk's start by every helper wave: their flag words, waited for above)
             // both tiles of chunk k+1 (the source rows requested at this chunk's start, the destination rows just now) must be
             // in before the barrier
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1036,7 +1064,7 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             // the accumulators are not needed before this chunk's first phase ends.  The helpers wait for the flag.
             // (Staging writes between the k-steps were measured slower: round 3.)
             if (DEFER && k > 0) {
-                write_rows(mt_prev, P1_OFF + ((k - 1) & 1) * TILE);
+                write_rows(mt_prev, tile_of(k - 2));
                 BX_LGKM0();
                 if (lane == 0) lds_st_b32(lds0 + FLAG_OFF + 16 + 4 * tw, k);
             }
@@ -1047,10 +1075,11 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             // round 4).  They stay because hipcc lays the whole kernel out differently without them — the schedule rewrite
             // takes them out with the rest.
             constexpr bool PRE1 = false;
+            static_assert(!PRE1, "the hook has no flag words of its own any more: wait_landed spins on words that mean something else (a hung CU)");
             auto wait_landed = [&]() __attribute__((always_inline)) {
                 for (;;) {
                     i32x4 f;
-                    asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(f) : "v"(lds0 + FLAG_OFF + 32) : "memory");
+                    asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(f) : "v"(lds0 + FLAG_OFF) : "memory");
                     const int lo = min(min(f[0], f[1]), min(f[2], f[3]));
                     if (__builtin_amdgcn_readfirstlane(lo) >= k + 1) break;
                     __builtin_amdgcn_s_sleep(1);
@@ -1059,12 +1088,15 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             auto next_pre = [&]() __attribute__((always_inline)) {
                 if (PRE1) {
                     wait_landed();
-                    prefetch_a(smem + P1_OFF + (k & 1) * TILE);
+                    prefetch_a(smem + tile_of(k - 1));
                 }
             };
             auto no_after = []() {};
             if (!(skip & 1))
-                stage_for(mt, std::false_type{}, P0_HALF, true, smem + P0_OFF + (k & 1) * TILE, meta, wscale, (skip & 2) ? nx.r : ch.r, (skip & 2) ? P0_HALF : 1, bias_v, next_pre);
+                stage_for(mt, std::false_type{}, P0_HALF, true, smem + tile_of(k), meta, wscale, (skip & 2) ? nx.r : ch.r, (skip & 2) ? P0_HALF : 1, bias_v, next_pre);
+            // the first phase's tile is read (its fragments have gone through the MFMAs): the helpers may gather the next chunk's
+            // destination rows into it
+            if (!(skip & 2) && lane == 0) lds_st_b32(lds0 + FLAG_OFF + 32 + 4 * tw, k + 1);
             dn = load_desc(k + 2);
             load_rel_words(nx.r, wscale_n, bias_n);
             if (skip & 1) {                                // no source phase ran: the destination phase adds to the bias
@@ -1073,7 +1105,7 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
 #pragma unroll
                     for (int t = 0; t < NTW; ++t) acc[m][t] = (f32x4){bias_v[t], bias_v[t], bias_v[t], bias_v[t]};
             }
-            if (!(skip & 2)) stage_for(mt, std::false_type{}, 1, false, smem + P1_OFF + (k & 1) * TILE, meta, wscale, nx.r, ph_first, bias_v, no_after);
+            if (!(skip & 2)) stage_for(mt, std::false_type{}, 1, false, smem + tile_of(k - 1), meta, wscale, nx.r, ph_first, bias_v, no_after);
             // the last chunk (and every chunk without DEFER) stages its rows here: they overwrite the chunk's destination-row tile
             // once all four consumer waves have read it (flag words)
             const bool stage_now = !DEFER || k + 1 == nchunks;
@@ -1088,7 +1120,7 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
                     if (__builtin_amdgcn_readfirstlane(lo) >= fv) break;
                     __builtin_amdgcn_s_sleep(1);
                 }
-                write_rows(mt, P1_OFF + (k & 1) * TILE);
+                write_rows(mt, tile_of(k - 1));
             }
             mt_prev = mt;
             ch = nx;
@@ -1125,7 +1157,7 @@ static int launch_bx_for(const MsgArgs& a, hipStream_t stream) {
     using C = BxCfg<D>;
     constexpr size_t lds = C::LDS;
     static_assert(lds <= 160 * 1024, "LDS budget");
-    static_assert((size_t)(C::BN / 2) * D * 4 <= (size_t)3 * 2 * C::CR * (D * 2), "the tail's dump of half a block must fit the three A tiles");
+    static_assert((size_t)(C::BN / 2) * D * 4 <= (size_t)3 * 2 * C::CR * (D * 2), "the tail's dump of half a block must fit three whole tiles of the ring");
     GHF_REQUIRE(a.block_nodes == C::BN, "message(bx): plan block_nodes=%d, kernel for d=%d needs %d", a.block_nodes, D, C::BN);
     GHF_REQUIRE(a.wlayout == GHF_WLAYOUT_SPLIT2H, "message(bx): weights must be in SPLIT2H layout");
     GHF_REQUIRE(a.chunk_tab && a.item_tab && a.blk_item_off, "message(bx): the plan's chunk / item tables are missing");
