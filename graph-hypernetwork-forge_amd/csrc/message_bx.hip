@@ -30,15 +30,24 @@
 // read).  The four tiles live during chunk k are distinct: S(k) = T[k], D(k) = T[k-1], Y(k-1) = T[k-2], S(k+1) = T[k+1].
 // ONE workgroup barrier per chunk.  During chunk k (between barriers k and k + 1):
 //   consumers: stage Y(k-1) into T[k-2] (behind the barrier every consumer is through with that tile; flag "staged");
-//              phase 0 (h_src x W_msg) from T[k], then flag "phase 0 of chunk k read"; phase 1 (h_dst x W_self) from T[k-1];
+//              phase 0 (h_src x W_msg) from T[k], flag "phase 0 of chunk k read" behind its last MFMAs (in front of its
+//              unscale); phase 1 (h_dst x W_self) from T[k-1];
 //              the accumulators keep Y(k) until the next barrier
 //   helpers:   DMA T[k+1] <- source rows of chunk k+1 (HBM: a whole chunk to land; the tile Y(k-2) was folded out of during
-//              chunk k-1); wait for "staged", fold Y(k-1) out of T[k-2]; wait for "phase 0 of chunk k read", DMA T[k] <-
-//              destination rows of chunk k+1 (L2) — no helper waits for another's fold: T[k-2] is next written by S(k+2),
-//              behind barrier k+1; the descriptor pipeline (chunk_tab entry k+5, edge words k+4, row scales k+3, publish k+2:
-//              each wave its rows, then its flag word "published" — the four words are waited for, in the round trip of the
-//              phase-0 flag, before the source ids of chunk k+2 are read by DMA pieces at the chunk's end);
+//              chunk k-1); wait for "staged", fold the wave's FIRST BX_FSPLIT rows of Y(k-1) out of T[k-2]; wait for "phase 0 of
+//              chunk k read", request the descriptor pipeline's loads and DMA T[k] <- destination rows of chunk k+1 (L2); fold
+//              the REST of the wave's rows beside those round trips — no helper waits for another's fold: T[k-2] is next
+//              written by S(k+2), behind barrier k+1; the descriptor pipeline (chunk_tab entry k+5, edge words k+4, row scales
+//              k+3, publish k+2: each wave its rows, then its flag word "published" — the four words are waited for, in the
+//              round trip of the phase-0 flag, before the source ids of chunk k+2 are read by DMA pieces at the chunk's end);
 //              vmcnt(0): both tiles of chunk k+1 are in before the barrier
+// No deadlock in the flag waits.  The ring's: a helper waits for "staged" and for "phase 0 of chunk k read", both raised by the
+// consumers behind barrier k without waiting for any helper progress of chunk k (the tiles they read landed before the barrier).
+// The split fold's: the wait for "phase 0 of chunk k read" now stands in the MIDDLE of a wave's fold, so a wave may block with
+// rows of Y(k-1) unfolded — but no consumer wave waits for a fold (T[k-2] is not written again before barrier k+1, which the
+// helpers reach only with their fold done), and the "published" words waited for in the same round trip were written by every
+// helper wave at the chunk's start, in front of any of its waits.  A wave with at most BX_FSPLIT rows has nothing left behind the
+// requests and waits for them as before.
 // One-phase instances (SKIP 1 / 2) use S and Y only.  Hidden 64 (no deferred staging) stages Y(k) at the end of chunk k, into
 // the same T[k-1].  (Fixed tile pairs P0[2] / P1[2] — the staged rows where the next destination rows go — made that DMA wait
 // for every helper wave's fold: see DESIGN.md §3.)
@@ -139,6 +148,9 @@ template <class T> __device__ __forceinline__ void bx_tail_st(T* p, T v) { __bui
 // launch non-temporal — the Infinity Cache serves part of a source row's ~10 gathers per layer); ZERO_SRC as a first phase;
 // the tail's batches of three four-row groups
 constexpr int BX_AD = 2, BX_TGB = 3;
+// the helpers fold this many of a chunk's staged rows (a multiple of eight: whole fold iterations) before they request the next
+// chunk's destination rows and the descriptor pipeline's loads; the rest of the fold runs beside those round trips
+constexpr int BX_FSPLIT = 8;
 
 template <int D> struct BxCfg;
 template <> struct BxCfg<128> {
@@ -665,10 +677,21 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
         struct FoldPlan { int n0, n1, ra, cnt; };
         // which of chunk j's rows are mine (one LDS round trip; taken BEFORE the wait for the staged rows: the descriptor has
         // long been published)
-        auto fold_plan = [&](int j, int rows, int lane) __attribute__((always_inline)) -> FoldPlan {
+        // With `staged` > 0 the same round trip takes a first look at the consumers' "staged" words: true in *ready when all four
+        // have reached `staged` (the caller then has no wait of its own: two dependent round trips of ~250 cycles were one too many).
+        auto fold_plan = [&](int j, int rows, int lane, int staged, bool* ready) __attribute__((always_inline)) -> FoldPlan {
             const unsigned dd = lds0 + meta_off(j) + 4 * (3 * CRP);
+            const unsigned a0 = dd + 4 * lane, a1 = dd + 4 * (lane + 64 < CRP ? lane + 64 : CRP - 1);
             int d0, d1;
-            lds_ld_b32_x2(dd + 4 * lane, dd + 4 * (lane + 64 < CRP ? lane + 64 : CRP - 1), d0, d1);
+            if (staged > 0) {
+                i32x4 f;
+                asm volatile("ds_read_b32 %0, %3\n\tds_read_b32 %1, %4\n\tds_read_b128 %2, %5\n\ts_waitcnt lgkmcnt(0)"
+                             : "=&v"(d0), "=&v"(d1), "=&v"(f) : "v"(a0), "v"(a1), "v"(lds0 + FLAG_OFF + 16) : "memory");
+                *ready = __builtin_amdgcn_readfirstlane(min(min(f[0], f[1]), min(f[2], f[3]))) >= staged;
+            } else {
+                lds_ld_b32_x2(a0, a1, d0, d1);
+                *ready = true;
+            }
             const int base = (int)node0 + hw * NPW;
             const int n0 = d0 - base, n1 = d1 - base;                    // wave-local node of rows lane, 64 + lane
             const unsigned long long q0 = __ballot(lane < rows && (unsigned)n0 < (unsigned)NPW);
@@ -677,7 +700,9 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             const int ra = q0 ? (int)__builtin_ctzll(q0) : 64 + (q1 ? (int)__builtin_ctzll(q1) : 0);
             return FoldPlan{n0, n1, ra, cnt};
         };
-        auto fold_rows = [&](int j, const FoldPlan& fp, int lane) __attribute__((always_inline)) {
+        // fold_rows takes the wave's rows [g_begin, min(cnt, g_end)), g_begin a multiple of eight: the chunk loop folds the
+        // first BX_FSPLIT rows, issues its requests, and folds the rest beside their round trips.
+        auto fold_rows = [&](int j, const FoldPlan& fp, int lane, int g_begin, int g_end) __attribute__((always_inline)) {
             const unsigned Y = lds0 + tile_of(j - 1);
             const int ra = fp.ra, cnt = fp.cnt;
             const unsigned zrow = lds0 + ZERO_OFF + (unsigned)(PL * 4 * lane), lb = (unsigned)(PL * 4 * lane);
@@ -721,12 +746,12 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
                 if constexpr (D == 128)
                     asm volatile("s_mov_b32 %[kp], m0\n\ts_set_gpr_idx_on %[i0], 0xa\n\t" BX_IDX_WAIT "v_pk_add_f32 v[64:65], %[y0], v[64:65]\n\t"
                                  BX_ROW128(1) BX_ROW128(2) BX_ROW128(3)
-                                 "s_set_gpr_idx_off\n\t" BX_IDX_WAIT "s_mov_b32 m0, %[kp]"
+                                 "s_set_gpr_idx_off\n\t" BX_IDX_WAIT "s_mov_b32 m0, %[kp]\n\ts_nop 0"
                                  : BX_PIN_128(sm), [kp] "=&s"(keep) : BX_ROW_OPS);
                 else
                     asm volatile("s_mov_b32 %[kp], m0\n\ts_set_gpr_idx_on %[i0], 0xa\n\t" BX_IDX_WAIT "v_add_f32 v64, %[y0], v64\n\t"
                                  BX_ROW64(1) BX_ROW64(2) BX_ROW64(3)
-                                 "s_set_gpr_idx_off\n\t" BX_IDX_WAIT "s_mov_b32 m0, %[kp]"
+                                 "s_set_gpr_idx_off\n\t" BX_IDX_WAIT "s_mov_b32 m0, %[kp]\n\ts_nop 0"
                                  : BX_PIN_64(sm), [kp] "=&s"(keep) : BX_ROW_OPS);
 #undef BX_ROW128
 #undef BX_ROW64
@@ -734,7 +759,7 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             };
             // (straight-line per iteration: a batch in flight across a branch or the loop's back edge gets copied by the
             // compiler — a phi — before its wait, i.e. read before it has landed)
-            for (int g = 0; g < cnt; g += 2 * FB) {
+            for (int g = g_begin; g < cnt && g < g_end; g += 2 * FB) {
                 yv_t ya[FB], yb[FB];
                 issue(ya, g);
                 issue(yb, g + FB);
@@ -827,10 +852,13 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             // this wave's part is in LDS (the writes have had the DMA's issue to complete) — say so
             BX_LGKM0();
             if (lane == 0) lds_st_b32(lds0 + FLAG_OFF + 4 * hw, k + 1);
+            // the fold of Y(k-1), first part: BX_FSPLIT rows.  (Chunk 0 has no fold: cnt = 0, straight to the requests.)
+            FoldPlan fp{0, 0, 0, 0};
             if (k > 0) {
-                const FoldPlan fp = fold_plan(k - 1, prev_rows, l0);
-                if (DEFER) wait_flags(lds0 + FLAG_OFF + 16, k);   // all four consumer waves have staged Y(k-1)
-                fold_rows(k - 1, fp, l0);
+                bool staged;
+                fp = fold_plan(k - 1, prev_rows, l0, DEFER ? k : 0, &staged);
+                if (DEFER && !staged) wait_flags(lds0 + FLAG_OFF + 16, k);   // all four consumer waves have staged Y(k-1)
+                fold_rows(k - 1, fp, l0, 0, BX_FSPLIT);
             }
             // the destination ids of chunk k+1's rows (published two chunks ago), then its tile: T[k], this chunk's source rows —
             // free once all four consumer waves are through with their first phase.  (No helper waits for another's FOLD: the
@@ -844,13 +872,17 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
                 wait_flags(lds0 + FLAG_OFF, k + 1);
             }
             const int l1 = opaque_lane(lane);
-            // the next requests of the descriptor pipeline: behind the loops above (a load in flight across a loop makes hipcc
-            // wait for everything — the source-row DMA included — at the loop), ahead of the rest of the chunk (requested
-            // at its end they were waited for right behind the next barrier)
+            // the next requests of the descriptor pipeline and the destination rows' DMA: behind the flag waits above (spin
+            // loops the compiler can see into), in front of the rest of the fold, so that their round trips run beside it and
+            // the wait at the chunk's end finds them landed.  The rest of the fold is a loop of asm statements that neither
+            // read nor write what is in flight: hipcc puts no s_waitcnt vmcnt of its own at it (checked in the listing of every
+            // instance: between these requests and the chunk's last wait there is none).  It does wait for everything at a
+            // loop whose body uses a value in flight; nothing here is used before the next chunk's start.
             scN = load_scales(ch[3], wdN);
             wdL = load_words(ch[4], l1);
             d5 = load_desc(k + 5);
             if (!(skip & 2)) dma_issue(tile_of(k), ch[1].rows, l1, did);
+            fold_rows(k - 1, fp, l1, BX_FSPLIT, CR + 8);    // the rest of Y(k-1): a wave with at most BX_FSPLIT rows has none
             prev_rows = ch[0].rows;
             if (!(skip & 1)) dma_ids(k + 2, P0_IDS, l1, sid);     // (published at this chunk's start by every helper wave: their flag words, waited for above)
             // both tiles of chunk k+1 (the source rows requested at this chunk's start, the destination rows just now) must be
@@ -861,7 +893,8 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
         __builtin_amdgcn_s_barrier();                      // ---- epilogue: the last chunk's rows
         if (nchunks > 0) {
             const int le = opaque_lane(lane);
-            fold_rows(nchunks - 1, fold_plan(nchunks - 1, prev_rows, le), le);
+            bool staged;                                   // (the last chunk was staged in front of this barrier)
+            fold_rows(nchunks - 1, fold_plan(nchunks - 1, prev_rows, le, 0, &staged), le, 0, CR + 8);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no DMA may still be landing when the tiles are reused below
         BX_LGKM0();
@@ -1073,7 +1106,7 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
             // The stages' prefetch hooks are compiled out (pre_c false, PRE1 false: the second phase's first fragments requested
             // ahead of the first phase's unscale spilled 44 registers; the first phase's behind the barrier measured no faster,
             // round 4).  They stay because hipcc lays the whole kernel out differently without them — the schedule rewrite
-            // takes them out with the rest.
+            // takes them out with the rest.  The first phase's hook also raises that phase's flag (next_pre).
             constexpr bool PRE1 = false;
             static_assert(!PRE1, "the hook has no flag words of its own any more: wait_landed spins on words that mean something else (a hung CU)");
             auto wait_landed = [&]() __attribute__((always_inline)) {
@@ -1090,13 +1123,16 @@ __global__ __launch_bounds__(512, D == 64 ? 4 : 2) void message_bx_kernel(   // 
                     wait_landed();
                     prefetch_a(smem + tile_of(k - 1));
                 }
+                // "phase 0 of chunk k read": behind the last k-step's MFMAs, whose operands every fragment read of the tile has
+                // delivered (and a wave's LDS accesses execute in order), in front of the unscale — the helpers wait for these
+                // words in mid-fold and may gather the next chunk's destination rows into the tile (raised behind the whole
+                // stage the flag came later by the length of the unscale: DESIGN.md §5)
+                if (!(skip & 2) && lane == 0) lds_st_b32(lds0 + FLAG_OFF + 32 + 4 * tw, k + 1);
             };
             auto no_after = []() {};
             if (!(skip & 1))
                 stage_for(mt, std::false_type{}, P0_HALF, true, smem + tile_of(k), meta, wscale, (skip & 2) ? nx.r : ch.r, (skip & 2) ? P0_HALF : 1, bias_v, next_pre);
-            // the first phase's tile is read (its fragments have gone through the MFMAs): the helpers may gather the next chunk's
-            // destination rows into it
-            if (!(skip & 2) && lane == 0) lds_st_b32(lds0 + FLAG_OFF + 32 + 4 * tw, k + 1);
+            // (the flag "phase 0 of chunk k read" went up inside the stage: next_pre)
             dn = load_desc(k + 2);
             load_rel_words(nx.r, wscale_n, bias_n);
             if (skip & 1) {                                // no source phase ran: the destination phase adds to the bias
