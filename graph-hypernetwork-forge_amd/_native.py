@@ -109,6 +109,11 @@ SIGNATURES = {
     "ghf_score_softmax_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ghf_relation_rows_workspace_bytes": (_sz, [_i64, _i32]),
     "ghf_relation_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
+    "ghf_relation_scores": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp]),
+    "ghf_relation_scores_bwd_rows_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "ghf_relation_scores_bwd_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _sz, _vp, _vp]),
+    "ghf_relation_scores_bwd_weights_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "ghf_relation_scores_bwd_weights": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _sz, _vp, _vp, _vp]),
     "ghf_rows_pack": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "ghf_rows_unpack": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "ghf_rows_accumulate": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp]),
@@ -791,6 +796,94 @@ def relation_rows(x: torch.Tensor, rel: torch.Tensor, W: torch.Tensor, bias: Opt
     _check(load().ghf_relation_rows(_ptr(x), _ptr(ix), _ptr(rel), _ptr(W), _ptr(bias), _ptr(perm), _ptr(goff), rows_x, B, R, d,
                                     flags, _ptr(ws), ws.numel(), _ptr(out), _stream()), "ghf_relation_rows")
     return out
+
+
+# ---- relation prediction: every relation's score for a pair (include/ghf.h: ghf_relation_scores, csrc/relation_predict.hip) ----
+def relation_scores_bwd_rows_workspace_bytes(B: int, U: int, d: int) -> int:
+    return int(load().ghf_relation_scores_bwd_rows_workspace_bytes(B, U, d))
+
+
+def relation_scores_bwd_weights_workspace_bytes(B: int, U: int, d: int) -> int:
+    return int(load().ghf_relation_scores_bwd_weights_workspace_bytes(B, U, d))
+
+
+def _relation_scores_args(x, ia, ib, W, bias, G, what: str):
+    x = _req(x, torch.float32, "x")
+    ia = _req(ia, torch.int64, "ia")
+    ib = None if ib is None else _req(ib, torch.int64, "ib")
+    if x.dim() != 2 or x.size(0) == 0 or x.size(1) == 0 or ia.dim() != 1 or ia.numel() == 0:
+        raise ValueError(f"{what}: need x [rows, d] and ia [B], got {tuple(x.shape)} and {tuple(ia.shape)}")
+    (rows_x, d), B = x.shape, ia.numel()
+    if ib is not None and (ib.dim() != 1 or ib.numel() != B):
+        raise ValueError(f"{what}: ib must name one row per entry of ia ({B}), got {tuple(ib.shape)}")
+    U = None
+    if W is not None:
+        W = _req(W, torch.float32, "W")
+        if W.dim() != 3 or W.size(0) == 0 or W.size(1) != d or W.size(2) != d:
+            raise ValueError(f"{what}: W must be [U, {d}, {d}], got {tuple(W.shape)}")
+        U = W.size(0)
+    if G is not None:
+        G = _req(G, torch.float32, "G")
+        if G.dim() != 2 or G.size(0) != B or G.size(1) == 0 or (U is not None and G.size(1) != U):
+            raise ValueError(f"{what}: G must be [B = {B}, U{'' if U is None else f' = {U}'}], got {tuple(G.shape)}")
+        U = G.size(1)
+    if bias is not None:
+        bias = _req(bias, torch.float32, "bias")
+        if tuple(bias.shape) != (U, d):
+            raise ValueError(f"{what}: bias must be [{U}, {d}], got {tuple(bias.shape)}")
+    for name, t in (("ia", ia), ("ib", ib), ("W", W), ("bias", bias), ("G", G)):
+        if t is not None and t.device != x.device:
+            raise RuntimeError(f"{what}: {name} is on {t.device}, x on {x.device}")
+    return x, ia, ib, W, bias, G, rows_x, B, U, d
+
+
+def relation_scores(x: torch.Tensor, ia: torch.Tensor, ib: torch.Tensor, W: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                    add_x: bool = True, transpose: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i][u] = q(i, u) . x[ib[i]] with q(i, u) = [x[ia[i]]] + x[ia[i]] @ op(W[u]) + [bias[u]]: every relation's score
+    for every pair, fp32 [B, U], in one sweep that stores nothing of size B x U x d.  x [rows, d]; ia, ib int64 [B];
+    W [U, d, d]; bias [U, d] or None.  An id out of range gives a NaN row.  With `out` given the call allocates nothing."""
+    x, ia, ib, W, bias, _, rows_x, B, U, d = _relation_scores_args(x, ia, ib, W, bias, None, "relation_scores")
+    out = _f32_out(out, (B, U), x.device, "relation_scores")
+    flags = (GHF_REL_ADD_X if add_x else 0) | (GHF_REL_TRANSPOSE if transpose else 0)
+    _check(load().ghf_relation_scores(_ptr(x), _ptr(ia), _ptr(ib), _ptr(W), _ptr(bias), rows_x, B, U, d, flags, _ptr(out),
+                                      _stream()), "ghf_relation_scores")
+    return out
+
+
+def relation_scores_bwd_rows(x: torch.Tensor, ia: torch.Tensor, G: torch.Tensor, W: torch.Tensor,
+                             bias: Optional[torch.Tensor] = None, add_x: bool = True, transpose: bool = False,
+                             workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i] = sum_u G[i][u] q(i, u), fp32 [B, d], u ascending (q as in relation_scores).  As called: the gradient of
+    the b rows; with ia = the forward's ib, `transpose` flipped and no bias: the gradient of the a rows."""
+    x, ia, _, W, bias, G, rows_x, B, U, d = _relation_scores_args(x, ia, None, W, bias, G, "relation_scores_bwd_rows")
+    need = relation_scores_bwd_rows_workspace_bytes(B, U, d)
+    if need == 0:
+        raise ValueError(f"relation_scores_bwd_rows: unsupported sizes B={B} U={U} d={d}")
+    ws = _rank_workspace(workspace, need, x.device, "relation_scores_bwd_rows")
+    out = _f32_out(out, (B, d), x.device, "relation_scores_bwd_rows")
+    flags = (GHF_REL_ADD_X if add_x else 0) | (GHF_REL_TRANSPOSE if transpose else 0)
+    _check(load().ghf_relation_scores_bwd_rows(_ptr(x), _ptr(ia), _ptr(G), _ptr(W), _ptr(bias), rows_x, B, U, d, flags, _ptr(ws),
+                                               ws.numel(), _ptr(out), _stream()), "ghf_relation_scores_bwd_rows")
+    return out
+
+
+def relation_scores_bwd_weights(x: torch.Tensor, ia: torch.Tensor, ib: torch.Tensor, G: torch.Tensor, want_bias: bool = True,
+                                workspace: Optional[torch.Tensor] = None,
+                                out: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None):
+    """(dW [U, d, d], dbias [U, d] or None): dW[u] = sum_i G[i][u] x[ia[i]]^T x[ib[i]], dbias[u] = sum_i G[i][u] x[ib[i]],
+    i ascending.  A query with an id out of range adds nothing."""
+    x, ia, ib, _, _, G, rows_x, B, U, d = _relation_scores_args(x, ia, ib, None, None, G, "relation_scores_bwd_weights")
+    if ib is None:
+        raise ValueError("relation_scores_bwd_weights: ib is needed")
+    need = relation_scores_bwd_weights_workspace_bytes(B, U, d)
+    if need == 0:
+        raise ValueError(f"relation_scores_bwd_weights: unsupported sizes B={B} U={U} d={d}")
+    ws = _rank_workspace(workspace, need, x.device, "relation_scores_bwd_weights")
+    dW = _f32_out(None if out is None else out[0], (U, d, d), x.device, "relation_scores_bwd_weights")
+    db = _f32_out(None if out is None else out[1], (U, d), x.device, "relation_scores_bwd_weights") if want_bias else None
+    _check(load().ghf_relation_scores_bwd_weights(_ptr(x), _ptr(ia), _ptr(ib), _ptr(G), rows_x, B, U, d, 0, _ptr(ws), ws.numel(),
+                                                  _ptr(dW), _ptr(db), _stream()), "ghf_relation_scores_bwd_weights")
+    return dW, db
 
 
 # ---- wide hidden sizes: relation-stationary layer (include/ghf.h, csrc/message_rs.hip) ---------------------------

@@ -496,6 +496,42 @@ class RelationRowsFn(torch.autograd.Function):
         return dx, None, None, dA, db
 
 
+class RelationScoresFn(torch.autograd.Function):
+    """S[i, u] = (x[ia_i] + x[ia_i] @ A[u] + b[u]) . x[ib_i] (ghf_relation_scores): every relation's score for every pair,
+    A [U, d, d] and b [U, d] normally a WeightGenerator's heads.  With G = dS:
+        db_rows_i = sum_u G[i, u] (a_i + a_i @ A[u] + b[u])        the sweep with "add G q" as its epilogue
+        da_rows_i = sum_u G[i, u] (b_i + b_i @ A[u]^T)             the same call on the b rows, transposed, no bias
+        dx        = _fold_rows([da_rows; db_rows], [ia; ib])   (= fold(da_rows, ia) + fold(db_rows, ib) in one fixed order)
+        dA[u]     = sum_i G[i, u] a_i^T b_i     db[u] = sum_i G[i, u] b_i      (ghf_relation_scores_bwd_weights)
+    Nothing of size B x U x d or B x d x d, no atomics: reproducible."""
+
+    @staticmethod
+    def forward(ctx, x, ia, ib, A, b):
+        x, A = x.contiguous().float(), A.contiguous().float()
+        b = None if b is None else b.contiguous().float()
+        ctx.save_for_backward(x, ia, ib, A, *(() if b is None else (b,)))
+        return _native.relation_scores(x, ia, ib, A, b, add_x=True)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, ia, ib, A, *rest = ctx.saved_tensors
+        b = rest[0] if rest else None
+        g = g.contiguous().float()
+        n = x.size(0)
+        dx = dA = db = None
+        if ctx.needs_input_grad[0]:
+            da_rows = _native.relation_scores_bwd_rows(x, ib, g, A, None, add_x=True, transpose=True)
+            db_rows = _native.relation_scores_bwd_rows(x, ia, g, A, b, add_x=True)
+            dx = _fold_rows(torch.cat([da_rows, db_rows]), torch.cat([ia, ib]), n)   # one grouping, one pass over [n, d]
+        want_b = b is not None and ctx.needs_input_grad[4]
+        if ctx.needs_input_grad[3] or want_b:
+            dA, db = _native.relation_scores_bwd_weights(x, ia, ib, g, want_bias=want_b)
+            if not ctx.needs_input_grad[3]:
+                dA = None
+        return dx, None, None, dA, db
+
+
 class ScoreRowsFn(torch.autograd.Function):
     """s_i = Q_i . embs[tail_i] (RelationDecoder.score).  dQ_i = g_i embs[tail_i]; d embs[v] = sum_{i: tail_i = v} g_i Q_i,
     grouped by node and summed in a fixed order as ScoreEdgesFn does."""

@@ -641,6 +641,38 @@ int ghf_relation_rows(const float* x, const int64_t* ix, const int64_t* rel, con
                                 (hipStream_t)stream);
 }
 
+int ghf_relation_scores(const float* x, const int64_t* ia, const int64_t* ib, const float* W, const float* bias, int64_t rows_x,
+                        int64_t B, int64_t U, int d, int flags, float* out, void* stream) {
+    GHF_REQUIRE(x && ia && ib && W && out, "relation_scores: null pointer argument");
+    return launch_relation_scores(x, ia, ib, W, bias, rows_x, B, U, d, flags, out, (hipStream_t)stream);
+}
+
+size_t ghf_relation_scores_bwd_rows_workspace_bytes(int64_t B, int64_t U, int d) {
+    return U >= ((int64_t)1 << 23) ? 0 : relation_scores_bwd_rows_workspace_bytes(B, (int)U, d);
+}
+
+int ghf_relation_scores_bwd_rows(const float* x, const int64_t* ia, const float* G, const float* W, const float* bias,
+                                 int64_t rows_x, int64_t B, int64_t U, int d, int flags, void* workspace, size_t workspace_bytes,
+                                 float* out, void* stream) {
+    GHF_REQUIRE(x && ia && G && W && workspace && out, "relation_scores_bwd_rows: null pointer argument");
+    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "relation_scores_bwd_rows: workspace not 256-byte aligned");
+    return launch_relation_scores_bwd_rows(x, ia, G, W, bias, rows_x, B, U, d, flags, workspace, workspace_bytes, out,
+                                           (hipStream_t)stream);
+}
+
+size_t ghf_relation_scores_bwd_weights_workspace_bytes(int64_t B, int64_t U, int d) {
+    return U >= ((int64_t)1 << 23) ? 0 : relation_scores_bwd_weights_workspace_bytes(B, (int)U, d);
+}
+
+int ghf_relation_scores_bwd_weights(const float* x, const int64_t* ia, const int64_t* ib, const float* G, int64_t rows_x, int64_t B,
+                                    int64_t U, int d, int flags, void* workspace, size_t workspace_bytes, float* dW, float* dbias,
+                                    void* stream) {
+    GHF_REQUIRE(x && ia && ib && G && workspace && dW, "relation_scores_bwd_weights: null pointer argument");
+    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "relation_scores_bwd_weights: workspace not 256-byte aligned");
+    return launch_relation_scores_bwd_weights(x, ia, ib, G, rows_x, B, U, d, flags, workspace, workspace_bytes, dW, dbias,
+                                              (hipStream_t)stream);
+}
+
 int ghf_tail_fwd(const float* agg, const float* h, const float* ln_gamma, const float* ln_beta, float ln_eps,
                  int64_t row0, int64_t rows, int d, float* h_out, const float* drop, void* stream) {
     GHF_REQUIRE(agg && h && ln_gamma && ln_beta && h_out, "tail_fwd: null pointer argument");

@@ -189,6 +189,17 @@ size_t relation_rows_workspace_bytes(int64_t B, int R);
 int launch_relation_rows(const float* x, const int64_t* ix, const int64_t* rel, const float* W, const float* bias,
                          const int64_t* perm, const int64_t* goff, int64_t rows_x, int64_t B, int R, int d, int flags,
                          void* ws, size_t ws_bytes, float* out, hipStream_t stream);
+// relation_predict.hip
+size_t relation_scores_bwd_rows_workspace_bytes(int64_t B, int U, int d);
+size_t relation_scores_bwd_weights_workspace_bytes(int64_t B, int U, int d);
+int launch_relation_scores(const float* x, const int64_t* ia, const int64_t* ib, const float* W, const float* bias,
+                           int64_t rows_x, int64_t B, int64_t U, int d, int flags, float* out, hipStream_t stream);
+int launch_relation_scores_bwd_rows(const float* x, const int64_t* ia, const float* G, const float* W, const float* bias,
+                                    int64_t rows_x, int64_t B, int64_t U, int d, int flags, void* ws, size_t ws_bytes, float* out,
+                                    hipStream_t stream);
+int launch_relation_scores_bwd_weights(const float* x, const int64_t* ia, const int64_t* ib, const float* G, int64_t rows_x,
+                                       int64_t B, int64_t U, int d, int flags, void* ws, size_t ws_bytes, float* dW, float* dbias,
+                                       hipStream_t stream);
 int launch_text_encode(const int32_t* ids, const int32_t* lens, int U, int Lmax, const float* E, int V, int C,
                        const float* W, const float* b, int T, float* out, hipStream_t stream);
 int launch_input_proj(const float* x, const float* W_in, const float* b_in, int64_t N, int F, int d,

@@ -13,6 +13,11 @@ relation-blind keeps its behaviour and learns the relation-specific deviation fr
 ``HyperGNN.rank_candidates / topk_candidates / softmax_loss`` take as ``query_rows``.  The rows are built by one kernel
 (``ghf_relation_rows``, csrc/relation.hip) that indexes ``A[r]`` in place: the ``[B, d, d]`` operand of
 ``torch.bmm(embs[h].unsqueeze(1), A[rel])`` does not exist, forward or backward.
+
+Relation prediction, (h, ?, t) — which relation holds between two given nodes: ``score_relations`` gives
+``S[i, u] = (x[h_i] + x[h_i] @ A_u + b_u) . x[t_i]`` for EVERY relation text u in one sweep (``ghf_relation_scores``,
+csrc/relation_predict.hip) that writes only the ``[B, U]`` table; ``rank_relations``, ``topk_relations`` and ``relation_loss``
+are tensor operations over that small table, with the other relations known for a directed pair filtered out.
 """
 
 from __future__ import annotations
@@ -82,6 +87,209 @@ class RelationDecoder(nn.Module):
             from ..autograd import ScoreRowsFn
             return ScoreRowsFn.apply(Q, embs, t)
         return _native.score_pairs_fwd(Q, embs.detach().float(), None, t)
+
+    # -- relation prediction: which relation holds between two given nodes, (head, ?, tail) (csrc/relation_predict.hip) --------
+    def _pair_ids(self, embs, head, tail, rel_embs, direction, what):
+        """The checks every relation-prediction method shares, cheapest first; ``(head, tail)`` int64 on embs' device."""
+        if direction not in DIRECTIONS:
+            raise ValueError(f"direction must be 'tail' or 'head', got {direction!r}")
+        if not isinstance(embs, torch.Tensor) or embs.dim() != 2 or embs.size(1) != self.hidden_dim:
+            raise ValueError(f"embs must be [N, {self.hidden_dim}], got {getattr(embs, 'shape', type(embs))}")
+        if not isinstance(rel_embs, torch.Tensor) or rel_embs.dim() != 2 or rel_embs.size(1) != self.text_dim or rel_embs.size(0) == 0:
+            raise ValueError(f"rel_embs must be [U, {self.text_dim}], got {getattr(rel_embs, 'shape', type(rel_embs))}")
+        h = HyperGNN._rank_ids(head, embs.size(0), embs, "head")
+        t = HyperGNN._rank_ids(tail, embs.size(0), embs, "tail")
+        if h.numel() != t.numel() or h.numel() == 0:
+            raise ValueError(f"{what}: {h.numel()} heads and {t.numel()} tails")
+        return h, t
+
+    @staticmethod
+    def _target_ids(rel, B: int, U: int, embs: torch.Tensor) -> torch.Tensor:
+        r = HyperGNN._rel_ids(rel, B, embs, "rel")
+        if r.numel() and int(r.max()) >= U:
+            raise IndexError(f"rel holds ids outside [0, {U}): the rows of rel_embs")
+        return r
+
+    def _device_only(self, embs, rel_embs, what):
+        for name, t in (("embs", embs), ("rel_embs", rel_embs)):
+            if not t.is_cuda:
+                raise RuntimeError(f"RelationDecoder.{what} computes on an MI355X HIP device only ({name} is on {t.device}); "
+                                   "this package has no CPU or eager-PyTorch fallback")
+
+    def _score_table(self, embs, h, t, rel_embs, direction):
+        heads = self.generator(rel_embs)                     # records WeightGeneratorFn when gradients are wanted
+        A, b = heads[("W_msg", "W_self")[DIRECTIONS[direction]]], heads["bias"]
+        ia, ib = (h, t) if direction == "tail" else (t, h)
+        if torch.is_grad_enabled() and (embs.requires_grad or A.requires_grad or b.requires_grad):
+            from ..autograd import RelationScoresFn
+            return RelationScoresFn.apply(embs, ia, ib, A, b)
+        return _native.relation_scores(embs.detach().float(), ia, ib, A.detach(), b.detach(), add_x=True)
+
+    def score_relations(self, embs: torch.Tensor, head: torch.Tensor, tail: torch.Tensor, rel_embs: torch.Tensor,
+                        direction: str = "tail") -> torch.Tensor:
+        """``S[i, u]`` = the score of the triple ``(head_i, text u, tail_i)`` for EVERY row ``u`` of ``rel_embs [U, text_dim]``
+        (any texts, seen in the graph or not), fp32 ``[B, U]``.  ``direction="tail"``: ``(x[h] + x[h] @ A_u + b_u) . x[t]``, the
+        score ``dec.score`` gives; ``"head"``: the reciprocal matrix with the roles swapped, ``(x[t] + x[t] @ A'_u + b_u) . x[h]``.
+        One sweep (``ghf_relation_scores``): every (64-pair tile, relation) multiplies on the fp32 matrix cores and ends in a
+        dot product; the ``[B, U, d]`` operand of ``einsum("bi,uij->buj", x[h], A)`` does not exist, forward or backward.
+        Recorded for autograd (decoder, text encoder and, through ``embs``, the model); gradients are bit-reproducible."""
+        h, t = self._pair_ids(embs, head, tail, rel_embs, direction, "score_relations")
+        self._device_only(embs, rel_embs, "score_relations")
+        return self._score_table(embs, h, t, rel_embs, direction)
+
+    @staticmethod
+    def _relation_filter_lists(embs: torch.Tensor, head: torch.Tensor, tail: torch.Tensor, rel: Optional[torch.Tensor], known,
+                               num_relations: Optional[int] = None):
+        """Per-pair filter lists (CSR ``ptr [B + 1]``, ``idx``; every list ascending, repeats gone), or ``(None, None)``:
+        pair i's list is every relation id ``r != rel_i`` (every ``r`` when ``rel`` is None) with a known triple
+        ``(head_i, r, tail_i)`` in ``known = (src, dst, rel)``.  Directed: a ``tail -> head`` edge does not count.  Node ids
+        wrap, relation ids do not; ids ``>= num_relations`` are dropped.  Sorted keys and ``searchsorted``, on embs' device
+        (CPU tensors work)."""
+        if known is None:
+            return None, None
+        if len(known) != 3:
+            raise ValueError(f"known must be (src, dst, rel), got {len(known)} members")
+        N = embs.size(0)
+        h = HyperGNN._rank_ids(head, N, embs, "head")
+        t = HyperGNN._rank_ids(tail, N, embs, "tail")
+        B = h.numel()
+        if t.numel() != B:
+            raise ValueError(f"{B} heads and {t.numel()} tails")
+        src = HyperGNN._rank_ids(known[0], N, embs, "known[0]")
+        dst = HyperGNN._rank_ids(known[1], N, embs, "known[1]")
+        if src.numel() != dst.numel():
+            raise ValueError(f"known: {src.numel()} sources and {dst.numel()} destinations")
+        krel = HyperGNN._rel_ids(known[2], src.numel(), embs, "known[2]")
+        qrel = None if rel is None else HyperGNN._rel_ids(rel, B, embs, "rel")
+        if src.numel() == 0 or B == 0:
+            return None, None
+        R = 1 + int(krel.max())
+        if N * N * R >= 1 << 63:
+            raise ValueError(f"known: {N} nodes x {R} relations do not fit the 64-bit (src, dst, rel) keys")
+        key = torch.unique((src * N + dst) * R + krel)            # sorted by (src, dst, rel), repeats gone
+        kp = torch.div(key, R, rounding_mode="floor")
+        qk = h * N + t
+        lo = torch.searchsorted(kp, qk)
+        lens = torch.searchsorted(kp, qk, right=True) - lo
+        nnz = int(lens.sum())
+        if nnz == 0:
+            return None, None
+        start = torch.cumsum(lens, 0) - lens
+        seg = torch.repeat_interleave(torch.arange(B, device=embs.device), lens, output_size=nnz)
+        pos = torch.arange(nnz, device=embs.device) + (lo - start)[seg]
+        r = key[pos] - kp[pos] * R
+        keep = torch.ones_like(r, dtype=torch.bool)
+        if qrel is not None:
+            keep &= r != qrel[seg]
+        if num_relations is not None:
+            keep &= r < num_relations
+        seg, r = seg[keep], r[keep]
+        if r.numel() == 0:
+            return None, None
+        ptr = torch.zeros(B + 1, dtype=torch.int64, device=embs.device)
+        torch.cumsum(torch.bincount(seg, minlength=B), 0, out=ptr[1:])
+        return ptr, r.contiguous()
+
+    @staticmethod
+    def _list_mask(S: torch.Tensor, ptr: Optional[torch.Tensor], idx: Optional[torch.Tensor]) -> torch.Tensor:
+        """bool ``[B, U]``: entry (i, u) is set when u is in pair i's list."""
+        B, U = S.shape
+        mask = torch.zeros(B, U, dtype=torch.bool, device=S.device)
+        if ptr is not None and idx is not None and idx.numel():
+            lens = ptr[1:] - ptr[:-1]
+            seg = torch.repeat_interleave(torch.arange(B, device=S.device), lens.to(S.device), output_size=idx.numel())
+            mask[seg, idx.to(S.device)] = True
+        return mask
+
+    @classmethod
+    def _ranks_from_scores(cls, S: torch.Tensor, rel: torch.Tensor, ptr: Optional[torch.Tensor] = None,
+                           idx: Optional[torch.Tensor] = None):
+        """``(greater, equal)`` int64 ``[B]``: how many relations score above / exactly as ``rel[i]`` in row i of ``S [B, U]``,
+        the target itself and the pair's listed relations left out.  Any device."""
+        ar = torch.arange(S.size(0), device=S.device)
+        out = cls._list_mask(S, ptr, idx)
+        out[ar, rel] = True
+        st = S[ar, rel].unsqueeze(1)
+        return ((S > st) & ~out).sum(1), ((S == st) & ~out).sum(1)
+
+    @classmethod
+    def _topk_from_scores(cls, S: torch.Tensor, k: int, ptr: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None):
+        """``(scores [B, k], ids [B, k] int64)``: the k best relations of every row outside its list, best first, ties to the
+        lower id (a stable descending sort), ``(-inf, -1)`` where fewer than k remain.  Any device."""
+        B, U = S.shape
+        out = cls._list_mask(S, ptr, idx)
+        order = torch.sort(S.masked_fill(out, float("-inf")), dim=1, descending=True, stable=True).indices
+        listed = out.gather(1, order)
+        order = order.gather(1, torch.sort(listed.to(torch.int8), dim=1, stable=True).indices)   # the listed ones last, in place
+        left = (U - out.sum(1)).unsqueeze(1)
+        scores = torch.full((B, k), float("-inf"), dtype=S.dtype, device=S.device)
+        ids = torch.full((B, k), -1, dtype=torch.int64, device=S.device)
+        m = min(k, U)
+        live = torch.arange(m, device=S.device).unsqueeze(0) < left
+        scores[:, :m] = torch.where(live, S.gather(1, order[:, :m]), scores[:, :m])
+        ids[:, :m] = torch.where(live, order[:, :m], ids[:, :m])
+        return scores, ids
+
+    @classmethod
+    def _loss_from_scores(cls, S: torch.Tensor, rel: torch.Tensor, ptr: Optional[torch.Tensor] = None,
+                          idx: Optional[torch.Tensor] = None, scale: float = 1.0) -> torch.Tensor:
+        """``[B]``: ``logsumexp_u(scale S[i, u]) - scale S[i, rel_i]`` over the relations outside pair i's list; the target
+        always stays in the sum.  Differentiable in ``S``; any device."""
+        ar = torch.arange(S.size(0), device=S.device)
+        out = cls._list_mask(S, ptr, idx)
+        out[ar, rel] = False
+        z = (scale * S).masked_fill(out, float("-inf"))
+        return torch.logsumexp(z, dim=1) - z[ar, rel]
+
+    def rank_relations(self, embs: torch.Tensor, head: torch.Tensor, tail: torch.Tensor, rel: torch.Tensor,
+                       rel_embs: torch.Tensor, *, known=None, direction: str = "tail"):
+        """Where the text ``rel[i]`` ranks among ALL rows of ``rel_embs`` as the relation of ``(head_i, ?, tail_i)``:
+        ``(greater, equal)`` int64 ``[B]`` for ``link_prediction_metrics``.  ``known=(src, dst, rel)`` names true triples: every
+        other relation known to hold for the same directed pair is left out (the filtered setting).  No autograd graph."""
+        h, t = self._pair_ids(embs, head, tail, rel_embs, direction, "rank_relations")
+        r = self._target_ids(rel, h.numel(), rel_embs.size(0), embs)
+        if known is not None and len(known) != 3:
+            raise ValueError(f"known must be (src, dst, rel), got {len(known)} members")
+        self._device_only(embs, rel_embs, "rank_relations")
+        with torch.no_grad():
+            S = self._score_table(embs, h, t, rel_embs, direction)
+            ptr, idx = self._relation_filter_lists(embs, h, t, r, known, rel_embs.size(0))
+            return self._ranks_from_scores(S, r, ptr, idx)
+
+    def topk_relations(self, embs: torch.Tensor, head: torch.Tensor, tail: torch.Tensor, k: int, rel_embs: torch.Tensor, *,
+                       known=None, direction: str = "tail"):
+        """``(scores [B, k] fp32, ids [B, k] int64)``: the k best relation texts for every pair, best first, ties to the lower
+        id, ``(-inf, -1)`` padding; ``1 <= k <= 128``.  ``known=(src, dst, rel)``: relations already known for the directed pair
+        are left out, so what remains are the NEW relations the decoder proposes.  No autograd graph."""
+        k = int(k)
+        if not 1 <= k <= 128:
+            raise ValueError(f"topk_relations: k = {k} outside 1..128")
+        h, t = self._pair_ids(embs, head, tail, rel_embs, direction, "topk_relations")
+        if known is not None and len(known) != 3:
+            raise ValueError(f"known must be (src, dst, rel), got {len(known)} members")
+        self._device_only(embs, rel_embs, "topk_relations")
+        with torch.no_grad():
+            S = self._score_table(embs, h, t, rel_embs, direction)
+            ptr, idx = self._relation_filter_lists(embs, h, t, None, known, rel_embs.size(0))
+            return self._topk_from_scores(S, k, ptr, idx)
+
+    def relation_loss(self, embs: torch.Tensor, head: torch.Tensor, tail: torch.Tensor, rel: torch.Tensor,
+                      rel_embs: torch.Tensor, scale: float = 1.0, *, known=None, direction: str = "tail") -> torch.Tensor:
+        """``[B]``: ``lse_u(scale S[i, u]) - scale S[i, rel_i]``, the softmax cross-entropy of the true relation against every
+        relation text; the other relations known for the pair (``known``) are left out of the sum, the target never is.
+        Recorded for autograd: one ``backward()`` reaches the decoder, the text encoder and the model."""
+        scale = float(scale)
+        if not (0.0 < scale < float("inf")):
+            raise ValueError(f"relation_loss: scale must be finite and positive, got {scale}")
+        h, t = self._pair_ids(embs, head, tail, rel_embs, direction, "relation_loss")
+        r = self._target_ids(rel, h.numel(), rel_embs.size(0), embs)
+        if known is not None and len(known) != 3:
+            raise ValueError(f"known must be (src, dst, rel), got {len(known)} members")
+        self._device_only(embs, rel_embs, "relation_loss")
+        S = self._score_table(embs, h, t, rel_embs, direction)
+        with torch.no_grad():
+            ptr, idx = self._relation_filter_lists(embs, h, t, r, known, rel_embs.size(0))
+        return self._loss_from_scores(S, r, ptr, idx, scale)
 
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)

@@ -544,6 +544,45 @@ int ghf_relation_rows(const float* x, const int64_t* ix /* [B] or NULL */, const
                       int64_t rows_x, int64_t B, int R, int d, int flags, void* workspace, size_t workspace_bytes,
                       float* out /* [B,d] */, void* stream);
 
+/* ---- relation prediction: every relation's score for a pair (csrc/relation_predict.hip) -----------------
+ * Which relation holds between two given nodes, (head, ?, tail).  With a = x[ia[i]], b = x[ib[i]]:
+ *   out[i][u] = sum_l q_l b_l,   q = [GHF_REL_ADD_X] a  +  a @ op(W[u])  +  [bias != NULL] bias[u],     i < B, u < U
+ * x [rows_x, d]; ia, ib int64 [B]; W [U, d, d] natural; op = identity or the transpose (GHF_REL_TRANSPOSE); bias [U, d] or
+ * NULL; out [B, U] fp32, addressed with 64 bits.  1 <= d <= 256 (GHF_EUNSUPPORTED beyond), 0 < B < 2^31, 0 < U < 2^23.
+ * One sweep: every (64-row query tile, relation) multiplies on v_mfma_f32_16x16x4_f32 and ends in a dot product in the
+ * epilogue; only the [B, U] table is written.  The [B, U, d] operand of einsum("bi,uij->buj", x[ia], W) does not exist.
+ * Numerics: q_l is bit for bit the element ghf_relation_rows gives for (ix = ia[i], rel = u, the same flags): the chain
+ * s = fmaf(a[k], op(W[u])[k][l], s), k = 0 .. d-1 from 0, then (a_l + s) + bias[u][l].  The sum over l has one fixed order:
+ * with DC = d rounded up to 64, p_c = the chain fmaf(q_l, b_l, p_c) over l = c, c + 16, .. < DC ascending from 0 (q = b = 0
+ * past d), c < 16; then t_c = p_c + p_(c^1); v_c = t_c + t_(c^2); w_c = v_c + v_(7-c) (c < 8; likewise in 8..15);
+ * out = w_0 + w_15.  An entry depends on its own two rows, W[u] and bias[u] only, bit for bit: not on the batch, the tile or
+ * the other relations of the call.  An ia[i] or ib[i] out of range does not fault (ids are tested before any address is
+ * formed): that row of out is NaN and no other row is touched.  Nothing allocates, reads back or synchronises.
+ *
+ * Backward, given G [B, U] (= d loss / d out).  Fixed summation orders, no floating-point atomics: bit-reproducible.
+ *   ghf_relation_scores_bwd_rows:     out[i][:] = sum_u G[i][u] q(i, u)[:], u ascending, [B, d] — the sweep with "add G q to
+ *     the row" as its epilogue.  As called it is d loss / d b rows; with ia := ib, the flags' transpose flipped and bias = NULL
+ *     it is d loss / d a rows = sum_u G[i][u] (b + b @ op(W[u])^T).  When the tiles alone would leave the machine idle the
+ *     relations of a tile are split over workgroups and the partials ([splits, B, d], in the workspace; the split count is
+ *     bounded so that they never reach B x U x d) are added in split order.  A bad ia[i]: NaN row.
+ *   ghf_relation_scores_bwd_weights:  dW[u] = sum_i G[i][u] a_i^T b_i  [U, d, d],  dbias[u] = sum_i G[i][u] b_i  [U, d] (or
+ *     NULL), i ascending: a GEMM whose contraction runs over the queries, the G-scaled a rows against the b rows.  Slabs of
+ *     queries (partials in the workspace, added in slab order).  A query with an id out of range adds nothing.  flags: none
+ *     defined, must be 0.  (For op = transpose pass ia and ib swapped and read dW as the gradient of W; dbias then needs
+ *     its own call: the decoder never transposes.)
+ * workspace: the matching _workspace_bytes query (works without a GPU; 0 = bad sizes), 256-byte aligned. */
+int ghf_relation_scores(const float* x, const int64_t* ia /* [B] */, const int64_t* ib /* [B] */, const float* W /* [U,d,d] */,
+                        const float* bias /* [U,d] or NULL */, int64_t rows_x, int64_t B, int64_t U, int d, int flags,
+                        float* out /* [B,U] */, void* stream);
+size_t ghf_relation_scores_bwd_rows_workspace_bytes(int64_t B, int64_t U, int d);
+int ghf_relation_scores_bwd_rows(const float* x, const int64_t* ia, const float* G /* [B,U] */, const float* W, const float* bias,
+                                 int64_t rows_x, int64_t B, int64_t U, int d, int flags, void* workspace, size_t workspace_bytes,
+                                 float* out /* [B,d] */, void* stream);
+size_t ghf_relation_scores_bwd_weights_workspace_bytes(int64_t B, int64_t U, int d);
+int ghf_relation_scores_bwd_weights(const float* x, const int64_t* ia, const int64_t* ib, const float* G /* [B,U] */, int64_t rows_x,
+                                    int64_t B, int64_t U, int d, int flags, void* workspace, size_t workspace_bytes,
+                                    float* dW /* [U,d,d] */, float* dbias /* [U,d] or NULL */, void* stream);
+
 /* ---- the sparse row exchange of the multi-GPU forward (no counterpart in the single-process reference) ----
  * packed[i] = rows[idx[i]] (row_bytes, a multiple of 16) followed by extra[idx[i]] (extra_bytes, a multiple of 4; extra may be
  * NULL with extra_bytes = 0), i < n: the listed rows of a [nrows, row_bytes] table (and of a second table indexed alike — the
