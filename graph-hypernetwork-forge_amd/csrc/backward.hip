@@ -1118,6 +1118,14 @@ __global__ __launch_bounds__(256) void add3_kernel(const float* __restrict__ a, 
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
         out[i] = c ? (a[i] + b[i]) + c[i] : a[i] + b[i];
 }
+__global__ __launch_bounds__(256) void ordered_sum_kernel(const float* __restrict__ part, int64_t nparts, int64_t n,
+                                                          float* __restrict__ out) {
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
+        float s = part[j];
+        for (int64_t p = 1; p < nparts; ++p) s += part[p * n + j];
+        out[j] = s;
+    }
+}
 __global__ __launch_bounds__(256) void rowscale_kernel(const float* __restrict__ X, const float* __restrict__ g, int64_t n, int d,
                                                        float* __restrict__ out) {
     const int64_t total = n * d;
@@ -1133,6 +1141,12 @@ int launch_scale_exp(const float* X, int64_t n, const float* log_scale, float* o
 }
 int launch_add3(const float* a, const float* b, const float* c, int64_t n, float* out, hipStream_t stream) {
     add3_kernel<<<ew_grid(n), 256, 0, stream>>>(a, b, c, n, out);
+    GHF_LAUNCH_CHECK();
+    return GHF_OK;
+}
+int launch_ordered_sum(const float* part, int64_t nparts, int64_t n, float* out, hipStream_t stream) {
+    const int64_t grid = cdiv(n, 256);
+    ordered_sum_kernel<<<(unsigned)(grid < MAX_GRID ? grid : MAX_GRID), 256, 0, stream>>>(part, nparts, n, out);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }

@@ -257,6 +257,10 @@ int launch_group_outer(const float* A, const int64_t* ia, int da, const float* B
                        const int64_t* gstart, const int64_t* gend, int ngroups, float* C, int accumulate, hipStream_t stream);
 int launch_scale_exp(const float* X, int64_t n, const float* log_scale, float* out, hipStream_t stream);
 int launch_add3(const float* a, const float* b, const float* c, int64_t n, float* out, hipStream_t stream);
+constexpr int64_t MAX_GRID = 1 << 20;                 // workgroups per launch of the kernels that stride over their work items
+// out[j] = part[0][j] + part[1][j] + .. + part[nparts - 1][j] in that order, j < n (part: [nparts][n]): the partials of split
+// relations (relation_predict.hip) and of candidate slabs (softmax.hip)
+int launch_ordered_sum(const float* part, int64_t nparts, int64_t n, float* out, hipStream_t stream);
 int launch_segment_axpy(const float* w, const int64_t* iw, const float* X, const int64_t* ix, const int64_t* off, int64_t nseg,
                         int64_t nx, int d, float* out, hipStream_t stream);
 int launch_rowscale(const float* X, const float* g, int64_t n, int d, float* out, hipStream_t stream);

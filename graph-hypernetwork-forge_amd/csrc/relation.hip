@@ -5,35 +5,17 @@
 //   The caller groups the queries by relation (ghf_group_edges: perm, goff).  rr_tiles_kernel cuts every relation's range
 //   into tiles of <= 64 grouped rows on the device: a table of at most ceil(B/64) + R (relation, first position) pairs in
 //   the workspace; the launch has that many workgroups and the ones past the table's end return at once (no host read).
-//   workgroup = 256 threads = 4 waves, one (relation, tile).  The tile's x rows are gathered through perm -> ix into LDS
-//   once; W[r] streams through two LDS buffers of 16 rows of k (all d columns), fetched into registers one slice ahead of
-//   the slice being multiplied: one barrier per slice.  Wave w owns rows 16 w .. 16 w + 15 of the tile and all d columns:
-//   DC / 16 accumulators of v_mfma_f32_16x16x4_f32 (A: lane l = x[row l & 15][k = l >> 4]; B: W[k = l >> 4][col l & 15];
-//   D: row 4 (l >> 4) + reg, col l & 15).  The transposed form reads the same slice of k out of W's COLUMNS and stores it
-//   transposed, so the multiply loop is the same.
-//   The epilogue adds residual and bias into the wave's own rows of the LDS tile (no other wave reads them), and the
-//   workgroup writes whole rows back through perm with 16-byte stores.
+//   relation_rows_kernel: one workgroup per (relation, tile).  The tile's x rows are gathered through perm -> ix, W[r] is
+//   streamed and multiplied as relation_sweep.h describes (tile, LDS layout, numerics).  The epilogue adds residual and bias
+//   into the wave's own rows of the LDS tile (no other wave reads them), and the workgroup writes whole rows back through
+//   perm.
 //
-// LDS: the x tile has a row stride of DC + 4 floats, a weight slice one of DC + 16 (DC = the padded width, 64 / 128 / 192 / 256):
-// the B operand's reads (ds_read_b32: 32 banks, half a wave per cycle: k = l >> 4 in {0, 1} x 16 columns) touch 32 distinct
-// banks; the A operand's four reads per slice are 2-way conflicted (rows r and r + 8), against 4 DC / 16 of B's.  The
-// transposed stash writes scalars 4-way conflicted: 4 DC / 64 writes per thread and slice next to DC / 4 matrix
-// instructions of 32 cycles each.
-//
-// Numerics: an output element is bit for bit the chain s = fmaf(x[k], W[k][l], s), k = 0 .. d-1 from s = 0 (the padded k
-// add fma(0, 0, s) = s), then (x[l] + s) + bias[l].  It depends on the row's own x, W[r] and bias[r] only: not on the tile
-// it shares, its position in it or the other queries of the call.
-#include "common.h"
-#include "rank_sweep.h"
+// Every id (a tile's relation and position, perm, rel, ix) is tested against its range before an address is formed from it.
+#include "relation_sweep.h"
 
 namespace ghf {
 
-constexpr int RR_ROWS = 64;                  // grouped query rows per workgroup
-constexpr int RR_BK = 16;                    // rows of k per weight slice
-constexpr int RR_NT = 256;
-constexpr int RR_MAX_D = 256;
-
-static inline int64_t rr_max_tiles(int64_t B, int R) { return cdiv(B, RR_ROWS) + R; }
+static inline int64_t rr_max_tiles(int64_t B, int R) { return cdiv(B, REL_ROWS) + R; }
 
 size_t relation_rows_workspace_bytes(int64_t B, int R) {
     if (B <= 0 || B >= (int64_t)1 << 31 || R <= 0 || R >= 1 << 23) return 0;
@@ -57,7 +39,7 @@ __global__ __launch_bounds__(256) void rr_tiles_kernel(const int64_t* __restrict
         if (r < R) {
             lo = rr_clamp(goff[r], 0, B);
             const int64_t hi = rr_clamp(goff[r + 1], lo, B);
-            n = (hi - lo + RR_ROWS - 1) / RR_ROWS;
+            n = (hi - lo + REL_ROWS - 1) / REL_ROWS;
         }
         sc[tid] = n;
         __syncthreads();
@@ -69,7 +51,7 @@ __global__ __launch_bounds__(256) void rr_tiles_kernel(const int64_t* __restrict
         }
         const int64_t first = run + sc[tid] - n;
         for (int64_t j = 0; j < n; ++j)
-            if (first + j < max_tiles) tab[first + j] = make_int2(r, (int)(lo + RR_ROWS * j));
+            if (first + j < max_tiles) tab[first + j] = make_int2(r, (int)(lo + REL_ROWS * j));
         __syncthreads();
         if (tid == 255) run += sc[255];
         __syncthreads();
@@ -85,20 +67,15 @@ struct RelArgs {
     float* out;
 };
 
-static inline size_t rr_lds_bytes(int NCT) {
-    const int DC = NCT * 16;
-    return ((size_t)RR_ROWS * (DC + 4) + 2 * (size_t)RR_BK * (DC + 16)) * 4 + RR_ROWS * (8 + 4 + 4);
-}
-
 template <int NCT, bool TR>
-__global__ __launch_bounds__(RR_NT) void relation_rows_kernel(const RelArgs a) {
+__global__ __launch_bounds__(REL_NT) void relation_rows_kernel(const RelArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int DC = NCT * 16, LDX = DC + 4, LDW = DC + 16, F4 = DC / 4, NL = RR_BK * F4 / RR_NT;
+    using G = RelGeom<NCT>;
     float* Xs = lds;
-    float* Ws = Xs + RR_ROWS * LDX;
-    int64_t* rowx = (int64_t*)(Ws + 2 * RR_BK * LDW);       // the row of x, -1: none (a row of zeros)
-    int* rowi = (int*)(rowx + RR_ROWS);                     // the query (row of out), -1: none
-    int* rowbad = rowi + RR_ROWS;                           // an id out of range: the row of out is NaN
+    float* Ws = Xs + G::XS;
+    int64_t* rowx = (int64_t*)(Ws + G::WS);                  // the row of x, -1: none (a row of zeros)
+    int* rowi = (int*)(rowx + REL_ROWS);                     // the query (row of out), -1: none
+    int* rowbad = rowi + REL_ROWS;                           // an id out of range: the row of out is NaN
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int d = a.d;
 
@@ -106,10 +83,10 @@ __global__ __launch_bounds__(RR_NT) void relation_rows_kernel(const RelArgs a) {
     const int r = te.x;
     if (r < 0 || r >= a.R) return;                          // past the table's end (the whole workgroup)
     const int64_t p0 = rr_clamp(te.y, 0, a.B);
-    const int64_t p1 = rr_clamp(a.goff[r + 1], p0, p0 + RR_ROWS < a.B ? p0 + RR_ROWS : a.B);
+    const int64_t p1 = rr_clamp(a.goff[r + 1], p0, p0 + REL_ROWS < a.B ? p0 + REL_ROWS : a.B);
     const int nrows = (int)(p1 - p0);
 
-    if (tid < RR_ROWS) {
+    if (tid < REL_ROWS) {
         int di = -1, bad = 0;
         int64_t xr = -1;
         if (tid < nrows) {
@@ -128,66 +105,23 @@ __global__ __launch_bounds__(RR_NT) void relation_rows_kernel(const RelArgs a) {
     __syncthreads();
 
     const bool vx = rows_vec(a.x, d), vw = rows_vec(a.W, d), vo = rows_vec(a.out, d);
-    for (int idx = tid; idx < RR_ROWS * F4; idx += RR_NT) {
-        const int row = idx / F4, c4 = idx - row * F4;
-        const int64_t xr = rowx[row];
-        *(f32x4*)(Xs + row * LDX + c4 * 4) = load_k4(xr >= 0 ? a.x + (size_t)xr * d : nullptr, c4 * 4, d, vx);
-    }
+    rel_gather<NCT>(Xs, rowx, a.x, d, vx, tid);
 
     const float* Wr = a.W + (size_t)r * d * d;
-    f32x4 pre[NL];
-    // slice s holds k = 16 s .. 16 s + 15 of op(W[r]) as [k][column], zeros past d either way
-    auto fetch = [&](int s) {
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const int idx = tid + RR_NT * i;
-            if (TR) {
-                const int l = idx >> 2, c4 = idx & 3;
-                pre[i] = load_k4(l < d ? Wr + (size_t)l * d : nullptr, s * RR_BK + c4 * 4, d, vw);
-            } else {
-                const int kk = idx / F4, c4 = idx - kk * F4, k = s * RR_BK + kk;
-                pre[i] = load_k4(k < d ? Wr + (size_t)k * d : nullptr, c4 * 4, d, vw);
-            }
-        }
-    };
-    auto stash = [&](int buf) {
-        float* w = Ws + buf * RR_BK * LDW;
-#pragma unroll
-        for (int i = 0; i < NL; ++i) {
-            const int idx = tid + RR_NT * i;
-            if (TR) {
-                const int l = idx >> 2, c4 = idx & 3;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) w[(c4 * 4 + e) * LDW + l] = pre[i][e];
-            } else {
-                const int kk = idx / F4, c4 = idx - kk * F4;
-                *(f32x4*)(w + kk * LDW + c4 * 4) = pre[i];
-            }
-        }
-    };
-
-    f32x4 acc[NCT];
+    f32x4 pre[G::NL], acc[NCT];
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    const int nsl = (d + RR_BK - 1) / RR_BK;
-    fetch(0);
-    stash(0);
+    const int nsl = (d + REL_BK - 1) / REL_BK;
+    rel_fetch<NCT, TR>(pre, Wr, 0, d, vw, tid);
+    rel_stash<NCT, TR>(pre, Ws, 0, tid);
     __syncthreads();
     int buf = 0;
     for (int s = 0; s < nsl; ++s) {
         const bool more = s + 1 < nsl;
-        if (more) fetch(s + 1);
-        const float* xa = Xs + (wave * 16 + (lane & 15)) * LDX + s * RR_BK + (lane >> 4);
-        const float* wb = Ws + buf * RR_BK * LDW + (lane >> 4) * LDW + (lane & 15);
-#pragma unroll
-        for (int kq = 0; kq < RR_BK / 4; ++kq) {
-            const float av = xa[4 * kq];
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct)      // every tile, also the ones past d (zeros): a test here costs the accumulators their registers
-                acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, wb[4 * kq * LDW + ct * 16], acc[ct], 0, 0, 0);
-        }
-        if (more) stash(buf ^ 1);
+        if (more) rel_fetch<NCT, TR>(pre, Wr, s + 1, d, vw, tid);
+        rel_multiply<NCT>(acc, Xs, Ws, buf, s, lane, wave);
+        if (more) rel_stash<NCT, TR>(pre, Ws, buf ^ 1, tid);
         __syncthreads();
         buf ^= 1;
     }
@@ -196,43 +130,24 @@ __global__ __launch_bounds__(RR_NT) void relation_rows_kernel(const RelArgs a) {
     const float* br = a.bias ? a.bias + (size_t)r * d : nullptr;
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
-        const int col = ct * 16 + (lane & 15);
-        const float bv = (br && col < d) ? br[col] : 0.f;
+        const int col = rel_dcol(ct, lane);
+        const float bv = rel_bias(br, col, d);
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-            float* px = Xs + (wave * 16 + 4 * (lane >> 4) + reg) * LDX + col;
-            float v = acc[ct][reg];
-            if (a.add_x) v = *px + v;
-            if (br) v += bv;
-            *px = v;
+            float* px = Xs + rel_drow(wave, lane, reg) * G::LDX + col;
+            *px = rel_value(acc[ct][reg], px, a.add_x, br, bv);
         }
     }
     __syncthreads();
 
-    const float nan = __int_as_float(0x7FC00000);
-    const int nf4 = (d + 3) >> 2;
-    for (int idx = tid; idx < nrows * nf4; idx += RR_NT) {
-        const int row = idx / nf4, c4 = idx - row * nf4;
-        const int di = rowi[row];
-        if (di < 0) continue;
-        f32x4 v = *(const f32x4*)(Xs + row * LDX + c4 * 4);
-        if (rowbad[row]) v = f32x4{nan, nan, nan, nan};
-        float* o = a.out + (size_t)di * d + c4 * 4;
-        if (vo) {
-            *(f32x4*)o = v;
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (c4 * 4 + e < d) o[e] = v[e];
-        }
-    }
+    rel_store_rows<NCT>(Xs, rowbad, nrows, d, a.out, vo, tid, [&](int row) { return rowi[row]; });
 }
 
 template <int NCT, bool TR>
 static int launch_rr(const RelArgs& a, unsigned grid, hipStream_t stream) {
-    const size_t lds = rr_lds_bytes(NCT);
+    const size_t lds = (size_t)(RelGeom<NCT>::XS + RelGeom<NCT>::WS) * 4 + REL_ROWS * (8 + 4 + 4);     // + rowx, rowi, rowbad
     GHF_SET_MAX_LDS((relation_rows_kernel<NCT, TR>), lds);
-    relation_rows_kernel<NCT, TR><<<grid, RR_NT, lds, stream>>>(a);
+    relation_rows_kernel<NCT, TR><<<grid, REL_NT, lds, stream>>>(a);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }
@@ -240,9 +155,7 @@ static int launch_rr(const RelArgs& a, unsigned grid, hipStream_t stream) {
 int launch_relation_rows(const float* x, const int64_t* ix, const int64_t* rel, const float* W, const float* bias,
                          const int64_t* perm, const int64_t* goff, int64_t rows_x, int64_t B, int R, int d, int flags,
                          void* ws, size_t ws_bytes, float* out, hipStream_t stream) {
-    GHF_REQUIRE(d > 0 && rows_x > 0 && B > 0 && R > 0, "relation_rows: bad shape");
-    if (d > RR_MAX_D) return set_err(GHF_EUNSUPPORTED, "relation_rows: d = %d exceeds %d", d, RR_MAX_D);
-    GHF_REQUIRE((flags & ~(GHF_REL_ADD_X | GHF_REL_TRANSPOSE)) == 0, "relation_rows: unknown flags %d", flags);
+    if (int rc = rel_check("relation_rows", rows_x, B, R, d, flags, GHF_REL_ADD_X | GHF_REL_TRANSPOSE)) return rc;
     const size_t need = relation_rows_workspace_bytes(B, R);
     GHF_REQUIRE(need > 0, "relation_rows: B or R out of range");
     GHF_REQUIRE(ix || B <= rows_x, "relation_rows: B exceeds the rows of x");
@@ -254,12 +167,9 @@ int launch_relation_rows(const float* x, const int64_t* ix, const int64_t* rel, 
     RelArgs a = {};
     a.x = x; a.ix = ix; a.rel = rel; a.W = W; a.bias = bias; a.perm = perm; a.goff = goff; a.tab = tab;
     a.rows_x = rows_x; a.B = B; a.R = R; a.d = d; a.add_x = (flags & GHF_REL_ADD_X) ? 1 : 0; a.out = out;
-    const unsigned grid = (unsigned)max_tiles;
-    const bool tr = (flags & GHF_REL_TRANSPOSE) != 0;
-    if (d <= 64) return tr ? launch_rr<4, true>(a, grid, stream) : launch_rr<4, false>(a, grid, stream);
-    if (d <= 128) return tr ? launch_rr<8, true>(a, grid, stream) : launch_rr<8, false>(a, grid, stream);
-    if (d <= 192) return tr ? launch_rr<12, true>(a, grid, stream) : launch_rr<12, false>(a, grid, stream);
-    return tr ? launch_rr<16, true>(a, grid, stream) : launch_rr<16, false>(a, grid, stream);
+    return rel_dispatch(d, (flags & GHF_REL_TRANSPOSE) != 0, [&](auto nct, auto tr) {
+        return launch_rr<decltype(nct)::value, decltype(tr)::value>(a, (unsigned)max_tiles, stream);
+    });
 }
 
 }  // namespace ghf

@@ -17,7 +17,7 @@
 // Backward: softmax_bwd_kernel recomputes score tiles from the saved lse, as an attention backward does:
 //   G_ij = grad[i] scale (p_ij - [j = target[i]]),   p_ij = exp(scale s(i,j) - lse[i]) on J_i, 0 outside
 //   dq[i] = sum_j G_ij c[j]       a workgroup owns (query tile, candidate slab): candidates stream, one partial per slab,
-//                                  the partials summed in slab order (dq_reduce_kernel)
+//                                  the partials summed in slab order (launch_ordered_sum)
 //   dc[j] = sum_i G_ij q[iq[i]]   a workgroup owns a candidate tile, streams ALL query tiles in ascending order and
 //                                  writes its rows once
 // One kernel serves both: 256 threads, an owner tile (128 rows; 64 for d > 128) resident in LDS, streamed tiles of 64
@@ -419,14 +419,6 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
     }
 }
 
-__global__ __launch_bounds__(256) void dq_reduce_kernel(const float* __restrict__ part, int64_t n, int64_t slabs, float* __restrict__ dq) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float s = part[i];
-    for (int64_t sl = 1; sl < slabs; ++sl) s += part[(size_t)sl * n + i];
-    dq[i] = s;
-}
-
 template <int OT, int DMAX>
 static int launch_bwd_tiles(const SmBwdArgs& a, hipStream_t stream) {
     const size_t lds = sb_lds_bytes(a.d, OT);
@@ -458,10 +450,7 @@ int launch_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, 
     a.dq_part = (float*)ws; a.dc = dc;
     const int rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128>(a, stream) : launch_bwd_tiles<64, 256>(a, stream);
     if (rc != GHF_OK) return rc;
-    const int64_t n = B * (int64_t)d;
-    dq_reduce_kernel<<<(unsigned)cdiv(n, 256), 256, 0, stream>>>(a.dq_part, n, g.slabs, dq);
-    GHF_LAUNCH_CHECK();
-    return GHF_OK;
+    return launch_ordered_sum(a.dq_part, g.slabs, B * (int64_t)d, dq, stream);
 }
 
 }  // namespace ghf

@@ -53,26 +53,14 @@ class RelationDecoder(nn.Module):
         int ids ``[B]`` into ``rel_embs [U, text_dim]`` (``model.text_encoder(rel_texts, device)``: any texts, seen in the
         graph or not).  fp32 ``[B, d]``.  Recorded for autograd when grad mode is on and anything upstream requires grad; in
         training mode with ``dropout > 0`` the generator draws its masks."""
-        if direction not in DIRECTIONS:
-            raise ValueError(f"direction must be 'tail' or 'head', got {direction!r}")
-        for name, t in (("embs", embs), ("rel_embs", rel_embs)):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise RuntimeError(f"RelationDecoder computes on an MI355X HIP device only ({name} is on "
-                                   f"{getattr(t, 'device', type(t))}); this package has no CPU or eager-PyTorch fallback")
-        if embs.dim() != 2 or embs.size(1) != self.hidden_dim:
-            raise ValueError(f"embs must be [N, {self.hidden_dim}], got {tuple(embs.shape)}")
-        if rel_embs.dim() != 2 or rel_embs.size(1) != self.text_dim or rel_embs.size(0) == 0:
-            raise ValueError(f"rel_embs must be [U, {self.text_dim}], got {tuple(rel_embs.shape)}")
+        self._check_inputs(embs, rel_embs, direction)
         ix = HyperGNN._rank_ids(nodes, embs.size(0), embs, "nodes")
         r = HyperGNN._rank_ids(rel, rel_embs.size(0), embs, "rel")
         if ix.numel() != r.numel() or ix.numel() == 0:
             raise ValueError(f"{ix.numel()} nodes and {r.numel()} relation ids")
-        heads = self.generator(rel_embs)                     # records WeightGeneratorFn when gradients are wanted
-        A, b = heads[("W_msg", "W_self")[DIRECTIONS[direction]]], heads["bias"]
-        if torch.is_grad_enabled() and (embs.requires_grad or A.requires_grad or b.requires_grad):
-            from ..autograd import RelationRowsFn
-            return RelationRowsFn.apply(embs, ix, r, A, b)
-        return _native.relation_rows(embs.detach().float(), r, A.detach(), b.detach(), ix=ix, add_x=True)
+        self._device_only(embs, rel_embs, "forward")
+        return self._generated(embs, rel_embs, direction, "RelationRowsFn", (ix, r),
+                               lambda x, A, b: _native.relation_rows(x, r, A, b, ix=ix, add_x=True))
 
     def score(self, embs: torch.Tensor, head: torch.Tensor, rel: torch.Tensor, tail: torch.Tensor,
               rel_embs: torch.Tensor) -> torch.Tensor:
@@ -88,42 +76,60 @@ class RelationDecoder(nn.Module):
             return ScoreRowsFn.apply(Q, embs, t)
         return _native.score_pairs_fwd(Q, embs.detach().float(), None, t)
 
-    # -- relation prediction: which relation holds between two given nodes, (head, ?, tail) (csrc/relation_predict.hip) --------
-    def _pair_ids(self, embs, head, tail, rel_embs, direction, what):
-        """The checks every relation-prediction method shares, cheapest first; ``(head, tail)`` int64 on embs' device."""
+    # -- the checks and the generated (A, b) that every method shares -----------------------------------------------------------
+    def _check_inputs(self, embs, rel_embs, direction):
+        """What every method tests first, cheapest first: the direction and the two shapes."""
         if direction not in DIRECTIONS:
             raise ValueError(f"direction must be 'tail' or 'head', got {direction!r}")
         if not isinstance(embs, torch.Tensor) or embs.dim() != 2 or embs.size(1) != self.hidden_dim:
             raise ValueError(f"embs must be [N, {self.hidden_dim}], got {getattr(embs, 'shape', type(embs))}")
         if not isinstance(rel_embs, torch.Tensor) or rel_embs.dim() != 2 or rel_embs.size(1) != self.text_dim or rel_embs.size(0) == 0:
             raise ValueError(f"rel_embs must be [U, {self.text_dim}], got {getattr(rel_embs, 'shape', type(rel_embs))}")
-        h = HyperGNN._rank_ids(head, embs.size(0), embs, "head")
-        t = HyperGNN._rank_ids(tail, embs.size(0), embs, "tail")
-        if h.numel() != t.numel() or h.numel() == 0:
-            raise ValueError(f"{what}: {h.numel()} heads and {t.numel()} tails")
-        return h, t
 
     @staticmethod
-    def _target_ids(rel, B: int, U: int, embs: torch.Tensor) -> torch.Tensor:
-        r = HyperGNN._rel_ids(rel, B, embs, "rel")
-        if r.numel() and int(r.max()) >= U:
-            raise IndexError(f"rel holds ids outside [0, {U}): the rows of rel_embs")
-        return r
-
-    def _device_only(self, embs, rel_embs, what):
+    def _device_only(embs, rel_embs, what):
         for name, t in (("embs", embs), ("rel_embs", rel_embs)):
             if not t.is_cuda:
                 raise RuntimeError(f"RelationDecoder.{what} computes on an MI355X HIP device only ({name} is on {t.device}); "
                                    "this package has no CPU or eager-PyTorch fallback")
 
-    def _score_table(self, embs, h, t, rel_embs, direction):
+    @staticmethod
+    def _check_known(known):
+        if known is not None and len(known) != 3:
+            raise ValueError(f"known must be (src, dst, rel), got {len(known)} members")
+
+    def _generated(self, embs, rel_embs, direction, recorded, ids, raw):
+        """The direction's ``(A, b)`` from the generator, then the autograd function named ``recorded`` when gradients are
+        wanted and the ``raw`` call otherwise."""
         heads = self.generator(rel_embs)                     # records WeightGeneratorFn when gradients are wanted
         A, b = heads[("W_msg", "W_self")[DIRECTIONS[direction]]], heads["bias"]
-        ia, ib = (h, t) if direction == "tail" else (t, h)
         if torch.is_grad_enabled() and (embs.requires_grad or A.requires_grad or b.requires_grad):
-            from ..autograd import RelationScoresFn
-            return RelationScoresFn.apply(embs, ia, ib, A, b)
-        return _native.relation_scores(embs.detach().float(), ia, ib, A.detach(), b.detach(), add_x=True)
+            from .. import autograd
+            return getattr(autograd, recorded).apply(embs, *ids, A, b)
+        return raw(embs.detach().float(), A.detach(), b.detach())
+
+    # -- relation prediction: which relation holds between two given nodes, (head, ?, tail) (csrc/relation_predict.hip) --------
+    def _pair_ids(self, embs, head, tail, rel_embs, direction, what, *rel, known=None):
+        """The checks every relation-prediction method shares, the device last; ``(head, tail, rel)`` int64 on embs' device
+        (``rel``: the target texts of the methods that take them, else None)."""
+        self._check_inputs(embs, rel_embs, direction)
+        h = HyperGNN._rank_ids(head, embs.size(0), embs, "head")
+        t = HyperGNN._rank_ids(tail, embs.size(0), embs, "tail")
+        if h.numel() != t.numel() or h.numel() == 0:
+            raise ValueError(f"{what}: {h.numel()} heads and {t.numel()} tails")
+        r = None
+        if rel:
+            r, U = HyperGNN._rel_ids(rel[0], h.numel(), embs, "rel"), rel_embs.size(0)
+            if r.numel() and int(r.max()) >= U:
+                raise IndexError(f"rel holds ids outside [0, {U}): the rows of rel_embs")
+        self._check_known(known)
+        self._device_only(embs, rel_embs, what)
+        return h, t, r
+
+    def _score_table(self, embs, h, t, rel_embs, direction):
+        ia, ib = (h, t) if direction == "tail" else (t, h)
+        return self._generated(embs, rel_embs, direction, "RelationScoresFn", (ia, ib),
+                               lambda x, A, b: _native.relation_scores(x, ia, ib, A, b, add_x=True))
 
     def score_relations(self, embs: torch.Tensor, head: torch.Tensor, tail: torch.Tensor, rel_embs: torch.Tensor,
                         direction: str = "tail") -> torch.Tensor:
@@ -133,8 +139,7 @@ class RelationDecoder(nn.Module):
         One sweep (``ghf_relation_scores``): every (64-pair tile, relation) multiplies on the fp32 matrix cores and ends in a
         dot product; the ``[B, U, d]`` operand of ``einsum("bi,uij->buj", x[h], A)`` does not exist, forward or backward.
         Recorded for autograd (decoder, text encoder and, through ``embs``, the model); gradients are bit-reproducible."""
-        h, t = self._pair_ids(embs, head, tail, rel_embs, direction, "score_relations")
-        self._device_only(embs, rel_embs, "score_relations")
+        h, t, _ = self._pair_ids(embs, head, tail, rel_embs, direction, "score_relations")
         return self._score_table(embs, h, t, rel_embs, direction)
 
     @staticmethod
@@ -147,8 +152,7 @@ class RelationDecoder(nn.Module):
         (CPU tensors work)."""
         if known is None:
             return None, None
-        if len(known) != 3:
-            raise ValueError(f"known must be (src, dst, rel), got {len(known)} members")
+        RelationDecoder._check_known(known)
         N = embs.size(0)
         h = HyperGNN._rank_ids(head, N, embs, "head")
         t = HyperGNN._rank_ids(tail, N, embs, "tail")
@@ -246,11 +250,7 @@ class RelationDecoder(nn.Module):
         """Where the text ``rel[i]`` ranks among ALL rows of ``rel_embs`` as the relation of ``(head_i, ?, tail_i)``:
         ``(greater, equal)`` int64 ``[B]`` for ``link_prediction_metrics``.  ``known=(src, dst, rel)`` names true triples: every
         other relation known to hold for the same directed pair is left out (the filtered setting).  No autograd graph."""
-        h, t = self._pair_ids(embs, head, tail, rel_embs, direction, "rank_relations")
-        r = self._target_ids(rel, h.numel(), rel_embs.size(0), embs)
-        if known is not None and len(known) != 3:
-            raise ValueError(f"known must be (src, dst, rel), got {len(known)} members")
-        self._device_only(embs, rel_embs, "rank_relations")
+        h, t, r = self._pair_ids(embs, head, tail, rel_embs, direction, "rank_relations", rel, known=known)
         with torch.no_grad():
             S = self._score_table(embs, h, t, rel_embs, direction)
             ptr, idx = self._relation_filter_lists(embs, h, t, r, known, rel_embs.size(0))
@@ -264,10 +264,7 @@ class RelationDecoder(nn.Module):
         k = int(k)
         if not 1 <= k <= 128:
             raise ValueError(f"topk_relations: k = {k} outside 1..128")
-        h, t = self._pair_ids(embs, head, tail, rel_embs, direction, "topk_relations")
-        if known is not None and len(known) != 3:
-            raise ValueError(f"known must be (src, dst, rel), got {len(known)} members")
-        self._device_only(embs, rel_embs, "topk_relations")
+        h, t, _ = self._pair_ids(embs, head, tail, rel_embs, direction, "topk_relations", known=known)
         with torch.no_grad():
             S = self._score_table(embs, h, t, rel_embs, direction)
             ptr, idx = self._relation_filter_lists(embs, h, t, None, known, rel_embs.size(0))
@@ -281,11 +278,7 @@ class RelationDecoder(nn.Module):
         scale = float(scale)
         if not (0.0 < scale < float("inf")):
             raise ValueError(f"relation_loss: scale must be finite and positive, got {scale}")
-        h, t = self._pair_ids(embs, head, tail, rel_embs, direction, "relation_loss")
-        r = self._target_ids(rel, h.numel(), rel_embs.size(0), embs)
-        if known is not None and len(known) != 3:
-            raise ValueError(f"known must be (src, dst, rel), got {len(known)} members")
-        self._device_only(embs, rel_embs, "relation_loss")
+        h, t, r = self._pair_ids(embs, head, tail, rel_embs, direction, "relation_loss", rel, known=known)
         S = self._score_table(embs, h, t, rel_embs, direction)
         with torch.no_grad():
             ptr, idx = self._relation_filter_lists(embs, h, t, r, known, rel_embs.size(0))
