@@ -107,6 +107,10 @@ SIGNATURES = {
     "ghf_score_softmax_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _sz, _vp, _vp, _vp]),
     "ghf_score_softmax_bwd_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "ghf_score_softmax_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "ghf_score_bce_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "ghf_score_bce_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _vp, _sz, _vp, _vp]),
+    "ghf_score_bce_bwd_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "ghf_score_bce_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ghf_relation_rows_workspace_bytes": (_sz, [_i64, _i32]),
     "ghf_relation_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
     "ghf_relation_scores": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp]),
@@ -745,6 +749,67 @@ def score_softmax_bwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, ls
     _check(load().ghf_score_softmax_bwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
                                         d, scale, _ptr(lse), _ptr(grad_loss), _ptr(ws), ws.numel(), _ptr(dq), _ptr(dc), _stream()),
            "ghf_score_softmax_bwd")
+    return dq, dc
+
+
+# ---- multi-label 1-vs-all BCE loss against every node (include/ghf.h: ghf_score_bce_fwd / _bwd, csrc/bce.hip) ---------
+def score_bce_workspace_bytes(B: int, N: int, d: int) -> int:
+    return int(load().ghf_score_bce_workspace_bytes(B, N, d))
+
+
+def score_bce_bwd_workspace_bytes(B: int, N: int, d: int) -> int:
+    return int(load().ghf_score_bce_bwd_workspace_bytes(B, N, d))
+
+
+def _bce_args(q, c, iq, pos_ptr, pos_idx, scale, smoothing, what: str):
+    q, c, iq, pos_ptr, pos_idx, B, nnz = _rank_args(q, c, iq, pos_ptr, pos_idx, what)
+    scale, smoothing = float(scale), float(smoothing)
+    if not (0.0 < scale < float("inf")):
+        raise ValueError(f"{what}: scale must be finite and positive, got {scale}")
+    if not (0.0 <= smoothing < 1.0):
+        raise ValueError(f"{what}: smoothing must be in [0, 1), got {smoothing}")
+    return q, c, iq, pos_ptr, pos_idx, B, nnz, scale, smoothing
+
+
+def score_bce_fwd(q: torch.Tensor, c: torch.Tensor, iq: Optional[torch.Tensor] = None, pos_ptr: Optional[torch.Tensor] = None,
+                  pos_idx: Optional[torch.Tensor] = None, scale: float = 1.0, smoothing: float = 0.0,
+                  workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """loss fp32 [B]: binary_cross_entropy_with_logits(scale q[iq[i]] . c[j], y_ij, reduction="sum") over every row j of c, with
+    y_ij = (1 - smoothing) [j in query i's list] + smoothing / N (CSR lists, each sorted ascending, a repeated id counting once).
+    Nothing of size B x N is stored.  With `workspace` (uint8, score_bce_workspace_bytes) and `out` given the call allocates
+    nothing."""
+    q, c, iq, pos_ptr, pos_idx, B, nnz, scale, smoothing = _bce_args(q, c, iq, pos_ptr, pos_idx, scale, smoothing, "score_bce_fwd")
+    N, d = c.size(0), c.size(1)
+    need = score_bce_workspace_bytes(B, N, d)
+    if need == 0:
+        raise ValueError(f"score_bce_fwd: unsupported sizes B={B} N={N} d={d}")
+    ws = _rank_workspace(workspace, need, q.device, "score_bce_fwd")
+    loss = _f32_out(out, (B,), q.device, "score_bce_fwd")
+    _check(load().ghf_score_bce_fwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(pos_ptr), _ptr(pos_idx), nnz, q.size(0), N, B, d, scale,
+                                    smoothing, _ptr(ws), ws.numel(), _ptr(loss), _stream()), "ghf_score_bce_fwd")
+    return loss
+
+
+def score_bce_bwd(q: torch.Tensor, c: torch.Tensor, loss: torch.Tensor, grad_loss: torch.Tensor, iq: Optional[torch.Tensor] = None,
+                  pos_ptr: Optional[torch.Tensor] = None, pos_idx: Optional[torch.Tensor] = None, scale: float = 1.0,
+                  smoothing: float = 0.0, workspace: Optional[torch.Tensor] = None,
+                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """(dq [B, d], dc [N, d]) fp32 of include/ghf.h: ghf_score_bce_bwd — dq per query (not scattered through iq), every row
+    of dc written.  `loss` is the forward's (a NaN entry: that query takes no part)."""
+    q, c, iq, pos_ptr, pos_idx, B, nnz, scale, smoothing = _bce_args(q, c, iq, pos_ptr, pos_idx, scale, smoothing, "score_bce_bwd")
+    loss, grad_loss = _req(loss, torch.float32, "loss"), _req(grad_loss, torch.float32, "grad_loss")
+    if loss.numel() != B or grad_loss.numel() != B:
+        raise ValueError(f"score_bce_bwd: loss and grad_loss must hold B = {B} values")
+    N, d = c.size(0), c.size(1)
+    need = score_bce_bwd_workspace_bytes(B, N, d)
+    if need == 0:
+        raise ValueError(f"score_bce_bwd: unsupported sizes B={B} N={N} d={d}")
+    ws = _rank_workspace(workspace, need, q.device, "score_bce_bwd")
+    dq = _f32_out(None if out is None else out[0], (B, d), q.device, "score_bce_bwd")
+    dc = _f32_out(None if out is None else out[1], (N, d), q.device, "score_bce_bwd")
+    _check(load().ghf_score_bce_bwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(pos_ptr), _ptr(pos_idx), nnz, q.size(0), N, B, d, scale,
+                                    smoothing, _ptr(loss), _ptr(grad_loss), _ptr(ws), ws.numel(), _ptr(dq), _ptr(dc), _stream()),
+           "ghf_score_bce_bwd")
     return dq, dc
 
 

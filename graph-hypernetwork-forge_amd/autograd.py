@@ -434,6 +434,31 @@ class SoftmaxLossFn(torch.autograd.Function):
         return _native.add3(dc, folded, out=dc), None, None, None, None, None
 
 
+class BceLossFn(torch.autograd.Function):
+    """loss_i = sum_j bce_with_logits(scale embs[query_i] . embs[j], y_ij) over ALL nodes j, y_ij = (1 - smoothing) [j in query
+    i's list] + smoothing / N (HyperGNN.bce_loss; include/ghf.h: ghf_score_bce_fwd).  Neither the [B, N] logits nor the labels
+    exist, here or in the backward, which recomputes the logits tile by tile (ghf_score_bce_bwd with q = c = embs): d embs =
+    dc + the per-query rows dq summed into the rows `query` names, grouped by node and added in that order as SoftmaxLossFn
+    does: reproducible."""
+
+    @staticmethod
+    def forward(ctx, embs, query, ptr, idx, scale: float, smoothing: float):
+        embs = embs.contiguous().float()
+        loss = _native.score_bce_fwd(embs, embs, iq=query, pos_ptr=ptr, pos_idx=idx, scale=scale, smoothing=smoothing)
+        ctx.save_for_backward(embs, loss, query, *(() if ptr is None else (ptr, idx)))
+        ctx.scale, ctx.smoothing = scale, smoothing
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        embs, loss, query, *lists = ctx.saved_tensors
+        ptr, idx = lists if lists else (None, None)
+        dq, dc = _native.score_bce_bwd(embs, embs, loss, g.contiguous().float(), iq=query, pos_ptr=ptr, pos_idx=idx,
+                                       scale=ctx.scale, smoothing=ctx.smoothing)
+        return _native.add3(dc, _fold_rows(dq, query, embs.size(0)), out=dc), None, None, None, None, None
+
+
 class ScorePairsFn(torch.autograd.Function):
     """s_i = a_i . b_i (reference score_triple, hypergnn.py:304-318)."""
 
@@ -576,4 +601,26 @@ class SoftmaxRowsLossFn(torch.autograd.Function):
         ptr, idx = lists if lists else (None, None)
         dq, dc = _native.score_softmax_bwd(rows, embs, target, lse, g.contiguous().float(), filt_ptr=ptr, filt_idx=idx,
                                            scale=ctx.scale)
+        return (dc if ctx.needs_input_grad[0] else None), (dq if ctx.needs_input_grad[1] else None), None, None, None, None
+
+
+class BceRowsLossFn(torch.autograd.Function):
+    """BceLossFn with the query rows given (``bce_loss(..., query_rows=Q)``): q = Q, c = embs.  ghf_score_bce_bwd's dq is the
+    gradient of Q and its dc that of embs, as they are."""
+
+    @staticmethod
+    def forward(ctx, embs, rows, ptr, idx, scale: float, smoothing: float):
+        embs, rows = embs.contiguous().float(), rows.contiguous().float()
+        loss = _native.score_bce_fwd(rows, embs, pos_ptr=ptr, pos_idx=idx, scale=scale, smoothing=smoothing)
+        ctx.save_for_backward(embs, rows, loss, *(() if ptr is None else (ptr, idx)))
+        ctx.scale, ctx.smoothing = scale, smoothing
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        embs, rows, loss, *lists = ctx.saved_tensors
+        ptr, idx = lists if lists else (None, None)
+        dq, dc = _native.score_bce_bwd(rows, embs, loss, g.contiguous().float(), pos_ptr=ptr, pos_idx=idx, scale=ctx.scale,
+                                       smoothing=ctx.smoothing)
         return (dc if ctx.needs_input_grad[0] else None), (dq if ctx.needs_input_grad[1] else None), None, None, None, None

@@ -1,0 +1,94 @@
+// bce.hip — the multi-label 1-vs-all binary cross-entropy link-prediction loss against every node (the 1-N objective of ConvE,
+// TuckER, CompGCN), forward; the B x N logits and labels never stored (include/ghf.h: ghf_score_bce_fwd / ghf_score_bce_bwd;
+// DESIGN.md §14).  With z_ij = scale s(i, j), s the sweep's fp32 chain (rank_sweep.h), and P_i the ids of query i's list:
+//
+//   y_ij    = (1 - smoothing) [j in P_i] + smoothing / N
+//   loss[i] = sum_j softplus(z_ij) - (1 - smoothing) sum_{j in P_i} z_ij - (smoothing / N) sum_j z_ij
+//           = binary_cross_entropy_with_logits(z_i, y_i, reduction = "sum")
+//
+// Forward: rank_tile_kernel with its fourth epilogue.  A lane keeps three running sums per query column (softplus(z), z over
+// the listed candidates, z) and folds a finished candidate tile's 32 registers of that column into them.  The list is walked
+// by the softmax epilogue's cursor: a full tile without a listed id touches no memory, the others look every id up (a hit
+// adds z to the positive sum; membership, so a repeated id counts once).  Candidates past N are left out, never scored as
+// zero rows: softplus(0) = ln 2.  softplus keeps its tail: log(1 + t) is a short series below t = 2^-6 (rank_sweep.h).
+// Partials merge as the softmax's: half-waves and waves through LDS, one triple per (query, slab) in the workspace,
+// bce_finish_kernel over the slabs in slab order; the slabs are softmax_geom's (N and d alone), so a query's loss has the
+// same bits whatever batch it is in.
+//
+// Backward: softmax_bwd_kernel with LOSS = SB_BCE (softmax.hip, which holds launch_score_bce_bwd).
+#include "common.h"
+#include "rank_sweep.h"
+
+namespace ghf {
+
+size_t score_bce_workspace_bytes(int64_t B, int64_t N, int d) {
+    RankGeom g;
+    if (d <= 0 || d > RK_MAX_D || !softmax_geom(B, N, d, &g)) return 0;
+    // valid [B] int32, (softplus, positive z, z) [B, slabs]
+    return rk_align((size_t)B * 4) + rk_align((size_t)B * (size_t)g.slabs * 12);
+}
+
+// a query whose row id is out of range takes no part (list_range_kernel then clears the queries with a bad list id)
+__global__ __launch_bounds__(256) void bce_prep_kernel(const int64_t* __restrict__ iq, int64_t rows_q, int64_t B,
+                                                       int* __restrict__ valid) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B) return;
+    const int64_t r = iq ? iq[i] : i;
+    valid[i] = r >= 0 && r < rows_q ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void bce_finish_kernel(const float* __restrict__ part, const int* __restrict__ valid, int64_t B,
+                                                         int64_t slabs, float pos_w, float neg_w, float* __restrict__ loss) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B) return;
+    const float* p = part + (size_t)i * slabs * 3;
+    float sp = 0.f, pos = 0.f, sz = 0.f;
+    for (int64_t s = 0; s < slabs; ++s) {
+        sp += p[3 * s];
+        pos += p[3 * s + 1];
+        sz += p[3 * s + 2];
+    }
+    loss[i] = valid[i] ? (sp - pos_w * pos) - neg_w * sz : __int_as_float(0x7FC00000);
+}
+
+int launch_score_bce_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
+                         int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, void* ws,
+                         size_t ws_bytes, float* loss, hipStream_t stream) {
+    RankGeom g;
+    GHF_REQUIRE(d > 0 && rows_q > 0 && N > 0 && B > 0 && nnz >= 0, "score_bce_fwd: bad shape");
+    if (d > RK_MAX_D) return set_err(GHF_EUNSUPPORTED, "score_bce_fwd: d = %d exceeds %d", d, RK_MAX_D);
+    GHF_REQUIRE(softmax_geom(B, N, d, &g), "score_bce_fwd: B or N out of range");
+    GHF_REQUIRE(iq || B <= rows_q, "score_bce_fwd: B exceeds the rows of q");
+    GHF_REQUIRE(ws_bytes >= score_bce_workspace_bytes(B, N, d), "score_bce_fwd: workspace of %zu bytes, need %zu", ws_bytes,
+                score_bce_workspace_bytes(B, N, d));
+    int* valid = (int*)ws;
+    float* part = (float*)((char*)ws + rk_align((size_t)B * 4));
+    const unsigned qb = (unsigned)cdiv(B, 256);
+    bce_prep_kernel<<<qb, 256, 0, stream>>>(iq, rows_q, B, valid);
+    GHF_LAUNCH_CHECK();
+    if (nnz > 0) {
+        list_range_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(pos_ptr, pos_idx, nnz, N, B, valid);
+        GHF_LAUNCH_CHECK();
+    }
+    RankArgs a = {};
+    a.q = q; a.c = c; a.iq = iq; a.rows_q = rows_q; a.N = N; a.B = B; a.d = d;
+    a.qtiles = g.qtiles; a.slab_tiles = g.slab_tiles; a.slabs = g.slabs;
+    a.filt_ptr = nnz > 0 ? pos_ptr : nullptr; a.filt_idx = pos_idx; a.nnz = nnz;
+    a.scale = scale; a.ws_bce = part;
+    const unsigned grid = (unsigned)(g.qtiles * g.slabs);
+    if (rank_ctile(d) == 256) {
+        const size_t lds = rank_lds_bytes(d, 32, 256);
+        GHF_SET_MAX_LDS((rank_tile_kernel<32, 256, RK_BCE>), lds);
+        rank_tile_kernel<32, 256, RK_BCE><<<grid, 512, lds, stream>>>(a);
+    } else {
+        const size_t lds = rank_lds_bytes(d, 16, 128);
+        GHF_SET_MAX_LDS((rank_tile_kernel<16, 128, RK_BCE>), lds);
+        rank_tile_kernel<16, 128, RK_BCE><<<grid, 256, lds, stream>>>(a);
+    }
+    GHF_LAUNCH_CHECK();
+    bce_finish_kernel<<<qb, 256, 0, stream>>>(part, valid, B, g.slabs, 1.f - smoothing, smoothing / (float)N, loss);
+    GHF_LAUNCH_CHECK();
+    return GHF_OK;
+}
+
+}  // namespace ghf

@@ -630,6 +630,34 @@ int ghf_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, con
                                     workspace_bytes, dq, dc, (hipStream_t)stream);
 }
 
+size_t ghf_score_bce_workspace_bytes(int64_t B, int64_t N, int d) { return score_bce_workspace_bytes(B, N, d); }
+
+int ghf_score_bce_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx, int64_t nnz,
+                      int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, void* workspace,
+                      size_t workspace_bytes, float* loss, void* stream) {
+    GHF_REQUIRE(q && c && workspace && loss, "score_bce_fwd: null pointer argument");
+    GHF_REQUIRE(nnz <= 0 || (pos_ptr && pos_idx), "score_bce_fwd: null positive list with nnz > 0");
+    GHF_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, "score_bce_fwd: scale must be finite and positive");
+    GHF_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "score_bce_fwd: smoothing must be in [0, 1)");
+    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "score_bce_fwd: workspace not 256-byte aligned");
+    return launch_score_bce_fwd(q, c, iq, pos_ptr, pos_idx, nnz, rows_q, N, B, d, scale, smoothing, workspace, workspace_bytes, loss,
+                                (hipStream_t)stream);
+}
+
+size_t ghf_score_bce_bwd_workspace_bytes(int64_t B, int64_t N, int d) { return score_bce_bwd_workspace_bytes(B, N, d); }
+
+int ghf_score_bce_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx, int64_t nnz,
+                      int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
+                      const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* dc, void* stream) {
+    GHF_REQUIRE(q && c && loss && grad_loss && workspace && dq && dc, "score_bce_bwd: null pointer argument");
+    GHF_REQUIRE(nnz <= 0 || (pos_ptr && pos_idx), "score_bce_bwd: null positive list with nnz > 0");
+    GHF_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, "score_bce_bwd: scale must be finite and positive");
+    GHF_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "score_bce_bwd: smoothing must be in [0, 1)");
+    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "score_bce_bwd: workspace not 256-byte aligned");
+    return launch_score_bce_bwd(q, c, iq, pos_ptr, pos_idx, nnz, rows_q, N, B, d, scale, smoothing, loss, grad_loss, workspace,
+                                workspace_bytes, dq, dc, (hipStream_t)stream);
+}
+
 size_t ghf_relation_rows_workspace_bytes(int64_t B, int R) { return relation_rows_workspace_bytes(B, R); }
 
 int ghf_relation_rows(const float* x, const int64_t* ix, const int64_t* rel, const float* W, const float* bias,

@@ -184,6 +184,15 @@ int launch_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, 
                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                              const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc,
                              hipStream_t stream);
+// bce.hip (forward) and softmax.hip (backward: softmax_bwd_kernel's second loss)
+size_t score_bce_workspace_bytes(int64_t B, int64_t N, int d);
+size_t score_bce_bwd_workspace_bytes(int64_t B, int64_t N, int d);
+int launch_score_bce_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
+                         int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, void* ws,
+                         size_t ws_bytes, float* loss, hipStream_t stream);
+int launch_score_bce_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
+                         int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
+                         const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc, hipStream_t stream);
 // relation.hip
 size_t relation_rows_workspace_bytes(int64_t B, int R);
 int launch_relation_rows(const float* x, const int64_t* ix, const int64_t* rel, const float* W, const float* bias,

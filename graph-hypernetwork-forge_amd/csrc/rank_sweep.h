@@ -1,6 +1,7 @@
-// rank_sweep.h — the tiled q . c^T sweep on the exact fp32 matrix instruction that rank.hip (rank counts, top-k) and
-// softmax.hip (1-vs-all softmax loss) share: geometry, the VALU form of the accumulator's chain, the LDS layout and
-// rank_tile_kernel with its three epilogues.  rank.hip's header comment describes the sweep.
+// rank_sweep.h — the tiled q . c^T sweep on the exact fp32 matrix instruction that rank.hip (rank counts, top-k),
+// softmax.hip (1-vs-all softmax loss) and bce.hip (multi-label 1-vs-all BCE loss) share: geometry, the VALU form of the
+// accumulator's chain, the LDS layout and rank_tile_kernel with its four epilogues.  rank.hip's header comment describes the
+// sweep.
 #pragma once
 #include "common.h"
 
@@ -35,6 +36,18 @@ static inline bool rank_geom(int64_t B, int64_t N, int d, int blocks_wanted, Ran
     if (slabs < 1) slabs = 1;
     g->slab_tiles = cdiv(g->ctiles, slabs);
     g->slabs = cdiv(g->ctiles, g->slab_tiles);       // every slab holds at least one tile
+    return g->qtiles * g->slabs < (int64_t)1 << 31;
+}
+
+// the two losses: a fixed number of candidate slabs (fewer when N is small), whatever B is — the slabs depend on N and d
+// alone, so a query's partial sums, and with them its loss, have the same bits whatever batch it is in
+constexpr int SM_SLABS = 128;
+static inline bool softmax_geom(int64_t B, int64_t N, int d, RankGeom* g) {
+    if (B <= 0 || N <= 0 || N >= (int64_t)1 << 31 || B >= (int64_t)1 << 31) return false;
+    g->qtiles = cdiv(B, RK_TILE);
+    g->ctiles = cdiv(N, rank_ctile(d));
+    g->slab_tiles = cdiv(g->ctiles, SM_SLABS);
+    g->slabs = cdiv(g->ctiles, g->slab_tiles);
     return g->qtiles * g->slabs < (int64_t)1 << 31;
 }
 
@@ -175,10 +188,12 @@ struct RankArgs {
     int k, cap; uint64_t* ws_key;
     // softmax (lists as for top-k)
     const int64_t* target; float scale; f32x2* ws_ms;
+    // bce (the lists name each query's positives; scale as for softmax)
+    float* ws_bce;
 };
 
 // the epilogue of rank_tile_kernel
-constexpr int RK_RANK = 0, RK_TOPK = 1, RK_SOFTMAX = 2;
+constexpr int RK_RANK = 0, RK_TOPK = 1, RK_SOFTMAX = 2, RK_BCE = 3;
 
 // first entry of the sorted list [lo, hi) that is not below `first`
 __device__ __forceinline__ int64_t filter_lower_bound(const int64_t* __restrict__ idx, int64_t lo, int64_t hi, int64_t first) {
@@ -196,6 +211,30 @@ __device__ __forceinline__ f32x2 lse_merge(f32x2 x, f32x2 y) {
     return f32x2{m, x[1] * expf(x[0] - m) + y[1] * expf(y[0] - m)};
 }
 
+// log(1 + t) for t = exp(-|z|) in (0, 1].  Forming 1 + t rounds t to a multiple of 2^-24: 4e-6 of the result at t = 2^-6,
+// 2 % at 6e-6, all of it below 6e-8.  Below 2^-6 the series t - t^2/2 + t^3/3 stands in (its next term is below 1e-6 of it).
+__device__ __forceinline__ float log1p_unit(float t) {
+    const float series = t * fmaf(t, fmaf(t, 1.f / 3.f, -0.5f), 1.f);
+    return t < 0.015625f ? series : __logf(1.f + t);
+}
+// softplus(z) = log(1 + exp(z)) = max(z, 0) + log(1 + exp(-|z|)): no overflow at either end
+__device__ __forceinline__ float softplus(float z) { return fmaxf(z, 0.f) + log1p_unit(__expf(-fabsf(z))); }
+
+// one thread per list entry: an id out of range marks the query whose list holds it
+static __global__ __launch_bounds__(256) void list_range_kernel(const int64_t* __restrict__ filt_ptr, const int64_t* __restrict__ filt_idx,
+                                                                int64_t nnz, int64_t N, int64_t B, int* valid) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= nnz) return;
+    const int64_t j = filt_idx[e];
+    if (j >= 0 && j < N) return;
+    int64_t lo = 0, hi = B;                          // last i with filt_ptr[i] <= e
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (filt_ptr[mid] <= e) lo = mid; else hi = mid;
+    }
+    if (filt_ptr[lo] <= e && filt_ptr[lo + 1] > e) valid[lo] = 0;
+}
+
 static inline size_t rank_lds_bytes(int d, int BK, int CT) {
     const int dpad = (d + 7) & ~7;
     return ((size_t)RK_TILE * (dpad + 4) + 2 * (size_t)CT * (BK + 4) + 2 * RK_TILE) * 4;
@@ -203,7 +242,8 @@ static inline size_t rank_lds_bytes(int d, int BK, int CT) {
 
 template <int BK, int CT, int MODE>
 __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const RankArgs a) {
-    constexpr bool TOPK = MODE == RK_TOPK, RANK = MODE == RK_RANK, SOFTMAX = MODE == RK_SOFTMAX;
+    constexpr bool TOPK = MODE == RK_TOPK, RANK = MODE == RK_RANK, SOFTMAX = MODE == RK_SOFTMAX, BCE = MODE == RK_BCE;
+    constexpr bool CURSOR = SOFTMAX || BCE;             // the lists are walked by a cursor, in step with the sweep
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int NT = CT * 2, NW = NT / 64;            // a wave per 64 candidates x 64 queries
     constexpr int LDC = BK + 4, F4 = BK / 4, NL = CT * F4 / NT;
@@ -253,6 +293,8 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const RankArgs a) {
     // softmax: running (max, sum) of the column's logits, its target, and the first listed id not yet behind the sweep
     float rm[2] = {-INFINITY, -INFINITY}, rs[2] = {0.f, 0.f};
     int64_t tgt[2] = {-1, -1}, nxt[2] = {INT64_MAX, INT64_MAX};
+    // bce: running sums of softplus(z), of z, and of z over the column's listed candidates (its positives)
+    float bsp[2] = {0.f, 0.f}, bsz[2] = {0.f, 0.f}, bpos[2] = {0.f, 0.f};
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn) {
         const int64_t qi = q0 + wn * 64 + tn * 32 + lr;
@@ -266,7 +308,7 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const RankArgs a) {
                 hi = hi < lo ? lo : (hi > a.nnz ? a.nnz : hi);
                 f0[tn] = lo;
                 f1[tn] = hi;
-                if (SOFTMAX) {                       // the cursor starts at the slab's first candidate
+                if (CURSOR) {                        // the cursor starts at the slab's first candidate
                     f0[tn] = filter_lower_bound(a.filt_idx, lo, hi, tile0 * CT);
                     if (f0[tn] < hi) nxt[tn] = a.filt_idx[f0[tn]];
                 }
@@ -372,6 +414,41 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const RankArgs a) {
                         rm[tn] = mx;
                     }
                 }
+            } else if (BCE) {
+                // the tile's 32 logits of a column enter its three sums in register order, whichever path the tile takes (a
+                // term left out adds +0): a full tile without a listed id touches no memory.  A candidate past N is left out,
+                // not scored as a zero row: softplus(0) = ln 2.
+                const int64_t tile_end = tile * CT + CT;
+#pragma unroll
+                for (int tn = 0; tn < 2; ++tn) {
+                    float tsp = 0.f, tsz = 0.f, tpos = 0.f;
+                    if (full && nxt[tn] >= tile_end) {
+#pragma unroll
+                        for (int e = 0; e < 32; ++e) {
+                            const float z = a.scale * acc[e >> 4][tn][e & 15];
+                            tsp += softplus(z);
+                            tsz += z;
+                        }
+                    } else {
+                        const bool look = nxt[tn] < tile_end;
+#pragma unroll
+                        for (int e = 0; e < 32; ++e) {
+                            const int64_t cand = base + 32 * (e >> 4) + (e & 3) + 8 * ((e & 15) >> 2);
+                            const float z = a.scale * acc[e >> 4][tn][e & 15];
+                            const bool in = cand < a.N;
+                            tsp += in ? softplus(z) : 0.f;
+                            tsz += in ? z : 0.f;
+                            tpos += (in && look && in_filter(a.filt_idx, f0[tn], f1[tn], cand)) ? z : 0.f;
+                        }
+                        while (nxt[tn] < tile_end) {
+                            ++f0[tn];
+                            nxt[tn] = f0[tn] < f1[tn] ? a.filt_idx[f0[tn]] : INT64_MAX;
+                        }
+                    }
+                    bsp[tn] += tsp;
+                    bsz[tn] += tsz;
+                    bpos[tn] += tpos;
+                }
             } else if (RANK) {
 #pragma unroll
                 for (int tm = 0; tm < 2; ++tm)
@@ -448,6 +525,31 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const RankArgs a) {
             f32x2 m = part[tid * NP];
             for (int p = 1; p < NP; ++p) m = lse_merge(m, part[tid * NP + p]);
             a.ws_ms[(size_t)(q0 + tid) * a.slabs + slab] = m;
+        }
+    } else if (BCE) {
+        // as the softmax's partials: the column's NP triples through LDS, added in that fixed order, one triple per (query,
+        // slab) in the workspace
+        constexpr int NP = NW;
+        float* part = Cs;
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) {
+            float* p = part + ((wn * 64 + tn * 32 + lr) * NP + wm * 2 + lh) * 3;
+            p[0] = bsp[tn];
+            p[1] = bpos[tn];
+            p[2] = bsz[tn];
+        }
+        __syncthreads();
+        if (tid < RK_TILE && q0 + tid < a.B) {
+            float sp = 0.f, pos = 0.f, sz = 0.f;
+            for (int p = 0; p < NP; ++p) {
+                sp += part[(tid * NP + p) * 3];
+                pos += part[(tid * NP + p) * 3 + 1];
+                sz += part[(tid * NP + p) * 3 + 2];
+            }
+            float* w = a.ws_bce + ((size_t)(q0 + tid) * a.slabs + slab) * 3;
+            w[0] = sp;
+            w[1] = pos;
+            w[2] = sz;
         }
     } else if (RANK) {
 #pragma unroll

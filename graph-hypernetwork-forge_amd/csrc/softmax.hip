@@ -30,27 +30,22 @@
 // workgroup first collects the (query, candidate) pairs of all lists that fall
 // into ITS candidate tile (one coalesced pass over filt_idx) and zeroes those entries of G in LDS after each step's
 // epilogue; a tile that more than SB_HCAP pairs fall into (a hub listed by thousands of queries) looks every id up instead.
+//
+// The multi-label BCE loss (bce.hip) runs its backward through the same kernel (LOSS = SB_BCE): only G differs,
+//   G_ij = grad[i] scale (sigma(scale s(i,j)) - smoothing / N - (1 - smoothing) [j listed]),
+// the lists naming positives, not masks: the dq sweep's cursor says which steps hold listed ids, and the dc sweep's collected
+// pairs SUBTRACT grad scale (1 - smoothing) from their entries of G instead of zeroing them.
 #include "common.h"
 #include "rank_sweep.h"
 
 namespace ghf {
 
-constexpr int SM_SLABS = 128;                // forward: candidate slabs (fewer when N is small), whatever B is
 constexpr int SB_ST = 64;                    // backward: streamed rows per step
 constexpr int SB_NT = 256;                   // backward: threads
 constexpr int SB_HCAP = 1024;                // backward, dc: listed pairs a candidate tile keeps in LDS
 constexpr int SB_MIN_SLAB_TILES = 64;        // backward, dq: a slab is at least 4,096 candidates, so that the partials stay
                                              // below 1/32 of a score matrix at d = 128
 static inline int sb_otile(int d) { return d <= 128 ? 128 : 64; }
-
-static inline bool softmax_geom(int64_t B, int64_t N, int d, RankGeom* g) {
-    if (B <= 0 || N <= 0 || N >= (int64_t)1 << 31 || B >= (int64_t)1 << 31) return false;
-    g->qtiles = cdiv(B, RK_TILE);
-    g->ctiles = cdiv(N, rank_ctile(d));
-    g->slab_tiles = cdiv(g->ctiles, SM_SLABS);
-    g->slabs = cdiv(g->ctiles, g->slab_tiles);
-    return g->qtiles * g->slabs < (int64_t)1 << 31;
-}
 
 // dq: two workgroups per CU over the call where the slabs' minimum length allows
 static inline bool softmax_bwd_geom(int64_t B, int64_t N, int d, RankGeom* g) {
@@ -91,21 +86,6 @@ __global__ __launch_bounds__(256) void softmax_prep_kernel(const float* __restri
     valid[i] = ok ? 1 : 0;
 }
 
-// one thread per filter entry: an id out of range marks the query whose list holds it
-__global__ __launch_bounds__(256) void softmax_filter_kernel(const int64_t* __restrict__ filt_ptr, const int64_t* __restrict__ filt_idx,
-                                                             int64_t nnz, int64_t N, int64_t B, int* valid) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= nnz) return;
-    const int64_t j = filt_idx[e];
-    if (j >= 0 && j < N) return;
-    int64_t lo = 0, hi = B;                          // last i with filt_ptr[i] <= e
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (filt_ptr[mid] <= e) lo = mid; else hi = mid;
-    }
-    if (filt_ptr[lo] <= e && filt_ptr[lo + 1] > e) valid[lo] = 0;
-}
-
 __global__ __launch_bounds__(256) void softmax_finish_kernel(const f32x2* __restrict__ ms, const float* __restrict__ t,
                                                              const int* __restrict__ valid, int64_t B, int64_t slabs, float scale,
                                                              float* __restrict__ loss, float* __restrict__ lse) {
@@ -135,7 +115,7 @@ int launch_score_softmax_fwd(const float* q, const float* c, const int64_t* iq, 
     softmax_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, target, rows_q, N, B, d, t, valid);
     GHF_LAUNCH_CHECK();
     if (nnz > 0) {
-        softmax_filter_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(filt_ptr, filt_idx, nnz, N, B, valid);
+        list_range_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(filt_ptr, filt_idx, nnz, N, B, valid);
         GHF_LAUNCH_CHECK();
     }
     RankArgs a = {};
@@ -166,10 +146,11 @@ struct SmBwdArgs {
     int64_t rows_q, N, B;
     int d;
     float scale;
-    const float* lse; const float* grad;
+    const float* lse; const float* grad;     // bce: lse is the forward's loss (only its NaNs are read), target is NULL
     int64_t qtiles, slab_tiles, slabs;       // dq
     float* dq_part;                          // dq: [slabs, B, d]
     float* dc;                               // dc: [N, d]
+    float pos_w, neg_w;                      // bce: 1 - smoothing, smoothing / N
 };
 
 static inline size_t sb_lds_bytes(int d, int OT) {
@@ -183,9 +164,13 @@ struct SmQuery {
     int64_t tgt, f0, f1;                     // target, filter list [f0, f1)
 };
 
-template <int OT, int DMAX, bool DC>
+// the loss whose G the backward forms
+constexpr int SB_SOFTMAX = 0, SB_BCE = 1;
+
+template <int OT, int DMAX, bool DC, int LOSS>
 __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    constexpr bool BCE = LOSS == SB_BCE;
     constexpr int ST = SB_ST, NT = SB_NT, LDG = OT + 1;
     constexpr int QR = DC ? ST : OT, CR = DC ? OT : ST;             // query / candidate rows of a step's score tile
     constexpr int QT = QR / 32, NTW = QT * (CR / 32) / 4;           // a wave: one query column tile, NTW candidate row tiles
@@ -227,7 +212,7 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
         if (qi < a.B) {
             const int64_t r = a.iq ? a.iq[qi] : qi;
             const float l = a.lse[qi];
-            m.tgt = a.target[qi];
+            if (!BCE) m.tgt = a.target[qi];
             if (r >= 0 && r < a.rows_q && l == l) {
                 m.lse = l;
                 m.gs = a.grad[qi] * a.scale;
@@ -249,7 +234,8 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
         store_perm(Xs + row * LDX, c4, load_k4(src, c4 * 4, d, DC ? vc : vq));
     }
 
-    // dc: the listed (query, candidate) pairs inside this candidate tile, the targets' own left out
+    // dc: the listed (query, candidate) pairs inside this candidate tile, the targets' own left out.  bce: the pairs of the
+    // queries that take part, an id that repeats its predecessor in the list left out (a positive counts once)
     if (DC) {
         if (tid == 0) *hcnt = 0;
         __syncthreads();
@@ -262,7 +248,15 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
                     const int64_t mid = (lo + hi) >> 1;
                     if (a.filt_ptr[mid] <= e) lo = mid; else hi = mid;
                 }
-                if (a.filt_ptr[lo] > e || a.filt_ptr[lo + 1] <= e || a.target[lo] == j) continue;
+                if (BCE) {
+                    if (a.filt_ptr[lo] > e || a.filt_ptr[lo + 1] <= e) continue;
+                    if (e > 0 && e > a.filt_ptr[lo] && a.filt_idx[e - 1] == j) continue;
+                    const int64_t r = a.iq ? a.iq[lo] : lo;
+                    const float l = a.lse[lo];
+                    if (r < 0 || r >= a.rows_q || l != l) continue;
+                } else {
+                    if (a.filt_ptr[lo] > e || a.filt_ptr[lo + 1] <= e || a.target[lo] == j) continue;
+                }
                 const int pos = atomicAdd(hcnt, 1);
                 if (pos < SB_HCAP) hits[pos] = (long long)(lo * 256 + (j - own0));
             }
@@ -313,8 +307,9 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
     fetch(tile0);
     stash();
     __syncthreads();
-    const int nh = DC ? (*hcnt < SB_HCAP ? *hcnt : SB_HCAP) : 0;
     const bool over = DC && *hcnt > SB_HCAP;
+    // (bce subtracts at the kept pairs: a tile that looks every id up must not apply them as well)
+    const int nh = DC && !(BCE && over) ? (*hcnt < SB_HCAP ? *hcnt : SB_HCAP) : 0;
 
     for (int64_t tile = tile0; tile < tile1; ++tile) {
         const bool more = tile + 1 < tile1;
@@ -363,9 +358,17 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
                 const int64_t cand = cand0 + cl;
                 float gv = 0.f;
                 if (live && cand < a.N) {
-                    const bool masked = look && cand != cur.tgt && in_filter(a.filt_idx, cur.f0, cur.f1, cand);
-                    const float p = masked ? 0.f : __expf(fmaf(a.scale, s[t][r], -cur.lse));
-                    gv = cur.gs * (p - (cand == cur.tgt ? 1.f : 0.f));
+                    if (BCE) {
+                        // sigma(z) from e = exp(-|z|) in (0, 1]: 1 / (1 + e) for z >= 0, e / (1 + e) below
+                        const float z = a.scale * s[t][r], e = __expf(-fabsf(z)), rcp = __builtin_amdgcn_rcpf(1.f + e);
+                        const float p = z >= 0.f ? rcp : e * rcp;
+                        const bool listed = look && in_filter(a.filt_idx, cur.f0, cur.f1, cand);
+                        gv = cur.gs * ((p - a.neg_w) - (listed ? a.pos_w : 0.f));
+                    } else {
+                        const bool masked = look && cand != cur.tgt && in_filter(a.filt_idx, cur.f0, cur.f1, cand);
+                        const float p = masked ? 0.f : __expf(fmaf(a.scale, s[t][r], -cur.lse));
+                        gv = cur.gs * (p - (cand == cur.tgt ? 1.f : 0.f));
+                    }
                 }
                 Gs[DC ? ql * LDG + cl : cl * LDG + ql] = gv;
             }
@@ -379,7 +382,12 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
         if (DC && nh > 0) {                          // the listed pairs of this candidate tile whose query is in the step
             for (int h = tid; h < nh; h += NT) {
                 const int64_t qi = hits[h] >> 8;
-                if (qi >= tile * ST && qi < tile * ST + ST) Gs[(int)(qi - tile * ST) * LDG + (int)(hits[h] & 255)] = 0.f;
+                if (BCE) {                           // one pair, one entry: no two threads meet
+                    if (qi >= tile * ST && qi < tile * ST + ST)
+                        Gs[(int)(qi - tile * ST) * LDG + (int)(hits[h] & 255)] -= a.grad[qi] * a.scale * a.pos_w;
+                } else {
+                    if (qi >= tile * ST && qi < tile * ST + ST) Gs[(int)(qi - tile * ST) * LDG + (int)(hits[h] & 255)] = 0.f;
+                }
             }
             __syncthreads();
         }
@@ -419,14 +427,14 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
     }
 }
 
-template <int OT, int DMAX>
+template <int OT, int DMAX, int LOSS>
 static int launch_bwd_tiles(const SmBwdArgs& a, hipStream_t stream) {
     const size_t lds = sb_lds_bytes(a.d, OT);
-    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, false>), lds);
-    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, true>), lds);
-    softmax_bwd_kernel<OT, DMAX, false><<<(unsigned)(a.qtiles * a.slabs), SB_NT, lds, stream>>>(a);
+    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, false, LOSS>), lds);
+    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, true, LOSS>), lds);
+    softmax_bwd_kernel<OT, DMAX, false, LOSS><<<(unsigned)(a.qtiles * a.slabs), SB_NT, lds, stream>>>(a);
     GHF_LAUNCH_CHECK();
-    softmax_bwd_kernel<OT, DMAX, true><<<(unsigned)cdiv(a.N, OT), SB_NT, lds, stream>>>(a);
+    softmax_bwd_kernel<OT, DMAX, true, LOSS><<<(unsigned)cdiv(a.N, OT), SB_NT, lds, stream>>>(a);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }
@@ -448,7 +456,33 @@ int launch_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, 
     a.rows_q = rows_q; a.N = N; a.B = B; a.d = d; a.scale = scale; a.lse = lse; a.grad = grad_loss;
     a.qtiles = g.qtiles; a.slab_tiles = g.slab_tiles; a.slabs = g.slabs;
     a.dq_part = (float*)ws; a.dc = dc;
-    const int rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128>(a, stream) : launch_bwd_tiles<64, 256>(a, stream);
+    const int rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128, SB_SOFTMAX>(a, stream)
+                                      : launch_bwd_tiles<64, 256, SB_SOFTMAX>(a, stream);
+    if (rc != GHF_OK) return rc;
+    return launch_ordered_sum(a.dq_part, g.slabs, B * (int64_t)d, dq, stream);
+}
+
+// ---- the multi-label BCE loss's backward (bce.hip holds its forward): the same two sweeps, G formed for that loss ---------
+size_t score_bce_bwd_workspace_bytes(int64_t B, int64_t N, int d) { return score_softmax_bwd_workspace_bytes(B, N, d); }
+
+int launch_score_bce_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
+                         int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
+                         const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc, hipStream_t stream) {
+    RankGeom g;
+    GHF_REQUIRE(d > 0 && rows_q > 0 && N > 0 && B > 0 && nnz >= 0, "score_bce_bwd: bad shape");
+    if (d > RK_MAX_D) return set_err(GHF_EUNSUPPORTED, "score_bce_bwd: d = %d exceeds %d", d, RK_MAX_D);
+    GHF_REQUIRE(softmax_bwd_geom(B, N, d, &g), "score_bce_bwd: B or N out of range");
+    GHF_REQUIRE(iq || B <= rows_q, "score_bce_bwd: B exceeds the rows of q");
+    GHF_REQUIRE(ws_bytes >= score_bce_bwd_workspace_bytes(B, N, d), "score_bce_bwd: workspace of %zu bytes, need %zu", ws_bytes,
+                score_bce_bwd_workspace_bytes(B, N, d));
+    SmBwdArgs a = {};
+    a.q = q; a.c = c; a.iq = iq;
+    a.filt_ptr = nnz > 0 ? pos_ptr : nullptr; a.filt_idx = pos_idx; a.nnz = nnz;
+    a.rows_q = rows_q; a.N = N; a.B = B; a.d = d; a.scale = scale; a.lse = loss; a.grad = grad_loss;
+    a.pos_w = 1.f - smoothing; a.neg_w = smoothing / (float)N;
+    a.qtiles = g.qtiles; a.slab_tiles = g.slab_tiles; a.slabs = g.slabs;
+    a.dq_part = (float*)ws; a.dc = dc;
+    const int rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128, SB_BCE>(a, stream) : launch_bwd_tiles<64, 256, SB_BCE>(a, stream);
     if (rc != GHF_OK) return rc;
     return launch_ordered_sum(a.dq_part, g.slabs, B * (int64_t)d, dq, stream);
 }

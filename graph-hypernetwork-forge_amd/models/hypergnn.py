@@ -657,6 +657,18 @@ class HyperGNN(nn.Module):
             raise RuntimeError(f"{what} computes on an MI355X HIP device only (query_rows is on {query_rows.device}, embs on "
                                f"{embs.device})")
 
+    @staticmethod
+    def _known_form(known, filt_ptr, filt_idx, query_rel) -> bool:
+        """Which of known / CSR lists / query_rel go together (no tensor is read); whether ``known`` is the typed form."""
+        if known is not None and (filt_ptr is not None or filt_idx is not None):
+            raise ValueError("pass either known=(src, dst) or filt_ptr / filt_idx, not both")
+        typed = known is not None and len(known) == 3
+        if query_rel is not None and not typed:
+            raise ValueError("query_rel needs the typed known=(src, dst, rel)")
+        if typed and query_rel is None:
+            raise ValueError("known=(src, dst, rel) needs query_rel: the relation of every query")
+        return typed
+
     @classmethod
     def _filter_lists(cls, embs: torch.Tensor, query: torch.Tensor, known, filt_ptr, filt_idx, query_rel=None):
         """Each query's filter list in the form the kernels take (CSR, every list sorted ascending), built on the device.
@@ -665,13 +677,7 @@ class HyperGNN(nn.Module):
         form: query[i]'s list is every dst of an edge with src == query[i] AND rel == query_rel[i] (for (?, r, t) queries
         pass known=(dst, src, rel))."""
         N, B = embs.size(0), query.numel()
-        if known is not None and (filt_ptr is not None or filt_idx is not None):
-            raise ValueError("pass either known=(src, dst) or filt_ptr / filt_idx, not both")
-        typed = known is not None and len(known) == 3
-        if query_rel is not None and not typed:
-            raise ValueError("query_rel needs the typed known=(src, dst, rel)")
-        if typed and query_rel is None:
-            raise ValueError("known=(src, dst, rel) needs query_rel: the relation of every query")
+        typed = cls._known_form(known, filt_ptr, filt_idx, query_rel)
         if known is not None:
             if len(known) not in (2, 3):
                 raise ValueError(f"known must be (src, dst) or (src, dst, rel), got {len(known)} members")
@@ -808,6 +814,48 @@ class HyperGNN(nn.Module):
             return SoftmaxLossFn.apply(embs, q, t, ptr, idx, scale)
         e = embs.detach().float()
         return _native.score_softmax_fwd(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, scale=scale)[0]
+
+    def bce_loss(self, embs: torch.Tensor, query: torch.Tensor, *, known=None, pos_ptr: Optional[torch.Tensor] = None,
+                 pos_idx: Optional[torch.Tensor] = None, scale: float = 1.0, smoothing: float = 0.0, normalize: bool = True,
+                 query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The multi-label 1-vs-all loss of ConvE / TuckER / CompGCN, fp32 ``[B]``: every ``query[i]`` is scored against ALL
+        nodes, all of its known partners are positives at once, and the loss is binary cross-entropy with label smoothing,
+        ``F.binary_cross_entropy_with_logits(scale * embs[query] @ embs.T, y, reduction="none").mean(1)`` with
+        ``y[i, j] = (1 - smoothing) * [j is a partner of query i] + smoothing / N`` — without the ``[B, N]`` logits or labels,
+        forward or backward (``ghf_score_bce_fwd`` / ``ghf_score_bce_bwd``, ``autograd.BceLossFn``).  One row per DISTINCT query,
+        however many partners it has.  The partners come as ``known`` (``(src, dst)``, or ``(src, dst, rel)`` with ``query_rel``)
+        or as CSR lists ``pos_ptr`` / ``pos_idx``, exactly as the filter lists of ``rank_candidates`` — here they are the label
+        set, not a mask; a repeated id counts once.  ``normalize=False`` returns the sum over the candidates instead of their
+        mean.  ``0 <= smoothing < 1``.  Bit-reproducible.  Recorded for autograd when grad mode is on and ``embs`` requires grad.
+        ``query_rows``: relation-typed queries, as in ``softmax_loss``; the loss is then recorded when ``embs`` or ``query_rows``
+        requires grad (``autograd.BceRowsLossFn``)."""
+        if embs.dim() != 2:
+            raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        self._query_rows(embs, query, query_rows, "bce_loss")
+        scale, smoothing = float(scale), float(smoothing)
+        if not (0.0 < scale < float("inf")):
+            raise ValueError(f"scale must be finite and positive, got {scale}")
+        if not (0.0 <= smoothing < 1.0):
+            raise ValueError(f"smoothing must be in [0, 1), got {smoothing}")
+        q = self._rank_ids(query, embs.size(0), embs, "query")
+        self._known_form(known, pos_ptr, pos_idx, query_rel)
+        if not embs.is_cuda:
+            raise RuntimeError(f"bce_loss computes on an MI355X HIP device only (input is on {embs.device})")
+        ptr, idx = self._filter_lists(embs, q, known, pos_ptr, pos_idx, query_rel)
+        if query_rows is not None:
+            if torch.is_grad_enabled() and (embs.requires_grad or query_rows.requires_grad):
+                from ..autograd import BceRowsLossFn
+                loss = BceRowsLossFn.apply(embs, query_rows, ptr, idx, scale, smoothing)
+            else:
+                loss = _native.score_bce_fwd(query_rows.detach(), embs.detach().float(), pos_ptr=ptr, pos_idx=idx, scale=scale,
+                                             smoothing=smoothing)
+        elif torch.is_grad_enabled() and embs.requires_grad:
+            from ..autograd import BceLossFn
+            loss = BceLossFn.apply(embs, q, ptr, idx, scale, smoothing)
+        else:
+            e = embs.detach().float()
+            loss = _native.score_bce_fwd(e, e, iq=q, pos_ptr=ptr, pos_idx=idx, scale=scale, smoothing=smoothing)
+        return loss * (1.0 / embs.size(0)) if normalize else loss
 
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)

@@ -516,6 +516,34 @@ int ghf_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, con
                           const float* lse, const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* dc,
                           void* stream);
 
+/* ---- multi-label 1-vs-all BCE link-prediction loss against every node (csrc/bce.hip, csrc/softmax.hip) --------
+ * The 1-N objective of ConvE / TuckER / CompGCN: one query scored against every node, ALL of its known partners positives at
+ * once, binary cross-entropy with label smoothing.  q, c, iq, rows_q, N, B, d and the limits exactly as ghf_score_softmax_fwd,
+ * s(i, j) the same chain; there is no target.  The CSR lists have the shape of the filter lists (pos_ptr int64 [B+1] ascending
+ * from 0, pos_idx int64 [nnz], every list sorted ascending) and name each query's positives P_i; an id that repeats counts
+ * once; nnz = 0 (both pointers may be NULL) means no positives.  scale: a finite float > 0; smoothing: 0 <= smoothing < 1
+ * (GHF_EINVAL otherwise).  With z_ij = scale s(i, j) and y_ij = (1 - smoothing) [j in P_i] + smoothing / N:
+ *   loss[i] = sum_{j<N} softplus(z_ij) - (1 - smoothing) sum_{j in P_i} z_ij - (smoothing / N) sum_{j<N} z_ij      (fp32 [B])
+ * = binary_cross_entropy_with_logits(z_i, y_i, reduction = "sum"); a mean over the candidates is the caller's division by N.
+ * softplus(z) = max(z, 0) + log1p(exp(-|z|)) with a log1p that keeps its tail (far-negative logits still count).
+ * ghf_score_bce_bwd: given grad_loss [B] and the forward's loss, with G_ij = grad_loss[i] scale (sigmoid(z_ij) - y_ij):
+ *   dq[i][:] = sum_j G_ij c[j][:]         [B, d], per query (NOT scattered through iq)
+ *   dc[j][:] = sum_i G_ij q[iq[i]][:]     [N, d], every row written (zeros included)
+ * An iq or list id out of range does not fault (no id is dereferenced before it is range-checked): that query's loss is NaN
+ * and it contributes nothing to dq / dc — the backward takes a NaN loss[i] as "this query takes no part" and reads nothing
+ * else from loss.  All sums run in a fixed order, no floating-point atomics: loss, dq and dc are bit-reproducible, and a
+ * query's loss does not depend on the other queries of the call.  workspace: the matching _workspace_bytes query (0 = bad
+ * sizes), 256-byte aligned; O(B) plus 12 bytes per (query, candidate slab) forward, the softmax backward's size backward.
+ * Nothing allocates or synchronises. */
+size_t ghf_score_bce_workspace_bytes(int64_t B, int64_t N, int d);
+int ghf_score_bce_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx, int64_t nnz,
+                      int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, void* workspace,
+                      size_t workspace_bytes, float* loss, void* stream);
+size_t ghf_score_bce_bwd_workspace_bytes(int64_t B, int64_t N, int d);
+int ghf_score_bce_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx, int64_t nnz,
+                      int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
+                      const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* dc, void* stream);
+
 /* ---- relation-typed query rows (csrc/relation.hip) ----------------------------------------------------
  * No counterpart in the reference, whose score_triple (models/hypergnn.py:304-318) ignores the relation.  The query side of
  * a (head, relation, ?) score: every query row multiplied by ITS relation's matrix, without gathering a matrix per query
