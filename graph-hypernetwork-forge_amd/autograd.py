@@ -399,6 +399,8 @@ class ScoreEdgesFn(torch.autograd.Function):
     def backward(ctx, g):
         embs, src, dst = ctx.saved_tensors
         P, N = src.numel(), embs.size(0)
+        if P == 0:                                          # no pair, nothing to group: the gradient of an empty sum
+            return torch.zeros_like(embs), None, None
         keys = torch.cat([src, dst]).clamp_(0, N - 1)
         perm, off = _native.group_edges(keys, N)
         partner = torch.cat([dst, src]).index_select(0, perm)
@@ -479,6 +481,8 @@ class ScorePairsFn(torch.autograd.Function):
 # ---- relation-typed scoring (models/relation_decoder.py; include/ghf.h: ghf_relation_rows) -----------------------------
 def _fold_rows(rows: torch.Tensor, ids: torch.Tensor, n: int) -> torch.Tensor:
     """out[v] = sum_{i: ids[i] = v} rows[i], [n, d]: grouped by v (ghf_group_edges, stable) and added in that order."""
+    if ids.numel() == 0:                                    # no row, nothing to group: zeros
+        return torch.zeros(n, rows.size(1), dtype=torch.float32, device=rows.device)
     perm, off = _native.group_edges(ids, n)
     return _native.segment_axpy(torch.ones(ids.numel(), dtype=torch.float32, device=rows.device), perm, rows, perm, off)
 

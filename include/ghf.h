@@ -615,7 +615,8 @@ int ghf_relation_scores_bwd_weights(const float* x, const int64_t* ia, const int
  * packed[i] = rows[idx[i]] (row_bytes, a multiple of 16) followed by extra[idx[i]] (extra_bytes, a multiple of 4; extra may be
  * NULL with extra_bytes = 0), i < n: the listed rows of a [nrows, row_bytes] table (and of a second table indexed alike — the
  * split form's scales) as one contiguous message; ghf_rows_unpack writes a received message to the rows' places.  idx: int64,
- * distinct for unpack (entries outside [0, nrows) are skipped).  Bit-exact copies. */
+ * distinct for unpack (entries outside [0, nrows) are skipped).  Bit-exact copies.  n = 0 is an empty message: nothing is
+ * read or written, idx and packed may be NULL. */
 int ghf_rows_pack(const void* rows, int64_t row_bytes, const void* extra, int64_t extra_bytes, const int64_t* idx, int64_t n,
                   int64_t nrows, void* packed, void* stream);
 int ghf_rows_unpack(const void* packed, const int64_t* idx, int64_t n, int64_t nrows, void* rows, int64_t row_bytes, void* extra,
