@@ -610,7 +610,12 @@ def _rank_args(q: torch.Tensor, c: torch.Tensor, iq: Optional[torch.Tensor], fil
     return q, c, iq, filt_ptr, filt_idx, B, nnz
 
 
-def _rank_workspace(workspace: Optional[torch.Tensor], need: int, device, what: str) -> torch.Tensor:
+def _workspace(workspace: Optional[torch.Tensor], size_fn, device, what: str, **sizes) -> torch.Tensor:
+    """The workspace of call `what`: size_fn (its *_workspace_bytes) says how many bytes `sizes` need, 0 meaning the library
+    cannot run them; the caller's workspace is checked against that, or a new one allocated."""
+    need = size_fn(*sizes.values())
+    if need == 0:
+        raise ValueError(f"{what}: unsupported sizes " + " ".join(f"{k}={v}" for k, v in sizes.items()))
     if workspace is None:
         return torch.empty(need, dtype=torch.uint8, device=device)
     workspace = _req(workspace, torch.uint8, "workspace")
@@ -638,10 +643,7 @@ def score_rank(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optio
     if target.dim() != 1 or target.numel() != B or target.device != q.device:
         raise ValueError(f"score_rank: target must be [B = {B}] on {q.device}, got {tuple(target.shape)} on {target.device}")
     N, d = c.size(0), c.size(1)
-    need = score_rank_workspace_bytes(B, N, d)
-    if need == 0:
-        raise ValueError(f"score_rank: unsupported sizes B={B} N={N} d={d}")
-    ws = _rank_workspace(workspace, need, q.device, "score_rank")
+    ws = _workspace(workspace, score_rank_workspace_bytes, q.device, "score_rank", B=B, N=N, d=d)
     if out is None:
         greater = torch.empty(B, dtype=torch.int64, device=q.device)
         equal = torch.empty(B, dtype=torch.int64, device=q.device)
@@ -664,10 +666,7 @@ def score_topk(q: torch.Tensor, c: torch.Tensor, k: int, iq: Optional[torch.Tens
     if not 1 <= k <= 128:
         raise ValueError(f"score_topk: k = {k} outside 1..128")
     N, d = c.size(0), c.size(1)
-    need = score_topk_workspace_bytes(B, N, d, k)
-    if need == 0:
-        raise ValueError(f"score_topk: unsupported sizes B={B} N={N} d={d} k={k}")
-    ws = _rank_workspace(workspace, need, q.device, "score_topk")
+    ws = _workspace(workspace, score_topk_workspace_bytes, q.device, "score_topk", B=B, N=N, d=d, k=k)
     if out is None:
         scores = torch.empty(B, k, dtype=torch.float32, device=q.device)
         ids = torch.empty(B, k, dtype=torch.int64, device=q.device)
@@ -694,10 +693,7 @@ def _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, what: str):
     target = _req(target, torch.int64, "target")
     if target.dim() != 1 or target.numel() != B or target.device != q.device:
         raise ValueError(f"{what}: target must be [B = {B}] on {q.device}, got {tuple(target.shape)} on {target.device}")
-    scale = float(scale)
-    if not (0.0 < scale < float("inf")):
-        raise ValueError(f"{what}: scale must be finite and positive, got {scale}")
-    return q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale
+    return q, c, target, iq, filt_ptr, filt_idx, B, nnz, _scale_arg(scale, what)
 
 
 def _f32_out(t: Optional[torch.Tensor], shape: Tuple[int, ...], device, what: str) -> torch.Tensor:
@@ -709,6 +705,18 @@ def _f32_out(t: Optional[torch.Tensor], shape: Tuple[int, ...], device, what: st
     return r
 
 
+def _f32_out_pair(out: Optional[Tuple[torch.Tensor, torch.Tensor]], shape0, shape1, device, what: str):
+    first, second = (None, None) if out is None else out
+    return _f32_out(first, shape0, device, what), _f32_out(second, shape1, device, what)
+
+
+def _scale_arg(scale, what: str) -> float:
+    scale = float(scale)
+    if not (0.0 < scale < float("inf")):
+        raise ValueError(f"{what}: scale must be finite and positive, got {scale}")
+    return scale
+
+
 def score_softmax_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optional[torch.Tensor] = None,
                       filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0,
                       workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
@@ -718,12 +726,8 @@ def score_softmax_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq
     allocates nothing."""
     q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, "score_softmax_fwd")
     N, d = c.size(0), c.size(1)
-    need = score_softmax_workspace_bytes(B, N, d)
-    if need == 0:
-        raise ValueError(f"score_softmax_fwd: unsupported sizes B={B} N={N} d={d}")
-    ws = _rank_workspace(workspace, need, q.device, "score_softmax_fwd")
-    loss = _f32_out(None if out is None else out[0], (B,), q.device, "score_softmax_fwd")
-    lse = _f32_out(None if out is None else out[1], (B,), q.device, "score_softmax_fwd")
+    ws = _workspace(workspace, score_softmax_workspace_bytes, q.device, "score_softmax_fwd", B=B, N=N, d=d)
+    loss, lse = _f32_out_pair(out, (B,), (B,), q.device, "score_softmax_fwd")
     _check(load().ghf_score_softmax_fwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
                                         d, scale, _ptr(ws), ws.numel(), _ptr(loss), _ptr(lse), _stream()), "ghf_score_softmax_fwd")
     return loss, lse
@@ -740,12 +744,8 @@ def score_softmax_bwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, ls
     if lse.numel() != B or grad_loss.numel() != B:
         raise ValueError(f"score_softmax_bwd: lse and grad_loss must hold B = {B} values")
     N, d = c.size(0), c.size(1)
-    need = score_softmax_bwd_workspace_bytes(B, N, d)
-    if need == 0:
-        raise ValueError(f"score_softmax_bwd: unsupported sizes B={B} N={N} d={d}")
-    ws = _rank_workspace(workspace, need, q.device, "score_softmax_bwd")
-    dq = _f32_out(None if out is None else out[0], (B, d), q.device, "score_softmax_bwd")
-    dc = _f32_out(None if out is None else out[1], (N, d), q.device, "score_softmax_bwd")
+    ws = _workspace(workspace, score_softmax_bwd_workspace_bytes, q.device, "score_softmax_bwd", B=B, N=N, d=d)
+    dq, dc = _f32_out_pair(out, (B, d), (N, d), q.device, "score_softmax_bwd")
     _check(load().ghf_score_softmax_bwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
                                         d, scale, _ptr(lse), _ptr(grad_loss), _ptr(ws), ws.numel(), _ptr(dq), _ptr(dc), _stream()),
            "ghf_score_softmax_bwd")
@@ -763,9 +763,7 @@ def score_bce_bwd_workspace_bytes(B: int, N: int, d: int) -> int:
 
 def _bce_args(q, c, iq, pos_ptr, pos_idx, scale, smoothing, what: str):
     q, c, iq, pos_ptr, pos_idx, B, nnz = _rank_args(q, c, iq, pos_ptr, pos_idx, what)
-    scale, smoothing = float(scale), float(smoothing)
-    if not (0.0 < scale < float("inf")):
-        raise ValueError(f"{what}: scale must be finite and positive, got {scale}")
+    scale, smoothing = _scale_arg(scale, what), float(smoothing)
     if not (0.0 <= smoothing < 1.0):
         raise ValueError(f"{what}: smoothing must be in [0, 1), got {smoothing}")
     return q, c, iq, pos_ptr, pos_idx, B, nnz, scale, smoothing
@@ -780,10 +778,7 @@ def score_bce_fwd(q: torch.Tensor, c: torch.Tensor, iq: Optional[torch.Tensor] =
     nothing."""
     q, c, iq, pos_ptr, pos_idx, B, nnz, scale, smoothing = _bce_args(q, c, iq, pos_ptr, pos_idx, scale, smoothing, "score_bce_fwd")
     N, d = c.size(0), c.size(1)
-    need = score_bce_workspace_bytes(B, N, d)
-    if need == 0:
-        raise ValueError(f"score_bce_fwd: unsupported sizes B={B} N={N} d={d}")
-    ws = _rank_workspace(workspace, need, q.device, "score_bce_fwd")
+    ws = _workspace(workspace, score_bce_workspace_bytes, q.device, "score_bce_fwd", B=B, N=N, d=d)
     loss = _f32_out(out, (B,), q.device, "score_bce_fwd")
     _check(load().ghf_score_bce_fwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(pos_ptr), _ptr(pos_idx), nnz, q.size(0), N, B, d, scale,
                                     smoothing, _ptr(ws), ws.numel(), _ptr(loss), _stream()), "ghf_score_bce_fwd")
@@ -801,12 +796,8 @@ def score_bce_bwd(q: torch.Tensor, c: torch.Tensor, loss: torch.Tensor, grad_los
     if loss.numel() != B or grad_loss.numel() != B:
         raise ValueError(f"score_bce_bwd: loss and grad_loss must hold B = {B} values")
     N, d = c.size(0), c.size(1)
-    need = score_bce_bwd_workspace_bytes(B, N, d)
-    if need == 0:
-        raise ValueError(f"score_bce_bwd: unsupported sizes B={B} N={N} d={d}")
-    ws = _rank_workspace(workspace, need, q.device, "score_bce_bwd")
-    dq = _f32_out(None if out is None else out[0], (B, d), q.device, "score_bce_bwd")
-    dc = _f32_out(None if out is None else out[1], (N, d), q.device, "score_bce_bwd")
+    ws = _workspace(workspace, score_bce_bwd_workspace_bytes, q.device, "score_bce_bwd", B=B, N=N, d=d)
+    dq, dc = _f32_out_pair(out, (B, d), (N, d), q.device, "score_bce_bwd")
     _check(load().ghf_score_bce_bwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(pos_ptr), _ptr(pos_idx), nnz, q.size(0), N, B, d, scale,
                                     smoothing, _ptr(loss), _ptr(grad_loss), _ptr(ws), ws.numel(), _ptr(dq), _ptr(dc), _stream()),
            "ghf_score_bce_bwd")
@@ -849,13 +840,12 @@ def relation_rows(x: torch.Tensor, rel: torch.Tensor, W: torch.Tensor, bias: Opt
     for name, t in (("W", W), ("rel", rel), ("ix", ix), ("bias", bias)):
         if t is not None and t.device != x.device:
             raise RuntimeError(f"relation_rows: {name} is on {t.device}, x on {x.device}")
-    need = relation_rows_workspace_bytes(B, R)
-    if need == 0 or rows_x == 0 or d == 0:
+    if rows_x == 0 or d == 0:
         raise ValueError(f"relation_rows: unsupported sizes B={B} R={R} rows={rows_x} d={d}")
+    ws = _workspace(workspace, relation_rows_workspace_bytes, x.device, "relation_rows", B=B, R=R)
     perm, goff = group_edges(rel, R) if group is None else (_req(group[0], torch.int64, "perm"), _req(group[1], torch.int64, "goff"))
     if perm.numel() != B or goff.numel() != R + 1:
         raise ValueError(f"relation_rows: group must be (perm [{B}], goff [{R + 1}])")
-    ws = _rank_workspace(workspace, need, x.device, "relation_rows")
     out = _f32_out(out, (B, d), x.device, "relation_rows")
     flags = (GHF_REL_ADD_X if add_x else 0) | (GHF_REL_TRANSPOSE if transpose else 0)
     _check(load().ghf_relation_rows(_ptr(x), _ptr(ix), _ptr(rel), _ptr(W), _ptr(bias), _ptr(perm), _ptr(goff), rows_x, B, R, d,
@@ -921,10 +911,7 @@ def relation_scores_bwd_rows(x: torch.Tensor, ia: torch.Tensor, G: torch.Tensor,
     """out[i] = sum_u G[i][u] q(i, u), fp32 [B, d], u ascending (q as in relation_scores).  As called: the gradient of
     the b rows; with ia = the forward's ib, `transpose` flipped and no bias: the gradient of the a rows."""
     x, ia, _, W, bias, G, rows_x, B, U, d = _relation_scores_args(x, ia, None, W, bias, G, "relation_scores_bwd_rows")
-    need = relation_scores_bwd_rows_workspace_bytes(B, U, d)
-    if need == 0:
-        raise ValueError(f"relation_scores_bwd_rows: unsupported sizes B={B} U={U} d={d}")
-    ws = _rank_workspace(workspace, need, x.device, "relation_scores_bwd_rows")
+    ws = _workspace(workspace, relation_scores_bwd_rows_workspace_bytes, x.device, "relation_scores_bwd_rows", B=B, U=U, d=d)
     out = _f32_out(out, (B, d), x.device, "relation_scores_bwd_rows")
     flags = (GHF_REL_ADD_X if add_x else 0) | (GHF_REL_TRANSPOSE if transpose else 0)
     _check(load().ghf_relation_scores_bwd_rows(_ptr(x), _ptr(ia), _ptr(G), _ptr(W), _ptr(bias), rows_x, B, U, d, flags, _ptr(ws),
@@ -940,10 +927,7 @@ def relation_scores_bwd_weights(x: torch.Tensor, ia: torch.Tensor, ib: torch.Ten
     x, ia, ib, _, _, G, rows_x, B, U, d = _relation_scores_args(x, ia, ib, None, None, G, "relation_scores_bwd_weights")
     if ib is None:
         raise ValueError("relation_scores_bwd_weights: ib is needed")
-    need = relation_scores_bwd_weights_workspace_bytes(B, U, d)
-    if need == 0:
-        raise ValueError(f"relation_scores_bwd_weights: unsupported sizes B={B} U={U} d={d}")
-    ws = _rank_workspace(workspace, need, x.device, "relation_scores_bwd_weights")
+    ws = _workspace(workspace, relation_scores_bwd_weights_workspace_bytes, x.device, "relation_scores_bwd_weights", B=B, U=U, d=d)
     dW = _f32_out(None if out is None else out[0], (U, d, d), x.device, "relation_scores_bwd_weights")
     db = _f32_out(None if out is None else out[1], (U, d), x.device, "relation_scores_bwd_weights") if want_bias else None
     _check(load().ghf_relation_scores_bwd_weights(_ptr(x), _ptr(ia), _ptr(ib), _ptr(G), rows_x, B, U, d, 0, _ptr(ws), ws.numel(),

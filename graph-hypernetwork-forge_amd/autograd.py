@@ -408,57 +408,67 @@ class ScoreEdgesFn(torch.autograd.Function):
         return _native.segment_axpy(g.contiguous().float(), pair, embs, partner, off), None, None
 
 
+def _all_node_loss_grads(ctx, embs, rows, query, dq, dc):
+    """(d embs, d rows) of a loss against every node from its backward call's dq (per query) and dc (per candidate).  With
+    the query rows given (q = rows, c = embs) they are those, as they are.  Without (q = c = embs): d embs = dc + dq summed
+    into the rows `query` names, grouped by node (ghf_group_edges, stable) and added per node in that order (_fold_rows), as
+    ScoreEdgesFn does: reproducible."""
+    if rows is None:
+        return _native.add3(dc, _fold_rows(dq, query, embs.size(0)), out=dc), None
+    return (dc if ctx.needs_input_grad[0] else None), (dq if ctx.needs_input_grad[1] else None)
+
+
 class SoftmaxLossFn(torch.autograd.Function):
-    """loss_i = log sum_{j in J_i} exp(scale embs[query_i] . embs[j]) - scale embs[query_i] . embs[target_i] over ALL nodes j
-    outside query i's filter list (HyperGNN.softmax_loss; include/ghf.h: ghf_score_softmax_fwd).  The [B, N] logits exist
-    neither here nor in the backward, which recomputes them tile by tile from the saved lse (ghf_score_softmax_bwd with
-    q = c = embs): d embs = dc + the per-query rows dq summed into the rows `query` names — grouped by node
-    (ghf_group_edges, stable) and added per node in that order, as ScoreEdgesFn does: reproducible."""
+    """loss_i = log sum_{j in J_i} exp(scale q_i . embs[j]) - scale q_i . embs[target_i] over ALL nodes j outside query i's
+    filter list (HyperGNN.softmax_loss; include/ghf.h: ghf_score_softmax_fwd), with q_i = embs[query_i], or q_i = rows_i where
+    the query rows are given (``softmax_loss(..., query_rows=Q)``): exactly one of `rows` and `query` is.  The [B, N] logits
+    exist neither here nor in the backward, which recomputes them tile by tile from the saved lse (ghf_score_softmax_bwd);
+    _all_node_loss_grads turns its (dq, dc) into the gradients."""
 
     @staticmethod
-    def forward(ctx, embs, query, target, ptr, idx, scale: float):
+    def forward(ctx, embs, rows, query, target, ptr, idx, scale: float):
+        assert (rows is None) != (query is None)
         embs = embs.contiguous().float()
-        loss, lse = _native.score_softmax_fwd(embs, embs, target, iq=query, filt_ptr=ptr, filt_idx=idx, scale=scale)
-        ctx.save_for_backward(embs, lse, query, target, *(() if ptr is None else (ptr, idx)))
+        rows = None if rows is None else rows.contiguous().float()
+        loss, lse = _native.score_softmax_fwd(embs if rows is None else rows, embs, target, iq=query, filt_ptr=ptr, filt_idx=idx,
+                                              scale=scale)
+        ctx.save_for_backward(embs, rows, query, target, ptr, idx, lse)
         ctx.scale = scale
         return loss
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        embs, lse, query, target, *lists = ctx.saved_tensors
-        ptr, idx = lists if lists else (None, None)
-        dq, dc = _native.score_softmax_bwd(embs, embs, target, lse, g.contiguous().float(), iq=query, filt_ptr=ptr, filt_idx=idx,
-                                           scale=ctx.scale)
-        B, N = query.numel(), embs.size(0)
-        perm, off = _native.group_edges(query, N)
-        folded = _native.segment_axpy(torch.ones(B, dtype=torch.float32, device=embs.device), perm, dq, perm, off)
-        return _native.add3(dc, folded, out=dc), None, None, None, None, None
+        embs, rows, query, target, ptr, idx, lse = ctx.saved_tensors
+        dq, dc = _native.score_softmax_bwd(embs if rows is None else rows, embs, target, lse, g.contiguous().float(), iq=query,
+                                           filt_ptr=ptr, filt_idx=idx, scale=ctx.scale)
+        return _all_node_loss_grads(ctx, embs, rows, query, dq, dc) + (None,) * 5
 
 
 class BceLossFn(torch.autograd.Function):
-    """loss_i = sum_j bce_with_logits(scale embs[query_i] . embs[j], y_ij) over ALL nodes j, y_ij = (1 - smoothing) [j in query
-    i's list] + smoothing / N (HyperGNN.bce_loss; include/ghf.h: ghf_score_bce_fwd).  Neither the [B, N] logits nor the labels
-    exist, here or in the backward, which recomputes the logits tile by tile (ghf_score_bce_bwd with q = c = embs): d embs =
-    dc + the per-query rows dq summed into the rows `query` names, grouped by node and added in that order as SoftmaxLossFn
-    does: reproducible."""
+    """loss_i = sum_j bce_with_logits(scale q_i . embs[j], y_ij) over ALL nodes j, y_ij = (1 - smoothing) [j in query i's list]
+    + smoothing / N (HyperGNN.bce_loss; include/ghf.h: ghf_score_bce_fwd), q_i and the pair `rows` / `query` as in
+    SoftmaxLossFn.  Neither the [B, N] logits nor the labels exist, here or in the backward, which recomputes the logits tile
+    by tile (ghf_score_bce_bwd); _all_node_loss_grads turns its (dq, dc) into the gradients."""
 
     @staticmethod
-    def forward(ctx, embs, query, ptr, idx, scale: float, smoothing: float):
+    def forward(ctx, embs, rows, query, ptr, idx, scale: float, smoothing: float):
+        assert (rows is None) != (query is None)
         embs = embs.contiguous().float()
-        loss = _native.score_bce_fwd(embs, embs, iq=query, pos_ptr=ptr, pos_idx=idx, scale=scale, smoothing=smoothing)
-        ctx.save_for_backward(embs, loss, query, *(() if ptr is None else (ptr, idx)))
+        rows = None if rows is None else rows.contiguous().float()
+        loss = _native.score_bce_fwd(embs if rows is None else rows, embs, iq=query, pos_ptr=ptr, pos_idx=idx, scale=scale,
+                                     smoothing=smoothing)
+        ctx.save_for_backward(embs, rows, query, ptr, idx, loss)
         ctx.scale, ctx.smoothing = scale, smoothing
         return loss
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        embs, loss, query, *lists = ctx.saved_tensors
-        ptr, idx = lists if lists else (None, None)
-        dq, dc = _native.score_bce_bwd(embs, embs, loss, g.contiguous().float(), iq=query, pos_ptr=ptr, pos_idx=idx,
-                                       scale=ctx.scale, smoothing=ctx.smoothing)
-        return _native.add3(dc, _fold_rows(dq, query, embs.size(0)), out=dc), None, None, None, None, None
+        embs, rows, query, ptr, idx, loss = ctx.saved_tensors
+        dq, dc = _native.score_bce_bwd(embs if rows is None else rows, embs, loss, g.contiguous().float(), iq=query, pos_ptr=ptr,
+                                       pos_idx=idx, scale=ctx.scale, smoothing=ctx.smoothing)
+        return _all_node_loss_grads(ctx, embs, rows, query, dq, dc) + (None,) * 5
 
 
 class ScorePairsFn(torch.autograd.Function):
@@ -583,48 +593,3 @@ class ScoreRowsFn(torch.autograd.Function):
             perm, off = _native.group_edges(tail, embs.size(0))
             dE = _native.segment_axpy(g, perm, Q, perm, off)
         return dQ, dE, None
-
-
-class SoftmaxRowsLossFn(torch.autograd.Function):
-    """SoftmaxLossFn with the query rows given (``softmax_loss(..., query_rows=Q)``): q = Q, c = embs.
-    ghf_score_softmax_bwd returns dq per query and dc per candidate: the gradients of Q and of embs as they are, with no
-    fold through the query ids."""
-
-    @staticmethod
-    def forward(ctx, embs, rows, target, ptr, idx, scale: float):
-        embs, rows = embs.contiguous().float(), rows.contiguous().float()
-        loss, lse = _native.score_softmax_fwd(rows, embs, target, filt_ptr=ptr, filt_idx=idx, scale=scale)
-        ctx.save_for_backward(embs, rows, lse, target, *(() if ptr is None else (ptr, idx)))
-        ctx.scale = scale
-        return loss
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        embs, rows, lse, target, *lists = ctx.saved_tensors
-        ptr, idx = lists if lists else (None, None)
-        dq, dc = _native.score_softmax_bwd(rows, embs, target, lse, g.contiguous().float(), filt_ptr=ptr, filt_idx=idx,
-                                           scale=ctx.scale)
-        return (dc if ctx.needs_input_grad[0] else None), (dq if ctx.needs_input_grad[1] else None), None, None, None, None
-
-
-class BceRowsLossFn(torch.autograd.Function):
-    """BceLossFn with the query rows given (``bce_loss(..., query_rows=Q)``): q = Q, c = embs.  ghf_score_bce_bwd's dq is the
-    gradient of Q and its dc that of embs, as they are."""
-
-    @staticmethod
-    def forward(ctx, embs, rows, ptr, idx, scale: float, smoothing: float):
-        embs, rows = embs.contiguous().float(), rows.contiguous().float()
-        loss = _native.score_bce_fwd(rows, embs, pos_ptr=ptr, pos_idx=idx, scale=scale, smoothing=smoothing)
-        ctx.save_for_backward(embs, rows, loss, *(() if ptr is None else (ptr, idx)))
-        ctx.scale, ctx.smoothing = scale, smoothing
-        return loss
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        embs, rows, loss, *lists = ctx.saved_tensors
-        ptr, idx = lists if lists else (None, None)
-        dq, dc = _native.score_bce_bwd(rows, embs, loss, g.contiguous().float(), pos_ptr=ptr, pos_idx=idx, scale=ctx.scale,
-                                       smoothing=ctx.smoothing)
-        return (dc if ctx.needs_input_grad[0] else None), (dq if ctx.needs_input_grad[1] else None), None, None, None, None

@@ -28,15 +28,6 @@ size_t score_bce_workspace_bytes(int64_t B, int64_t N, int d) {
     return rk_align((size_t)B * 4) + rk_align((size_t)B * (size_t)g.slabs * 12);
 }
 
-// a query whose row id is out of range takes no part (list_range_kernel then clears the queries with a bad list id)
-__global__ __launch_bounds__(256) void bce_prep_kernel(const int64_t* __restrict__ iq, int64_t rows_q, int64_t B,
-                                                       int* __restrict__ valid) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= B) return;
-    const int64_t r = iq ? iq[i] : i;
-    valid[i] = r >= 0 && r < rows_q ? 1 : 0;
-}
-
 __global__ __launch_bounds__(256) void bce_finish_kernel(const float* __restrict__ part, const int* __restrict__ valid, int64_t B,
                                                          int64_t slabs, float pos_w, float neg_w, float* __restrict__ loss) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -54,39 +45,23 @@ __global__ __launch_bounds__(256) void bce_finish_kernel(const float* __restrict
 int launch_score_bce_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, void* ws,
                          size_t ws_bytes, float* loss, hipStream_t stream) {
-    RankGeom g;
-    GHF_REQUIRE(d > 0 && rows_q > 0 && N > 0 && B > 0 && nnz >= 0, "score_bce_fwd: bad shape");
-    if (d > RK_MAX_D) return set_err(GHF_EUNSUPPORTED, "score_bce_fwd: d = %d exceeds %d", d, RK_MAX_D);
-    GHF_REQUIRE(softmax_geom(B, N, d, &g), "score_bce_fwd: B or N out of range");
-    GHF_REQUIRE(iq || B <= rows_q, "score_bce_fwd: B exceeds the rows of q");
-    GHF_REQUIRE(ws_bytes >= score_bce_workspace_bytes(B, N, d), "score_bce_fwd: workspace of %zu bytes, need %zu", ws_bytes,
-                score_bce_workspace_bytes(B, N, d));
+    RankArgs a;
+    int rc = score_open("score_bce_fwd", softmax_geom, score_bce_workspace_bytes(B, N, d), q, c, iq, pos_ptr, pos_idx, nnz, rows_q, N, B,
+                        d, ws_bytes, &a);
+    if (rc != GHF_OK) return rc;
     int* valid = (int*)ws;
-    float* part = (float*)((char*)ws + rk_align((size_t)B * 4));
     const unsigned qb = (unsigned)cdiv(B, 256);
-    bce_prep_kernel<<<qb, 256, 0, stream>>>(iq, rows_q, B, valid);
+    // a query whose row id is out of range takes no part; list_range_kernel then clears the queries with a bad list id
+    score_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, nullptr, rows_q, N, B, d, nullptr, valid, nullptr, nullptr);
     GHF_LAUNCH_CHECK();
     if (nnz > 0) {
         list_range_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(pos_ptr, pos_idx, nnz, N, B, valid);
         GHF_LAUNCH_CHECK();
     }
-    RankArgs a = {};
-    a.q = q; a.c = c; a.iq = iq; a.rows_q = rows_q; a.N = N; a.B = B; a.d = d;
-    a.qtiles = g.qtiles; a.slab_tiles = g.slab_tiles; a.slabs = g.slabs;
-    a.filt_ptr = nnz > 0 ? pos_ptr : nullptr; a.filt_idx = pos_idx; a.nnz = nnz;
-    a.scale = scale; a.ws_bce = part;
-    const unsigned grid = (unsigned)(g.qtiles * g.slabs);
-    if (rank_ctile(d) == 256) {
-        const size_t lds = rank_lds_bytes(d, 32, 256);
-        GHF_SET_MAX_LDS((rank_tile_kernel<32, 256, RK_BCE>), lds);
-        rank_tile_kernel<32, 256, RK_BCE><<<grid, 512, lds, stream>>>(a);
-    } else {
-        const size_t lds = rank_lds_bytes(d, 16, 128);
-        GHF_SET_MAX_LDS((rank_tile_kernel<16, 128, RK_BCE>), lds);
-        rank_tile_kernel<16, 128, RK_BCE><<<grid, 256, lds, stream>>>(a);
-    }
-    GHF_LAUNCH_CHECK();
-    bce_finish_kernel<<<qb, 256, 0, stream>>>(part, valid, B, g.slabs, 1.f - smoothing, smoothing / (float)N, loss);
+    a.scale = scale; a.ws_bce = (float*)((char*)ws + rk_align((size_t)B * 4));
+    rc = launch_rank_tiles<RK_BCE>(a, stream);
+    if (rc != GHF_OK) return rc;
+    bce_finish_kernel<<<qb, 256, 0, stream>>>(a.ws_bce, valid, B, a.slabs, 1.f - smoothing, smoothing / (float)N, loss);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }

@@ -579,14 +579,26 @@ int ghf_score_pairs_fwd(const float* a, const float* b, const int64_t* ia, const
     return launch_score_pairs(a, b, ia, ib, rows_a, rows_b, n, d, scores, (hipStream_t)stream);
 }
 
+// What the six ghf_score_* calls check before they launch, in this order.  `ptrs`: every pointer the call needs is there;
+// `noun`: what its lists are ("filter" or "positive"); an operation without a scale or smoothing passes 1 and 0.
+static int score_entry_check(const char* op, const char* noun, bool ptrs, const int64_t* list_ptr, const int64_t* list_idx,
+                             int64_t nnz, float scale, float smoothing, const void* workspace) {
+    GHF_REQUIRE(ptrs && workspace, "%s: null pointer argument", op);
+    GHF_REQUIRE(nnz <= 0 || (list_ptr && list_idx), "%s: null %s list with nnz > 0", op, noun);
+    GHF_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, "%s: scale must be finite and positive", op);
+    GHF_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "%s: smoothing must be in [0, 1)", op);
+    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace not 256-byte aligned", op);
+    return GHF_OK;
+}
+
 size_t ghf_score_rank_workspace_bytes(int64_t B, int64_t N, int d) { return score_rank_workspace_bytes(B, N, d); }
 
 int ghf_score_rank(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                    const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, void* workspace,
                    size_t workspace_bytes, int64_t* greater, int64_t* equal, void* stream) {
-    GHF_REQUIRE(q && c && target && workspace && greater && equal, "score_rank: null pointer argument");
-    GHF_REQUIRE(nnz <= 0 || (filt_ptr && filt_idx), "score_rank: null filter list with nnz > 0");
-    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "score_rank: workspace not 256-byte aligned");
+    const int rc = score_entry_check("score_rank", "filter", q && c && target && greater && equal, filt_ptr, filt_idx, nnz, 1.f, 0.f,
+                                     workspace);
+    if (rc != GHF_OK) return rc;
     return launch_score_rank(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, workspace, workspace_bytes, greater, equal,
                              (hipStream_t)stream);
 }
@@ -596,9 +608,8 @@ size_t ghf_score_topk_workspace_bytes(int64_t B, int64_t N, int d, int k) { retu
 int ghf_score_topk(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
                    int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, void* workspace, size_t workspace_bytes,
                    float* scores, int64_t* ids, void* stream) {
-    GHF_REQUIRE(q && c && workspace && scores && ids, "score_topk: null pointer argument");
-    GHF_REQUIRE(nnz <= 0 || (filt_ptr && filt_idx), "score_topk: null filter list with nnz > 0");
-    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "score_topk: workspace not 256-byte aligned");
+    const int rc = score_entry_check("score_topk", "filter", q && c && scores && ids, filt_ptr, filt_idx, nnz, 1.f, 0.f, workspace);
+    if (rc != GHF_OK) return rc;
     return launch_score_topk(q, c, iq, filt_ptr, filt_idx, nnz, rows_q, N, B, d, k, workspace, workspace_bytes, scores, ids,
                              (hipStream_t)stream);
 }
@@ -608,10 +619,9 @@ size_t ghf_score_softmax_workspace_bytes(int64_t B, int64_t N, int d) { return s
 int ghf_score_softmax_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                           const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                           void* workspace, size_t workspace_bytes, float* loss, float* lse, void* stream) {
-    GHF_REQUIRE(q && c && target && workspace && loss && lse, "score_softmax_fwd: null pointer argument");
-    GHF_REQUIRE(nnz <= 0 || (filt_ptr && filt_idx), "score_softmax_fwd: null filter list with nnz > 0");
-    GHF_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, "score_softmax_fwd: scale must be finite and positive");
-    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "score_softmax_fwd: workspace not 256-byte aligned");
+    const int rc = score_entry_check("score_softmax_fwd", "filter", q && c && target && loss && lse, filt_ptr, filt_idx, nnz, scale, 0.f,
+                                     workspace);
+    if (rc != GHF_OK) return rc;
     return launch_score_softmax_fwd(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, workspace, workspace_bytes,
                                     loss, lse, (hipStream_t)stream);
 }
@@ -622,10 +632,9 @@ int ghf_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, con
                           const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                           const float* lse, const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* dc,
                           void* stream) {
-    GHF_REQUIRE(q && c && target && lse && grad_loss && workspace && dq && dc, "score_softmax_bwd: null pointer argument");
-    GHF_REQUIRE(nnz <= 0 || (filt_ptr && filt_idx), "score_softmax_bwd: null filter list with nnz > 0");
-    GHF_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, "score_softmax_bwd: scale must be finite and positive");
-    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "score_softmax_bwd: workspace not 256-byte aligned");
+    const int rc = score_entry_check("score_softmax_bwd", "filter", q && c && target && lse && grad_loss && dq && dc, filt_ptr, filt_idx,
+                                     nnz, scale, 0.f, workspace);
+    if (rc != GHF_OK) return rc;
     return launch_score_softmax_bwd(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, lse, grad_loss, workspace,
                                     workspace_bytes, dq, dc, (hipStream_t)stream);
 }
@@ -635,11 +644,8 @@ size_t ghf_score_bce_workspace_bytes(int64_t B, int64_t N, int d) { return score
 int ghf_score_bce_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx, int64_t nnz,
                       int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, void* workspace,
                       size_t workspace_bytes, float* loss, void* stream) {
-    GHF_REQUIRE(q && c && workspace && loss, "score_bce_fwd: null pointer argument");
-    GHF_REQUIRE(nnz <= 0 || (pos_ptr && pos_idx), "score_bce_fwd: null positive list with nnz > 0");
-    GHF_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, "score_bce_fwd: scale must be finite and positive");
-    GHF_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "score_bce_fwd: smoothing must be in [0, 1)");
-    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "score_bce_fwd: workspace not 256-byte aligned");
+    const int rc = score_entry_check("score_bce_fwd", "positive", q && c && loss, pos_ptr, pos_idx, nnz, scale, smoothing, workspace);
+    if (rc != GHF_OK) return rc;
     return launch_score_bce_fwd(q, c, iq, pos_ptr, pos_idx, nnz, rows_q, N, B, d, scale, smoothing, workspace, workspace_bytes, loss,
                                 (hipStream_t)stream);
 }
@@ -649,11 +655,9 @@ size_t ghf_score_bce_bwd_workspace_bytes(int64_t B, int64_t N, int d) { return s
 int ghf_score_bce_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx, int64_t nnz,
                       int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
                       const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* dc, void* stream) {
-    GHF_REQUIRE(q && c && loss && grad_loss && workspace && dq && dc, "score_bce_bwd: null pointer argument");
-    GHF_REQUIRE(nnz <= 0 || (pos_ptr && pos_idx), "score_bce_bwd: null positive list with nnz > 0");
-    GHF_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, "score_bce_bwd: scale must be finite and positive");
-    GHF_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "score_bce_bwd: smoothing must be in [0, 1)");
-    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "score_bce_bwd: workspace not 256-byte aligned");
+    const int rc = score_entry_check("score_bce_bwd", "positive", q && c && loss && grad_loss && dq && dc, pos_ptr, pos_idx, nnz, scale,
+                                     smoothing, workspace);
+    if (rc != GHF_OK) return rc;
     return launch_score_bce_bwd(q, c, iq, pos_ptr, pos_idx, nnz, rows_q, N, B, d, scale, smoothing, loss, grad_loss, workspace,
                                 workspace_bytes, dq, dc, (hipStream_t)stream);
 }

@@ -22,7 +22,7 @@
 // adds fma(0, 0, s) = s).  dot_chain() below is that chain on the VALU: the target's score t_i and the filter corrections
 // come from it and compare equal to the tile's value of the same pair.
 //
-// Rank:   greater / equal start at 0 (rank_prep_kernel, which also computes t_i), every (query tile, candidate slab)
+// Rank:   greater / equal start at 0 (score_prep_kernel, which also computes t_i), every (query tile, candidate slab)
 //         workgroup adds its integer counts with atomics (order-free, so reproducible), rank_filter_kernel takes the listed
 //         known-true candidates out again by recomputing their scores, rank_finish_kernel takes the target out of `equal`
 //         and writes -1 for a query with an id out of range.
@@ -31,7 +31,11 @@
 //         loses).  An entry is one 64-bit key ordered as (score descending, id ascending).  A candidate above the threshold
 //         that is not in the query's (sorted) filter list is appended; when the next step could overflow the buffer a wave
 //         selects the k best in place (select_in_place).  topk_merge_kernel merges the slabs' sorted lists: a key's
-//         position is the number of keys above it, one binary search per slab.
+//         position is the number of keys above it, one binary search per slab.  A query with an id out of range
+//         (score_prep_kernel, list_range_kernel) gets NaN scores and ids -1.
+//
+// The host side the four operations share (the prep kernel, the lists' range check, the checks that open a launch, the
+// choice of the sweep's instantiation) is in rank_sweep.h.
 #include "common.h"
 #include "rank_sweep.h"
 
@@ -56,29 +60,8 @@ size_t score_topk_workspace_bytes(int64_t B, int64_t N, int d, int k) {
 }
 
 // ---- rank: the small kernels around the sweep -----------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rank_prep_kernel(const float* __restrict__ q, const float* __restrict__ c,
-                                                        const int64_t* __restrict__ iq, const int64_t* __restrict__ target,
-                                                        int64_t rows_q, int64_t N, int64_t B, int d, float* __restrict__ t,
-                                                        int* __restrict__ valid, long long* __restrict__ greater,
-                                                        long long* __restrict__ equal) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= B) return;
-    const int64_t r = iq ? iq[i] : i;
-    bool ok = r >= 0 && r < rows_q;
-    float ti = __int_as_float(0x7FC00000);          // NaN: compares false with every score, so a bad query counts nothing
-    if (target) {
-        const int64_t tg = target[i];
-        ok = ok && tg >= 0 && tg < N;
-        if (ok) ti = dot_chain(q + (size_t)r * d, c + (size_t)tg * d, d, rows_vec(q, d) && rows_vec(c, d));
-        greater[i] = 0;
-        equal[i] = 0;
-        t[i] = ti;
-    }
-    valid[i] = ok ? 1 : 0;
-}
-
-// one thread per filter entry: an id out of range marks its query; in the rank call the entry's score is recomputed and taken
-// out of the count it went into (lists are sorted: a repeat is the entry before; the target is taken out by rank_finish)
+// one thread per filter entry: an id out of range marks its query; any other entry's score is recomputed and taken out of the
+// count it went into (lists are sorted: a repeat is the entry before; the target is taken out by rank_finish)
 __global__ __launch_bounds__(256) void rank_filter_kernel(const float* __restrict__ q, const float* __restrict__ c,
                                                           const int64_t* __restrict__ iq, const int64_t* __restrict__ target,
                                                           const int64_t* __restrict__ filt_ptr, const int64_t* __restrict__ filt_idx,
@@ -87,21 +70,16 @@ __global__ __launch_bounds__(256) void rank_filter_kernel(const float* __restric
                                                           unsigned long long* __restrict__ equal) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= nnz) return;
-    int64_t lo = 0, hi = B;                          // the query whose list holds e: last i with filt_ptr[i] <= e
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (filt_ptr[mid] <= e) lo = mid; else hi = mid;
-    }
-    const int64_t i = lo;
-    if (filt_ptr[i] > e || filt_ptr[i + 1] <= e) return;      // not inside any list (a malformed pointer array)
+    int64_t i;
+    if (!list_owner(filt_ptr, B, e, &i)) return;
     const int64_t j = filt_idx[e];
     if (j < 0 || j >= N) {
         valid[i] = 0;
         return;
     }
-    if (!target || !valid[i]) return;
+    if (!valid[i]) return;
     if (j == target[i] || (e > filt_ptr[i] && filt_idx[e - 1] == j)) return;
-    const int64_t r = iq ? iq[i] : i;                // in range: rank_prep_kernel said so (valid[i] was 1)
+    const int64_t r = iq ? iq[i] : i;                // in range: score_prep_kernel said so (valid[i] was 1)
     const float s = dot_chain(q + (size_t)r * d, c + (size_t)j * d, d, rows_vec(q, d) && rows_vec(c, d));
     const float ti = t[i];
     if (s > ti) atomicAdd(&greater[i], ~0ull);
@@ -168,43 +146,20 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* __restr
 }
 
 // ---- launches -------------------------------------------------------------------------------------------------------------
-template <bool TOPK>
-static int launch_tiles(const RankArgs& a, hipStream_t stream) {
-    constexpr int MODE = TOPK ? RK_TOPK : RK_RANK;
-    const unsigned grid = (unsigned)(a.qtiles * a.slabs);
-    if (rank_ctile(a.d) == 256) {
-        const size_t lds = rank_lds_bytes(a.d, 32, 256);
-        GHF_SET_MAX_LDS((rank_tile_kernel<32, 256, MODE>), lds);
-        rank_tile_kernel<32, 256, MODE><<<grid, 512, lds, stream>>>(a);
-    } else {
-        const size_t lds = rank_lds_bytes(a.d, 16, 128);
-        GHF_SET_MAX_LDS((rank_tile_kernel<16, 128, MODE>), lds);
-        rank_tile_kernel<16, 128, MODE><<<grid, 256, lds, stream>>>(a);
-    }
-    GHF_LAUNCH_CHECK();
-    return GHF_OK;
-}
-
 int launch_score_rank(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                       const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, void* ws,
                       size_t ws_bytes, int64_t* greater, int64_t* equal, hipStream_t stream) {
-    RankGeom g;
-    GHF_REQUIRE(d > 0 && rows_q > 0 && N > 0 && B > 0 && nnz >= 0, "score_rank: bad shape");
-    if (d > RK_MAX_D) return set_err(GHF_EUNSUPPORTED, "score_rank: d = %d exceeds %d", d, RK_MAX_D);
-    GHF_REQUIRE(rank_geom_rank(B, N, d, &g), "score_rank: B or N out of range");
-    GHF_REQUIRE(iq || B <= rows_q, "score_rank: B exceeds the rows of q");
-    GHF_REQUIRE(ws_bytes >= score_rank_workspace_bytes(B, N, d), "score_rank: workspace of %zu bytes, need %zu", ws_bytes,
-                score_rank_workspace_bytes(B, N, d));
+    RankArgs a;
+    int rc = score_open("score_rank", rank_geom_rank, score_rank_workspace_bytes(B, N, d), q, c, iq, filt_ptr, filt_idx, nnz, rows_q,
+                        N, B, d, ws_bytes, &a);
+    if (rc != GHF_OK) return rc;
     float* t = (float*)ws;
     int* valid = (int*)((char*)ws + rk_align((size_t)B * 4));
     const unsigned qb = (unsigned)cdiv(B, 256);
-    rank_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, target, rows_q, N, B, d, t, valid, (long long*)greater, (long long*)equal);
+    score_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, target, rows_q, N, B, d, t, valid, (long long*)greater, (long long*)equal);
     GHF_LAUNCH_CHECK();
-    RankArgs a = {};
-    a.q = q; a.c = c; a.iq = iq; a.rows_q = rows_q; a.N = N; a.B = B; a.d = d;
-    a.qtiles = g.qtiles; a.slab_tiles = g.slab_tiles; a.slabs = g.slabs;
     a.t = t; a.greater = (unsigned long long*)greater; a.equal = (unsigned long long*)equal;
-    const int rc = launch_tiles<false>(a, stream);
+    rc = launch_rank_tiles<RK_RANK>(a, stream);
     if (rc != GHF_OK) return rc;
     if (nnz > 0) {
         rank_filter_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(q, c, iq, target, filt_ptr, filt_idx, nnz, N, B, d, t, valid,
@@ -219,32 +174,22 @@ int launch_score_rank(const float* q, const float* c, const int64_t* iq, const i
 int launch_score_topk(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
                       int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, void* ws, size_t ws_bytes, float* scores,
                       int64_t* ids, hipStream_t stream) {
-    RankGeom g;
-    GHF_REQUIRE(d > 0 && rows_q > 0 && N > 0 && B > 0 && nnz >= 0, "score_topk: bad shape");
+    RankArgs a;
     GHF_REQUIRE(k >= 1 && k <= TOPK_MAX_K, "score_topk: k = %d outside 1..%d", k, TOPK_MAX_K);
-    if (d > RK_MAX_D) return set_err(GHF_EUNSUPPORTED, "score_topk: d = %d exceeds %d", d, RK_MAX_D);
-    GHF_REQUIRE(rank_geom_topk(B, N, d, &g), "score_topk: B or N out of range");
-    GHF_REQUIRE(iq || B <= rows_q, "score_topk: B exceeds the rows of q");
-    GHF_REQUIRE(ws_bytes >= score_topk_workspace_bytes(B, N, d, k), "score_topk: workspace of %zu bytes, need %zu", ws_bytes,
-                score_topk_workspace_bytes(B, N, d, k));
-    const int cap = topk_cap(d, k);
+    int rc = score_open("score_topk", rank_geom_topk, score_topk_workspace_bytes(B, N, d, k), q, c, iq, filt_ptr, filt_idx, nnz,
+                        rows_q, N, B, d, ws_bytes, &a);
+    if (rc != GHF_OK) return rc;
     int* valid = (int*)ws;
-    uint64_t* ws_key = (uint64_t*)((char*)ws + rk_align((size_t)B * 4));
-    rank_prep_kernel<<<(unsigned)cdiv(B, 256), 256, 0, stream>>>(q, c, iq, nullptr, rows_q, N, B, d, nullptr, valid, nullptr, nullptr);
+    a.k = k; a.cap = topk_cap(d, k); a.ws_key = (uint64_t*)((char*)ws + rk_align((size_t)B * 4));
+    score_prep_kernel<<<(unsigned)cdiv(B, 256), 256, 0, stream>>>(q, c, iq, nullptr, rows_q, N, B, d, nullptr, valid, nullptr, nullptr);
     GHF_LAUNCH_CHECK();
     if (nnz > 0) {
-        rank_filter_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(q, c, iq, nullptr, filt_ptr, filt_idx, nnz, N, B, d, nullptr,
-                                                                        valid, nullptr, nullptr);
+        list_range_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(filt_ptr, filt_idx, nnz, N, B, valid);
         GHF_LAUNCH_CHECK();
     }
-    RankArgs a = {};
-    a.q = q; a.c = c; a.iq = iq; a.rows_q = rows_q; a.N = N; a.B = B; a.d = d;
-    a.qtiles = g.qtiles; a.slab_tiles = g.slab_tiles; a.slabs = g.slabs;
-    a.filt_ptr = nnz > 0 ? filt_ptr : nullptr; a.filt_idx = filt_idx; a.nnz = nnz;
-    a.k = k; a.cap = cap; a.ws_key = ws_key;
-    const int rc = launch_tiles<true>(a, stream);
+    rc = launch_rank_tiles<RK_TOPK>(a, stream);
     if (rc != GHF_OK) return rc;
-    topk_merge_kernel<<<(unsigned)cdiv(B, 4), 256, 0, stream>>>(ws_key, valid, B, g.slabs, cap, k, scores, (long long*)ids);
+    topk_merge_kernel<<<(unsigned)cdiv(B, 4), 256, 0, stream>>>(a.ws_key, valid, B, a.slabs, a.cap, k, scores, (long long*)ids);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }

@@ -1,7 +1,8 @@
 // rank_sweep.h — the tiled q . c^T sweep on the exact fp32 matrix instruction that rank.hip (rank counts, top-k),
 // softmax.hip (1-vs-all softmax loss) and bce.hip (multi-label 1-vs-all BCE loss) share: geometry, the VALU form of the
-// accumulator's chain, the LDS layout and rank_tile_kernel with its four epilogues.  rank.hip's header comment describes the
-// sweep.
+// accumulator's chain, the LDS layout and rank_tile_kernel with its four epilogues, and the host side around it: the two
+// kernels that validate ids ahead of a sweep, the checks that open a launch (score_open) and the choice of the instantiation
+// (launch_rank_tiles).  rank.hip's header comment describes the sweep.
 #pragma once
 #include "common.h"
 
@@ -220,6 +221,19 @@ __device__ __forceinline__ float log1p_unit(float t) {
 // softplus(z) = log(1 + exp(z)) = max(z, 0) + log(1 + exp(-|z|)): no overflow at either end
 __device__ __forceinline__ float softplus(float z) { return fmaxf(z, 0.f) + log1p_unit(__expf(-fabsf(z))); }
 
+// *owner = the query whose list holds entry e, i.e. the last i with filt_ptr[i] <= e; false when e lies inside no list (a
+// malformed pointer array).  A flag, not a -1 owner: the caller's test is then a branch on the two comparisons themselves,
+// and softmax_bwd_kernel's dc pass keeps the instruction stream it had with the search written out.
+__device__ __forceinline__ bool list_owner(const int64_t* __restrict__ filt_ptr, int64_t B, int64_t e, int64_t* owner) {
+    int64_t lo = 0, hi = B;
+    while (hi - lo > 1) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (filt_ptr[mid] <= e) lo = mid; else hi = mid;
+    }
+    *owner = lo;
+    return filt_ptr[lo] <= e && filt_ptr[lo + 1] > e;
+}
+
 // one thread per list entry: an id out of range marks the query whose list holds it
 static __global__ __launch_bounds__(256) void list_range_kernel(const int64_t* __restrict__ filt_ptr, const int64_t* __restrict__ filt_idx,
                                                                 int64_t nnz, int64_t N, int64_t B, int* valid) {
@@ -227,12 +241,32 @@ static __global__ __launch_bounds__(256) void list_range_kernel(const int64_t* _
     if (e >= nnz) return;
     const int64_t j = filt_idx[e];
     if (j >= 0 && j < N) return;
-    int64_t lo = 0, hi = B;                          // last i with filt_ptr[i] <= e
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (filt_ptr[mid] <= e) lo = mid; else hi = mid;
+    int64_t i;
+    if (list_owner(filt_ptr, B, e, &i)) valid[i] = 0;
+}
+
+// one thread per query, ahead of every sweep: valid[i] says whether the query's row id, and its target where the call has
+// one, are in range.  With `t` (which needs `target`): the target's score by the sweep's chain, NaN for a query that is not
+// valid (it compares false with every score, so a bad query counts nothing).  With the rank counters: their reset.
+static __global__ __launch_bounds__(256) void score_prep_kernel(const float* __restrict__ q, const float* __restrict__ c,
+                                                                const int64_t* __restrict__ iq, const int64_t* __restrict__ target,
+                                                                int64_t rows_q, int64_t N, int64_t B, int d, float* __restrict__ t,
+                                                                int* __restrict__ valid, long long* __restrict__ greater,
+                                                                long long* __restrict__ equal) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B) return;
+    const int64_t r = iq ? iq[i] : i;
+    bool ok = r >= 0 && r < rows_q;
+    if (target) {
+        const int64_t tg = target[i];
+        ok = ok && tg >= 0 && tg < N;
+        if (t) t[i] = ok ? dot_chain(q + (size_t)r * d, c + (size_t)tg * d, d, rows_vec(q, d) && rows_vec(c, d)) : __int_as_float(0x7FC00000);
     }
-    if (filt_ptr[lo] <= e && filt_ptr[lo + 1] > e) valid[lo] = 0;
+    if (greater) {
+        greater[i] = 0;
+        equal[i] = 0;
+    }
+    valid[i] = ok ? 1 : 0;
 }
 
 static inline size_t rank_lds_bytes(int d, int BK, int CT) {
@@ -572,6 +606,43 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const RankArgs a) {
             select_in_place(a.ws_key + row, m, a.k, lane, &thrS[qc], &sm0[qc], true);
         }
     }
+}
+
+// ---- the host side every operation shares ---------------------------------------------------------------------------------
+// the sweep with epilogue MODE over a.qtiles x a.slabs workgroups: the one place that picks the instantiation
+template <int MODE>
+static int launch_rank_tiles(const RankArgs& a, hipStream_t stream) {
+    const unsigned grid = (unsigned)(a.qtiles * a.slabs);
+    if (rank_ctile(a.d) == 256) {
+        const size_t lds = rank_lds_bytes(a.d, 32, 256);
+        GHF_SET_MAX_LDS((rank_tile_kernel<32, 256, MODE>), lds);
+        rank_tile_kernel<32, 256, MODE><<<grid, 512, lds, stream>>>(a);
+    } else {
+        const size_t lds = rank_lds_bytes(a.d, 16, 128);
+        GHF_SET_MAX_LDS((rank_tile_kernel<16, 128, MODE>), lds);
+        rank_tile_kernel<16, 128, MODE><<<grid, 256, lds, stream>>>(a);
+    }
+    GHF_LAUNCH_CHECK();
+    return GHF_OK;
+}
+
+// What every launch_score_* opens with: the shape checks (`op` names the operation in the messages), the geometry by the
+// operation's own function, the workspace against `need` (the operation's *_workspace_bytes).  On success *a holds what
+// every sweep reads (rows, sizes, geometry, the lists: absent when they are empty); the caller sets its own fields.
+static inline int score_open(const char* op, bool (*geom)(int64_t, int64_t, int, RankGeom*), size_t need, const float* q,
+                             const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz,
+                             int64_t rows_q, int64_t N, int64_t B, int d, size_t ws_bytes, RankArgs* a) {
+    RankGeom g;
+    GHF_REQUIRE(d > 0 && rows_q > 0 && N > 0 && B > 0 && nnz >= 0, "%s: bad shape", op);
+    if (d > RK_MAX_D) return set_err(GHF_EUNSUPPORTED, "%s: d = %d exceeds %d", op, d, RK_MAX_D);
+    GHF_REQUIRE(geom(B, N, d, &g), "%s: B or N out of range", op);
+    GHF_REQUIRE(iq || B <= rows_q, "%s: B exceeds the rows of q", op);
+    GHF_REQUIRE(ws_bytes >= need, "%s: workspace of %zu bytes, need %zu", op, ws_bytes, need);
+    *a = RankArgs{};
+    a->q = q; a->c = c; a->iq = iq; a->rows_q = rows_q; a->N = N; a->B = B; a->d = d;
+    a->qtiles = g.qtiles; a->slab_tiles = g.slab_tiles; a->slabs = g.slabs;
+    a->filt_ptr = nnz > 0 ? filt_ptr : nullptr; a->filt_idx = filt_idx; a->nnz = nnz;
+    return GHF_OK;
 }
 
 }  // namespace ghf

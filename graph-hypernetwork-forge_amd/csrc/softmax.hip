@@ -73,19 +73,7 @@ size_t score_softmax_bwd_workspace_bytes(int64_t B, int64_t N, int d) {
     return rk_align((size_t)g.slabs * (size_t)B * (size_t)d * 4);      // dq partials [slabs, B, d]
 }
 
-// ---- forward: the small kernels around the sweep --------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void softmax_prep_kernel(const float* __restrict__ q, const float* __restrict__ c,
-                                                           const int64_t* __restrict__ iq, const int64_t* __restrict__ target,
-                                                           int64_t rows_q, int64_t N, int64_t B, int d, float* __restrict__ t,
-                                                           int* __restrict__ valid) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= B) return;
-    const int64_t r = iq ? iq[i] : i, tg = target[i];
-    const bool ok = r >= 0 && r < rows_q && tg >= 0 && tg < N;
-    t[i] = ok ? dot_chain(q + (size_t)r * d, c + (size_t)tg * d, d, rows_vec(q, d) && rows_vec(c, d)) : __int_as_float(0x7FC00000);
-    valid[i] = ok ? 1 : 0;
-}
-
+// ---- forward: the sweep between score_prep_kernel / list_range_kernel (rank_sweep.h) and the merge over the slabs ---------
 __global__ __launch_bounds__(256) void softmax_finish_kernel(const f32x2* __restrict__ ms, const float* __restrict__ t,
                                                              const int* __restrict__ valid, int64_t B, int64_t slabs, float scale,
                                                              float* __restrict__ loss, float* __restrict__ lse) {
@@ -101,40 +89,23 @@ __global__ __launch_bounds__(256) void softmax_finish_kernel(const f32x2* __rest
 int launch_score_softmax_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                              void* ws, size_t ws_bytes, float* loss, float* lse, hipStream_t stream) {
-    RankGeom g;
-    GHF_REQUIRE(d > 0 && rows_q > 0 && N > 0 && B > 0 && nnz >= 0, "score_softmax_fwd: bad shape");
-    if (d > RK_MAX_D) return set_err(GHF_EUNSUPPORTED, "score_softmax_fwd: d = %d exceeds %d", d, RK_MAX_D);
-    GHF_REQUIRE(softmax_geom(B, N, d, &g), "score_softmax_fwd: B or N out of range");
-    GHF_REQUIRE(iq || B <= rows_q, "score_softmax_fwd: B exceeds the rows of q");
-    GHF_REQUIRE(ws_bytes >= score_softmax_workspace_bytes(B, N, d), "score_softmax_fwd: workspace of %zu bytes, need %zu", ws_bytes,
-                score_softmax_workspace_bytes(B, N, d));
+    RankArgs a;
+    int rc = score_open("score_softmax_fwd", softmax_geom, score_softmax_workspace_bytes(B, N, d), q, c, iq, filt_ptr, filt_idx, nnz,
+                        rows_q, N, B, d, ws_bytes, &a);
+    if (rc != GHF_OK) return rc;
     float* t = (float*)ws;
     int* valid = (int*)((char*)ws + rk_align((size_t)B * 4));
-    f32x2* ms = (f32x2*)((char*)ws + 2 * rk_align((size_t)B * 4));
     const unsigned qb = (unsigned)cdiv(B, 256);
-    softmax_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, target, rows_q, N, B, d, t, valid);
+    score_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, target, rows_q, N, B, d, t, valid, nullptr, nullptr);
     GHF_LAUNCH_CHECK();
     if (nnz > 0) {
         list_range_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(filt_ptr, filt_idx, nnz, N, B, valid);
         GHF_LAUNCH_CHECK();
     }
-    RankArgs a = {};
-    a.q = q; a.c = c; a.iq = iq; a.rows_q = rows_q; a.N = N; a.B = B; a.d = d;
-    a.qtiles = g.qtiles; a.slab_tiles = g.slab_tiles; a.slabs = g.slabs;
-    a.filt_ptr = nnz > 0 ? filt_ptr : nullptr; a.filt_idx = filt_idx; a.nnz = nnz;
-    a.target = target; a.scale = scale; a.ws_ms = ms;
-    const unsigned grid = (unsigned)(g.qtiles * g.slabs);
-    if (rank_ctile(d) == 256) {
-        const size_t lds = rank_lds_bytes(d, 32, 256);
-        GHF_SET_MAX_LDS((rank_tile_kernel<32, 256, RK_SOFTMAX>), lds);
-        rank_tile_kernel<32, 256, RK_SOFTMAX><<<grid, 512, lds, stream>>>(a);
-    } else {
-        const size_t lds = rank_lds_bytes(d, 16, 128);
-        GHF_SET_MAX_LDS((rank_tile_kernel<16, 128, RK_SOFTMAX>), lds);
-        rank_tile_kernel<16, 128, RK_SOFTMAX><<<grid, 256, lds, stream>>>(a);
-    }
-    GHF_LAUNCH_CHECK();
-    softmax_finish_kernel<<<qb, 256, 0, stream>>>(ms, t, valid, B, g.slabs, scale, loss, lse);
+    a.target = target; a.scale = scale; a.ws_ms = (f32x2*)((char*)ws + 2 * rk_align((size_t)B * 4));
+    rc = launch_rank_tiles<RK_SOFTMAX>(a, stream);
+    if (rc != GHF_OK) return rc;
+    softmax_finish_kernel<<<qb, 256, 0, stream>>>(a.ws_ms, t, valid, B, a.slabs, scale, loss, lse);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }
@@ -243,19 +214,15 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
             for (int64_t e = tid; e < a.nnz; e += NT) {
                 const int64_t j = a.filt_idx[e];
                 if (j < own0 || j >= own0 + OT) continue;
-                int64_t lo = 0, hi = a.B;                            // last i with filt_ptr[i] <= e
-                while (hi - lo > 1) {
-                    const int64_t mid = (lo + hi) >> 1;
-                    if (a.filt_ptr[mid] <= e) lo = mid; else hi = mid;
-                }
+                int64_t lo;
+                if (!list_owner(a.filt_ptr, a.B, e, &lo)) continue;
                 if (BCE) {
-                    if (a.filt_ptr[lo] > e || a.filt_ptr[lo + 1] <= e) continue;
                     if (e > 0 && e > a.filt_ptr[lo] && a.filt_idx[e - 1] == j) continue;
                     const int64_t r = a.iq ? a.iq[lo] : lo;
                     const float l = a.lse[lo];
                     if (r < 0 || r >= a.rows_q || l != l) continue;
                 } else {
-                    if (a.filt_ptr[lo] > e || a.filt_ptr[lo + 1] <= e || a.target[lo] == j) continue;
+                    if (a.target[lo] == j) continue;
                 }
                 const int pos = atomicAdd(hcnt, 1);
                 if (pos < SB_HCAP) hits[pos] = (long long)(lo * 256 + (j - own0));
@@ -439,52 +406,45 @@ static int launch_bwd_tiles(const SmBwdArgs& a, hipStream_t stream) {
     return GHF_OK;
 }
 
+// both losses' backward: the lists are the softmax's filter lists or the BCE's positives, `lse` the forward's lse or (BCE, of
+// which only the NaNs are read) its loss; target and smoothing belong to one loss each
+template <int LOSS>
+static int launch_score_loss_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* list_ptr,
+                                 const int64_t* list_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                                 float smoothing, const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq,
+                                 float* dc, hipStream_t stream) {
+    RankArgs r;
+    int rc = score_open(LOSS == SB_BCE ? "score_bce_bwd" : "score_softmax_bwd", softmax_bwd_geom,
+                        score_softmax_bwd_workspace_bytes(B, N, d), q, c, iq, list_ptr, list_idx, nnz, rows_q, N, B, d, ws_bytes, &r);
+    if (rc != GHF_OK) return rc;
+    SmBwdArgs a = {};
+    a.q = q; a.c = c; a.iq = iq; a.target = target;
+    a.filt_ptr = r.filt_ptr; a.filt_idx = list_idx; a.nnz = nnz;
+    a.rows_q = rows_q; a.N = N; a.B = B; a.d = d; a.scale = scale; a.lse = lse; a.grad = grad_loss;
+    if (LOSS == SB_BCE) { a.pos_w = 1.f - smoothing; a.neg_w = smoothing / (float)N; }
+    a.qtiles = r.qtiles; a.slab_tiles = r.slab_tiles; a.slabs = r.slabs;
+    a.dq_part = (float*)ws; a.dc = dc;
+    rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128, LOSS>(a, stream) : launch_bwd_tiles<64, 256, LOSS>(a, stream);
+    if (rc != GHF_OK) return rc;
+    return launch_ordered_sum(a.dq_part, a.slabs, B * (int64_t)d, dq, stream);
+}
+
 int launch_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                              const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc,
                              hipStream_t stream) {
-    RankGeom g;
-    GHF_REQUIRE(d > 0 && rows_q > 0 && N > 0 && B > 0 && nnz >= 0, "score_softmax_bwd: bad shape");
-    if (d > RK_MAX_D) return set_err(GHF_EUNSUPPORTED, "score_softmax_bwd: d = %d exceeds %d", d, RK_MAX_D);
-    GHF_REQUIRE(softmax_bwd_geom(B, N, d, &g), "score_softmax_bwd: B or N out of range");
-    GHF_REQUIRE(iq || B <= rows_q, "score_softmax_bwd: B exceeds the rows of q");
-    GHF_REQUIRE(ws_bytes >= score_softmax_bwd_workspace_bytes(B, N, d), "score_softmax_bwd: workspace of %zu bytes, need %zu",
-                ws_bytes, score_softmax_bwd_workspace_bytes(B, N, d));
-    SmBwdArgs a = {};
-    a.q = q; a.c = c; a.iq = iq; a.target = target;
-    a.filt_ptr = nnz > 0 ? filt_ptr : nullptr; a.filt_idx = filt_idx; a.nnz = nnz;
-    a.rows_q = rows_q; a.N = N; a.B = B; a.d = d; a.scale = scale; a.lse = lse; a.grad = grad_loss;
-    a.qtiles = g.qtiles; a.slab_tiles = g.slab_tiles; a.slabs = g.slabs;
-    a.dq_part = (float*)ws; a.dc = dc;
-    const int rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128, SB_SOFTMAX>(a, stream)
-                                      : launch_bwd_tiles<64, 256, SB_SOFTMAX>(a, stream);
-    if (rc != GHF_OK) return rc;
-    return launch_ordered_sum(a.dq_part, g.slabs, B * (int64_t)d, dq, stream);
+    return launch_score_loss_bwd<SB_SOFTMAX>(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, 0.f, lse, grad_loss, ws,
+                                             ws_bytes, dq, dc, stream);
 }
 
-// ---- the multi-label BCE loss's backward (bce.hip holds its forward): the same two sweeps, G formed for that loss ---------
+// the multi-label BCE loss's backward (bce.hip holds its forward): the same two sweeps and workspace, G formed for that loss
 size_t score_bce_bwd_workspace_bytes(int64_t B, int64_t N, int d) { return score_softmax_bwd_workspace_bytes(B, N, d); }
 
 int launch_score_bce_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
                          const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc, hipStream_t stream) {
-    RankGeom g;
-    GHF_REQUIRE(d > 0 && rows_q > 0 && N > 0 && B > 0 && nnz >= 0, "score_bce_bwd: bad shape");
-    if (d > RK_MAX_D) return set_err(GHF_EUNSUPPORTED, "score_bce_bwd: d = %d exceeds %d", d, RK_MAX_D);
-    GHF_REQUIRE(softmax_bwd_geom(B, N, d, &g), "score_bce_bwd: B or N out of range");
-    GHF_REQUIRE(iq || B <= rows_q, "score_bce_bwd: B exceeds the rows of q");
-    GHF_REQUIRE(ws_bytes >= score_bce_bwd_workspace_bytes(B, N, d), "score_bce_bwd: workspace of %zu bytes, need %zu", ws_bytes,
-                score_bce_bwd_workspace_bytes(B, N, d));
-    SmBwdArgs a = {};
-    a.q = q; a.c = c; a.iq = iq;
-    a.filt_ptr = nnz > 0 ? pos_ptr : nullptr; a.filt_idx = pos_idx; a.nnz = nnz;
-    a.rows_q = rows_q; a.N = N; a.B = B; a.d = d; a.scale = scale; a.lse = loss; a.grad = grad_loss;
-    a.pos_w = 1.f - smoothing; a.neg_w = smoothing / (float)N;
-    a.qtiles = g.qtiles; a.slab_tiles = g.slab_tiles; a.slabs = g.slabs;
-    a.dq_part = (float*)ws; a.dc = dc;
-    const int rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128, SB_BCE>(a, stream) : launch_bwd_tiles<64, 256, SB_BCE>(a, stream);
-    if (rc != GHF_OK) return rc;
-    return launch_ordered_sum(a.dq_part, g.slabs, B * (int64_t)d, dq, stream);
+    return launch_score_loss_bwd<SB_BCE>(q, c, iq, nullptr, pos_ptr, pos_idx, nnz, rows_q, N, B, d, scale, smoothing, loss, grad_loss,
+                                         ws, ws_bytes, dq, dc, stream);
 }
 
 }  // namespace ghf

@@ -788,7 +788,7 @@ class HyperGNN(nn.Module):
         (``ghf_score_softmax_fwd``), and a backward that recomputes the scores from the saved log-sum (``ghf_score_softmax_bwd``,
         ``autograd.SoftmaxLossFn``).  Bit-reproducible.  Recorded for autograd when grad mode is on and ``embs`` requires grad.
         ``query_rows`` / ``known=(src, dst, rel)`` with ``query_rel``: relation-typed queries, as in ``rank_candidates``; the
-        loss is then recorded when ``embs`` or ``query_rows`` requires grad (``autograd.SoftmaxRowsLossFn``: the per-query
+        loss is then recorded when ``embs`` or ``query_rows`` requires grad (``autograd.SoftmaxLossFn`` with the rows: the per-query
         gradient is ``query_rows``' own, the per-candidate one ``embs``')."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
@@ -805,13 +805,13 @@ class HyperGNN(nn.Module):
         ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
         if query_rows is not None:
             if torch.is_grad_enabled() and (embs.requires_grad or query_rows.requires_grad):
-                from ..autograd import SoftmaxRowsLossFn
-                return SoftmaxRowsLossFn.apply(embs, query_rows, t, ptr, idx, scale)
+                from ..autograd import SoftmaxLossFn
+                return SoftmaxLossFn.apply(embs, query_rows, None, t, ptr, idx, scale)
             return _native.score_softmax_fwd(query_rows.detach(), embs.detach().float(), t, filt_ptr=ptr, filt_idx=idx,
                                              scale=scale)[0]
         if torch.is_grad_enabled() and embs.requires_grad:
             from ..autograd import SoftmaxLossFn
-            return SoftmaxLossFn.apply(embs, q, t, ptr, idx, scale)
+            return SoftmaxLossFn.apply(embs, None, q, t, ptr, idx, scale)
         e = embs.detach().float()
         return _native.score_softmax_fwd(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, scale=scale)[0]
 
@@ -828,7 +828,7 @@ class HyperGNN(nn.Module):
         set, not a mask; a repeated id counts once.  ``normalize=False`` returns the sum over the candidates instead of their
         mean.  ``0 <= smoothing < 1``.  Bit-reproducible.  Recorded for autograd when grad mode is on and ``embs`` requires grad.
         ``query_rows``: relation-typed queries, as in ``softmax_loss``; the loss is then recorded when ``embs`` or ``query_rows``
-        requires grad (``autograd.BceRowsLossFn``)."""
+        requires grad (``autograd.BceLossFn`` with the rows)."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
         self._query_rows(embs, query, query_rows, "bce_loss")
@@ -844,14 +844,14 @@ class HyperGNN(nn.Module):
         ptr, idx = self._filter_lists(embs, q, known, pos_ptr, pos_idx, query_rel)
         if query_rows is not None:
             if torch.is_grad_enabled() and (embs.requires_grad or query_rows.requires_grad):
-                from ..autograd import BceRowsLossFn
-                loss = BceRowsLossFn.apply(embs, query_rows, ptr, idx, scale, smoothing)
+                from ..autograd import BceLossFn
+                loss = BceLossFn.apply(embs, query_rows, None, ptr, idx, scale, smoothing)
             else:
                 loss = _native.score_bce_fwd(query_rows.detach(), embs.detach().float(), pos_ptr=ptr, pos_idx=idx, scale=scale,
                                              smoothing=smoothing)
         elif torch.is_grad_enabled() and embs.requires_grad:
             from ..autograd import BceLossFn
-            loss = BceLossFn.apply(embs, q, ptr, idx, scale, smoothing)
+            loss = BceLossFn.apply(embs, None, q, ptr, idx, scale, smoothing)
         else:
             e = embs.detach().float()
             loss = _native.score_bce_fwd(e, e, iq=q, pos_ptr=ptr, pos_idx=idx, scale=scale, smoothing=smoothing)

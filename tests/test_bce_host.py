@@ -1,6 +1,7 @@
 """Host-side checks of the multi-label 1-vs-all BCE loss (HyperGNN.bce_loss, ghf_score_bce_fwd / _bwd): no GPU needed."""
 
 import ctypes
+import inspect
 import os
 import re
 
@@ -23,8 +24,8 @@ def test_bce_entry_points_are_declared_bound_and_exported():
         assert name in _native.header_symbols() and name in _native.SIGNATURES
         assert hasattr(lib, name), f"libghf_hip.so does not export {name}"
     assert callable(HyperGNN.bce_loss)
-    for fn in (autograd.BceLossFn, autograd.BceRowsLossFn):
-        assert issubclass(fn, torch.autograd.Function)
+    assert issubclass(autograd.BceLossFn, torch.autograd.Function)     # one Function: query ids, or the query rows given
+    assert {"rows", "query"} <= set(inspect.signature(autograd.BceLossFn.forward).parameters)
     assert callable(_native.score_bce_fwd) and callable(_native.score_bce_bwd)
 
 

@@ -27,8 +27,6 @@ Cases, the smallest that reach each branch (geometry from rp_span / rp_wgrad_sla
             ordered sum of 12 slab partials."""
 
 import functools
-import hashlib
-import json
 import os
 import sys
 
@@ -39,29 +37,13 @@ import torch
 if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from _bits import affine, dev, digest, hashed, load_fixture, record_main  # noqa: E402
 from graph_hypernetwork_forge_amd import _native  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "relation_bits.json")
 WIDTHS = (18, 20, 64, 160, 256)
 ROWS_X = 997
-
-
-def hashed(n, m, salt):
-    """fp32 [n, m] in [-0.5, 0.5): 16 bits of a multiplicative hash of (i, j, salt)."""
-    i = np.arange(n, dtype=np.uint64)[:, None]
-    j = np.arange(m, dtype=np.uint64)[None, :]
-    h = (i * np.uint64(2654435761) + j * np.uint64(40503) + np.uint64(salt) * np.uint64(2246822519)) & np.uint64(0xFFFFFFFF)
-    h = ((h * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)) >> np.uint64(16)
-    return ((h.astype(np.int64) - 32768).astype(np.float32) / np.float32(65536.0))
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
-
-
-def affine(n, mul, add, mod):
-    return dev((np.arange(n, dtype=np.int64) * mul + add) % mod)
 
 
 @functools.lru_cache(maxsize=None)
@@ -151,17 +133,9 @@ def build_cases():
 CASES = build_cases()
 
 
-def digest(tensors):
-    h = hashlib.sha256()
-    for t in tensors:
-        h.update(t.cpu().numpy().tobytes())
-    return h.hexdigest()
-
-
 @functools.lru_cache(maxsize=None)
 def recorded():
-    with open(FIXTURE) as f:
-        return json.load(f)["cases"]
+    return load_fixture(FIXTURE)
 
 
 def test_the_fixture_names_exactly_these_cases():
@@ -181,17 +155,4 @@ def test_output_bytes_are_the_recorded_ones(name):
 
 
 if __name__ == "__main__":
-    import argparse
-
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--record", action="store_true", required=True)
-    ap.add_argument("--out", default=FIXTURE)
-    ap.add_argument("--commit", default=None, help="the commit whose build is recorded")
-    args = ap.parse_args()
-    doc = {"recorded_at": args.commit, "device": torch.cuda.get_device_name(0),
-           "cases": {name: digest(CASES[name]()) for name in sorted(CASES)}}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(doc, f, indent=1, sort_keys=True)
-        f.write("\n")
-    print(f"recorded {len(doc['cases'])} cases to {args.out}")
+    record_main(FIXTURE, CASES)

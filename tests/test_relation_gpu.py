@@ -1,5 +1,5 @@
 """Relation-typed link prediction on the GPU: ghf_relation_rows (csrc/relation.hip), autograd.RelationRowsFn / ScoreRowsFn /
-SoftmaxRowsLossFn, RelationDecoder and the query_rows / query_rel arguments of HyperGNN.rank_candidates, topk_candidates
+SoftmaxLossFn with the query rows given, RelationDecoder and the query_rows / query_rel arguments of HyperGNN.rank_candidates, topk_candidates
 and softmax_loss, against a float64 restatement:  out_i = x[ix_i] + x[ix_i] @ op(W[rel_i]) + b[rel_i].
 
 Tolerances are the project's own: values under tests/_util.assert_close's defaults (rtol 1e-4, atol 1e-5, relative L2
