@@ -167,8 +167,8 @@ static size_t scan_temp_bytes(int64_t n) {
 static int64_t num_segments(int64_t N, int R, int BN) { return BN == 1 ? N : cdiv(N, BN) * R; }
 
 // The last round of workgroups: with NB blocks on `cus` compute units, NB % cus blocks remain for a last round that keeps
-// only as many CUs busy.  When that is less than half of them (and there is more than one round), each of these blocks
-// becomes floor(cus / remainder) <= 8 work items.
+// only as many CUs busy.  When that is at most half of them (and there is more than one round), each of these blocks
+// becomes up to floor(cus / remainder) <= 8 work items (plan_item_count_kernel: of at least 8 chunks each).
 static int tail_split(int64_t NB, int64_t* tail0) {
     static const int cus = [] {
         int dev = 0, n = 0;

@@ -93,9 +93,16 @@ int ghf_message_config(int d, int* block_nodes, int* wlayout, int* chunk_rows, i
  *              equal destinations spans a 16-row tile boundary inside the chunk; block b owns
  *              chunks [blk_chunk_off[b], blk_chunk_off[b+1]),
  *   item_tab [4*max_items] int32 and blk_item_off [ceil(N/BN)+1] int32 (BN > 1 only): the work items.
- *              A block with more than split_chunks chunks (the hub of a power-law graph) is cut into
- *              ceil(chunks/split_chunks) items; item i = { block, first chunk, one past its last chunk,
- *              scratch slot (-1 for the only item of a block) }; block b owns items
+ *              A block is one item, or several for one of two reasons.  A block with more than split_chunks
+ *              chunks (the hub of a power-law graph) is cut into ceil(chunks/split_chunks) items.  And the blocks
+ *              of the last, partly filled round of workgroups: with NB = ceil(N/BN) blocks on the current device's
+ *              C compute units and rem = NB % C, when NB > C and 0 < 2*rem <= C each of the blocks NB-rem .. NB-1
+ *              becomes min(8, C / rem, chunks / 8) items (integer divisions: at least 8 chunks per item) where
+ *              that is more than the hub rule gives it — so the item count of a plan depends on the compute-unit
+ *              count of the device it was built on.  k items cut a block's n chunks evenly: per = ceil(n / k),
+ *              item j = chunks [j*per, min((j+1)*per, n)), none of them empty.  Item i = { block, first chunk,
+ *              one past its last chunk, scratch slot }: the items of blocks with several take the slots 0, 1, ..
+ *              in item order, the only item of a block has slot -1; block b owns items
  *              [blk_item_off[b], blk_item_off[b+1]),
  *   status [3] int32: [0] 0 ok, bit0 = a src/dst outside [0,N), bit1 = a rel outside [0,R) (read it back
  *              before trusting the plan; offending edges are dropped); [1] number of items; [2] number of

@@ -485,7 +485,11 @@ def test_plan_is_a_sorted_permutation_of_the_edges(bn, cr, sc):
         want_cross = any(key[e0[c] + b - 1] == key[e0[c] + b] for b in range(16, rows[c], 16))
         assert cross[c] == int(want_cross)
         assert (e0[c] - off[seg[e0[c]]]) % cr == 0
-    # work items: a block's chunks in order, cut evenly into ceil(chunks / sc) items when there are more than sc
+    # work items: a block's chunks in order, cut evenly into ceil(chunks / sc) items when there are more than sc — the whole
+    # rule only while the blocks fit one round of workgroups (with more blocks than compute units the last round's blocks
+    # are cut further: tests/test_plan_gpu.py::test_last_round_split)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert nb <= cus, f"{nb} blocks on {cus} compute units: the item rule asserted below holds only for plans of one round"
     ioff = pl["blk_item_off"].cpu().numpy()
     n_items, n_slots = int(status[1].item()), int(status[2].item())
     items = pl["item_tab"].cpu().numpy()[: 4 * n_items].reshape(-1, 4)
