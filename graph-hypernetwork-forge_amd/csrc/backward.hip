@@ -10,7 +10,7 @@
 //   the gradient with respect to h is two more passes of the forward message kernel with transposed weights
 //   (GHF_FLAG_RAW_SUM): sum_{e->v} G_v Ws[r]^T on the forward plan, sum_{e: src=u} G_v Wm[r]^T on the reversed one.
 // First version: exact fp32 (v_mfma_f32_16x16x4_f32 / vector ALU), deterministic summation orders, any d <= 1024.
-#include "common.h"
+#include "row_pieces.h"
 #include <type_traits>
 
 
@@ -30,28 +30,6 @@ constexpr int BW_PER_LANE = BW_MAX_D / 64;
 constexpr int TB_MAX_BLOCKS = 2048;
 typedef _Float16 tb_f16x4 __attribute__((ext_vector_type(4)));
 
-// sum / max over the groups of LPR consecutive lanes (LPR a power of two); every lane of a group gets the same bits
-template <int LPR>
-__device__ __forceinline__ float group_sum(float v) {
-    if constexpr (LPR >= 2) v += dpp_take<0xB1, 0xF>(v);
-    if constexpr (LPR >= 4) v += dpp_take<0x4E, 0xF>(v);
-    if constexpr (LPR >= 8) v += dpp_take<0x141, 0xF>(v);
-    if constexpr (LPR >= 16) v += dpp_take<0x140, 0xF>(v);
-    if constexpr (LPR >= 32) v += __shfl_xor(v, 16);
-    if constexpr (LPR >= 64) v += __shfl_xor(v, 32);
-    return v;
-}
-template <int LPR>
-__device__ __forceinline__ float group_absmax(float v) {
-    if constexpr (LPR >= 2) v = fmaxf(v, dpp_take<0xB1, 0xF>(v));
-    if constexpr (LPR >= 4) v = fmaxf(v, dpp_take<0x4E, 0xF>(v));
-    if constexpr (LPR >= 8) v = fmaxf(v, dpp_take<0x141, 0xF>(v));
-    if constexpr (LPR >= 16) v = fmaxf(v, dpp_take<0x140, 0xF>(v));
-    if constexpr (LPR >= 32) v = fmaxf(v, __shfl_xor(v, 16));
-    if constexpr (LPR >= 64) v = fmaxf(v, __shfl_xor(v, 32));
-    return v;
-}
-
 // d = 4 * LPR * NV: a row is NV float4 per lane of a group of LPR lanes, a wave visits 64 / LPR consecutive rows at a time
 template <int LPR, int NV>
 __global__ __launch_bounds__(256) void tail_bwd_v4_kernel(const float* __restrict__ g_out, const float* __restrict__ agg,
@@ -61,6 +39,7 @@ __global__ __launch_bounds__(256) void tail_bwd_v4_kernel(const float* __restric
                                                           float* __restrict__ part, const float* __restrict__ drop,
                                                           int32_t* __restrict__ range_flag) {
     constexpr int D = 4 * LPR * NV, RPW = 64 / LPR;
+    using Row = LaneGroup<LPR>;                                    // the lanes that hold a row (row_pieces.h)
     __shared__ float red[4][2][D];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane / LPR, cl = lane % LPR;
@@ -77,7 +56,6 @@ __global__ __launch_bounds__(256) void tail_bwd_v4_kernel(const float* __restric
         const int64_t v = ok ? base + sub : N - 1;                 // (a short last visit: the spare groups redo the last row, unstored)
         const size_t row = (size_t)v * D;
         f32x4 pre[NV], x[NV], dm[NV], go[NV];
-        float s = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const size_t o = row + 4 * (j * LPR + cl);
@@ -85,18 +63,10 @@ __global__ __launch_bounds__(256) void tail_bwd_v4_kernel(const float* __restric
             go[j] = *(const f32x4*)(g_out + o);
             dm[j] = drop ? *(const f32x4*)(drop + o) : (f32x4){1.f, 1.f, 1.f, 1.f};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                x[j][k] = fmaxf(pre[j][k], 0.f) * dm[j][k];
-                s += x[j][k];
-            }
+            for (int k = 0; k < 4; ++k) x[j][k] = fmaxf(pre[j][k], 0.f) * dm[j][k];
         }
-        const float mean = group_sum<LPR>(s) / (float)D;
-        float var = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { const float t = x[j][k] - mean; var += t * t; }
-        const float rstd = 1.0f / sqrtf(group_sum<LPR>(var) / (float)D + eps);
+        float mean, rstd;                                          // the forward's statistics again (D is a power of two)
+        row_mean_rstd<Row, D, 4 * NV>([&](int i) { return x[i / 4][i % 4]; }, eps, mean, rstd);
         float s1 = 0.f, s2 = 0.f;                                  // mean(gamma g'), mean(gamma g' xhat)
         f32x4 gg[NV];
 #pragma unroll
@@ -110,8 +80,8 @@ __global__ __launch_bounds__(256) void tail_bwd_v4_kernel(const float* __restric
                 if (ok) { dg[j][k] += go[j][k] * xh; db[j][k] += go[j][k]; }
                 x[j][k] = xh;
             }
-        s1 = group_sum<LPR>(s1) / (float)D;
-        s2 = group_sum<LPR>(s2) / (float)D;
+        s1 = Row::sum(s1) / (float)D;
+        s2 = Row::sum(s2) / (float)D;
         const int deg = indeg[v];
         const float inv = 1.0f / (float)(deg > 1 ? deg : 1);
         float mx = 0.f;
@@ -131,35 +101,25 @@ __global__ __launch_bounds__(256) void tail_bwd_v4_kernel(const float* __restric
             }
             x[j] = gv;
         }
-        if (Gs) {                                                  // as split2h_rows_kernel (message_hx.hip) cuts a row
-            const int sh = split2h_shift(group_absmax<LPR>(mx));
-            const float up = pow2f(sh);
-            float tiny = 0.f, nz = 0.f;
+        if (Gs) {                                                  // as split2h_rows_kernel (message_bx.hip) cuts a row
+            RowCut<Row> cut(mx);
             _Float16* __restrict__ dst = (_Float16*)(Gs + (size_t)v * (4 * (size_t)D));
 #pragma unroll
             for (int j = 0; j < NV; ++j) {
                 tb_f16x4 hi, lo;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float xs = x[j][k] * up;
                     _Float16 a, b;
-                    split2h(xs, a, b);
+                    cut.piece(x[j][k], a, b);
                     hi[k] = a;
                     lo[k] = b;
-                    tiny += range_tiny(xs) ? 1.f : 0.f;
-                    nz += xs != 0.f ? 1.f : 0.f;
                 }
                 if (ok) {
                     *(tb_f16x4*)(dst + 4 * (j * LPR + cl)) = hi;
                     *(tb_f16x4*)(dst + D + 4 * (j * LPR + cl)) = lo;
                 }
             }
-            tiny = group_sum<LPR>(tiny);
-            nz = group_sum<LPR>(nz);
-            if (ok && cl == 0) {
-                *(float*)(Gs + (size_t)N * (4 * (size_t)D) + (size_t)v * 4) = pow2f(-sh);
-                range_raise(range_flag, GHF_RANGE_ROWS, (int)tiny, (int)nz);
-            }
+            cut.finish(ok && cl == 0, (float*)(Gs + (size_t)N * (4 * (size_t)D)) + v, range_flag);
         }
     }
     // the wave's row groups, then the workgroup's waves, in order

@@ -9,7 +9,7 @@
 // columns of one row, so h0 goes out in 16-byte stores and its fp16 pieces in 8-byte stores (with x as the A operand a
 // lane held one column of four rows: 4- and 2-byte stores, 0.61 ms at C3 against 0.44 without the pieces).
 // Shapes the tile does not cover (F % 16, d % 16, d > 256) take a vector-ALU kernel.
-#include "common.h"
+#include "row_pieces.h"
 
 
 namespace ghf {
@@ -18,6 +18,53 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 ip_f16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int IP_MT = 2;       // m-tiles (16 rows each) per wave
+
+// The epilogue of both MFMA kernels: lane (c16, q) holds, before the ReLU, value(t, s) = column 16 t + 4 q + s of row r.
+// Stores the row (r < N) and, SPLIT, its GHF_WLAYOUT_SPLIT2H pieces, scale and range-guard count (row_pieces.h): a row lives
+// in the four lanes {c16, c16 + 16, c16 + 32, c16 + 48}.  All lanes take part.
+template <int NT, bool SPLIT, class V>
+__device__ __forceinline__ void ip_store_row(V value, int64_t r, int64_t N, int lane, float* __restrict__ h0,
+                                             char* __restrict__ h_split, int32_t* __restrict__ range_flag) {
+    constexpr int D = 16 * NT;
+    const int q = lane >> 4;
+    f32x4 v[NT];
+    float mx = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            v[t][s] = fmaxf(value(t, s), 0.f);
+            mx = fmaxf(mx, v[t][s]);
+        }
+    auto store_h0 = [&] {
+        float* __restrict__ o = h0 + (size_t)r * D + 4 * q;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) *(f32x4*)(o + 16 * t) = v[t];
+    };
+    if constexpr (!SPLIT) {
+        if (r < N) store_h0();
+    } else {
+        RowCut<MfmaRowGroup> cut(mx);
+        if (r < N) {                                     // (a clamped row r >= N fills whole lane groups: they reduce, uncounted)
+            store_h0();
+            _Float16* __restrict__ sp = (_Float16*)(h_split + (size_t)r * (4 * D)) + 4 * q;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                ip_f16x4 hi4, lo4;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    _Float16 hi, lo;
+                    cut.piece(v[t][s], hi, lo);
+                    hi4[s] = hi;
+                    lo4[s] = lo;
+                }
+                *(ip_f16x4*)(sp + 16 * t) = hi4;
+                *(ip_f16x4*)(sp + D + 16 * t) = lo4;
+            }
+        }
+        cut.finish(r < N && MfmaRowGroup::leader(lane), (float*)(h_split + (size_t)N * (4 * D)) + r, range_flag);
+    }
+}
 
 // SPLIT: also write the rows in GHF_WLAYOUT_SPLIT2H form (ghf_split_rows) for the first message layer's gathers: a row
 // lives in the four lanes {c16, c16 + 16, c16 + 32, c16 + 48}, so its largest magnitude is two lane exchanges away.
@@ -88,66 +135,9 @@ __global__ __launch_bounds__(256) void input_proj_mfma_kernel(const float* __res
 #pragma unroll
         for (int m = 0; m < IP_MT; ++m) a[m] = an[m];
     }
-    auto across_q = [&](float v, bool take_max) -> float {     // over the four lanes that hold one row
 #pragma unroll
-        for (int off = 16; off < 64; off <<= 1) {
-            const float o = __shfl_xor(v, off);
-            v = take_max ? fmaxf(v, o) : v + o;
-        }
-        return v;
-    };
-#pragma unroll
-    for (int m = 0; m < IP_MT; ++m) {
-        const int64_t r = row_base + 16 * m + c16;
-        f32x4 v[NT];
-        float mx = 0.f;
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                v[t][s] = fmaxf(acc[m][t][s], 0.f);
-                mx = fmaxf(mx, v[t][s]);
-            }
-        float up = 1.f;
-        if (SPLIT) {                                      // (all lanes take part in the reduction)
-            const int sh = split2h_shift(across_q(mx, true));
-            up = pow2f(sh);
-            if (r < N && q == 0) *(float*)(h_split + (size_t)N * (4 * D) + (size_t)r * 4) = pow2f(-sh);
-        }
-        if (r < N) {
-            float* __restrict__ o = h0 + (size_t)r * D + 4 * q;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) *(f32x4*)(o + 16 * t) = v[t];
-            if (SPLIT) {
-                _Float16* __restrict__ sp = (_Float16*)(h_split + (size_t)r * (4 * D)) + 4 * q;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    ip_f16x4 hi4, lo4;
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        _Float16 hi, lo;
-                        split2h(v[t][s] * up, hi, lo);
-                        hi4[s] = hi;
-                        lo4[s] = lo;
-                    }
-                    *(ip_f16x4*)(sp + 16 * t) = hi4;
-                    *(ip_f16x4*)(sp + D + 16 * t) = lo4;
-                }
-            }
-        }
-        if (SPLIT) {                                      // range guard (common.h); all lanes take part in the reduction
-            float tiny = 0.f, nz = 0.f;
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int s = 0; s < 4; ++s) { tiny += (float)range_tiny(v[t][s] * up); nz += v[t][s] != 0.f ? 1.f : 0.f; }
-            if (__ballot(tiny != 0.f)) {
-                tiny = across_q(tiny, false);
-                nz = across_q(nz, false);
-                if (r < N && q == 0) range_raise(range_flag, GHF_RANGE_ROWS, (int)tiny, (int)nz);
-            }
-        }
-    }
+    for (int m = 0; m < IP_MT; ++m)
+        ip_store_row<NT, SPLIT>([&](int t, int s) { return acc[m][t][s]; }, row_base + 16 * m + c16, N, lane, h0, h_split, range_flag);
   }
 }
 
@@ -248,14 +238,6 @@ __global__ __launch_bounds__(256, 2) void input_proj_h_kernel(const float* __res
                 xr[m][j][1] = *(const f32x4*)(p + 32 * j + 4);
             }
         }
-        auto across_q = [&](float v, bool take_max) -> float {     // over the four lanes that hold one row
-#pragma unroll
-            for (int off = 16; off < 64; off <<= 1) {
-                const float o = __shfl_xor(v, off);
-                v = take_max ? fmaxf(v, o) : v + o;
-            }
-            return v;
-        };
         ip_i32x4 xh[IP_MT][KS], xl[IP_MT][KS];
         float xinv[IP_MT];
 #pragma unroll
@@ -267,10 +249,8 @@ __global__ __launch_bounds__(256, 2) void input_proj_h_kernel(const float* __res
                 for (int u = 0; u < 2; ++u)
 #pragma unroll
                     for (int c = 0; c < 4; ++c) mx = fmaxf(mx, fabsf(xr[m][j][u][c]));
-            const int sh = split2h_shift(across_q(mx, true));
-            const float up = pow2f(sh);
-            xinv[m] = pow2f(-sh) * winv;
-            float tiny = 0.f, nz = 0.f;
+            RowCut<MfmaRowGroup> cut(mx);                // (range guard: the rows of x as the contraction sees them)
+            xinv[m] = pow2f(-cut.sh) * winv;
 #pragma unroll
             for (int j = 0; j < KS; ++j) {
                 ip_f16x8 hi8, lo8;
@@ -279,21 +259,14 @@ __global__ __launch_bounds__(256, 2) void input_proj_h_kernel(const float* __res
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         _Float16 hi, lo;
-                        const float xs = xr[m][j][u][c] * up;
-                        split2h(xs, hi, lo);
+                        cut.piece(xr[m][j][u][c], hi, lo);
                         hi8[4 * u + c] = hi;
                         lo8[4 * u + c] = lo;
-                        tiny += (float)range_tiny(xs);
-                        nz += xs != 0.f ? 1.f : 0.f;
                     }
                 xh[m][j] = __builtin_bit_cast(ip_i32x4, hi8);
                 xl[m][j] = __builtin_bit_cast(ip_i32x4, lo8);
             }
-            if (__ballot(tiny != 0.f)) {                 // range guard (common.h): the rows of x as the contraction sees them
-                tiny = across_q(tiny, false);
-                nz = across_q(nz, false);
-                if (row_base + 16 * m + c16 < N && q == 0) range_raise(range_flag, GHF_RANGE_ROWS, (int)tiny, (int)nz);
-            }
+            cut.finish(row_base + 16 * m + c16 < N && MfmaRowGroup::leader(lane), range_flag);
         }
         f32x4 acc[IP_MT][NT];
 #pragma unroll
@@ -324,50 +297,11 @@ __global__ __launch_bounds__(256, 2) void input_proj_h_kernel(const float* __res
         // ---- epilogue: scales out, bias, ReLU, h0 and its pieces (as the fp32 kernel's) ----
 #pragma unroll
         for (int m = 0; m < IP_MT; ++m) {
-            const int64_t r = row_base + 16 * m + c16;
-            f32x4 v[NT];
-            float mx = 0.f;
+            f32x4 bv[NT];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const f32x4 bv = *(const f32x4*)(bias + 16 * t + 4 * q);
-#pragma unroll
-                for (int sI = 0; sI < 4; ++sI) {
-                    v[t][sI] = fmaxf(fmaf(acc[m][t][sI], xinv[m], bv[sI]), 0.f);
-                    mx = fmaxf(mx, v[t][sI]);
-                }
-            }
-            const int sh = split2h_shift(across_q(mx, true));
-            const float up = pow2f(sh);
-            if (r < N && q == 0) *(float*)(h_split + (size_t)N * (4 * D) + (size_t)r * 4) = pow2f(-sh);
-            if (r < N) {
-                float* __restrict__ o = h0 + (size_t)r * D + 4 * q;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) *(f32x4*)(o + 16 * t) = v[t];
-                _Float16* __restrict__ sp = (_Float16*)(h_split + (size_t)r * (4 * D)) + 4 * q;
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    ip_f16x4 hi4, lo4;
-#pragma unroll
-                    for (int sI = 0; sI < 4; ++sI) {
-                        _Float16 hi, lo;
-                        split2h(v[t][sI] * up, hi, lo);
-                        hi4[sI] = hi;
-                        lo4[sI] = lo;
-                    }
-                    *(ip_f16x4*)(sp + 16 * t) = hi4;
-                    *(ip_f16x4*)(sp + D + 16 * t) = lo4;
-                }
-            }
-            float tiny = 0.f, nz = 0.f;                  // range guard on the rows of h0 (common.h)
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int sI = 0; sI < 4; ++sI) { tiny += (float)range_tiny(v[t][sI] * up); nz += v[t][sI] != 0.f ? 1.f : 0.f; }
-            if (__ballot(tiny != 0.f)) {
-                tiny = across_q(tiny, false);
-                nz = across_q(nz, false);
-                if (r < N && q == 0) range_raise(range_flag, GHF_RANGE_ROWS, (int)tiny, (int)nz);
-            }
+            for (int t = 0; t < NT; ++t) bv[t] = *(const f32x4*)(bias + 16 * t + 4 * q);
+            ip_store_row<NT, true>([&](int t, int s) { return fmaf(acc[m][t][s], xinv[m], bv[t][s]); }, row_base + 16 * m + c16, N, lane,
+                                   h0, h_split, range_flag);
         }
     }
 }

@@ -68,7 +68,7 @@
 // s_set_gpr_idx_on directly, nor a VALU instruction that must not be indexed follow s_set_gpr_idx_off directly.
 // Template parameter SKIP: the instances for the backward's two gradient passes, whose weights have one zero half
 // (GHF_FLAG_ZERO_SRC / GHF_FLAG_ZERO_DST): that half's gathers and products are compiled out.
-#include "common.h"
+#include "row_pieces.h"
 
 #include <type_traits>
 
@@ -1237,23 +1237,15 @@ __global__ __launch_bounds__(256) void split2h_rows_kernel(const float* __restri
     const float* __restrict__ src = h + row * d;
     float mx = 0.f;
     for (int k = lane; k < d; k += 64) mx = fmaxf(mx, fabsf(src[k]));
-    const int sh = split2h_shift(wave_absmax(mx));
-    const float up = pow2f(sh);
+    RowCut<LaneGroup<64>> cut(mx);
     _Float16* __restrict__ dst = (_Float16*)(out + row * (4 * (int64_t)d));
-    int tiny = 0, nz = 0;
     for (int k = lane; k < d; k += 64) {
         _Float16 hi, lo;
-        const float xs = src[k] * up;
-        split2h(xs, hi, lo);
+        cut.piece(src[k], hi, lo);
         dst[k] = hi;
         dst[d + k] = lo;
-        tiny += __popcll(__ballot(range_tiny(xs)));
-        nz += __popcll(__ballot(xs != 0.f));
     }
-    if (lane == 0) {
-        *(float*)(out + N * (4 * (int64_t)d) + row * 4) = pow2f(-sh);
-        range_raise(range_flag, GHF_RANGE_ROWS, tiny, nz);
-    }
+    cut.finish(lane == 0, (float*)(out + N * (4 * (int64_t)d) + row * 4), range_flag);
 }
 
 int launch_split2h_rows(const float* h, int64_t N, int d, int64_t row0, int64_t rows, void* h_split, hipStream_t stream) {

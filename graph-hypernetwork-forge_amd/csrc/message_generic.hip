@@ -11,7 +11,7 @@
 // bitwise reproducible run to run.
 // This is the correctness-first kernel; the MFMA kernels (message_bx.hip, message_pp.hip) take over
 // for the hidden sizes it is built for.
-#include "common.h"
+#include "row_pieces.h"
 
 #include <stdlib.h>
 
@@ -130,12 +130,10 @@ __global__ __launch_bounds__(GEN_TPB) void tail_kernel(const float* __restrict__
 // Second stage for split destination blocks (hubs, and the blocks of a launch's last, partly filled round): sum the block's
 // partial slots in a fixed order (reproducible), then the K3 tail.  Grid: (the row range's work items) x COMB_Y; an item of
 // an unsplit block returns at once, item j of a block cut into k items takes the block's groups of rows j, j + k, ... (with
-// blockIdx.y: j + k y, ...) — no search for the block, its id is in the item.  Two kernels: d % 4 == 0 up to 256 on
-// 16-byte accesses, d / 4 lanes per row, every slot's load of a row in flight at once (round 3: the previous kernel — one
-// wave per row, two columns per lane, four loads in flight — took 55-85 us per launch at BASELINE config 3 for 45 blocks of
-// eight slots, 0.25 ms per forward); any d on the old scheme.
-constexpr int COMB_MAX_PER_LANE = GEN_MAX_D / 64;
-constexpr int COMB_ROWS = 8, COMB_Y = 6;
+// blockIdx.y: j + k y, ...) — no search for the block, its id is in the item.  16-byte accesses, d / 4 lanes per row,
+// every slot's load of a row in flight at once (round 3: the previous kernel — one wave per row, two columns per lane, four
+// loads in flight — took 55-85 us per launch at BASELINE config 3 for 45 blocks of eight slots, 0.25 ms per forward).
+constexpr int COMB_Y = 6;
 typedef float comb_f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 comb_f16x4 __attribute__((ext_vector_type(4)));
 
@@ -169,14 +167,6 @@ __global__ __launch_bounds__(256) void combine_split4_kernel(
     const int nrows_blk = (int)((row_end - node0) < BN ? (row_end - node0) : BN);
     const int nwg = (int)gridDim.y * cb.nslots;
     const size_t sstr = (size_t)BN * D;                     // slot stride
-    auto across = [&](float v, bool take_max) -> float {    // over the LPR lanes of a row
-#pragma unroll
-        for (int off = 1; off < LPR; off <<= 1) {
-            const float o = __shfl_xor(v, off);
-            v = take_max ? fmaxf(v, o) : v + o;
-        }
-        return v;
-    };
     const comb_f32x4 gm = no_tail ? (comb_f32x4){1.f, 1.f, 1.f, 1.f} : *(const comb_f32x4*)(g + c0);
     const comb_f32x4 bt = no_tail ? (comb_f32x4){0.f, 0.f, 0.f, 0.f} : *(const comb_f32x4*)(b + c0);
     for (int vb = ((int)blockIdx.y * cb.nslots + cb.j) * (4 * RPW); vb < nrows_blk; vb += nwg * (4 * RPW)) {
@@ -205,18 +195,11 @@ __global__ __launch_bounds__(256) void combine_split4_kernel(
         t *= inv;
         if (agg_out && live) *(comb_f32x4*)(agg_out + (size_t)node * D + c0) = t;
         comb_f32x4 y;
-        float s = 0.f;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            y[e] = no_tail ? t[e] + hv[e] : fmaxf(t[e] + hv[e], 0.f);          // (hv = 0 without ADD_H)
-            s += y[e];
-        }
+        for (int e = 0; e < 4; ++e) y[e] = no_tail ? t[e] + hv[e] : fmaxf(t[e] + hv[e], 0.f);      // (hv = 0 without ADD_H)
         if (!no_tail) {
-            const float mean = across(s, false) * (1.0f / D);
-            float var = 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { const float q = y[e] - mean; var += q * q; }
-            const float rstd = 1.0f / sqrtf(across(var, false) * (1.0f / D) + eps);
+            float mean, rstd;
+            row_mean_rstd<LaneGroup<LPR>, D, 4>([&](int e) { return y[e]; }, eps, mean, rstd);
 #pragma unroll
             for (int e = 0; e < 4; ++e) y[e] = (y[e] - mean) * rstd * gm[e] + bt[e];
         }
@@ -225,123 +208,22 @@ __global__ __launch_bounds__(256) void combine_split4_kernel(
             float mx = 0.f;
 #pragma unroll
             for (int e = 0; e < 4; ++e) mx = fmaxf(mx, fabsf(y[e]));
-            const int sh = split2h_shift(across(mx, true));
-            const float up = pow2f(sh);
+            RowCut<LaneGroup<LPR>> cut(mx);
             comb_f16x4 hi4, lo4;
-            float tiny = 0.f, nz = 0.f;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 _Float16 hi, lo;
-                split2h(y[e] * up, hi, lo);
+                cut.piece(y[e], hi, lo);
                 hi4[e] = hi;
                 lo4[e] = lo;
-                tiny += (float)range_tiny(y[e] * up);
-                nz += y[e] != 0.f ? 1.f : 0.f;
             }
-            tiny = across(tiny, false);
-            nz = across(nz, false);
             if (live) {
                 _Float16* sp = (_Float16*)h_split_out + (size_t)node * 2 * D + c0;
                 *(comb_f16x4*)sp = hi4;
                 *(comb_f16x4*)(sp + D) = lo4;
-                if (lane % LPR == 0) {
-                    *(float*)((char*)h_split_out + (size_t)N * D * 4 + (size_t)node * 4) = pow2f(-sh);
-                    range_raise(range_flag, GHF_RANGE_ROWS, (int)tiny, (int)nz);
-                }
             }
+            cut.finish(live && LaneGroup<LPR>::leader(lane), (float*)((char*)h_split_out + (size_t)N * D * 4) + node, range_flag);
         }
-    }
-}
-
-// any d: one wave per destination row, lanes stride the columns
-__global__ __launch_bounds__(256) void combine_split_kernel(
-    const float* __restrict__ partial, const int32_t* __restrict__ item_tab, const int32_t* __restrict__ blk_item_off, int64_t item0,
-    const float* __restrict__ h, const int32_t* __restrict__ indeg, const float* __restrict__ g,
-    const float* __restrict__ b, float eps, int64_t N, int d, int BN, int64_t row_end,
-    float* __restrict__ h_out, void* __restrict__ h_split_out, int split_layout, int no_tail, int32_t* __restrict__ range_flag,
-    float* __restrict__ agg_out) {
-    const CombBlock cb = comb_block(item_tab, blk_item_off, item0);
-    if (!cb.live) return;
-    const int slot0 = cb.slot0, nslots = cb.nslots;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t node0 = cb.blk * BN;
-    const int nrows_blk = (int)((row_end - node0) < BN ? (row_end - node0) : BN);
-    const int wg = (int)blockIdx.y * nslots + cb.j, nwg = (int)gridDim.y * nslots;
-    for (int vb = wg * COMB_ROWS; vb < nrows_blk; vb += nwg * COMB_ROWS) {
-    const int nrows = nrows_blk < vb + COMB_ROWS ? nrows_blk : vb + COMB_ROWS;
-    for (int v = vb + w; v < nrows; v += 4) {
-        const int64_t node = node0 + v;
-        const int deg = indeg[node];
-        const float inv = (no_tail & GHF_FLAG_RAW_SUM) ? 1.0f : 1.0f / (float)(deg > 1 ? deg : 1);
-        float x[COMB_MAX_PER_LANE];
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < COMB_MAX_PER_LANE; ++c) {
-            const int o = lane + 64 * c;
-            x[c] = 0.f;
-            if (o < d) {
-                const float* __restrict__ p = partial + ((size_t)slot0 * BN + v) * d + o;
-                const size_t sstr = (size_t)BN * d;                 // slot stride
-                float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
-                int j = 0;
-                for (; j + 4 <= nslots; j += 4) {
-                    t0 += p[(size_t)j * sstr];
-                    t1 += p[(size_t)(j + 1) * sstr];
-                    t2 += p[(size_t)(j + 2) * sstr];
-                    t3 += p[(size_t)(j + 3) * sstr];
-                }
-                for (; j < nslots; ++j) t0 += p[(size_t)j * sstr];
-                float t = ((t0 + t1) + (t2 + t3)) * inv;
-                if (agg_out) agg_out[(size_t)node * d + o] = t;
-                x[c] = no_tail ? ((no_tail & GHF_FLAG_ADD_H) ? t + h[(size_t)node * d + o] : t) : fmaxf(t + h[(size_t)node * d + o], 0.f);
-                s += x[c];
-            }
-        }
-        if (!no_tail) {
-            const float mean = wave_sum(s) / (float)d;
-            float var = 0.f;
-#pragma unroll
-            for (int c = 0; c < COMB_MAX_PER_LANE; ++c)
-                if (lane + 64 * c < d) { const float t = x[c] - mean; var += t * t; }
-            const float rstd = 1.0f / sqrtf(wave_sum(var) / (float)d + eps);
-#pragma unroll
-            for (int c = 0; c < COMB_MAX_PER_LANE; ++c) {
-                const int o = lane + 64 * c;
-                if (o < d) x[c] = (x[c] - mean) * rstd * g[o] + b[o];
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < COMB_MAX_PER_LANE; ++c) {
-            const int o = lane + 64 * c;
-            if (o < d) h_out[(size_t)node * d + o] = x[c];
-        }
-        if (h_split_out) {                                 // SPLIT2H: the wave holds the whole row
-            float mx = 0.f;
-#pragma unroll
-            for (int c = 0; c < COMB_MAX_PER_LANE; ++c)
-                if (lane + 64 * c < d) mx = fmaxf(mx, fabsf(x[c]));
-            const int sh = split2h_shift(wave_absmax(mx));
-            const float up = pow2f(sh);
-            _Float16* sp = (_Float16*)h_split_out + (size_t)node * 2 * d;
-            int tiny = 0, nz = 0;
-#pragma unroll
-            for (int c = 0; c < COMB_MAX_PER_LANE; ++c) {
-                const int o = lane + 64 * c;
-                if (o < d) {
-                    _Float16 hi, lo;
-                    split2h(x[c] * up, hi, lo);
-                    sp[o] = hi;
-                    sp[d + o] = lo;
-                    tiny += range_tiny(x[c] * up);
-                    nz += x[c] != 0.f;
-                }
-            }
-            tiny = (int)wave_sum((float)tiny);
-            nz = (int)wave_sum((float)nz);
-            if (lane == 0) range_raise(range_flag, GHF_RANGE_ROWS, tiny, nz);
-            if (lane == 0) *(float*)((char*)h_split_out + (size_t)N * d * 4 + (size_t)node * 4) = pow2f(-sh);
-        }
-    }
     }
 }
 
@@ -352,19 +234,13 @@ int launch_combine_split(const MsgArgs& a, hipStream_t stream) {
     GHF_REQUIRE(a.n_items < (1ll << 31), "combine_split: too many work items");
     const dim3 grid((unsigned)a.n_items, (unsigned)COMB_Y);
     const int nt = a.flags & (GHF_FLAG_NO_TAIL | GHF_FLAG_RAW_SUM | GHF_FLAG_ADD_H);
-    const bool vec = (a.d % 4) == 0 && (a.d == 64 || a.d == 128 || a.d == 256) &&
-                     (!a.h_split_out || a.wlayout == GHF_WLAYOUT_SPLIT2H);
 #define GHF_COMB4(LPR)                                                                                                      \
     combine_split4_kernel<LPR><<<grid, 256, 0, stream>>>(a.partial, a.item_tab, a.blk_item_off, a.item0, a.h, a.indeg, a.ln_gamma, \
                                                         a.ln_beta, a.ln_eps, a.N, a.block_nodes, row_end, a.h_out, a.h_split_out, \
                                                         nt, range_flag_ptr(), a.agg_out)
-    if (vec && a.d == 64) GHF_COMB4(16);
-    else if (vec && a.d == 128) GHF_COMB4(32);
-    else if (vec && a.d == 256) GHF_COMB4(64);
-    else
-        combine_split_kernel<<<grid, 256, 0, stream>>>(a.partial, a.item_tab, a.blk_item_off, a.item0, a.h, a.indeg, a.ln_gamma, a.ln_beta,
-                                                       a.ln_eps, a.N, a.d, a.block_nodes, row_end, a.h_out, a.h_split_out, a.wlayout,
-                                                       nt, range_flag_ptr(), a.agg_out);
+    if (a.d == 64) GHF_COMB4(16);
+    else if (a.d == 128) GHF_COMB4(32);
+    else return set_err(GHF_EUNSUPPORTED, "combine_split: split blocks exist at d = 64 and 128 only, got d = %d", a.d);
 #undef GHF_COMB4
     GHF_LAUNCH_CHECK();
     return GHF_OK;

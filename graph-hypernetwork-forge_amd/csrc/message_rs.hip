@@ -1,7 +1,7 @@
 // message_rs.hip — the message layer for wide hidden sizes (d a multiple of 128, d >= 256: BASELINE config 5), relation-
 // stationary in two passes.  reference: models/hypergnn.py:201-230 (messages, mean, mean-W_self self-loop), :288-296 (tail).
 //
-// Why not the destination-block kernels (message_hx.hip & co.): they re-stream a relation's [2d, d] weights for every
+// Why not the destination-block kernels (message_bx.hip & co.): they re-stream a relation's [2d, d] weights for every
 // (destination block, relation) chunk — 512 KB per ~10 rows at d = 256 with 256 relations — and their block sums plus
 // A tiles no longer fit 160 KB of LDS.  Here the edges are grouped by RELATION instead (inside one by destination) and
 // cut into tiles of 128 edges; a workgroup multiplies a tile's gathered rows [h_src | h_dst] (128 x 2d) with 128
@@ -16,7 +16,7 @@
 // "16 contiguous k per row"), double buffered.  A wave owns 32 rows x 128 columns = 2 x 8 accumulator tiles; per k-step
 // its operands are 10 ds_read_b128 (lane (i, q) reads k = 4q..4q+3 of row i: register s feeds MFMA s of the step, the
 // same k-permutation on both operands).
-#include "common.h"
+#include "row_pieces.h"
 
 #include <type_traits>
 
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void edge_transform_kernel(
         }
 }
 
-// ---- pass 1 with the contraction of message_hx.hip: two fp16 pieces per operand, three 16x16x32 products -----------
+// ---- pass 1 with the contraction of message_bx.hip: two fp16 pieces per operand, three 16x16x32 products -----------
 // (its header: x 2^s = hi + lo, hi*hi + hi*lo + lo*hi in fp32, the exact scales taken out again).  Operands:
 //   h_split        ghf_split_rows(h, SPLIT2H): N rows [hi d | lo d] fp16, then N float 2^-s(row)
 //   w2h            ghf_weights_pack_rs: per relation [half: msg, self][piece: hi, lo][n][k] fp16 (TRANSPOSED: k contiguous),
@@ -126,51 +126,42 @@ __global__ __launch_bounds__(256) void edge_transform_kernel(
 // buffered.  fp32 MFMA: 64 MFMAs x 32 cycles per 16 k; here 48 x 16 cycles per 32 k — 5.3 x less matrix time.
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-// Launched as <32, 1> only (d % 256 != 0; d % 256 == 0 runs edge_transform_h3_kernel below); <64, 1> and <32, 2> were
-// measured and retired (DESIGN_HISTORY.md).
-// KH = k per step: 32 (64-byte pieces of a row per visit; two workgroups per CU) or, for d % 256 == 0, 64 (whole 128-byte
-// lines, a half-row in four visits instead of eight; 129 KB of LDS, one workgroup per CU, the 16-byte granules of a row
-// XOR-swizzled by row & 7 so that a fragment read of 16 rows covers all banks).
-// NCT = 128-column groups per workgroup (round 3): at d % 256 == 0 a workgroup of EIGHT waves takes a row tile's 128 rows
-// times 256 columns — waves 0-3 the first 128 columns, waves 4-7 the next, all eight reading the one A tile in LDS — so the
-// tile's rows are gathered once per 256 columns instead of once per 128: at d = 256 every gathered row is fetched once, not
-// twice (BASELINE config 5: 91 GB of 205 GB per layer were pass 1's fetches, profiles/r02_c5_kernel_pmc.json).
-template <int KH, int NCT>
-__global__ __launch_bounds__(256 * NCT, KH == 32 ? 2 : 1) void edge_transform_h_kernel(
+// For d % 256 != 0 (d % 256 == 0 runs edge_transform_h3_kernel below).  32 k per step: 64-byte pieces of a row per visit,
+// two workgroups per CU; one 128-column group per workgroup of four waves.  Steps of 64 k and eight-wave workgroups
+// with two column groups were measured and retired (DESIGN_HISTORY.md).
+__global__ __launch_bounds__(256, 2) void edge_transform_h_kernel(
     const char* __restrict__ h_split, int64_t N, int d, const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
     const int64_t* __restrict__ ypos, const int64_t* __restrict__ slice_tab, const char* __restrict__ w2h, int R,
     const float* __restrict__ bias, const char* __restrict__ x_split, int64_t NX, const float* __restrict__ row_cnt,
     float* __restrict__ Y) {
-    constexpr int RS_KH = KH, GR = KH / 8, GPT = KH / 16;  // granules (8 fp16) per tile row; per thread, piece and step of B
-    constexpr int GPA = GPT / NCT, TPR = GR / GPA;         // A tile: granules per thread, threads per row (NCT x 256 threads, 128 rows)
-    static_assert(GPA >= 1 && (NCT == 1 || NCT == 2), "at most two column groups per workgroup");
+    // k per step; 16-byte granules (8 fp16) per thread, piece and step; threads per tile row
+    constexpr int KH = 32, GPT = KH / 16, TPR = 2;
     extern __shared__ __attribute__((aligned(16))) char rs_lds[];
     typedef _Float16 (*tile_t)[2][RS_TM][KH];              // [buffer][piece][row][k]
-    typedef _Float16 (*btile_t)[2][RS_TN * NCT][KH];
+    typedef _Float16 (*btile_t)[2][RS_TN][KH];
     tile_t At = (tile_t)rs_lds;
     btile_t Bt = (btile_t)(rs_lds + (size_t)2 * 2 * RS_TM * KH * 2);
     // per tile row: 2^-s of its source row, n 2^-s of its destination row, n — n = the number of edges the row stands for
     // (ghf.h: rows of pre-summed runs; 1 without them, and every product below is then what it was)
-    float (*rsc)[RS_TM] = (float (*)[RS_TM])(rs_lds + (size_t)2 * 2 * (1 + NCT) * RS_TM * KH * 2);
-    // 16-byte granule g of tile row `row` sits at slot swz(row, g) of the row.  KH = 64: 8 granules, key row & 7.  KH = 32: a row
-    // is 64 bytes, four rows share a 256-byte bank line, and a ds_read_b128 serves lanes {0-3, 12-15, 20-27}, {4-11, 16-19,
-    // 28-31}, ... together (MI355X_MICROARCH.md, LDS): unswizzled, rows r and r + 12 (and r + 4, r + 8 of the neighbouring
+    float (*rsc)[RS_TM] = (float (*)[RS_TM])(rs_lds + (size_t)2 * 2 * 2 * RS_TM * KH * 2);
+    // 16-byte granule g of tile row `row` sits at slot swz(row, g) of the row.  A row is 64 bytes, four rows share a
+    // 256-byte bank line, and a ds_read_b128 serves lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... together (MI355X_MICROARCH.md, LDS): unswizzled, rows r and r + 12 (and r + 4, r + 8 of the neighbouring
     // k-quarter) of such a group shared banks — every fragment read took two passes (round 3: LDS time per step was at the
     // matrix time).  Key (-(row >> 2)) & 3 = 0, 3, 2, 1 for the four row quads puts the sixteen lanes of every group in
     // sixteen different slots.
-    auto swz = [](int row, int g) { return KH == 64 ? (g ^ (row & 7)) : (g ^ ((0 - (row >> 2)) & 3)); };
+    auto swz = [](int row, int g) { return g ^ ((0 - (row >> 2)) & 3); };
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int w = wv & 3, cg = wv >> 2;                     // row group (32 rows) and column group (128 columns) of this wave
+    const int w = wv;                                      // row group (32 rows) of this wave
     const int c16 = lane & 15, q = lane >> 4;
-    const unsigned ncol = (unsigned)d / (RS_TN * NCT), tile = blockIdx.x / ncol;
+    const unsigned ncol = (unsigned)d / RS_TN, tile = blockIdx.x / ncol;
     const int64_t r = slice_tab[3 * (size_t)tile], e0 = slice_tab[3 * (size_t)tile + 1], e1 = slice_tab[3 * (size_t)tile + 2];
-    const int n0 = (int)(blockIdx.x % ncol) * RS_TN * NCT;
+    const int n0 = (int)(blockIdx.x % ncol) * RS_TN;
     const size_t hrow = (size_t)4 * d;                     // bytes per split row
     const float* __restrict__ hscale = (const float*)(h_split + (size_t)N * hrow);
-    // staging map: thread t moves the 16-byte granules (row t/TPR, k 8 (GPA (t%TPR) + i) .. +7), i < GPA, of both pieces of
-    // the A tile, and (row t/2 of 128 NCT, k 8 (GPT (t%2) + i) .. +7), i < GPT, of the B tile
-    const int srow = t / TPR, sg = GPA * (t % TPR);
-    const int brow_i = t >> 1, sgb = GPT * (t & 1);
+    // staging map: thread t moves the 16-byte granules (row t/2, k 8 (GPT (t%2) + i) .. +7), i < GPT, of both pieces of the A
+    // tile and of the B tile
+    const int srow = t / TPR, sg = GPT * (t % TPR);
+    const int brow_i = srow, sgb = sg;
     int64_t e = e0 + srow;
     if (e >= e1) e = e1 - 1;                               // rows past the tile's end repeat its last edge (never stored)
     const int64_t su = src[e], sv = dst[e];               // su < 0: row ~su of x_split (the sum of a run's source rows)
@@ -186,7 +177,7 @@ __global__ __launch_bounds__(256 * NCT, KH == 32 ? 2 : 1) void edge_transform_h_
     // Four register sets: the rows of a step are requested three steps before they are written to LDS — this kernel's 293
     // registers leave one wave per SIMD, so a gather's latency (an HBM miss, ~2 us) has to be covered by this wave's own
     // MFMAs (768 cycles per step).
-    struct Stage { i32x4 a[2][GPA], b[2][GPT]; };          // [piece][i]
+    struct Stage { i32x4 a[2][GPT], b[2][GPT]; };          // [piece][i]
     Stage st[4];
     auto fetch = [&](int k0, Stage& S) {                   // k0: first contraction index of the step, in [0, 2d)
         const int half = k0 >= d;
@@ -196,7 +187,7 @@ __global__ __launch_bounds__(256 * NCT, KH == 32 ? 2 : 1) void edge_transform_h_
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
 #pragma unroll
-            for (int i = 0; i < GPA; ++i) S.a[pl][i] = *(const i32x4*)(arow + (size_t)pl * d * 2 + (size_t)(kk + 8 * (sg + i)) * 2);
+            for (int i = 0; i < GPT; ++i) S.a[pl][i] = *(const i32x4*)(arow + (size_t)pl * d * 2 + (size_t)(kk + 8 * (sg + i)) * 2);
 #pragma unroll
             for (int i = 0; i < GPT; ++i) S.b[pl][i] = *(const i32x4*)(brow + (size_t)pl * d * d * 2 + (size_t)(kk + 8 * (sgb + i)) * 2);
         }
@@ -205,7 +196,7 @@ __global__ __launch_bounds__(256 * NCT, KH == 32 ? 2 : 1) void edge_transform_h_
 #pragma unroll
         for (int pl = 0; pl < 2; ++pl) {
 #pragma unroll
-            for (int i = 0; i < GPA; ++i) *(i32x4*)&At[buf][pl][srow][8 * swz(srow, sg + i)] = S.a[pl][i];
+            for (int i = 0; i < GPT; ++i) *(i32x4*)&At[buf][pl][srow][8 * swz(srow, sg + i)] = S.a[pl][i];
 #pragma unroll
             for (int i = 0; i < GPT; ++i) *(i32x4*)&Bt[buf][pl][brow_i][8 * swz(brow_i, sgb + i)] = S.b[pl][i];
         }
@@ -217,10 +208,10 @@ __global__ __launch_bounds__(256 * NCT, KH == 32 ? 2 : 1) void edge_transform_h_
 #pragma unroll
         for (int b = 0; b < 8; ++b) acc[a][b] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    const int half_steps = d / RS_KH, total = 2 * half_steps;              // (half_steps % 4 == 0: d % 128 == 0, d % 256 == 0 for KH = 64)
+    const int half_steps = d / KH, total = 2 * half_steps;                 // (half_steps % 4 == 0: d % 128 == 0)
     fetch(0, st[0]);
-    fetch(1 * RS_KH, st[1]);
-    fetch(2 * RS_KH, st[2]);
+    fetch(1 * KH, st[1]);
+    fetch(2 * KH, st[2]);
     commit(0, st[0]);
     __syncthreads();
     auto run_step = [&](auto hf_tag, auto i_tag, int step) {
@@ -228,43 +219,40 @@ __global__ __launch_bounds__(256 * NCT, KH == 32 ? 2 : 1) void edge_transform_h_
         {
             const int buf = step & 1;
             const int pre = step + 3 < total ? step + 3 : total - 1;       // (past the end: the last step again, no branch around loads)
-            fetch(pre * RS_KH, st[(i4 + 3) & 3]);
+            fetch(pre * KH, st[(i4 + 3) & 3]);
+            i32x4 a[2][2];
 #pragma unroll
-            for (int kk = 0; kk < KH / 32; ++kk) {
-                i32x4 a[2][2];
+            for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+                for (int pl = 0; pl < 2; ++pl) {
+                    const int row = 32 * w + 16 * rt + c16;
+                    a[rt][pl] = *(const i32x4*)&At[buf][pl][row][8 * swz(row, q)];
+                }
+#pragma unroll
+            for (int ch = 0; ch < 2; ++ch) {           // the column tiles in two groups of four: 32 fragment registers live, not 64
+                i32x4 b[4][2];
+#pragma unroll
+                for (int c4 = 0; c4 < 4; ++c4)
+#pragma unroll
+                    for (int pl = 0; pl < 2; ++pl) {
+                        const int row = 16 * (4 * ch + c4) + c16;
+                        b[c4][pl] = *(const i32x4*)&Bt[buf][pl][row][8 * swz(row, q)];
+                    }
 #pragma unroll
                 for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-                    for (int pl = 0; pl < 2; ++pl) {
-                        const int row = 32 * w + 16 * rt + c16;
-                        a[rt][pl] = *(const i32x4*)&At[buf][pl][row][8 * swz(row, 4 * kk + q)];
+                    for (int c4 = 0; c4 < 4; ++c4) {
+                        const int ct = 4 * ch + c4;
+                        // the product TRANSPOSED (the weights' fragment as the A operand): a lane then holds four
+                        // consecutive columns of ONE row — 16-byte stores of the results (one column of four rows:
+                        // 4-byte stores, four times the store instructions)
+                        auto fma = [&](int pa, int pb) {
+                            acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, b[c4][pb]),
+                                                                                 __builtin_bit_cast(f16x8, a[rt][pa]), acc[rt][ct], 0, 0, 0);
+                        };
+                        fma(1, 0); fma(0, 1);          // lo*hi, hi*lo
+                        fma(0, 0);                     // hi*hi
                     }
-#pragma unroll
-                for (int ch = 0; ch < 2; ++ch) {           // the column tiles in two groups of four: 32 fragment registers live, not 64
-                    i32x4 b[4][2];
-#pragma unroll
-                    for (int c4 = 0; c4 < 4; ++c4)
-#pragma unroll
-                        for (int pl = 0; pl < 2; ++pl) {
-                            const int row = RS_TN * cg + 16 * (4 * ch + c4) + c16;
-                            b[c4][pl] = *(const i32x4*)&Bt[buf][pl][row][8 * swz(row, 4 * kk + q)];
-                        }
-#pragma unroll
-                    for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                        for (int c4 = 0; c4 < 4; ++c4) {
-                            const int ct = 4 * ch + c4;
-                            // the product TRANSPOSED (the weights' fragment as the A operand): a lane then holds four
-                            // consecutive columns of ONE row — 16-byte stores of the results (one column of four rows:
-                            // 4-byte stores, four times the store instructions)
-                            auto fma = [&](int pa, int pb) {
-                                acc[rt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, b[c4][pb]),
-                                                                                     __builtin_bit_cast(f16x8, a[rt][pa]), acc[rt][ct], 0, 0, 0);
-                            };
-                            fma(1, 0); fma(0, 1);          // lo*hi, hi*lo
-                            fma(0, 0);                     // hi*hi
-                        }
-                }
             }
             commit(buf ^ 1, st[(i4 + 1) & 3]);
             __syncthreads();
@@ -294,14 +282,14 @@ __global__ __launch_bounds__(256 * NCT, KH == 32 ? 2 : 1) void edge_transform_h_
 #pragma unroll
     for (int ct = 0; ct < 8; ++ct)
 #pragma unroll
-        for (int s = 0; s < 4; ++s) bv[ct][s] = bias[(size_t)r * d + n0 + RS_TN * cg + 16 * ct + 4 * q + s];
+        for (int s = 0; s < 4; ++s) bv[ct][s] = bias[(size_t)r * d + n0 + 16 * ct + 4 * q + s];
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt) {
         const int row = 32 * w + 16 * rt + c16;
         const int64_t ee = e0 + row;
         if (ee < e1) {
             const float fv = rsc[1][row] * wscale, n = rsc[2][row];
-            float* __restrict__ y = Y + (size_t)ypos[ee] * d + n0 + RS_TN * cg + 4 * q;
+            float* __restrict__ y = Y + (size_t)ypos[ee] * d + n0 + 4 * q;
 #pragma unroll
             for (int ct = 0; ct < 8; ++ct) {
                 f32x4 o;
@@ -623,6 +611,26 @@ __global__ __launch_bounds__(256) void segment_partial_kernel(const float* __res
     for (int o = threadIdx.x; o < d; o += 256) P[(size_t)slot * d + o] = ((red[0][o] + red[1][o]) + red[2][o]) + red[3][o];
 }
 
+// A row of d = 64 CPL elements held by one wave (x[c]: column lane + 64 c), cut into its two fp16 pieces (row_pieces.h)
+template <int CPL>
+__device__ __forceinline__ void cut_wave_row(const float (&x)[CPL], int lane, char* __restrict__ pieces, float* __restrict__ scale,
+                                             int32_t* __restrict__ range_flag) {
+    constexpr int d = 64 * CPL;
+    float mx = 0.f;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) mx = fmaxf(mx, fabsf(x[c]));
+    RowCut<LaneGroup<64>> cut(mx);
+    _Float16* __restrict__ sp = (_Float16*)pieces;
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) {
+        _Float16 hi, lo;
+        cut.piece(x[c], hi, lo);
+        sp[lane + 64 * c] = hi;
+        sp[d + lane + 64 * c] = lo;
+    }
+    cut.finish(lane == 0, scale, range_flag);
+}
+
 // Pass 2: out_v = (1/max(indeg,1)) * sum of v's rows of Y (contiguous: off[v] .. off[v+1]; a hub's slots of P instead),
 // then the tail.  One wave per destination; CPL = d / 64 columns per lane, all of a row's loads issued together and two
 // rows in flight (most destinations of a sharded power-law graph have a handful of rows: the wave's time is the
@@ -667,48 +675,21 @@ __global__ __launch_bounds__(256) void segment_tail_kernel(
         for (int c = 0; c < CPL; ++c) t0[c] += p[(size_t)j * d + 64 * c];
     }
     float x[CPL];
-    float s = 0.f;
 #pragma unroll
     for (int c = 0; c < CPL; ++c) {
         const float tt = (t0[c] + t1[c]) * inv;
         x[c] = no_tail ? tt : fmaxf(tt + hv[c], 0.f);
-        s += x[c];
     }
     if (!no_tail) {
-        const float mean = wave_sum(s) * (1.0f / d);
-        float var = 0.f;
-#pragma unroll
-        for (int c = 0; c < CPL; ++c) { const float tt = x[c] - mean; var += tt * tt; }
-        const float rstd = 1.0f / sqrtf(wave_sum(var) * (1.0f / d) + eps);
+        float mean, rstd;
+        row_mean_rstd<LaneGroup<64>, d, CPL>([&](int c) { return x[c]; }, eps, mean, rstd);
 #pragma unroll
         for (int c = 0; c < CPL; ++c) x[c] = (x[c] - mean) * rstd * g[lane + 64 * c] + b[lane + 64 * c];
     }
 #pragma unroll
     for (int c = 0; c < CPL; ++c) h_out[(size_t)v * d + lane + 64 * c] = x[c];
-    if (h_split_out) {                                     // the same row cut into its two fp16 pieces, for the next layer's pass 1
-        float mx = 0.f;
-#pragma unroll
-        for (int c = 0; c < CPL; ++c) mx = fmaxf(mx, fabsf(x[c]));
-        const int sh = split2h_shift(wave_absmax(mx));
-        const float up = pow2f(sh);
-        _Float16* __restrict__ sp = (_Float16*)(h_split_out + (size_t)v * 4 * d);
-        int tiny = 0, nz = 0;
-#pragma unroll
-        for (int c = 0; c < CPL; ++c) {
-            _Float16 hi, lo;
-            split2h(x[c] * up, hi, lo);
-            sp[lane + 64 * c] = hi;
-            sp[d + lane + 64 * c] = lo;
-            tiny += range_tiny(x[c] * up);
-            nz += x[c] != 0.f;
-        }
-        if (lane == 0) *(float*)(h_split_out + (size_t)n_split * 4 * d + (size_t)v * 4) = pow2f(-sh);
-        if (__ballot(tiny != 0)) {                         // range guard (common.h)
-            tiny = (int)wave_sum((float)tiny);
-            nz = (int)wave_sum((float)nz);
-            if (lane == 0) range_raise(range_flag, GHF_RANGE_ROWS, tiny, nz);
-        }
-    }
+    if (h_split_out)                                       // the same row cut into its two fp16 pieces, for the next layer's pass 1
+        cut_wave_row<CPL>(x, lane, h_split_out + (size_t)v * 4 * d, (float*)(h_split_out + (size_t)n_split * 4 * d) + v, range_flag);
 }
 
 // Pass 0 (graphs with hubs): the layer is linear in the source rows, so the edges of one (destination, relation) run need one
@@ -749,31 +730,9 @@ __global__ __launch_bounds__(256) void run_rows_kernel(const float* __restrict__
         for (int c = 0; c < CPL; ++c) t[0][c] += r0[64 * c];
     }
     float v[CPL];
-    float mx = 0.f;
 #pragma unroll
-    for (int c = 0; c < CPL; ++c) {
-        v[c] = (t[0][c] + t[1][c]) + (t[2][c] + t[3][c]);
-        mx = fmaxf(mx, fabsf(v[c]));
-    }
-    const int sh = split2h_shift(wave_absmax(mx));
-    const float up = pow2f(sh);
-    _Float16* __restrict__ sp = (_Float16*)(x_split + (size_t)x * 4 * d);
-    int tiny = 0, nz = 0;
-#pragma unroll
-    for (int c = 0; c < CPL; ++c) {
-        _Float16 hi, lo;
-        split2h(v[c] * up, hi, lo);
-        sp[lane + 64 * c] = hi;
-        sp[d + lane + 64 * c] = lo;
-        tiny += range_tiny(v[c] * up);
-        nz += v[c] != 0.f;
-    }
-    if (lane == 0) *(float*)(x_split + (size_t)nruns * 4 * d + (size_t)x * 4) = pow2f(-sh);
-    if (__ballot(tiny != 0)) {                             // range guard (common.h)
-        tiny = (int)wave_sum((float)tiny);
-        nz = (int)wave_sum((float)nz);
-        if (lane == 0) range_raise(range_flag, GHF_RANGE_ROWS, tiny, nz);
-    }
+    for (int c = 0; c < CPL; ++c) v[c] = (t[0][c] + t[1][c]) + (t[2][c] + t[3][c]);
+    cut_wave_row<CPL>(v, lane, x_split + (size_t)x * 4 * d, (float*)(x_split + (size_t)nruns * 4 * d) + x, range_flag);
 }
 
 int launch_run_rows(const float* h, int64_t N, int d, const int64_t* run_src, const int64_t* run_start, int64_t nruns,
@@ -838,9 +797,9 @@ int launch_edge_transform_h(const void* h_split, int64_t N, int d, const int64_t
         edge_transform_h3_kernel<<<grid / 2, 512, lds, stream>>>((const char*)h_split, N, d, src, dst, ypos, slice_tab,
                                                                  (const char*)w2h, R, bias, (const char*)x_split, NX, row_cnt, Y);
     } else {
-        constexpr size_t lds = (size_t)2 * 2 * 2 * RS_TM * 32 * 2 + 3 * RS_TM * 4;
-        GHF_SET_MAX_LDS((edge_transform_h_kernel<32, 1>), lds);
-        edge_transform_h_kernel<32, 1><<<grid, 256, lds, stream>>>((const char*)h_split, N, d, src, dst, ypos, slice_tab,
+        constexpr size_t lds = (size_t)2 * 2 * 2 * RS_TM * 32 * 2 + 3 * RS_TM * 4;    // A and B tiles (32 k, two pieces, two buffers) + row scales
+        GHF_SET_MAX_LDS(edge_transform_h_kernel, lds);
+        edge_transform_h_kernel<<<grid, 256, lds, stream>>>((const char*)h_split, N, d, src, dst, ypos, slice_tab,
                                                                  (const char*)w2h, R, bias, (const char*)x_split, NX, row_cnt, Y);
     }
     GHF_LAUNCH_CHECK();
