@@ -54,6 +54,11 @@ SIGNATURES = {
     "ghf_subgraph_sample_hops": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _i32, C.POINTER(_i32), C.c_uint64, _vp, _sz,
                                         _vp, _vp, C.POINTER(_i64), _vp]),
     "ghf_subgraph_sample_edges": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "ghf_subgraph_hops_excl": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _i32, _vp, _sz, _vp, _vp, _vp, _i64, _i32]),
+    "ghf_subgraph_edges_excl": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i64,
+                                       _i32]),
+    "ghf_subgraph_sample_hops_excl": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _i32, C.POINTER(_i32), C.c_uint64, _vp,
+                                             _sz, _vp, _vp, C.POINTER(_i64), _vp, _vp, _i64, _i32]),
     "ghf_weightgen_fwd": (_i32, [_vp, C.POINTER(_vp), C.POINTER(_vp), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _vp]),
     "ghf_weightgen_fwd_batched": (_i32, [_i32, _vp, C.POINTER(_vp), C.POINTER(_vp), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp,
@@ -299,14 +304,27 @@ def message_config(d: int, kernel: Optional[str] = None) -> Tuple[int, int, int,
     return bn.value, wl.value, cr.value, sc.value
 
 
-def subgraph(plan, seeds: torch.Tensor, k: int) -> dict:
+def _exclude_args(exclude, seeds: torch.Tensor):
+    """`exclude` = (keys, typed) of subgraph / subgraph_sample as the C arguments (excl, n_excl, typed): keys a sorted int64
+    tensor on the seeds' device (include/ghf.h: the key encoding; sorting is the caller's duty), typed a bool."""
+    keys, typed = exclude
+    keys = _req(keys, torch.int64, "exclude keys")
+    if keys.dim() != 1 or keys.device != seeds.device:
+        raise ValueError(f"exclude keys must be a 1-D tensor on {seeds.device}, got {tuple(keys.shape)} on {keys.device}")
+    return keys, (_ptr(keys) if keys.numel() else None, keys.numel(), 1 if typed else 0)
+
+
+def subgraph(plan, seeds: torch.Tensor, k: int, exclude=None) -> dict:
     """The k-hop in-neighbourhood of `seeds` (int64, on the plan's device, ids in [0, N)) in `plan`'s graph
     (include/ghf.h: ghf_subgraph_*): dist [N] int32, node_list [m_k] int64 ordered by (dist, id), new_id [N] int64 (-1 beyond
     k hops), m: the host list m_0..m_k (m_j = nodes within j hops: the first m_j entries of node_list), and the induced edges
     edge_index [2, E'] / rel [E'] int64 (destinations within k - 1 hops), renumbered, in the plan's sorted order.  One host
-    sync (the counts)."""
+    sync (the counts).  `exclude` = (keys, typed): the edges named by the sorted keys do not exist for the call
+    (ghf_subgraph_*_excl); None calls exactly what is called without it."""
     lib = load()
     seeds = _req(seeds, torch.int64, "seeds")
+    if exclude is not None:
+        excl_keys, excl = _exclude_args(exclude, seeds)             # (excl_keys: alive until the counts are read)
     dev, N, E = seeds.device, plan.N, plan.E
     ws_bytes = lib.ghf_subgraph_workspace_bytes(N, E, k)
     if ws_bytes == 0:
@@ -319,25 +337,35 @@ def subgraph(plan, seeds: torch.Tensor, k: int) -> dict:
     edge_out = torch.empty((2, max(E, 1)), dtype=torch.int64, device=dev)
     rel_out = torch.empty(max(E, 1), dtype=torch.int64, device=dev)
     key, src, st = _ptr(plan.sorted_key), _ptr(plan.sorted_src), _stream()
-    _check(lib.ghf_subgraph_hops(key, src, N, E, plan.R, plan.block_nodes, _ptr(seeds), seeds.numel(), k, _ptr(ws), ws_bytes,
-                                 _ptr(dist), st), "ghf_subgraph_hops")
+    hops = (key, src, N, E, plan.R, plan.block_nodes, _ptr(seeds), seeds.numel(), k, _ptr(ws), ws_bytes, _ptr(dist), st)
+    if exclude is None:
+        _check(lib.ghf_subgraph_hops(*hops), "ghf_subgraph_hops")
+    else:
+        _check(lib.ghf_subgraph_hops_excl(*hops, *excl), "ghf_subgraph_hops_excl")
     _check(lib.ghf_subgraph_nodes(_ptr(dist), N, k, _ptr(ws), ws_bytes, _ptr(node_list), _ptr(new_id), _ptr(counts), st),
            "ghf_subgraph_nodes")
-    _check(lib.ghf_subgraph_edges(key, src, N, E, plan.R, plan.block_nodes, _ptr(dist), _ptr(new_id), k, _ptr(ws), ws_bytes,
-                                  _ptr(edge_out), _ptr(rel_out), counts.data_ptr() + 8 * (k + 1), st), "ghf_subgraph_edges")
+    edges = (key, src, N, E, plan.R, plan.block_nodes, _ptr(dist), _ptr(new_id), k, _ptr(ws), ws_bytes, _ptr(edge_out),
+             _ptr(rel_out), counts.data_ptr() + 8 * (k + 1), st)
+    if exclude is None:
+        _check(lib.ghf_subgraph_edges(*edges), "ghf_subgraph_edges")
+    else:
+        _check(lib.ghf_subgraph_edges_excl(*edges, *excl), "ghf_subgraph_edges_excl")
     c = counts.cpu().tolist()
     m, E_sub = c[:k + 1], c[k + 1]
     return dict(dist=dist, node_list=node_list[:m[k]], new_id=new_id, m=m,
                 edge_index=edge_out[:, :E_sub] if E else edge_out[:, :0], rel=rel_out[:E_sub])
 
 
-def subgraph_sample(plan, seeds: torch.Tensor, fanout: Sequence[int], seed: int) -> dict:
+def subgraph_sample(plan, seeds: torch.Tensor, fanout: Sequence[int], seed: int, exclude=None) -> dict:
     """`subgraph` with per-hop fanout caps (include/ghf.h: ghf_subgraph_sample_*): k = len(fanout) hops, hop j keeping at most
     fanout[j] in-edges (-1: all) of each node first reached at sampled distance j — the ones with the smallest
     (priority(seed, plan position), plan position).  The keys of `subgraph`, plus host_reads: the words read back inside the
-    hops stage (at most one per capped hop); one more host sync for the counts."""
+    hops stage (at most one per capped hop); one more host sync for the counts.  `exclude` as in `subgraph`: excluded edges
+    are no candidates (ghf_subgraph_sample_hops_excl); the priorities stay those of the full plan's positions."""
     lib = load()
     seeds = _req(seeds, torch.int64, "seeds")
+    if exclude is not None:
+        excl_keys, excl = _exclude_args(exclude, seeds)             # (excl_keys: alive until the counts are read)
     fanout = [int(f) for f in fanout]
     k = len(fanout)
     if not 0 <= int(seed) < 1 << 64:
@@ -356,9 +384,12 @@ def subgraph_sample(plan, seeds: torch.Tensor, fanout: Sequence[int], seed: int)
     rel_out = torch.empty(max(E, 1), dtype=torch.int64, device=dev)
     key, src, st = _ptr(plan.sorted_key), _ptr(plan.sorted_src), _stream()
     reads = _i64(0)
-    _check(lib.ghf_subgraph_sample_hops(key, src, N, E, plan.R, plan.block_nodes, _ptr(seeds), seeds.numel(), k,
-                                        (_i32 * k)(*fanout), int(seed), _ptr(ws), ws_bytes, _ptr(dist), _ptr(keep),
-                                        C.byref(reads), st), "ghf_subgraph_sample_hops")
+    hops = (key, src, N, E, plan.R, plan.block_nodes, _ptr(seeds), seeds.numel(), k, (_i32 * k)(*fanout), int(seed), _ptr(ws),
+            ws_bytes, _ptr(dist), _ptr(keep), C.byref(reads), st)
+    if exclude is None:
+        _check(lib.ghf_subgraph_sample_hops(*hops), "ghf_subgraph_sample_hops")
+    else:
+        _check(lib.ghf_subgraph_sample_hops_excl(*hops, *excl), "ghf_subgraph_sample_hops_excl")
     _check(lib.ghf_subgraph_nodes(_ptr(dist), N, k, _ptr(ws), ws_bytes, _ptr(node_list), _ptr(new_id), _ptr(counts), st),
            "ghf_subgraph_nodes")
     _check(lib.ghf_subgraph_sample_edges(key, src, N, E, plan.R, plan.block_nodes, _ptr(keep), _ptr(new_id), _ptr(ws), ws_bytes,

@@ -534,7 +534,7 @@ int ghf_subgraph_hops(const uint32_t* sorted_key, const int32_t* sorted_src, int
     GHF_REQUIRE(workspace && dist && (seeds || S == 0) && ((sorted_key && sorted_src) || E == 0),
                 "subgraph_hops: null pointer argument");
     return launch_subgraph_hops(sorted_key, sorted_src, N, E, R, block_nodes, seeds, S, k, workspace, workspace_bytes, dist,
-                                (hipStream_t)stream);
+                                nullptr, 0, 0, (hipStream_t)stream);
 }
 
 int ghf_subgraph_nodes(const int32_t* dist, int64_t N, int k, void* workspace, size_t workspace_bytes, int64_t* node_list,
@@ -549,7 +549,7 @@ int ghf_subgraph_edges(const uint32_t* sorted_key, const int32_t* sorted_src, in
     GHF_REQUIRE(dist && new_id && workspace && num_edges && ((sorted_key && sorted_src && edge_out && rel_out) || E == 0),
                 "subgraph_edges: null pointer argument");
     return launch_subgraph_edges(sorted_key, sorted_src, N, E, R, block_nodes, dist, new_id, k, workspace, workspace_bytes,
-                                 edge_out, rel_out, num_edges, (hipStream_t)stream);
+                                 edge_out, rel_out, num_edges, nullptr, 0, 0, (hipStream_t)stream);
 }
 
 size_t ghf_subgraph_sample_workspace_bytes(int64_t N, int64_t E, int k) { return subgraph_sample_workspace_bytes(N, E, k); }
@@ -561,7 +561,7 @@ int ghf_subgraph_sample_hops(const uint32_t* sorted_key, const int32_t* sorted_s
                 "subgraph_sample_hops: null pointer argument");
     GHF_REQUIRE(k >= 1, "subgraph_sample_hops: k must be positive");
     return launch_subgraph_sample_hops(sorted_key, sorted_src, N, E, R, block_nodes, seeds, S, k, fanout, seed, workspace,
-                                       workspace_bytes, dist, keep, host_reads, (hipStream_t)stream);
+                                       workspace_bytes, dist, keep, host_reads, nullptr, 0, 0, (hipStream_t)stream);
 }
 
 int ghf_subgraph_sample_edges(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
@@ -571,6 +571,50 @@ int ghf_subgraph_sample_edges(const uint32_t* sorted_key, const int32_t* sorted_
                 "subgraph_sample_edges: null pointer argument");
     return launch_subgraph_sample_edges(sorted_key, sorted_src, N, E, R, block_nodes, keep, new_id, workspace, workspace_bytes,
                                         edge_out, rel_out, num_edges, (hipStream_t)stream);
+}
+
+// the exclusion list of the *_excl calls, checked on the host before anything else is looked at
+static int excl_check(const uint64_t* excl, int64_t n_excl, int typed, const char* what) {
+    GHF_REQUIRE(n_excl >= 0, "%s: negative exclusion count", what);
+    GHF_REQUIRE(excl || n_excl == 0, "%s: null exclusion list with n_excl = %lld", what, (long long)n_excl);
+    GHF_REQUIRE(typed == 0 || typed == 1, "%s: typed = %d (needs 0 or 1)", what, typed);
+    return GHF_OK;
+}
+
+int ghf_subgraph_hops_excl(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
+                           const int64_t* seeds, int64_t S, int k, void* workspace, size_t workspace_bytes, int32_t* dist,
+                           void* stream, const uint64_t* excl, int64_t n_excl, int typed) {
+    const int rc = excl_check(excl, n_excl, typed, "subgraph_hops_excl");
+    if (rc) return rc;
+    GHF_REQUIRE(workspace && dist && (seeds || S == 0) && ((sorted_key && sorted_src) || E == 0),
+                "subgraph_hops_excl: null pointer argument");
+    return launch_subgraph_hops(sorted_key, sorted_src, N, E, R, block_nodes, seeds, S, k, workspace, workspace_bytes, dist,
+                                excl, n_excl, typed, (hipStream_t)stream);
+}
+
+int ghf_subgraph_edges_excl(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
+                            const int32_t* dist, const int64_t* new_id, int k, void* workspace, size_t workspace_bytes,
+                            int64_t* edge_out, int64_t* rel_out, int64_t* num_edges, void* stream, const uint64_t* excl,
+                            int64_t n_excl, int typed) {
+    const int rc = excl_check(excl, n_excl, typed, "subgraph_edges_excl");
+    if (rc) return rc;
+    GHF_REQUIRE(dist && new_id && workspace && num_edges && ((sorted_key && sorted_src && edge_out && rel_out) || E == 0),
+                "subgraph_edges_excl: null pointer argument");
+    return launch_subgraph_edges(sorted_key, sorted_src, N, E, R, block_nodes, dist, new_id, k, workspace, workspace_bytes,
+                                 edge_out, rel_out, num_edges, excl, n_excl, typed, (hipStream_t)stream);
+}
+
+int ghf_subgraph_sample_hops_excl(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R,
+                                  int block_nodes, const int64_t* seeds, int64_t S, int k, const int* fanout, uint64_t seed,
+                                  void* workspace, size_t workspace_bytes, int32_t* dist, int32_t* keep, int64_t* host_reads,
+                                  void* stream, const uint64_t* excl, int64_t n_excl, int typed) {
+    const int rc = excl_check(excl, n_excl, typed, "subgraph_sample_hops_excl");
+    if (rc) return rc;
+    GHF_REQUIRE(workspace && dist && fanout && (seeds || S == 0) && ((sorted_key && sorted_src && keep) || E == 0),
+                "subgraph_sample_hops_excl: null pointer argument");
+    GHF_REQUIRE(k >= 1, "subgraph_sample_hops_excl: k must be positive");
+    return launch_subgraph_sample_hops(sorted_key, sorted_src, N, E, R, block_nodes, seeds, S, k, fanout, seed, workspace,
+                                       workspace_bytes, dist, keep, host_reads, excl, n_excl, typed, (hipStream_t)stream);
 }
 
 int ghf_score_pairs_fwd(const float* a, const float* b, const int64_t* ia, const int64_t* ib, int64_t rows_a, int64_t rows_b,

@@ -241,16 +241,19 @@ int launch_group_edges(const int64_t* rel, int64_t E, int R, void* ws, size_t ws
 // subgraph.hip
 size_t subgraph_workspace_bytes(int64_t N, int64_t E, int k);
 int launch_subgraph_hops(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
-                         const int64_t* seeds, int64_t S, int k, void* ws, size_t ws_bytes, int32_t* dist, hipStream_t stream);
+                         const int64_t* seeds, int64_t S, int k, void* ws, size_t ws_bytes, int32_t* dist,
+                         const uint64_t* excl, int64_t n_excl, int typed, hipStream_t stream);
 int launch_subgraph_nodes(const int32_t* dist, int64_t N, int k, void* ws, size_t ws_bytes, int64_t* node_list,
                           int64_t* new_id, int64_t* m, hipStream_t stream);
 int launch_subgraph_edges(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
                           const int32_t* dist, const int64_t* new_id, int k, void* ws, size_t ws_bytes, int64_t* edge_out,
-                          int64_t* rel_out, int64_t* num_edges, hipStream_t stream);
+                          int64_t* rel_out, int64_t* num_edges, const uint64_t* excl, int64_t n_excl, int typed,
+                          hipStream_t stream);
 size_t subgraph_sample_workspace_bytes(int64_t N, int64_t E, int k);
 int launch_subgraph_sample_hops(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
                                 const int64_t* seeds, int64_t S, int k, const int* fanout, uint64_t seed, void* ws,
-                                size_t ws_bytes, int32_t* dist, int32_t* keep, int64_t* host_reads, hipStream_t stream);
+                                size_t ws_bytes, int32_t* dist, int32_t* keep, int64_t* host_reads, const uint64_t* excl,
+                                int64_t n_excl, int typed, hipStream_t stream);
 int launch_subgraph_sample_edges(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
                                  const int32_t* keep, const int64_t* new_id, void* ws, size_t ws_bytes, int64_t* edge_out,
                                  int64_t* rel_out, int64_t* num_edges, hipStream_t stream);

@@ -37,6 +37,36 @@ __device__ __forceinline__ void sub_decode(uint32_t key, int32_t raw, const Edge
     }
 }
 
+// ---- excluded edges (the *_excl calls; semantics and key encoding in include/ghf.h) ----------------------------------
+// keys [n] ascending: (uint64)src << 32 | dst, or (typed) | dst * R + rel.  An edge is probed only once every cheaper test
+// has passed (it would be taken otherwise), so the searches follow the subgraph, not E.  Whether an edge is excluded is a
+// function of the edge alone: the "every writer writes the same value" arguments below stand.  The search never leaves
+// [0, n) whatever the list's order; an unsorted list can only miss matches.
+struct Excl {
+    const uint64_t* keys;
+    int64_t n;
+    int typed;
+};
+
+__device__ __forceinline__ bool sub_excluded(const Excl x, uint32_t s, uint32_t t, uint32_t r, uint32_t R) {
+    const uint64_t want = ((uint64_t)s << 32) | (uint64_t)(x.typed ? t * R + r : t);   // (t * R + r < 2^32: the plan's key space)
+    int64_t lo = 0, hi = x.n;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (x.keys[mid] < want) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < x.n && x.keys[lo] == want;
+}
+
+static Excl sub_excl(const uint64_t* keys, int64_t n, int typed) {
+    Excl x;
+    x.keys = keys;
+    x.n = n;
+    x.typed = typed;
+    return x;
+}
+
 static unsigned sub_grid(int64_t n) {
     const int64_t g = cdiv(n > 0 ? n : 1, 256);
     return (unsigned)(g < 8192 ? g : 8192);
@@ -60,10 +90,11 @@ __global__ __launch_bounds__(256) void sub_dist_seeds_kernel(const int64_t* __re
     }
 }
 
-// hop j: sources of edges into distance-j nodes that are still unvisited get distance j + 1
+// hop j: sources of edges into distance-j nodes that are still unvisited get distance j + 1 (X: unless the edge is excluded)
+template <bool X>
 __global__ __launch_bounds__(256) void sub_hop_kernel(const uint32_t* __restrict__ sorted_key, const int32_t* __restrict__ sorted_src,
                                                       int64_t N, int64_t E, EdgeCode c, int j, int k, int32_t* dist,
-                                                      int32_t* found) {
+                                                      int32_t* found, Excl x) {
     if (j > 0 && found[j - 1] == 0) return;                 // hop j - 1 reached nobody: no node is at distance j
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     int any = 0;
@@ -72,6 +103,7 @@ __global__ __launch_bounds__(256) void sub_hop_kernel(const uint32_t* __restrict
         sub_decode(sorted_key[e], sorted_src[e], c, s, t, r);
         if (t >= (uint64_t)N || s >= (uint64_t)N) continue;
         if (dist[t] == j && dist[s] > k) {
+            if (X && sub_excluded(x, s, t, r, c.R)) continue;
             dist[s] = j + 1;                                // every writer of dist[s] in this pass writes j + 1
             any = 1;
         }
@@ -121,10 +153,11 @@ __device__ __forceinline__ bool sub_keep(uint32_t s, uint32_t t, int64_t N, cons
     return t < (uint64_t)N && s < (uint64_t)N && dist[t] <= k - 1;
 }
 
+template <bool X>
 __global__ __launch_bounds__(256) void sub_edge_flags_kernel(const uint32_t* __restrict__ sorted_key,
                                                              const int32_t* __restrict__ sorted_src, int64_t N, int64_t E,
                                                              EdgeCode c, const int32_t* __restrict__ dist, int k,
-                                                             int32_t* __restrict__ f) {
+                                                             int32_t* __restrict__ f, Excl x) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e <= E; e += stride) {
         if (e == E) {
@@ -133,25 +166,29 @@ __global__ __launch_bounds__(256) void sub_edge_flags_kernel(const uint32_t* __r
         }
         uint32_t s, t, r;
         sub_decode(sorted_key[e], sorted_src[e], c, s, t, r);
-        f[e] = sub_keep(s, t, N, dist, k);
+        f[e] = sub_keep(s, t, N, dist, k) && !(X && sub_excluded(x, s, t, r, c.R));
     }
 }
 
+// (X: the flags pass has probed the list; its flags f[] are read here instead of probing again)
+template <bool X>
 __global__ __launch_bounds__(256) void sub_edge_scatter_kernel(const uint32_t* __restrict__ sorted_key,
                                                                const int32_t* __restrict__ sorted_src, int64_t N, int64_t E,
                                                                EdgeCode c, const int32_t* __restrict__ dist,
                                                                const int64_t* __restrict__ new_id, int k,
-                                                               const int32_t* __restrict__ pos, int64_t* __restrict__ edge_out,
-                                                               int64_t* __restrict__ rel_out, int64_t* __restrict__ num_edges) {
+                                                               const int32_t* __restrict__ f, const int32_t* __restrict__ pos,
+                                                               int64_t* __restrict__ edge_out, int64_t* __restrict__ rel_out,
+                                                               int64_t* __restrict__ num_edges) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e <= E; e += stride) {
         if (e == E) {
             num_edges[0] = pos[E];
             continue;
         }
+        if (X && !f[e]) continue;
         uint32_t s, t, r;
         sub_decode(sorted_key[e], sorted_src[e], c, s, t, r);
-        if (!sub_keep(s, t, N, dist, k)) continue;
+        if (!X && !sub_keep(s, t, N, dist, k)) continue;
         const int64_t p = pos[e];
         edge_out[p] = new_id[s];
         edge_out[E + p] = new_id[t];
@@ -211,7 +248,8 @@ static EdgeCode sub_code(int R, int BN) {
 }
 
 int launch_subgraph_hops(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
-                         const int64_t* seeds, int64_t S, int k, void* ws, size_t ws_bytes, int32_t* dist, hipStream_t stream) {
+                         const int64_t* seeds, int64_t S, int k, void* ws, size_t ws_bytes, int32_t* dist,
+                         const uint64_t* excl, int64_t n_excl, int typed, hipStream_t stream) {
     const int rc = sub_check(N, E, R, BN, k, ws, ws_bytes, "subgraph_hops");
     if (rc) return rc;
     GHF_REQUIRE(S >= 0, "subgraph_hops: negative seed count");
@@ -224,8 +262,12 @@ int launch_subgraph_hops(const uint32_t* sorted_key, const int32_t* sorted_src, 
     }
     if (E == 0) return GHF_OK;
     const EdgeCode c = sub_code(R, BN);
+    const Excl x = sub_excl(excl, n_excl, typed);
     for (int j = 0; j < k; ++j) {
-        sub_hop_kernel<<<sub_grid(E), 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, j, k, dist, w.found);
+        if (n_excl > 0)
+            sub_hop_kernel<true><<<sub_grid(E), 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, j, k, dist, w.found, x);
+        else
+            sub_hop_kernel<false><<<sub_grid(E), 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, j, k, dist, w.found, x);
         GHF_LAUNCH_CHECK();
     }
     return GHF_OK;
@@ -251,17 +293,26 @@ int launch_subgraph_nodes(const int32_t* dist, int64_t N, int k, void* ws, size_
 
 int launch_subgraph_edges(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
                           const int32_t* dist, const int64_t* new_id, int k, void* ws, size_t ws_bytes, int64_t* edge_out,
-                          int64_t* rel_out, int64_t* num_edges, hipStream_t stream) {
+                          int64_t* rel_out, int64_t* num_edges, const uint64_t* excl, int64_t n_excl, int typed,
+                          hipStream_t stream) {
     const int rc = sub_check(N, E, R, BN, k, ws, ws_bytes, "subgraph_edges");
     if (rc) return rc;
     SubWs w = sub_ws(ws, N, E, k);
     const EdgeCode c = sub_code(R, BN);
     const unsigned g = sub_grid(E + 1);
-    sub_edge_flags_kernel<<<g, 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, dist, k, w.f);
+    const Excl x = sub_excl(excl, n_excl, typed);
+    if (n_excl > 0)
+        sub_edge_flags_kernel<true><<<g, 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, dist, k, w.f, x);
+    else
+        sub_edge_flags_kernel<false><<<g, 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, dist, k, w.f, x);
     GHF_LAUNCH_CHECK();
     GHF_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(w.tmp, w.tmp_bytes, (const int32_t*)w.f, w.pos, (int)(E + 1), stream));
-    sub_edge_scatter_kernel<<<g, 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, dist, new_id, k, w.pos, edge_out, rel_out,
-                                                   num_edges);
+    if (n_excl > 0)
+        sub_edge_scatter_kernel<true><<<g, 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, dist, new_id, k, w.f, w.pos,
+                                                             edge_out, rel_out, num_edges);
+    else
+        sub_edge_scatter_kernel<false><<<g, 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, dist, new_id, k, w.f, w.pos,
+                                                              edge_out, rel_out, num_edges);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }
@@ -293,11 +344,12 @@ __global__ __launch_bounds__(256) void sample_init_kernel(int32_t* __restrict__ 
     if (t < k) found[t] = 0;
 }
 
-// a hop without a cap: sub_hop_kernel, which also marks the edges it walks
+// a hop without a cap: sub_hop_kernel, which also marks the edges it walks (X: an excluded edge is not a candidate)
+template <bool X>
 __global__ __launch_bounds__(256) void sample_hop_all_kernel(const uint32_t* __restrict__ sorted_key,
                                                              const int32_t* __restrict__ sorted_src, int64_t N, int64_t E,
                                                              EdgeCode c, int j, int k, int32_t* dist,
-                                                             int32_t* __restrict__ keep, int32_t* found) {
+                                                             int32_t* __restrict__ keep, int32_t* found, Excl x) {
     if (j > 0 && found[j - 1] == 0) return;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     int any = 0;
@@ -306,6 +358,7 @@ __global__ __launch_bounds__(256) void sample_hop_all_kernel(const uint32_t* __r
         sub_decode(sorted_key[e], sorted_src[e], c, s, t, r);
         if (t >= (uint64_t)N || s >= (uint64_t)N) continue;
         if (dist[t] != j) continue;
+        if (X && sub_excluded(x, s, t, r, c.R)) continue;
         keep[e] = 1;
         if (dist[s] > k) {
             dist[s] = j + 1;                                // every writer of dist[s] in this pass writes j + 1
@@ -315,11 +368,12 @@ __global__ __launch_bounds__(256) void sample_hop_all_kernel(const uint32_t* __r
     if (any) atomicOr(&found[j], 1);
 }
 
-// f[e] = (the destination of edge e is at distance j), f[E] = 0
+// f[e] = (the destination of edge e is at distance j) (X: and the edge is not excluded), f[E] = 0
+template <bool X>
 __global__ __launch_bounds__(256) void sample_cand_flags_kernel(const uint32_t* __restrict__ sorted_key,
                                                                 const int32_t* __restrict__ sorted_src, int64_t N, int64_t E,
                                                                 EdgeCode c, const int32_t* __restrict__ dist, int j,
-                                                                int32_t* __restrict__ f) {
+                                                                int32_t* __restrict__ f, Excl x) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e <= E; e += stride) {
         if (e == E) {
@@ -328,7 +382,7 @@ __global__ __launch_bounds__(256) void sample_cand_flags_kernel(const uint32_t* 
         }
         uint32_t s, t, r;
         sub_decode(sorted_key[e], sorted_src[e], c, s, t, r);
-        f[e] = t < (uint64_t)N && s < (uint64_t)N && dist[t] == j;
+        f[e] = t < (uint64_t)N && s < (uint64_t)N && dist[t] == j && !(X && sub_excluded(x, s, t, r, c.R));
     }
 }
 
@@ -487,7 +541,8 @@ static int sample_check(int64_t N, int64_t E, int R, int BN, int k, void* ws, si
 
 int launch_subgraph_sample_hops(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int BN,
                                 const int64_t* seeds, int64_t S, int k, const int* fanout, uint64_t seed, void* ws,
-                                size_t ws_bytes, int32_t* dist, int32_t* keep, int64_t* host_reads, hipStream_t stream) {
+                                size_t ws_bytes, int32_t* dist, int32_t* keep, int64_t* host_reads, const uint64_t* excl,
+                                int64_t n_excl, int typed, hipStream_t stream) {
     GHF_REQUIRE(S >= 0, "subgraph_sample_hops: negative seed count");
     for (int j = 0; j < k; ++j)
         GHF_REQUIRE(fanout[j] == -1 || fanout[j] >= 1, "subgraph_sample_hops: fanout[%d] = %d (needs -1 or >= 1)", j, fanout[j]);
@@ -506,13 +561,22 @@ int launch_subgraph_sample_hops(const uint32_t* sorted_key, const int32_t* sorte
     if (E == 0) return GHF_OK;
     const EdgeCode c = sub_code(R, BN);
     const int end_bit = sample_end_bit(N);
+    const Excl x = sub_excl(excl, n_excl, typed);
     for (int j = 0; j < k; ++j) {
         if (fanout[j] == -1) {
-            sample_hop_all_kernel<<<sub_grid(E), 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, j, k, dist, keep, w.s.found);
+            if (n_excl > 0)
+                sample_hop_all_kernel<true><<<sub_grid(E), 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, j, k, dist, keep,
+                                                                            w.s.found, x);
+            else
+                sample_hop_all_kernel<false><<<sub_grid(E), 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, j, k, dist, keep,
+                                                                             w.s.found, x);
             GHF_LAUNCH_CHECK();
             continue;
         }
-        sample_cand_flags_kernel<<<sub_grid(E + 1), 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, dist, j, w.s.f);
+        if (n_excl > 0)
+            sample_cand_flags_kernel<true><<<sub_grid(E + 1), 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, dist, j, w.s.f, x);
+        else
+            sample_cand_flags_kernel<false><<<sub_grid(E + 1), 256, 0, stream>>>(sorted_key, sorted_src, N, E, c, dist, j, w.s.f, x);
         GHF_LAUNCH_CHECK();
         GHF_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(w.s.tmp, w.s.tmp_bytes, (const int32_t*)w.s.f, w.s.pos, (int)(E + 1), stream));
         int32_t C = 0;                                      // the hop's one host read: the number of candidate edges

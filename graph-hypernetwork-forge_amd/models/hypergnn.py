@@ -265,7 +265,7 @@ class HyperGNN(nn.Module):
 
     # -- node batches: the rows of a few nodes from their k-hop subgraph (include/ghf.h: ghf_subgraph_*) ---------------
     def forward_nodes(self, node_features: torch.Tensor, edge_index: torch.Tensor, edge_texts: List[str],
-                      nodes: torch.Tensor, fanout=None, seed: Optional[int] = None) -> torch.Tensor:
+                      nodes: torch.Tensor, fanout=None, seed: Optional[int] = None, exclude=None) -> torch.Tensor:
         """``forward(node_features, edge_index, edge_texts)[nodes]`` computed on the nodes' ``num_layers``-hop
         in-neighbourhood only: an L-layer row depends on the rows within L hops upstream of it (reference hypergnn.py:190-230,
         288-296), so the result is exact, not sampled.  `nodes`: a 1-D int32 / int64 tensor (device or CPU), duplicates and
@@ -279,24 +279,98 @@ class HyperGNN(nn.Module):
         [0, 2**63); None: drawn from torch's default CPU generator, so ``torch.manual_seed`` reproduces a run) fixes the
         draw, which is a pure function of (plan, nodes, fanout, seed) (include/ghf.h).  The plan's geometry depends on the
         hidden size and on whether gradients are recorded, so one seed may pick different edges in ``train()`` and
-        ``eval()``.  ``last_subgraph`` records `fanout` (a tuple) and the seed used."""
+        ``eval()``.  ``last_subgraph`` records `fanout` (a tuple) and the seed used.
+
+        `exclude` (None: nothing) leaves edges out of the subgraph — the batch's own edges when the rows are scored for link
+        prediction, which would otherwise show the model the answer: ``(src, dst)`` drops every edge src[i] -> dst[i] whatever
+        its relation, ``(src, dst, rel)`` with one relation text per entry only those labelled rel[i].  1-D int32 / int64 id
+        tensors of equal length, negative ids as torch indexing; direction matters (list the reverses to drop them too);
+        entries that match no edge — a text that labels no edge among them — do nothing.  The result is
+        ``forward`` on the graph without those edges, rows `nodes` (include/ghf.h: ghf_subgraph_*_excl); with `fanout`
+        excluded edges are no candidates.  The plan of the full graph stays cached.  ``last_subgraph["exclude"]`` records
+        (entries, typed), or None."""
         self._check_inputs(node_features, edge_index, edge_texts, "edge_texts")
         sample = self._sample_args(fanout, seed)
+        excl = self._exclude_args(exclude, node_features, texts=True)
         seeds = self._seed_ids(nodes, node_features)
         grad = wants_grad(self, node_features) or self._dropping()
         plan = self._plan_lookup(edge_index, edge_texts, node_features.size(0), node_features.device, training=grad)[0]
-        return self._forward_nodes(node_features, plan, seeds, grad, edge_index, sample)
+        return self._forward_nodes(node_features, plan, seeds, grad, edge_index, sample, self._exclude_keys(excl, plan))
 
     def forward_nodes_ids(self, node_features: torch.Tensor, edge_index: torch.Tensor, edge_rel_ids: torch.Tensor,
                           relation_texts: Sequence[str], nodes: torch.Tensor, fanout=None,
-                          seed: Optional[int] = None) -> torch.Tensor:
-        """``forward_nodes`` for callers that already hold relation ids (see ``forward_ids``)."""
+                          seed: Optional[int] = None, exclude=None) -> torch.Tensor:
+        """``forward_nodes`` for callers that already hold relation ids (see ``forward_ids``); the typed `exclude` is
+        ``(src, dst, rel)`` with `rel` a 1-D int tensor of ids into `relation_texts` (negative: ValueError, beyond the list:
+        IndexError)."""
         self._check_inputs(node_features, edge_index, edge_rel_ids, "edge_rel_ids")
         sample = self._sample_args(fanout, seed)
+        excl = self._exclude_args(exclude, node_features, num_relations=len(relation_texts))
         seeds = self._seed_ids(nodes, node_features)
         grad = wants_grad(self, node_features) or self._dropping()
         plan = self._ids_plan(edge_index, edge_rel_ids, relation_texts, node_features, grad)
-        return self._forward_nodes(node_features, plan, seeds, grad, edge_index, sample)
+        return self._forward_nodes(node_features, plan, seeds, grad, edge_index, sample, self._exclude_keys(excl, plan))
+
+    @classmethod
+    def _exclude_args(cls, exclude, node_features: torch.Tensor, texts: bool = False, num_relations: int = 0):
+        """forward_nodes' `exclude` checked without a GPU: None, or (src, dst, rel or None) — the node ids through _rank_ids
+        (on the features' device), `rel` the relation texts (texts=True: a list of strings, mapped to ids once the plan is
+        known) or a checked int64 tensor of ids below `num_relations`."""
+        if exclude is None:
+            return None
+        if isinstance(exclude, (torch.Tensor, str, bytes)) or not hasattr(exclude, "__len__") or len(exclude) not in (2, 3):
+            n = len(exclude) if hasattr(exclude, "__len__") and not isinstance(exclude, (torch.Tensor, str, bytes)) else None
+            raise ValueError("exclude must be (src, dst) or (src, dst, rel)" +
+                             (f", got {n} members" if n is not None else f", got {type(exclude).__name__}"))
+        N = node_features.size(0)
+        src = cls._rank_ids(exclude[0], N, node_features, "exclude[0]")
+        dst = cls._rank_ids(exclude[1], N, node_features, "exclude[1]")
+        if src.numel() != dst.numel():
+            raise ValueError(f"exclude: {src.numel()} sources and {dst.numel()} destinations")
+        if len(exclude) == 2:
+            return src, dst, None
+        rel = exclude[2]
+        if texts:
+            if isinstance(rel, (str, bytes, torch.Tensor)) or not hasattr(rel, "__len__"):
+                raise TypeError(f"exclude[2] must be a sequence of relation texts, one per entry, got {type(rel).__name__}")
+            if len(rel) != src.numel():
+                raise ValueError(f"exclude[2] holds {len(rel)} relation texts, expected {src.numel()}")
+            rel = list(rel)
+            if not all(isinstance(t, str) for t in rel):
+                raise TypeError("exclude[2] must hold relation texts (strings); forward_nodes_ids takes relation ids")
+            return src, dst, rel
+        rel = cls._rel_ids(rel, src.numel(), node_features, "exclude[2]")
+        if rel.numel() and int(rel.max()) >= num_relations:
+            raise IndexError(f"exclude[2] holds relation ids outside [0, {num_relations})")
+        return src, dst, rel
+
+    @staticmethod
+    def _exclude_keys(excl, plan: GraphPlan):
+        """The checked `exclude` as (sorted int64 keys on the device, typed, entries): include/ghf.h's encoding, src << 32 | dst
+        or src << 32 | (dst * R + rel) in the plan's relation ids; built and sorted on the device.  Texts that label no edge
+        of the plan match nothing: their entries are dropped here."""
+        if excl is None:
+            return None
+        src, dst, rel = excl
+        entries, typed = src.numel(), rel is not None
+        if typed:
+            if isinstance(rel, list):
+                ids = {t: i for i, t in enumerate(plan.unique_texts)}
+                rel = torch.tensor([ids.get(t, -1) for t in rel], dtype=torch.int64).to(src.device)
+                known = rel >= 0
+                src, dst, rel = src[known], dst[known], rel[known]
+            dst = dst * plan.R + rel
+        return torch.sort((src << 32) | dst).values, typed, entries
+
+    @staticmethod
+    def _without_excluded(plan: GraphPlan, edge_index: torch.Tensor, keys: torch.Tensor, typed: bool):
+        """The caller's edges and relation ids without the excluded ones, in the caller's order (on the plan's device)."""
+        ei = edge_index.to(device=keys.device, dtype=torch.int64)
+        low = ei[1] * plan.R + plan.rel_ids if typed else ei[1]
+        mine = (ei[0] << 32) | low
+        at = torch.searchsorted(keys, mine).clamp_(max=keys.numel() - 1)
+        stay = keys[at] != mine
+        return ei[:, stay].contiguous(), plan.rel_ids[stay].contiguous()
 
     def _sample_args(self, fanout, seed):
         """forward_nodes' `fanout` / `seed` checked on the host: None (the exact call), or (fanout tuple of num_layers ints,
@@ -338,18 +412,22 @@ class HyperGNN(nn.Module):
         return ids
 
     def _forward_nodes(self, x: torch.Tensor, plan: GraphPlan, seeds: torch.Tensor, grad: bool,
-                       edge_index: torch.Tensor, sample=None) -> torch.Tensor:
+                       edge_index: torch.Tensor, sample=None, exclude=None) -> torch.Tensor:
         """The rows `seeds` (int64, in range) of the forward on `plan`'s graph, from the seeds' k-hop subgraph: its nodes
         ordered by (hop distance, id), so that the rows within j hops are a prefix; inference layer l (0-based) then computes
         the first m_{k-1-l} rows only (the last layer: the seeds).  The sub-plan is built per call and not cached.
-        `sample` = (fanout, seed): the sampled subgraph instead (_native.subgraph_sample), which keeps the prefix property."""
+        `sample` = (fanout, seed): the sampled subgraph instead (_native.subgraph_sample), which keeps the prefix property.
+        `exclude` = (keys, typed, entries) of _exclude_keys: the extraction leaves those edges out, and everything after it
+        follows from the edges it emits."""
         k, d, device = self.num_layers, self.hidden_dim, x.device
         if seeds.numel() == 0:
             return x.new_zeros((0, d), dtype=torch.float32)
+        excl = None if exclude is None or exclude[0].numel() == 0 else exclude[:2]    # (an empty list: today's calls)
         if sample is None:
-            sub, drawn = _native.subgraph(plan, seeds, k), {}
+            sub, drawn = _native.subgraph(plan, seeds, k, exclude=excl), {}
         else:
-            sub, drawn = _native.subgraph_sample(plan, seeds, *sample), dict(fanout=sample[0], seed=sample[1])
+            sub, drawn = _native.subgraph_sample(plan, seeds, *sample, exclude=excl), dict(fanout=sample[0], seed=sample[1])
+        drawn["exclude"] = None if exclude is None else (exclude[2], exclude[1])
         m, n = sub["m"], sub["m"][k]
         xs = x.index_select(0, sub["node_list"])                     # differentiable: gradients reach node_features
         rows = sub["new_id"].index_select(0, seeds)
@@ -357,6 +435,12 @@ class HyperGNN(nn.Module):
         if sub["edge_index"].size(1) == 0:
             if grad:                                                  # (no edge to train through: the full recorded forward)
                 self.last_subgraph = dict(m=m, edges=0, block_nodes=plan.block_nodes, wlayout=plan.wlayout, **drawn)
+                if excl is not None:
+                    # ... on the graph without the excluded edges, or they would be back: a plan of the reduced edge arrays,
+                    # built for this call (build_plan refuses a graph with no edge left, as forward does)
+                    ei, rel = self._without_excluded(plan, edge_index, *excl)
+                    reduced = build_plan(ei, rel, plan.unique_texts, plan.N, d, device)
+                    return self._forward_recorded(x, reduced, ei).index_select(0, seeds)
                 return self._forward_recorded(x, plan, edge_index).index_select(0, seeds)
             sub_plan = empty_plan(n, plan.unique_texts, config or plan_config(d, 0, n), device)
         else:

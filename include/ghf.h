@@ -191,6 +191,47 @@ int ghf_subgraph_sample_edges(const uint32_t* sorted_key, const int32_t* sorted_
                               const int32_t* keep, const int64_t* new_id, void* workspace, size_t workspace_bytes,
                               int64_t* edge_out /* [2, E] */, int64_t* rel_out /* [E] */, int64_t* num_edges /* [1] */, void* stream);
 
+/* ---- node-batch subgraph without given edges (HyperGNN.forward_nodes(..., exclude=)) -----------------------------
+ * Link prediction trains on batches of edges (head, relation, tail) that the model is asked to score; the subgraph the
+ * rows are computed on must not contain them (PyG's LinkNeighborLoader, DGL's as_edge_prediction_sampler(exclude=...)).
+ * An exclusion set X is a list of pairs (s, t) (typed == 0) or triples (s, t, r) (typed == 1).  An edge u -> v with
+ * relation id p of the plan is EXCLUDED iff (u, v) is in X (untyped) or (u, v, p) is in X (typed):
+ *   every parallel edge that matches is excluded; direction matters ((t, s) is another entry: callers who want the
+ *   reverses list them); entries that match no edge do nothing; duplicates change nothing.
+ * Excluded edges do not exist for the call: no hop walks them, they are not emitted, so they count in no in-degree of the
+ * plan built from the emitted edges, and in the sampled form they are not candidates — a destination with f + 1 in-edges
+ * of which one is excluded keeps the remaining f under cap f.  priority(e) stays a function of the edge's position in the
+ * FULL plan, as defined above.  So the outputs are those of the twin call on a plan of the graph without the excluded
+ * edges, except that the sampled draw numbers the edges by the full plan.
+ * Key encoding: excl [n_excl] uint64 on the device, SORTED ASCENDING by the caller (as the filter lists of ghf_score_rank):
+ *   untyped: (uint64)s << 32 | t
+ *   typed:   (uint64)s << 32 | (t * R + r)          (t * R + r < 2^32: every plan requires ceil(N/BN)*BN*R < 2^32)
+ * An unsorted list may miss matches but never faults: the binary search stays inside [0, n_excl), and node and relation
+ * ids are compared as numbers, never used as indices, so no entry needs to be in range.
+ * The list is probed only for an edge that would otherwise be taken — a hop: destination at distance j and source
+ * unvisited; the edges stage: destination within k - 1 hops; the sampled hop: a candidate (flag pass, or the uncapped
+ * pass) — so the probes follow the subgraph's size, not E * log n.  Whether an edge is excluded is a function of the edge
+ * alone: the results stay independent of which thread lands first.
+ *   ghf_subgraph_hops_excl, ghf_subgraph_edges_excl, ghf_subgraph_sample_hops_excl: their twins' arguments, then excl,
+ *                       n_excl, typed.  The same workspaces (ghf_subgraph_workspace_bytes / _sample_workspace_bytes): there
+ *                       is no per-edge array of excluded edges.  With n_excl == 0 (excl may be NULL) they equal their twins
+ *                       bit for bit.  n_excl < 0, excl == NULL with n_excl > 0, and typed other than 0 or 1 are GHF_EINVAL,
+ *                       checked on the host before any other argument is looked at.
+ *   ghf_subgraph_nodes and ghf_subgraph_sample_edges serve unchanged: dist has no distance through an excluded edge, and
+ *                       keep[] never marks one. */
+int ghf_subgraph_hops_excl(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
+                           const int64_t* seeds, int64_t S, int k, void* workspace, size_t workspace_bytes, int32_t* dist,
+                           void* stream, const uint64_t* excl /* [n_excl] ascending */, int64_t n_excl, int typed);
+int ghf_subgraph_edges_excl(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
+                            const int32_t* dist, const int64_t* new_id, int k, void* workspace, size_t workspace_bytes,
+                            int64_t* edge_out /* [2, E] */, int64_t* rel_out /* [E] */, int64_t* num_edges /* [1] */,
+                            void* stream, const uint64_t* excl /* [n_excl] ascending */, int64_t n_excl, int typed);
+int ghf_subgraph_sample_hops_excl(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R,
+                                  int block_nodes, const int64_t* seeds, int64_t S, int k, const int* fanout /* HOST [k] */,
+                                  uint64_t seed, void* workspace, size_t workspace_bytes, int32_t* dist,
+                                  int32_t* keep /* [E] */, int64_t* host_reads /* HOST [1] or NULL */, void* stream,
+                                  const uint64_t* excl /* [n_excl] ascending */, int64_t n_excl, int typed);
+
 /* ---- K1: weight generation ------------------------------------------------------
  * Replaces models/weight_generator.py:137-141 (three nn.Sequential heads, reshape,
  * * exp(log_scale)) for B = R relation embeddings at once.

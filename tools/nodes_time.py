@@ -2,6 +2,7 @@
 synthetic graphs and seeds), with a breakdown of where a call's time goes.  Prints one JSON line.
 
     python tools/nodes_time.py [--configs c3,c2] [--reps 5] [--kind uniform|powerlaw] [--fanout 5,5,5[;10,10,10]]
+                               [--exclude B[,B2]]
 
 Per config: the full inference forward; forward_nodes (eval) at 1,024 and 16,384 random seeds, split into the subgraph
 extraction (ghf_subgraph_*, with its one host sync for the counts), the sub-plan build (build_plan: a device sort and
@@ -12,7 +13,13 @@ step (forward_nodes in train mode + backward) on 1,024 seeds against the same st
 --fanout adds, per cap list (the first num_layers entries of each are used) and per seed count, the sampled call beside
 the exact one: m, the sampled edges, the sampled extraction (ghf_subgraph_sample_*: its hop passes, sorts and host reads
 together — split them with a kernel trace), the whole inference call and the training step, each with its exact
-counterpart from the same process."""
+counterpart from the same process.
+
+--exclude B draws B existing edges (the batch a link-prediction step scores), takes their heads and tails as the seeds
+(2 B of them) and the batch in both directions, typed, as forward_nodes' exclusion list (2 B entries: --exclude 512,8192
+gives 1,024 and 16,384 seeds with a list of the same size), and times — in one process, for the exact form and for
+every --fanout list (default 5,5,5) — the extraction (ghf_subgraph_*_excl against ghf_subgraph_*, the sorted keys ready)
+and the whole inference call (which also builds and sorts the keys) with and without the list."""
 
 from __future__ import annotations
 
@@ -104,6 +111,40 @@ def run_sampled(name, reps, kind, fanouts):
     return res
 
 
+def run_exclude(name, reps, kind, fanouts, batches):
+    """Per batch size B: B existing edges excluded in both directions, seeds = their heads and tails; extraction and
+    inference call with and without the list, exact and per cap list."""
+    model, x, ei, texts, N, d, L, dev = setup(name, kind)
+    res = {}
+    with torch.no_grad():
+        plan = model.plan_for(ei, texts, N, dev)
+        for B in batches:
+            batch = torch.from_numpy(np.random.default_rng(B).choice(ei.size(1), B, replace=False)).to(dev)
+            r = plan.rel_ids[batch].repeat(2)
+            seeds = torch.cat([ei[0][batch], ei[1][batch]])
+            h, t = seeds, torch.cat([ei[1][batch], ei[0][batch]])
+            names = [plan.unique_texts[i] for i in r.tolist()]
+            keys = torch.sort((h << 32) | (t * plan.R + r)).values
+            row = {}
+            for fan in [None] + [tuple(f[:L]) for f in fanouts]:
+                kw = {} if fan is None else dict(fanout=fan, seed=12345)
+                if fan is None:
+                    extract = lambda ex: _native.subgraph(plan, seeds, L, exclude=ex)                    # noqa: E731
+                else:
+                    extract = lambda ex: _native.subgraph_sample(plan, seeds, fan, 12345, exclude=ex)    # noqa: E731
+                out = {}
+                out["extract_ms"], plain = timed(lambda: extract(None), reps)
+                out["extract_excl_ms"], sub = timed(lambda: extract((keys, True)), reps)
+                out["ms"], _ = timed(lambda: model.forward_nodes(x, ei, texts, seeds, **kw), reps)
+                out["excl_ms"], _ = timed(lambda: model.forward_nodes(x, ei, texts, seeds, exclude=(h, t, names), **kw), reps)
+                out["m"], out["edges"] = plain["m"], int(plain["edge_index"].size(1))
+                out["excl_m"], out["excl_edges"] = sub["m"], int(sub["edge_index"].size(1))
+                out["seeds"], out["entries"] = int(seeds.numel()), int(keys.numel())
+                row["exact" if fan is None else "fanout " + ",".join(map(str, fan))] = out
+            res[f"batch{B}"] = row
+    return res
+
+
 def run_config(name, reps, kind="uniform"):
     model, x, ei, texts, N, d, L, dev = setup(name, kind)
     res = {}
@@ -158,8 +199,13 @@ def main():
     ap.add_argument("--kind", default="uniform", choices=["uniform", "powerlaw"], help="the synthetic graph's degree law")
     ap.add_argument("--fanout", default="", help="per-hop caps, e.g. 5,5,5 (several lists: separate with ';'; -1 = no cap): "
                     "time the sampled forward_nodes beside the exact one instead of the exact call's breakdown")
+    ap.add_argument("--exclude", default="", help="batch sizes B, e.g. 1024,16384: exclude B existing edges (seeds: their ends) "
+                    "and time the extraction and the inference call with and without the list, exact and per --fanout list")
     args = ap.parse_args()
     fanouts = [[int(f) for f in part.split(",")] for part in args.fanout.split(";") if part.strip()]
+    batches = [int(b) for b in args.exclude.split(",") if b.strip()]
+    if batches and not fanouts:
+        fanouts = [[5, 5, 5]]
     for name in args.configs.split(","):
         if any(len(f) < CONFIGS[name]["L"] for f in fanouts):
             raise SystemExit(f"--fanout needs {CONFIGS[name]['L']} caps per list for {name}")
@@ -167,7 +213,10 @@ def main():
         raise SystemExit("nodes_time.py measures on an MI355X; no HIP device here")
     out = {"tool": "nodes_time", "device": torch.cuda.get_device_name(0), "kind": args.kind}
     for name in args.configs.split(","):
-        out[name] = run_sampled(name, args.reps, args.kind, fanouts) if fanouts else run_config(name, args.reps, args.kind)
+        if batches:
+            out[name] = run_exclude(name, args.reps, args.kind, fanouts, batches)
+        else:
+            out[name] = run_sampled(name, args.reps, args.kind, fanouts) if fanouts else run_config(name, args.reps, args.kind)
     print(json.dumps(out))
 
 
