@@ -116,6 +116,20 @@ SIGNATURES = {
     "ghf_score_bce_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _vp, _sz, _vp, _vp]),
     "ghf_score_bce_bwd_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "ghf_score_bce_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "ghf_score_rank_sub_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "ghf_score_rank_sub": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "ghf_score_topk_sub_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i64]),
+    "ghf_score_topk_sub": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "ghf_score_softmax_sub_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "ghf_score_softmax_fwd_sub": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "ghf_score_softmax_bwd_sub_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "ghf_score_softmax_bwd_sub": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _i64, _vp, _sz, _vp,
+                                         _vp, _vp]),
+    "ghf_score_bce_sub_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "ghf_score_bce_fwd_sub": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _vp, _i64, _vp, _sz, _vp, _vp]),
+    "ghf_score_bce_bwd_sub_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "ghf_score_bce_bwd_sub": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _i64, _vp, _sz, _vp,
+                                     _vp, _vp]),
     "ghf_relation_rows_workspace_bytes": (_sz, [_i64, _i32]),
     "ghf_relation_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
     "ghf_relation_scores": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp]),
@@ -126,6 +140,7 @@ SIGNATURES = {
     "ghf_rows_pack": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp]),
     "ghf_rows_unpack": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
     "ghf_rows_accumulate": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp]),
+    "ghf_rows_accumulate_any": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _vp]),
     "ghf_tail_fwd": (_i32, [_vp, _vp, _vp, _vp, _f32, _i64, _i64, _i32, _vp, _vp, _vp]),
     "ghf_set_range_flag": (_i32, [_vp]),
 }
@@ -655,8 +670,29 @@ def _workspace(workspace: Optional[torch.Tensor], size_fn, device, what: str, **
     return workspace
 
 
+def _ic_arg(ic: Optional[torch.Tensor], c: torch.Tensor, what: str) -> Optional[torch.Tensor]:
+    """The candidate subset of the ghf_score_*_sub calls (include/ghf.h): int64 [C] node ids on c's device, 1 <= C <= N.  That
+    they ascend strictly and stay inside [0, N) is the device's check (a bad list makes every query invalid)."""
+    if ic is None:
+        return None
+    ic = _req(ic, torch.int64, "ic")
+    if ic.dim() != 1 or not 1 <= ic.numel() <= c.size(0):
+        raise ValueError(f"{what}: ic must hold 1..N = {c.size(0)} candidate ids, got {tuple(ic.shape)}")
+    if ic.device != c.device:
+        raise RuntimeError(f"{what}: ic is on {ic.device}, the embeddings on {c.device}")
+    return ic
+
+
 def score_rank_workspace_bytes(B: int, N: int, d: int) -> int:
     return int(load().ghf_score_rank_workspace_bytes(B, N, d))
+
+
+def score_rank_sub_workspace_bytes(B: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_rank_sub_workspace_bytes(B, C, d, nnz))
+
+
+def score_topk_sub_workspace_bytes(B: int, C: int, d: int, k: int, nnz: int) -> int:
+    return int(load().ghf_score_topk_sub_workspace_bytes(B, C, d, k, nnz))
 
 
 def score_topk_workspace_bytes(B: int, N: int, d: int, k: int) -> int:
@@ -665,16 +701,23 @@ def score_topk_workspace_bytes(B: int, N: int, d: int, k: int) -> int:
 
 def score_rank(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optional[torch.Tensor] = None,
                filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
-               workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+               workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+               ic: Optional[torch.Tensor] = None):
     """(greater, equal) int64 [B]: how many rows of c score above / the same as row target[i] against query q[iq[i]], the
     target and the query's filter list (CSR, each list sorted ascending) left out.  Nothing of size B x N is stored.  With
-    `workspace` (uint8, score_rank_workspace_bytes) and `out` given the call allocates nothing (graph capture)."""
+    `workspace` (uint8, score_rank_workspace_bytes) and `out` given the call allocates nothing (graph capture).  `ic` (int64
+    [C], strictly ascending node ids): only those rows of c are counted (ghf_score_rank_sub; the workspace is then
+    score_rank_sub_workspace_bytes'); target and lists stay node ids, the target need not be a candidate."""
     q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, "score_rank")
     target = _req(target, torch.int64, "target")
     if target.dim() != 1 or target.numel() != B or target.device != q.device:
         raise ValueError(f"score_rank: target must be [B = {B}] on {q.device}, got {tuple(target.shape)} on {target.device}")
     N, d = c.size(0), c.size(1)
-    ws = _workspace(workspace, score_rank_workspace_bytes, q.device, "score_rank", B=B, N=N, d=d)
+    ic = _ic_arg(ic, c, "score_rank")
+    if ic is None:
+        ws = _workspace(workspace, score_rank_workspace_bytes, q.device, "score_rank", B=B, N=N, d=d)
+    else:
+        ws = _workspace(workspace, score_rank_sub_workspace_bytes, q.device, "score_rank", B=B, C=ic.numel(), d=d, nnz=nnz)
     if out is None:
         greater = torch.empty(B, dtype=torch.int64, device=q.device)
         equal = torch.empty(B, dtype=torch.int64, device=q.device)
@@ -682,6 +725,11 @@ def score_rank(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optio
         greater, equal = (_req(t, torch.int64, "out") for t in out)
         if greater.numel() != B or equal.numel() != B or not (out[0].is_contiguous() and out[1].is_contiguous()):
             raise ValueError(f"score_rank: out must be two contiguous int64 [{B}] tensors")
+    if ic is not None:
+        _check(load().ghf_score_rank_sub(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
+                                         d, _ptr(ic), ic.numel(), _ptr(ws), ws.numel(), _ptr(greater), _ptr(equal), _stream()),
+               "ghf_score_rank_sub")
+        return greater, equal
     _check(load().ghf_score_rank(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d,
                                  _ptr(ws), ws.numel(), _ptr(greater), _ptr(equal), _stream()), "ghf_score_rank")
     return greater, equal
@@ -689,15 +737,21 @@ def score_rank(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optio
 
 def score_topk(q: torch.Tensor, c: torch.Tensor, k: int, iq: Optional[torch.Tensor] = None,
                filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
-               workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+               workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+               ic: Optional[torch.Tensor] = None):
     """(scores [B, k] fp32 descending, ids [B, k] int64): the k best rows of c for every query, ties towards the lower id,
-    (-inf, -1) where fewer than k candidates remain outside the query's filter list."""
+    (-inf, -1) where fewer than k candidates remain outside the query's filter list.  `ic` (int64 [C], strictly ascending node
+    ids): the k best among those rows only (ghf_score_topk_sub); the ids returned are node ids."""
     q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, "score_topk")
     k = int(k)
     if not 1 <= k <= 128:
         raise ValueError(f"score_topk: k = {k} outside 1..128")
     N, d = c.size(0), c.size(1)
-    ws = _workspace(workspace, score_topk_workspace_bytes, q.device, "score_topk", B=B, N=N, d=d, k=k)
+    ic = _ic_arg(ic, c, "score_topk")
+    if ic is None:
+        ws = _workspace(workspace, score_topk_workspace_bytes, q.device, "score_topk", B=B, N=N, d=d, k=k)
+    else:
+        ws = _workspace(workspace, score_topk_sub_workspace_bytes, q.device, "score_topk", B=B, C=ic.numel(), d=d, k=k, nnz=nnz)
     if out is None:
         scores = torch.empty(B, k, dtype=torch.float32, device=q.device)
         ids = torch.empty(B, k, dtype=torch.int64, device=q.device)
@@ -705,6 +759,11 @@ def score_topk(q: torch.Tensor, c: torch.Tensor, k: int, iq: Optional[torch.Tens
         scores, ids = _req(out[0], torch.float32, "out[0]"), _req(out[1], torch.int64, "out[1]")
         if tuple(scores.shape) != (B, k) or tuple(ids.shape) != (B, k) or not (out[0].is_contiguous() and out[1].is_contiguous()):
             raise ValueError(f"score_topk: out must be contiguous fp32 and int64 [{B}, {k}] tensors")
+    if ic is not None:
+        _check(load().ghf_score_topk_sub(_ptr(q), _ptr(c), _ptr(iq), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d, k,
+                                         _ptr(ic), ic.numel(), _ptr(ws), ws.numel(), _ptr(scores), _ptr(ids), _stream()),
+               "ghf_score_topk_sub")
+        return scores, ids
     _check(load().ghf_score_topk(_ptr(q), _ptr(c), _ptr(iq), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d, k, _ptr(ws),
                                  ws.numel(), _ptr(scores), _ptr(ids), _stream()), "ghf_score_topk")
     return scores, ids
@@ -717,6 +776,14 @@ def score_softmax_workspace_bytes(B: int, N: int, d: int) -> int:
 
 def score_softmax_bwd_workspace_bytes(B: int, N: int, d: int) -> int:
     return int(load().ghf_score_softmax_bwd_workspace_bytes(B, N, d))
+
+
+def score_softmax_sub_workspace_bytes(B: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_softmax_sub_workspace_bytes(B, C, d, nnz))
+
+
+def score_softmax_bwd_sub_workspace_bytes(B: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_softmax_bwd_sub_workspace_bytes(B, C, d, nnz))
 
 
 def _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, what: str):
@@ -750,15 +817,25 @@ def _scale_arg(scale, what: str) -> float:
 
 def score_softmax_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optional[torch.Tensor] = None,
                       filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0,
-                      workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+                      workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                      ic: Optional[torch.Tensor] = None):
     """(loss, lse) fp32 [B]: lse[i] = log sum_j exp(scale q[iq[i]] . c[j]) over every row j of c outside query i's filter
     list (CSR, each list sorted ascending; the target always stays in), loss[i] = lse[i] - scale q[iq[i]] . c[target[i]].
     Nothing of size B x N is stored.  With `workspace` (uint8, score_softmax_workspace_bytes) and `out` given the call
-    allocates nothing."""
+    allocates nothing.  `ic` (int64 [C], strictly ascending node ids): the sum runs over those rows of c only
+    (ghf_score_softmax_fwd_sub; workspace: score_softmax_sub_workspace_bytes); a query whose target is not among them gets
+    NaN."""
     q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, "score_softmax_fwd")
     N, d = c.size(0), c.size(1)
-    ws = _workspace(workspace, score_softmax_workspace_bytes, q.device, "score_softmax_fwd", B=B, N=N, d=d)
+    ic = _ic_arg(ic, c, "score_softmax_fwd")
     loss, lse = _f32_out_pair(out, (B,), (B,), q.device, "score_softmax_fwd")
+    if ic is not None:
+        ws = _workspace(workspace, score_softmax_sub_workspace_bytes, q.device, "score_softmax_fwd", B=B, C=ic.numel(), d=d, nnz=nnz)
+        _check(load().ghf_score_softmax_fwd_sub(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0),
+                                                N, B, d, scale, _ptr(ic), ic.numel(), _ptr(ws), ws.numel(), _ptr(loss), _ptr(lse),
+                                                _stream()), "ghf_score_softmax_fwd_sub")
+        return loss, lse
+    ws = _workspace(workspace, score_softmax_workspace_bytes, q.device, "score_softmax_fwd", B=B, N=N, d=d)
     _check(load().ghf_score_softmax_fwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
                                         d, scale, _ptr(ws), ws.numel(), _ptr(loss), _ptr(lse), _stream()), "ghf_score_softmax_fwd")
     return loss, lse
@@ -767,14 +844,24 @@ def score_softmax_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq
 def score_softmax_bwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, lse: torch.Tensor, grad_loss: torch.Tensor,
                       iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
                       filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0, workspace: Optional[torch.Tensor] = None,
-                      out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+                      out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ic: Optional[torch.Tensor] = None):
     """(dq [B, d], dc [N, d]) fp32 of include/ghf.h: ghf_score_softmax_bwd — dq per query (not scattered through iq), every
-    row of dc written.  `lse` is the forward's."""
+    row of dc written.  `lse` is the forward's.  With `ic` (the forward's): ghf_score_softmax_bwd_sub, dc is [C, d], row j the
+    gradient of row ic[j] of c."""
     q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, "score_softmax_bwd")
     lse, grad_loss = _req(lse, torch.float32, "lse"), _req(grad_loss, torch.float32, "grad_loss")
     if lse.numel() != B or grad_loss.numel() != B:
         raise ValueError(f"score_softmax_bwd: lse and grad_loss must hold B = {B} values")
     N, d = c.size(0), c.size(1)
+    ic = _ic_arg(ic, c, "score_softmax_bwd")
+    if ic is not None:
+        C = ic.numel()
+        ws = _workspace(workspace, score_softmax_bwd_sub_workspace_bytes, q.device, "score_softmax_bwd", B=B, C=C, d=d, nnz=nnz)
+        dq, dc = _f32_out_pair(out, (B, d), (C, d), q.device, "score_softmax_bwd")
+        _check(load().ghf_score_softmax_bwd_sub(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0),
+                                                N, B, d, scale, _ptr(lse), _ptr(grad_loss), _ptr(ic), C, _ptr(ws), ws.numel(), _ptr(dq),
+                                                _ptr(dc), _stream()), "ghf_score_softmax_bwd_sub")
+        return dq, dc
     ws = _workspace(workspace, score_softmax_bwd_workspace_bytes, q.device, "score_softmax_bwd", B=B, N=N, d=d)
     dq, dc = _f32_out_pair(out, (B, d), (N, d), q.device, "score_softmax_bwd")
     _check(load().ghf_score_softmax_bwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
@@ -792,6 +879,14 @@ def score_bce_bwd_workspace_bytes(B: int, N: int, d: int) -> int:
     return int(load().ghf_score_bce_bwd_workspace_bytes(B, N, d))
 
 
+def score_bce_sub_workspace_bytes(B: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_bce_sub_workspace_bytes(B, C, d, nnz))
+
+
+def score_bce_bwd_sub_workspace_bytes(B: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_bce_bwd_sub_workspace_bytes(B, C, d, nnz))
+
+
 def _bce_args(q, c, iq, pos_ptr, pos_idx, scale, smoothing, what: str):
     q, c, iq, pos_ptr, pos_idx, B, nnz = _rank_args(q, c, iq, pos_ptr, pos_idx, what)
     scale, smoothing = _scale_arg(scale, what), float(smoothing)
@@ -802,15 +897,24 @@ def _bce_args(q, c, iq, pos_ptr, pos_idx, scale, smoothing, what: str):
 
 def score_bce_fwd(q: torch.Tensor, c: torch.Tensor, iq: Optional[torch.Tensor] = None, pos_ptr: Optional[torch.Tensor] = None,
                   pos_idx: Optional[torch.Tensor] = None, scale: float = 1.0, smoothing: float = 0.0,
-                  workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                  ic: Optional[torch.Tensor] = None) -> torch.Tensor:
     """loss fp32 [B]: binary_cross_entropy_with_logits(scale q[iq[i]] . c[j], y_ij, reduction="sum") over every row j of c, with
     y_ij = (1 - smoothing) [j in query i's list] + smoothing / N (CSR lists, each sorted ascending, a repeated id counting once).
     Nothing of size B x N is stored.  With `workspace` (uint8, score_bce_workspace_bytes) and `out` given the call allocates
-    nothing."""
+    nothing.  `ic` (int64 [C], strictly ascending node ids): the loss over those rows of c alone, smoothing / C, listed ids
+    that are no candidates taking no part (ghf_score_bce_fwd_sub; workspace: score_bce_sub_workspace_bytes)."""
     q, c, iq, pos_ptr, pos_idx, B, nnz, scale, smoothing = _bce_args(q, c, iq, pos_ptr, pos_idx, scale, smoothing, "score_bce_fwd")
     N, d = c.size(0), c.size(1)
-    ws = _workspace(workspace, score_bce_workspace_bytes, q.device, "score_bce_fwd", B=B, N=N, d=d)
+    ic = _ic_arg(ic, c, "score_bce_fwd")
     loss = _f32_out(out, (B,), q.device, "score_bce_fwd")
+    if ic is not None:
+        ws = _workspace(workspace, score_bce_sub_workspace_bytes, q.device, "score_bce_fwd", B=B, C=ic.numel(), d=d, nnz=nnz)
+        _check(load().ghf_score_bce_fwd_sub(_ptr(q), _ptr(c), _ptr(iq), _ptr(pos_ptr), _ptr(pos_idx), nnz, q.size(0), N, B, d, scale,
+                                            smoothing, _ptr(ic), ic.numel(), _ptr(ws), ws.numel(), _ptr(loss), _stream()),
+               "ghf_score_bce_fwd_sub")
+        return loss
+    ws = _workspace(workspace, score_bce_workspace_bytes, q.device, "score_bce_fwd", B=B, N=N, d=d)
     _check(load().ghf_score_bce_fwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(pos_ptr), _ptr(pos_idx), nnz, q.size(0), N, B, d, scale,
                                     smoothing, _ptr(ws), ws.numel(), _ptr(loss), _stream()), "ghf_score_bce_fwd")
     return loss
@@ -819,14 +923,24 @@ def score_bce_fwd(q: torch.Tensor, c: torch.Tensor, iq: Optional[torch.Tensor] =
 def score_bce_bwd(q: torch.Tensor, c: torch.Tensor, loss: torch.Tensor, grad_loss: torch.Tensor, iq: Optional[torch.Tensor] = None,
                   pos_ptr: Optional[torch.Tensor] = None, pos_idx: Optional[torch.Tensor] = None, scale: float = 1.0,
                   smoothing: float = 0.0, workspace: Optional[torch.Tensor] = None,
-                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ic: Optional[torch.Tensor] = None):
     """(dq [B, d], dc [N, d]) fp32 of include/ghf.h: ghf_score_bce_bwd — dq per query (not scattered through iq), every row
-    of dc written.  `loss` is the forward's (a NaN entry: that query takes no part)."""
+    of dc written.  `loss` is the forward's (a NaN entry: that query takes no part).  With `ic` (the forward's):
+    ghf_score_bce_bwd_sub, dc is [C, d], row j the gradient of row ic[j] of c."""
     q, c, iq, pos_ptr, pos_idx, B, nnz, scale, smoothing = _bce_args(q, c, iq, pos_ptr, pos_idx, scale, smoothing, "score_bce_bwd")
     loss, grad_loss = _req(loss, torch.float32, "loss"), _req(grad_loss, torch.float32, "grad_loss")
     if loss.numel() != B or grad_loss.numel() != B:
         raise ValueError(f"score_bce_bwd: loss and grad_loss must hold B = {B} values")
     N, d = c.size(0), c.size(1)
+    ic = _ic_arg(ic, c, "score_bce_bwd")
+    if ic is not None:
+        C = ic.numel()
+        ws = _workspace(workspace, score_bce_bwd_sub_workspace_bytes, q.device, "score_bce_bwd", B=B, C=C, d=d, nnz=nnz)
+        dq, dc = _f32_out_pair(out, (B, d), (C, d), q.device, "score_bce_bwd")
+        _check(load().ghf_score_bce_bwd_sub(_ptr(q), _ptr(c), _ptr(iq), _ptr(pos_ptr), _ptr(pos_idx), nnz, q.size(0), N, B, d, scale,
+                                            smoothing, _ptr(loss), _ptr(grad_loss), _ptr(ic), C, _ptr(ws), ws.numel(), _ptr(dq),
+                                            _ptr(dc), _stream()), "ghf_score_bce_bwd_sub")
+        return dq, dc
     ws = _workspace(workspace, score_bce_bwd_workspace_bytes, q.device, "score_bce_bwd", B=B, N=N, d=d)
     dq, dc = _f32_out_pair(out, (B, d), (N, d), q.device, "score_bce_bwd")
     _check(load().ghf_score_bce_bwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(pos_ptr), _ptr(pos_idx), nnz, q.size(0), N, B, d, scale,
@@ -1362,9 +1476,10 @@ def rows_unpack(tables, idx: torch.Tensor, packed: torch.Tensor) -> None:
     _check(load().ghf_rows_unpack(_ptr(packed), _ptr(idx), idx.numel(), rows.size(0), _ptr(rows), rb, _ptr(extra), xb, _stream()), "ghf_rows_unpack")
 
 
-def rows_accumulate(rows: torch.Tensor, idx: Optional[torch.Tensor], packed: torch.Tensor) -> torch.Tensor:
+def rows_accumulate(rows: torch.Tensor, idx: Optional[torch.Tensor], packed: torch.Tensor, any_width: bool = False) -> torch.Tensor:
     """rows[idx[i]] += packed[i] in place (fp32 [nrows, d] and [n, d]; idx None = rows 0..n-1) — ghf_rows_accumulate, the
-    adjoint of rows_unpack.  idx entries must be distinct; entries outside [0, nrows) are skipped."""
+    adjoint of rows_unpack.  idx entries must be distinct; entries outside [0, nrows) are skipped.  `any_width`:
+    ghf_rows_accumulate_any, which also takes a d that is no multiple of 4 (the same bits where d is one)."""
     if rows.dim() != 2 or not rows.is_contiguous() or rows.dtype != torch.float32:
         raise ValueError(f"rows_accumulate: rows must be a contiguous float32 [nrows, d] tensor, got {rows.dtype} {tuple(rows.shape)}")
     rows = _req(rows, torch.float32, "rows")
@@ -1378,5 +1493,8 @@ def rows_accumulate(rows: torch.Tensor, idx: Optional[torch.Tensor], packed: tor
     n = idx.numel() if idx is not None else packed.numel() // max(d, 1)
     if packed.device != rows.device or packed.numel() != n * d:
         raise ValueError(f"rows_accumulate: message of {packed.numel()} floats on {packed.device} for {n} rows of {d} on {rows.device}")
+    if any_width:
+        _check(load().ghf_rows_accumulate_any(_ptr(packed), _ptr(idx), n, nrows, _ptr(rows), d, _stream()), "ghf_rows_accumulate_any")
+        return rows
     _check(load().ghf_rows_accumulate(_ptr(packed), _ptr(idx), n, nrows, _ptr(rows), d, _stream()), "ghf_rows_accumulate")
     return rows

@@ -408,11 +408,16 @@ class ScoreEdgesFn(torch.autograd.Function):
         return _native.segment_axpy(g.contiguous().float(), pair, embs, partner, off), None, None
 
 
-def _all_node_loss_grads(ctx, embs, rows, query, dq, dc):
+def _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand=None):
     """(d embs, d rows) of a loss against every node from its backward call's dq (per query) and dc (per candidate).  With
     the query rows given (q = rows, c = embs) they are those, as they are.  Without (q = c = embs): d embs = dc + dq summed
     into the rows `query` names, grouped by node (ghf_group_edges, stable) and added per node in that order (_fold_rows), as
-    ScoreEdgesFn does: reproducible."""
+    ScoreEdgesFn does: reproducible.  Over a candidate subset `cand` (ascending node ids) dc is [C, d]: its rows are first
+    added into a zeroed [N, d] gradient at the rows `cand` names (ghf_rows_accumulate_any — ghf_rows_accumulate for every
+    row width the losses take —: the ids are distinct, one add per element, so reproducible too); every other row of it
+    stays exactly zero.  Nothing of size [N, d] is made when embs needs no gradient."""
+    if cand is not None and (rows is None or ctx.needs_input_grad[0]):
+        dc = _native.rows_accumulate(torch.zeros_like(embs), cand, dc, any_width=True)
     if rows is None:
         return _native.add3(dc, _fold_rows(dq, query, embs.size(0)), out=dc), None
     return (dc if ctx.needs_input_grad[0] else None), (dq if ctx.needs_input_grad[1] else None)
@@ -423,52 +428,55 @@ class SoftmaxLossFn(torch.autograd.Function):
     filter list (HyperGNN.softmax_loss; include/ghf.h: ghf_score_softmax_fwd), with q_i = embs[query_i], or q_i = rows_i where
     the query rows are given (``softmax_loss(..., query_rows=Q)``): exactly one of `rows` and `query` is.  The [B, N] logits
     exist neither here nor in the backward, which recomputes them tile by tile from the saved lse (ghf_score_softmax_bwd);
-    _all_node_loss_grads turns its (dq, dc) into the gradients."""
+    _all_node_loss_grads turns its (dq, dc) into the gradients.  `cand` (ascending node ids, HyperGNN._candidate_ids' form with
+    the targets added) restricts the sum to those nodes (ghf_score_softmax_fwd_sub / _bwd_sub): dc is then one row per
+    candidate and is added into embs' own rows."""
 
     @staticmethod
-    def forward(ctx, embs, rows, query, target, ptr, idx, scale: float):
+    def forward(ctx, embs, rows, query, target, ptr, idx, scale: float, cand=None):
         assert (rows is None) != (query is None)
         embs = embs.contiguous().float()
         rows = None if rows is None else rows.contiguous().float()
         loss, lse = _native.score_softmax_fwd(embs if rows is None else rows, embs, target, iq=query, filt_ptr=ptr, filt_idx=idx,
-                                              scale=scale)
-        ctx.save_for_backward(embs, rows, query, target, ptr, idx, lse)
+                                              scale=scale, ic=cand)
+        ctx.save_for_backward(embs, rows, query, target, ptr, idx, lse, cand)
         ctx.scale = scale
         return loss
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        embs, rows, query, target, ptr, idx, lse = ctx.saved_tensors
+        embs, rows, query, target, ptr, idx, lse, cand = ctx.saved_tensors
         dq, dc = _native.score_softmax_bwd(embs if rows is None else rows, embs, target, lse, g.contiguous().float(), iq=query,
-                                           filt_ptr=ptr, filt_idx=idx, scale=ctx.scale)
-        return _all_node_loss_grads(ctx, embs, rows, query, dq, dc) + (None,) * 5
+                                           filt_ptr=ptr, filt_idx=idx, scale=ctx.scale, ic=cand)
+        return _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand) + (None,) * 6
 
 
 class BceLossFn(torch.autograd.Function):
     """loss_i = sum_j bce_with_logits(scale q_i . embs[j], y_ij) over ALL nodes j, y_ij = (1 - smoothing) [j in query i's list]
     + smoothing / N (HyperGNN.bce_loss; include/ghf.h: ghf_score_bce_fwd), q_i and the pair `rows` / `query` as in
     SoftmaxLossFn.  Neither the [B, N] logits nor the labels exist, here or in the backward, which recomputes the logits tile
-    by tile (ghf_score_bce_bwd); _all_node_loss_grads turns its (dq, dc) into the gradients."""
+    by tile (ghf_score_bce_bwd); _all_node_loss_grads turns its (dq, dc) into the gradients.  `cand` (ascending node ids): the
+    loss over those C nodes alone, smoothing / C (ghf_score_bce_fwd_sub / _bwd_sub), dc one row per candidate."""
 
     @staticmethod
-    def forward(ctx, embs, rows, query, ptr, idx, scale: float, smoothing: float):
+    def forward(ctx, embs, rows, query, ptr, idx, scale: float, smoothing: float, cand=None):
         assert (rows is None) != (query is None)
         embs = embs.contiguous().float()
         rows = None if rows is None else rows.contiguous().float()
         loss = _native.score_bce_fwd(embs if rows is None else rows, embs, iq=query, pos_ptr=ptr, pos_idx=idx, scale=scale,
-                                     smoothing=smoothing)
-        ctx.save_for_backward(embs, rows, query, ptr, idx, loss)
+                                     smoothing=smoothing, ic=cand)
+        ctx.save_for_backward(embs, rows, query, ptr, idx, loss, cand)
         ctx.scale, ctx.smoothing = scale, smoothing
         return loss
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        embs, rows, query, ptr, idx, loss = ctx.saved_tensors
+        embs, rows, query, ptr, idx, loss, cand = ctx.saved_tensors
         dq, dc = _native.score_bce_bwd(embs if rows is None else rows, embs, loss, g.contiguous().float(), iq=query, pos_ptr=ptr,
-                                       pos_idx=idx, scale=ctx.scale, smoothing=ctx.smoothing)
-        return _all_node_loss_grads(ctx, embs, rows, query, dq, dc) + (None,) * 5
+                                       pos_idx=idx, scale=ctx.scale, smoothing=ctx.smoothing, ic=cand)
+        return _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand) + (None,) * 6
 
 
 class ScorePairsFn(torch.autograd.Function):

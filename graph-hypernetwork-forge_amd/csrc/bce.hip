@@ -28,6 +28,12 @@ size_t score_bce_workspace_bytes(int64_t B, int64_t N, int d) {
     return rk_align((size_t)B * 4) + rk_align((size_t)B * (size_t)g.slabs * 12);
 }
 
+// a candidate subset (candidates.hip): the all-node workspace for N := C, then the id map's
+size_t score_bce_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz) {
+    const size_t base = score_bce_workspace_bytes(B, C, d), map = cand_workspace_bytes(B, nnz);
+    return base && map ? base + map : 0;
+}
+
 __global__ __launch_bounds__(256) void bce_finish_kernel(const float* __restrict__ part, const int* __restrict__ valid, int64_t B,
                                                          int64_t slabs, float pos_w, float neg_w, float* __restrict__ loss) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -44,24 +50,35 @@ __global__ __launch_bounds__(256) void bce_finish_kernel(const float* __restrict
 
 int launch_score_bce_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, void* ws,
-                         size_t ws_bytes, float* loss, hipStream_t stream) {
+                         size_t ws_bytes, float* loss, hipStream_t stream, const int64_t* ic, int64_t C) {
     RankArgs a;
-    int rc = score_open("score_bce_fwd", softmax_geom, score_bce_workspace_bytes(B, N, d), q, c, iq, pos_ptr, pos_idx, nnz, rows_q, N, B,
-                        d, ws_bytes, &a);
+    const int64_t M = ic ? C : N;                    // the candidates the sweep runs over, and the labels' smoothing / M
+    GHF_REQUIRE(!ic || (C > 0 && C <= N), "score_bce_fwd: need 1 <= C <= N candidates");
+    const size_t base = score_bce_workspace_bytes(B, M, d);
+    const size_t need = ic ? score_bce_sub_workspace_bytes(B, C, d, nnz) : base;
+    int rc = score_open("score_bce_fwd", softmax_geom, need, q, c, iq, pos_ptr, pos_idx, nnz, rows_q, M, B, d, ws_bytes, &a);
     if (rc != GHF_OK) return rc;
     int* valid = (int*)ws;
     const unsigned qb = (unsigned)cdiv(B, 256);
-    // a query whose row id is out of range takes no part; list_range_kernel then clears the queries with a bad list id
-    score_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, nullptr, rows_q, N, B, d, nullptr, valid, nullptr, nullptr);
-    GHF_LAUNCH_CHECK();
-    if (nnz > 0) {
-        list_range_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(pos_ptr, pos_idx, nnz, N, B, valid);
+    if (ic) {
+        CandMap m;
+        rc = launch_cand_map(q, c, iq, nullptr, false, pos_ptr, pos_idx, nnz, ic, C, rows_q, N, B, d, nullptr, nullptr, valid, nullptr,
+                             nullptr, (char*)ws + base, need > base ? need - base : 0, &m, stream);
+        if (rc != GHF_OK) return rc;
+        a.filt_ptr = m.ptr; a.filt_idx = m.idx;
+    } else {
+        // a query whose row id is out of range takes no part; list_range_kernel then clears the queries with a bad list id
+        score_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, nullptr, rows_q, N, B, d, nullptr, valid, nullptr, nullptr);
         GHF_LAUNCH_CHECK();
+        if (nnz > 0) {
+            list_range_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(pos_ptr, pos_idx, nnz, N, B, valid);
+            GHF_LAUNCH_CHECK();
+        }
     }
     a.scale = scale; a.ws_bce = (float*)((char*)ws + rk_align((size_t)B * 4));
-    rc = launch_rank_tiles<RK_BCE>(a, stream);
+    rc = launch_rank_tiles<RK_BCE>(a, stream, ic, N);
     if (rc != GHF_OK) return rc;
-    bce_finish_kernel<<<qb, 256, 0, stream>>>(a.ws_bce, valid, B, a.slabs, 1.f - smoothing, smoothing / (float)N, loss);
+    bce_finish_kernel<<<qb, 256, 0, stream>>>(a.ws_bce, valid, B, a.slabs, 1.f - smoothing, smoothing / (float)M, loss);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }

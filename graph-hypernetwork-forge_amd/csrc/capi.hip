@@ -527,6 +527,11 @@ int ghf_rows_accumulate(const float* packed, const int64_t* idx, int64_t n, int6
     return launch_rows_accumulate(packed, idx, n, nrows, rows, d, (hipStream_t)stream);
 }
 
+int ghf_rows_accumulate_any(const float* packed, const int64_t* idx, int64_t n, int64_t nrows, float* rows, int d, void* stream) {
+    GHF_REQUIRE(rows && (packed || n == 0), "rows_accumulate_any: null pointer argument");
+    return launch_rows_accumulate(packed, idx, n, nrows, rows, d, (hipStream_t)stream, true);
+}
+
 size_t ghf_subgraph_workspace_bytes(int64_t N, int64_t E, int k) { return subgraph_workspace_bytes(N, E, k); }
 
 int ghf_subgraph_hops(const uint32_t* sorted_key, const int32_t* sorted_src, int64_t N, int64_t E, int R, int block_nodes,
@@ -705,6 +710,103 @@ int ghf_score_bce_bwd(const float* q, const float* c, const int64_t* iq, const i
     return launch_score_bce_bwd(q, c, iq, pos_ptr, pos_idx, nnz, rows_q, N, B, d, scale, smoothing, loss, grad_loss, workspace,
                                 workspace_bytes, dq, dc, (hipStream_t)stream);
 }
+
+// the same six against a candidate subset (candidates.hip): score_entry_check, then the list itself
+#define GHF_SUB_CHECK(op) GHF_REQUIRE(ic && C > 0 && C <= N, op ": need ic and 1 <= C <= N")
+
+size_t ghf_score_rank_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz) {
+    return score_rank_sub_workspace_bytes(B, C, d, nnz);
+}
+
+int ghf_score_rank_sub(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                       const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, const int64_t* ic,
+                       int64_t C, void* workspace, size_t workspace_bytes, int64_t* greater, int64_t* equal, void* stream) {
+    const int rc = score_entry_check("score_rank_sub", "filter", q && c && target && greater && equal, filt_ptr, filt_idx, nnz, 1.f,
+                                     0.f, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_SUB_CHECK("score_rank_sub");
+    return launch_score_rank(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, workspace, workspace_bytes, greater, equal,
+                             (hipStream_t)stream, ic, C);
+}
+
+size_t ghf_score_topk_sub_workspace_bytes(int64_t B, int64_t C, int d, int k, int64_t nnz) {
+    return score_topk_sub_workspace_bytes(B, C, d, k, nnz);
+}
+
+int ghf_score_topk_sub(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
+                       int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, const int64_t* ic, int64_t C,
+                       void* workspace, size_t workspace_bytes, float* scores, int64_t* ids, void* stream) {
+    const int rc = score_entry_check("score_topk_sub", "filter", q && c && scores && ids, filt_ptr, filt_idx, nnz, 1.f, 0.f, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_SUB_CHECK("score_topk_sub");
+    return launch_score_topk(q, c, iq, filt_ptr, filt_idx, nnz, rows_q, N, B, d, k, workspace, workspace_bytes, scores, ids,
+                             (hipStream_t)stream, ic, C);
+}
+
+size_t ghf_score_softmax_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz) {
+    return score_softmax_sub_workspace_bytes(B, C, d, nnz);
+}
+
+int ghf_score_softmax_fwd_sub(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                              const int64_t* ic, int64_t C, void* workspace, size_t workspace_bytes, float* loss, float* lse,
+                              void* stream) {
+    const int rc = score_entry_check("score_softmax_fwd_sub", "filter", q && c && target && loss && lse, filt_ptr, filt_idx, nnz, scale,
+                                     0.f, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_SUB_CHECK("score_softmax_fwd_sub");
+    return launch_score_softmax_fwd(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, workspace, workspace_bytes,
+                                    loss, lse, (hipStream_t)stream, ic, C);
+}
+
+size_t ghf_score_softmax_bwd_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz) {
+    return score_softmax_bwd_sub_workspace_bytes(B, C, d, nnz);
+}
+
+int ghf_score_softmax_bwd_sub(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                              const float* lse, const float* grad_loss, const int64_t* ic, int64_t C, void* workspace,
+                              size_t workspace_bytes, float* dq, float* dc, void* stream) {
+    const int rc = score_entry_check("score_softmax_bwd_sub", "filter", q && c && target && lse && grad_loss && dq && dc, filt_ptr,
+                                     filt_idx, nnz, scale, 0.f, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_SUB_CHECK("score_softmax_bwd_sub");
+    return launch_score_softmax_bwd(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, lse, grad_loss, workspace,
+                                    workspace_bytes, dq, dc, (hipStream_t)stream, ic, C);
+}
+
+size_t ghf_score_bce_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz) {
+    return score_bce_sub_workspace_bytes(B, C, d, nnz);
+}
+
+int ghf_score_bce_fwd_sub(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
+                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const int64_t* ic,
+                          int64_t C, void* workspace, size_t workspace_bytes, float* loss, void* stream) {
+    const int rc = score_entry_check("score_bce_fwd_sub", "positive", q && c && loss, pos_ptr, pos_idx, nnz, scale, smoothing,
+                                     workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_SUB_CHECK("score_bce_fwd_sub");
+    return launch_score_bce_fwd(q, c, iq, pos_ptr, pos_idx, nnz, rows_q, N, B, d, scale, smoothing, workspace, workspace_bytes, loss,
+                                (hipStream_t)stream, ic, C);
+}
+
+size_t ghf_score_bce_bwd_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz) {
+    return score_bce_bwd_sub_workspace_bytes(B, C, d, nnz);
+}
+
+int ghf_score_bce_bwd_sub(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
+                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
+                          const float* grad_loss, const int64_t* ic, int64_t C, void* workspace, size_t workspace_bytes, float* dq,
+                          float* dc, void* stream) {
+    const int rc = score_entry_check("score_bce_bwd_sub", "positive", q && c && loss && grad_loss && dq && dc, pos_ptr, pos_idx, nnz,
+                                     scale, smoothing, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_SUB_CHECK("score_bce_bwd_sub");
+    return launch_score_bce_bwd(q, c, iq, pos_ptr, pos_idx, nnz, rows_q, N, B, d, scale, smoothing, loss, grad_loss, workspace,
+                                workspace_bytes, dq, dc, (hipStream_t)stream, ic, C);
+}
+
+#undef GHF_SUB_CHECK
 
 size_t ghf_relation_rows_workspace_bytes(int64_t B, int R) { return relation_rows_workspace_bytes(B, R); }
 

@@ -162,37 +162,45 @@ int launch_weightgen_batched(int L, const float* text_emb, const float* const* h
 
 int launch_rows_pack(bool unpack, void* rows, int64_t row_bytes, void* extra, int64_t extra_bytes, const int64_t* idx, int64_t n,
                      int64_t nrows, void* packed, hipStream_t stream);
-int launch_rows_accumulate(const float* packed, const int64_t* idx, int64_t n, int64_t nrows, float* rows, int d, hipStream_t stream);
+int launch_rows_accumulate(const float* packed, const int64_t* idx, int64_t n, int64_t nrows, float* rows, int d, hipStream_t stream,
+                           bool any_width = false);
 int launch_score_pairs(const float* a, const float* b, const int64_t* ia, const int64_t* ib, int64_t rows_a, int64_t rows_b,
                        int64_t n, int d, float* scores, hipStream_t stream);
-// rank.hip
+// rank.hip.  Every launch_score_* takes a candidate subset last (candidates.hip): ic [C] node ids, strictly ascending; NULL =
+// every row of c.  The *_sub_workspace_bytes are the subset calls' (C candidates, lists of nnz entries).
 size_t score_rank_workspace_bytes(int64_t B, int64_t N, int d);
 size_t score_topk_workspace_bytes(int64_t B, int64_t N, int d, int k);
+size_t score_rank_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
+size_t score_topk_sub_workspace_bytes(int64_t B, int64_t C, int d, int k, int64_t nnz);
 int launch_score_rank(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                       const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, void* ws,
-                      size_t ws_bytes, int64_t* greater, int64_t* equal, hipStream_t stream);
+                      size_t ws_bytes, int64_t* greater, int64_t* equal, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0);
 int launch_score_topk(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
                       int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, void* ws, size_t ws_bytes, float* scores,
-                      int64_t* ids, hipStream_t stream);
+                      int64_t* ids, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0);
 // softmax.hip
 size_t score_softmax_workspace_bytes(int64_t B, int64_t N, int d);
 size_t score_softmax_bwd_workspace_bytes(int64_t B, int64_t N, int d);
+size_t score_softmax_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
+size_t score_softmax_bwd_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
 int launch_score_softmax_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
-                             void* ws, size_t ws_bytes, float* loss, float* lse, hipStream_t stream);
+                             void* ws, size_t ws_bytes, float* loss, float* lse, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0);
 int launch_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                              const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc,
-                             hipStream_t stream);
+                             hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0);
 // bce.hip (forward) and softmax.hip (backward: softmax_bwd_kernel's second loss)
 size_t score_bce_workspace_bytes(int64_t B, int64_t N, int d);
 size_t score_bce_bwd_workspace_bytes(int64_t B, int64_t N, int d);
+size_t score_bce_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
+size_t score_bce_bwd_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
 int launch_score_bce_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, void* ws,
-                         size_t ws_bytes, float* loss, hipStream_t stream);
+                         size_t ws_bytes, float* loss, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0);
 int launch_score_bce_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
-                         const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc, hipStream_t stream);
+                         const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0);
 // relation.hip
 size_t relation_rows_workspace_bytes(int64_t B, int R);
 int launch_relation_rows(const float* x, const int64_t* ix, const int64_t* rel, const float* W, const float* bias,

@@ -78,14 +78,37 @@ __global__ __launch_bounds__(256) void rows_accumulate_kernel(const float* __res
     }
 }
 
-int launch_rows_accumulate(const float* packed, const int64_t* idx, int64_t n, int64_t nrows, float* rows, int d, hipStream_t stream) {
+// the same sum for rows of any width: one float per lane at a time
+__global__ __launch_bounds__(256) void rows_accumulate_scalar_kernel(const float* __restrict__ packed, const int64_t* __restrict__ idx,
+                                                                     int64_t n, int64_t nrows, float* __restrict__ rows, int d) {
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
+    for (int64_t i = wave; i < n; i += nwaves) {
+        const int64_t r = idx ? idx[i] : i;
+        if (r < 0 || r >= nrows) continue;
+        const float* __restrict__ m = packed + i * d;
+        float* __restrict__ p = rows + r * d;
+        for (int k = lane; k < d; k += 64) p[k] += m[k];
+    }
+}
+
+// any_width: rows whose width is no multiple of 4 floats, or buffers aligned to 4 bytes only, are accepted and take the
+// scalar kernel (ghf_rows_accumulate_any; the multi-GPU exchange's rows are always whole float4s and keep the strict check)
+int launch_rows_accumulate(const float* packed, const int64_t* idx, int64_t n, int64_t nrows, float* rows, int d, hipStream_t stream,
+                           bool any_width) {
     GHF_REQUIRE(n >= 0 && nrows >= 0, "rows_accumulate: negative row count");
-    GHF_REQUIRE(d > 0 && d % 4 == 0, "rows_accumulate: d must be a positive multiple of 4");
-    GHF_REQUIRE((((uintptr_t)rows | (uintptr_t)packed) & 15) == 0, "rows_accumulate: misaligned buffer");
+    const bool vec = d % 4 == 0 && (((uintptr_t)rows | (uintptr_t)packed) & 15) == 0;
+    if (any_width) {
+        GHF_REQUIRE(d > 0 && (((uintptr_t)rows | (uintptr_t)packed) & 3) == 0, "rows_accumulate_any: d must be positive, buffers 4-byte aligned");
+    } else {
+        GHF_REQUIRE(d > 0 && d % 4 == 0, "rows_accumulate: d must be a positive multiple of 4");
+        GHF_REQUIRE((((uintptr_t)rows | (uintptr_t)packed) & 15) == 0, "rows_accumulate: misaligned buffer");
+    }
     if (n == 0) return GHF_OK;
     const int64_t want = cdiv(n, 4);
     const unsigned grid = (unsigned)(want < 256 * 32 ? want : 256 * 32);
-    rows_accumulate_kernel<<<grid, 256, 0, stream>>>(packed, idx, n, nrows, rows, d);
+    if (vec) rows_accumulate_kernel<<<grid, 256, 0, stream>>>(packed, idx, n, nrows, rows, d);
+    else rows_accumulate_scalar_kernel<<<grid, 256, 0, stream>>>(packed, idx, n, nrows, rows, d);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }

@@ -59,6 +59,17 @@ size_t score_topk_workspace_bytes(int64_t B, int64_t N, int d, int k) {
     return rk_align((size_t)B * 4) + rk_align(entries * 8);           // valid [B] int32, keys (8 bytes per entry)
 }
 
+// a candidate subset (candidates.hip): the all-node workspace for N := C, then the id map's
+size_t score_rank_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz) {
+    const size_t base = score_rank_workspace_bytes(B, C, d), map = cand_workspace_bytes(B, nnz);
+    return base && map ? base + map : 0;
+}
+
+size_t score_topk_sub_workspace_bytes(int64_t B, int64_t C, int d, int k, int64_t nnz) {
+    const size_t base = score_topk_workspace_bytes(B, C, d, k), map = cand_workspace_bytes(B, nnz);
+    return base && map ? base + map : 0;
+}
+
 // ---- rank: the small kernels around the sweep -----------------------------------------------------------------------------
 // one thread per filter entry: an id out of range marks its query; any other entry's score is recomputed and taken out of the
 // count it went into (lists are sorted: a repeat is the entry before; the target is taken out by rank_finish)
@@ -67,7 +78,7 @@ __global__ __launch_bounds__(256) void rank_filter_kernel(const float* __restric
                                                           const int64_t* __restrict__ filt_ptr, const int64_t* __restrict__ filt_idx,
                                                           int64_t nnz, int64_t N, int64_t B, int d, const float* __restrict__ t,
                                                           int* valid, unsigned long long* __restrict__ greater,
-                                                          unsigned long long* __restrict__ equal) {
+                                                          unsigned long long* __restrict__ equal, const int64_t* __restrict__ ic) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= nnz) return;
     int64_t i;
@@ -80,28 +91,31 @@ __global__ __launch_bounds__(256) void rank_filter_kernel(const float* __restric
     if (!valid[i]) return;
     if (j == target[i] || (e > filt_ptr[i] && filt_idx[e - 1] == j)) return;
     const int64_t r = iq ? iq[i] : i;                // in range: score_prep_kernel said so (valid[i] was 1)
-    const float s = dot_chain(q + (size_t)r * d, c + (size_t)j * d, d, rows_vec(q, d) && rows_vec(c, d));
+    // over a candidate subset j and target[] are positions in ic (candidates.hip, which has checked ic)
+    const float s = dot_chain(q + (size_t)r * d, c + (size_t)(ic ? ic[j] : j) * d, d, rows_vec(q, d) && rows_vec(c, d));
     const float ti = t[i];
     if (s > ti) atomicAdd(&greater[i], ~0ull);
     else if (s == ti) atomicAdd(&equal[i], ~0ull);
 }
 
 __global__ __launch_bounds__(256) void rank_finish_kernel(const float* __restrict__ t, const int* __restrict__ valid, int64_t B,
-                                                          long long* __restrict__ greater, long long* __restrict__ equal) {
+                                                          long long* __restrict__ greater, long long* __restrict__ equal,
+                                                          const int64_t* __restrict__ tpos) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= B) return;
     if (!valid[i]) {
         greater[i] = -1;
         equal[i] = -1;
-    } else if (t[i] == t[i]) {
-        equal[i] -= 1;                               // the target's own score, counted by the tile that holds it
+    } else if (t[i] == t[i] && (!tpos || tpos[i] >= 0)) {
+        equal[i] -= 1;                               // the target's own score, counted by the tile that holds it (over a
+                                                     // candidate subset: when the target is a candidate)
     }
 }
 
 // ---- top-k: merge the slabs' sorted lists; one wave per query -------------------------------------------------------------
 __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* __restrict__ ws_key, const int* __restrict__ valid,
                                                          int64_t B, int64_t slabs, int cap, int k, float* __restrict__ out_sc,
-                                                         long long* __restrict__ out_id) {
+                                                         long long* __restrict__ out_id, const int64_t* __restrict__ ic) {
     const int lane = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= B) return;
@@ -134,7 +148,7 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* __restr
         }
         if (rank < k) {
             os[rank] = key_score(key);
-            oi[rank] = key_id(key);
+            oi[rank] = ic ? ic[key_id(key)] : key_id(key);      // a candidate subset: the position back to its node id
         }
     }
     // entries in all: positions from there on hold no candidate
@@ -148,48 +162,71 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* __restr
 // ---- launches -------------------------------------------------------------------------------------------------------------
 int launch_score_rank(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                       const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, void* ws,
-                      size_t ws_bytes, int64_t* greater, int64_t* equal, hipStream_t stream) {
+                      size_t ws_bytes, int64_t* greater, int64_t* equal, hipStream_t stream, const int64_t* ic, int64_t C) {
     RankArgs a;
-    int rc = score_open("score_rank", rank_geom_rank, score_rank_workspace_bytes(B, N, d), q, c, iq, filt_ptr, filt_idx, nnz, rows_q,
-                        N, B, d, ws_bytes, &a);
+    const int64_t M = ic ? C : N;                    // the candidates the sweep runs over
+    GHF_REQUIRE(!ic || (C > 0 && C <= N), "score_rank: need 1 <= C <= N candidates");
+    const size_t base = score_rank_workspace_bytes(B, M, d);
+    const size_t need = ic ? score_rank_sub_workspace_bytes(B, C, d, nnz) : base;
+    int rc = score_open("score_rank", rank_geom_rank, need, q, c, iq, filt_ptr, filt_idx, nnz, rows_q, M, B, d, ws_bytes, &a);
     if (rc != GHF_OK) return rc;
     float* t = (float*)ws;
     int* valid = (int*)((char*)ws + rk_align((size_t)B * 4));
     const unsigned qb = (unsigned)cdiv(B, 256);
-    score_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, target, rows_q, N, B, d, t, valid, (long long*)greater, (long long*)equal);
-    GHF_LAUNCH_CHECK();
-    a.t = t; a.greater = (unsigned long long*)greater; a.equal = (unsigned long long*)equal;
-    rc = launch_rank_tiles<RK_RANK>(a, stream);
-    if (rc != GHF_OK) return rc;
-    if (nnz > 0) {
-        rank_filter_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(q, c, iq, target, filt_ptr, filt_idx, nnz, N, B, d, t, valid,
-                                                                        a.greater, a.equal);
+    CandMap m = {};
+    if (ic) {
+        rc = launch_cand_map(q, c, iq, target, false, filt_ptr, filt_idx, nnz, ic, C, rows_q, N, B, d, nullptr, t, valid, greater,
+                             equal, (char*)ws + base, need > base ? need - base : 0, &m, stream);
+        if (rc != GHF_OK) return rc;
+        a.filt_ptr = m.ptr; a.filt_idx = m.idx;
+        target = m.tpos; filt_ptr = m.ptr; filt_idx = m.idx;
+    } else {
+        score_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, target, rows_q, N, B, d, t, valid, (long long*)greater, (long long*)equal);
         GHF_LAUNCH_CHECK();
     }
-    rank_finish_kernel<<<qb, 256, 0, stream>>>(t, valid, B, (long long*)greater, (long long*)equal);
+    a.t = t; a.greater = (unsigned long long*)greater; a.equal = (unsigned long long*)equal;
+    rc = launch_rank_tiles<RK_RANK>(a, stream, ic, N);
+    if (rc != GHF_OK) return rc;
+    if (nnz > 0) {
+        rank_filter_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(q, c, iq, target, filt_ptr, filt_idx, nnz, M, B, d, t, valid,
+                                                                        a.greater, a.equal, ic);
+        GHF_LAUNCH_CHECK();
+    }
+    rank_finish_kernel<<<qb, 256, 0, stream>>>(t, valid, B, (long long*)greater, (long long*)equal, m.tpos);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }
 
 int launch_score_topk(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
                       int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, void* ws, size_t ws_bytes, float* scores,
-                      int64_t* ids, hipStream_t stream) {
+                      int64_t* ids, hipStream_t stream, const int64_t* ic, int64_t C) {
     RankArgs a;
+    const int64_t M = ic ? C : N;
     GHF_REQUIRE(k >= 1 && k <= TOPK_MAX_K, "score_topk: k = %d outside 1..%d", k, TOPK_MAX_K);
-    int rc = score_open("score_topk", rank_geom_topk, score_topk_workspace_bytes(B, N, d, k), q, c, iq, filt_ptr, filt_idx, nnz,
-                        rows_q, N, B, d, ws_bytes, &a);
+    GHF_REQUIRE(!ic || (C > 0 && C <= N), "score_topk: need 1 <= C <= N candidates");
+    const size_t base = score_topk_workspace_bytes(B, M, d, k);
+    const size_t need = ic ? score_topk_sub_workspace_bytes(B, C, d, k, nnz) : base;
+    int rc = score_open("score_topk", rank_geom_topk, need, q, c, iq, filt_ptr, filt_idx, nnz, rows_q, M, B, d, ws_bytes, &a);
     if (rc != GHF_OK) return rc;
     int* valid = (int*)ws;
     a.k = k; a.cap = topk_cap(d, k); a.ws_key = (uint64_t*)((char*)ws + rk_align((size_t)B * 4));
-    score_prep_kernel<<<(unsigned)cdiv(B, 256), 256, 0, stream>>>(q, c, iq, nullptr, rows_q, N, B, d, nullptr, valid, nullptr, nullptr);
-    GHF_LAUNCH_CHECK();
-    if (nnz > 0) {
-        list_range_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(filt_ptr, filt_idx, nnz, N, B, valid);
+    if (ic) {
+        CandMap m;
+        rc = launch_cand_map(q, c, iq, nullptr, false, filt_ptr, filt_idx, nnz, ic, C, rows_q, N, B, d, nullptr, nullptr, valid,
+                             nullptr, nullptr, (char*)ws + base, need > base ? need - base : 0, &m, stream);
+        if (rc != GHF_OK) return rc;
+        a.filt_ptr = m.ptr; a.filt_idx = m.idx;
+    } else {
+        score_prep_kernel<<<(unsigned)cdiv(B, 256), 256, 0, stream>>>(q, c, iq, nullptr, rows_q, N, B, d, nullptr, valid, nullptr, nullptr);
         GHF_LAUNCH_CHECK();
+        if (nnz > 0) {
+            list_range_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(filt_ptr, filt_idx, nnz, N, B, valid);
+            GHF_LAUNCH_CHECK();
+        }
     }
-    rc = launch_rank_tiles<RK_TOPK>(a, stream);
+    rc = launch_rank_tiles<RK_TOPK>(a, stream, ic, N);
     if (rc != GHF_OK) return rc;
-    topk_merge_kernel<<<(unsigned)cdiv(B, 4), 256, 0, stream>>>(a.ws_key, valid, B, a.slabs, a.cap, k, scores, (long long*)ids);
+    topk_merge_kernel<<<(unsigned)cdiv(B, 4), 256, 0, stream>>>(a.ws_key, valid, B, a.slabs, a.cap, k, scores, (long long*)ids, ic);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }

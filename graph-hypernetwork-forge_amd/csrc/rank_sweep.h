@@ -193,6 +193,22 @@ struct RankArgs {
     float* ws_bce;
 };
 
+// a candidate subset (the SUB instantiations; candidates.hip): the sweep's candidate j is row ic[j] of c, which has Nn rows;
+// N, the lists and the targets are then the count of, and positions in, ic.  A type of its own, so that the all-node
+// instantiations keep their argument block, and with it their code, as they are.
+struct RankSubArgs : RankArgs { const int64_t* ic; int64_t Nn; };
+template <bool SUB> struct RankKernelArgs { typedef RankArgs type; };
+template <> struct RankKernelArgs<true> { typedef RankSubArgs type; };
+
+// row j of a sweep over the candidate subset ic [C] of a table of `rows` rows: absent past C or when the id is outside the
+// table (candidates.hip reports such a list; the sweep only has to read nothing outside c)
+__device__ __forceinline__ const float* sub_row(const float* __restrict__ c, const int64_t* __restrict__ ic, int64_t j, int64_t C,
+                                                int64_t rows, int d) {
+    if (j >= C) return nullptr;
+    const int64_t id = ic[j];
+    return (uint64_t)id < (uint64_t)rows ? c + (size_t)id * d : nullptr;
+}
+
 // the epilogue of rank_tile_kernel
 constexpr int RK_RANK = 0, RK_TOPK = 1, RK_SOFTMAX = 2, RK_BCE = 3;
 
@@ -274,8 +290,8 @@ static inline size_t rank_lds_bytes(int d, int BK, int CT) {
     return ((size_t)RK_TILE * (dpad + 4) + 2 * (size_t)CT * (BK + 4) + 2 * RK_TILE) * 4;
 }
 
-template <int BK, int CT, int MODE>
-__global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const RankArgs a) {
+template <int BK, int CT, int MODE, bool SUB = false>
+__global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKernelArgs<SUB>::type a) {
     constexpr bool TOPK = MODE == RK_TOPK, RANK = MODE == RK_RANK, SOFTMAX = MODE == RK_SOFTMAX, BCE = MODE == RK_BCE;
     constexpr bool CURSOR = SOFTMAX || BCE;             // the lists are walked by a cursor, in step with the sweep
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -354,12 +370,27 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const RankArgs a) {
     const int64_t total = (tile1 - tile0) * nch;
 
     f32x4 pre[NL];
+    // SUB: a row's address needs its id first, two loads in a row where the all-node sweep has one.  The ids of the rows this
+    // thread fetches (the same NL rows of a tile for every chunk of it) are therefore loaded a whole tile ahead: cid for the
+    // tile being fetched, nid for the one after it; -1 = no row (past C, or an id outside the table).
+    int cid[NL], nid[NL];
+    auto load_ids = [&](int64_t tile, int* out) {
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            if constexpr (SUB) {
+                const int64_t cand = tile * CT + (tid + NT * i) / F4;
+                const int64_t id = cand < a.N ? a.ic[cand] : -1;
+                out[i] = (uint64_t)id < (uint64_t)a.Nn ? (int)id : -1;
+            }
+        }
+    };
     auto fetch = [&](int64_t tile, int kc) {
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
             const int idx = tid + NT * i, row = idx / F4, c4 = idx % F4;
             const int64_t cand = tile * CT + row;
-            pre[i] = load_k4(cand < a.N ? a.c + (size_t)cand * d : nullptr, kc * BK + c4 * 4, d, vc);
+            if constexpr (SUB) pre[i] = load_k4(cid[i] >= 0 ? a.c + (size_t)cid[i] * d : nullptr, kc * BK + c4 * 4, d, vc);
+            else pre[i] = load_k4(cand < a.N ? a.c + (size_t)cand * d : nullptr, kc * BK + c4 * 4, d, vc);
         }
     };
     auto stash = [&](int buf) {
@@ -378,6 +409,10 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const RankArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[x][y][r] = 0.f;
 
+    if constexpr (SUB) {
+        load_ids(tile0, cid);
+        load_ids(tile0 + 1, nid);
+    }
     fetch(tile0, 0);
     stash(0);
     __syncthreads();
@@ -389,6 +424,13 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const RankArgs a) {
         int nkc = kc + 1;
         if (nkc == nch) { nkc = 0; ++ntile; }
         const bool more = step + 1 < total;
+        if constexpr (SUB) {
+            if (more && nkc == 0) {                     // the next fetch opens a tile: its ids are here, request the one after
+#pragma unroll
+                for (int i = 0; i < NL; ++i) cid[i] = nid[i];
+                load_ids(ntile + 1, nid);
+            }
+        }
         if (more) fetch(ntile, nkc);
 
         const int k0 = kc * BK;
@@ -609,11 +651,25 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const RankArgs a) {
 }
 
 // ---- the host side every operation shares ---------------------------------------------------------------------------------
-// the sweep with epilogue MODE over a.qtiles x a.slabs workgroups: the one place that picks the instantiation
+// the sweep with epilogue MODE over a.qtiles x a.slabs workgroups: the one place that picks the instantiation.  With `ic`
+// (node ids of the a.N candidates, rows of a table of Nn rows) the sweep over that subset.
 template <int MODE>
-static int launch_rank_tiles(const RankArgs& a, hipStream_t stream) {
+static int launch_rank_tiles(const RankArgs& a, hipStream_t stream, const int64_t* ic = nullptr, int64_t Nn = 0) {
     const unsigned grid = (unsigned)(a.qtiles * a.slabs);
-    if (rank_ctile(a.d) == 256) {
+    if (ic) {                                           // the same two shapes, rows through ic
+        RankSubArgs s;
+        static_cast<RankArgs&>(s) = a;
+        s.ic = ic; s.Nn = Nn;
+        if (rank_ctile(a.d) == 256) {
+            const size_t lds = rank_lds_bytes(a.d, 32, 256);
+            GHF_SET_MAX_LDS((rank_tile_kernel<32, 256, MODE, true>), lds);
+            rank_tile_kernel<32, 256, MODE, true><<<grid, 512, lds, stream>>>(s);
+        } else {
+            const size_t lds = rank_lds_bytes(a.d, 16, 128);
+            GHF_SET_MAX_LDS((rank_tile_kernel<16, 128, MODE, true>), lds);
+            rank_tile_kernel<16, 128, MODE, true><<<grid, 256, lds, stream>>>(s);
+        }
+    } else if (rank_ctile(a.d) == 256) {
         const size_t lds = rank_lds_bytes(a.d, 32, 256);
         GHF_SET_MAX_LDS((rank_tile_kernel<32, 256, MODE>), lds);
         rank_tile_kernel<32, 256, MODE><<<grid, 512, lds, stream>>>(a);
@@ -644,5 +700,22 @@ static inline int score_open(const char* op, bool (*geom)(int64_t, int64_t, int,
     a->filt_ptr = nnz > 0 ? filt_ptr : nullptr; a->filt_idx = filt_idx; a->nnz = nnz;
     return GHF_OK;
 }
+
+// ---- candidate subsets (candidates.hip) -----------------------------------------------------------------------------------
+// What a sweep over the subset ic [C] reads in place of the caller's node ids: every query's target as a position in ic
+// (-1: not a candidate), its list cut down to the candidates and renumbered the same way (a new CSR pair, each list still
+// ascending; NULL where the call has no lists), and for a backward the forward's lse with NaN for a query that takes no part.
+struct CandMap { const int64_t* tpos; const int64_t* ptr; const int64_t* idx; const float* lse; };
+
+size_t cand_workspace_bytes(int64_t B, int64_t nnz);
+// The pass ahead of every sweep over a subset, in place of score_prep_kernel / list_range_kernel: checks ic (strictly
+// ascending, inside [0, N)), writes valid [B] (the query's row id in range, its target a node — with `target_in` a
+// candidate —, no listed id outside [0, N), ic good), t [B] where given (the target's score from its own row of c, NaN for a
+// query that is not valid), resets the rank counters where given, and fills *m from `ws` (ws_bytes = cand_workspace_bytes,
+// 0 where the sizes are out of range).
+int launch_cand_map(const float* q, const float* c, const int64_t* iq, const int64_t* target, bool target_in,
+                    const int64_t* list_ptr, const int64_t* list_idx, int64_t nnz, const int64_t* ic, int64_t C, int64_t rows_q,
+                    int64_t N, int64_t B, int d, const float* lse, float* t, int* valid, int64_t* greater, int64_t* equal, void* ws,
+                    size_t ws_bytes, CandMap* m, hipStream_t stream);
 
 }  // namespace ghf

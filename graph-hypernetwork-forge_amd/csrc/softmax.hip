@@ -73,6 +73,17 @@ size_t score_softmax_bwd_workspace_bytes(int64_t B, int64_t N, int d) {
     return rk_align((size_t)g.slabs * (size_t)B * (size_t)d * 4);      // dq partials [slabs, B, d]
 }
 
+// a candidate subset (candidates.hip): the all-node workspace for N := C, then the id map's
+size_t score_softmax_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz) {
+    const size_t base = score_softmax_workspace_bytes(B, C, d), map = cand_workspace_bytes(B, nnz);
+    return base && map ? base + map : 0;
+}
+
+size_t score_softmax_bwd_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz) {
+    const size_t base = score_softmax_bwd_workspace_bytes(B, C, d), map = cand_workspace_bytes(B, nnz);
+    return base && map ? base + map : 0;
+}
+
 // ---- forward: the sweep between score_prep_kernel / list_range_kernel (rank_sweep.h) and the merge over the slabs ---------
 __global__ __launch_bounds__(256) void softmax_finish_kernel(const f32x2* __restrict__ ms, const float* __restrict__ t,
                                                              const int* __restrict__ valid, int64_t B, int64_t slabs, float scale,
@@ -88,22 +99,35 @@ __global__ __launch_bounds__(256) void softmax_finish_kernel(const f32x2* __rest
 
 int launch_score_softmax_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
-                             void* ws, size_t ws_bytes, float* loss, float* lse, hipStream_t stream) {
+                             void* ws, size_t ws_bytes, float* loss, float* lse, hipStream_t stream, const int64_t* ic,
+                             int64_t C) {
     RankArgs a;
-    int rc = score_open("score_softmax_fwd", softmax_geom, score_softmax_workspace_bytes(B, N, d), q, c, iq, filt_ptr, filt_idx, nnz,
-                        rows_q, N, B, d, ws_bytes, &a);
+    const int64_t M = ic ? C : N;                    // the candidates the sweep runs over
+    GHF_REQUIRE(!ic || (C > 0 && C <= N), "score_softmax_fwd: need 1 <= C <= N candidates");
+    const size_t base = score_softmax_workspace_bytes(B, M, d);
+    const size_t need = ic ? score_softmax_sub_workspace_bytes(B, C, d, nnz) : base;
+    int rc = score_open("score_softmax_fwd", softmax_geom, need, q, c, iq, filt_ptr, filt_idx, nnz, rows_q, M, B, d, ws_bytes, &a);
     if (rc != GHF_OK) return rc;
     float* t = (float*)ws;
     int* valid = (int*)((char*)ws + rk_align((size_t)B * 4));
     const unsigned qb = (unsigned)cdiv(B, 256);
-    score_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, target, rows_q, N, B, d, t, valid, nullptr, nullptr);
-    GHF_LAUNCH_CHECK();
-    if (nnz > 0) {
-        list_range_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(filt_ptr, filt_idx, nnz, N, B, valid);
+    if (ic) {                                        // a target that is no candidate: the query is not valid
+        CandMap m;
+        rc = launch_cand_map(q, c, iq, target, true, filt_ptr, filt_idx, nnz, ic, C, rows_q, N, B, d, nullptr, t, valid, nullptr,
+                             nullptr, (char*)ws + base, need > base ? need - base : 0, &m, stream);
+        if (rc != GHF_OK) return rc;
+        a.filt_ptr = m.ptr; a.filt_idx = m.idx;
+        target = m.tpos;
+    } else {
+        score_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, target, rows_q, N, B, d, t, valid, nullptr, nullptr);
         GHF_LAUNCH_CHECK();
+        if (nnz > 0) {
+            list_range_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(filt_ptr, filt_idx, nnz, N, B, valid);
+            GHF_LAUNCH_CHECK();
+        }
     }
     a.target = target; a.scale = scale; a.ws_ms = (f32x2*)((char*)ws + 2 * rk_align((size_t)B * 4));
-    rc = launch_rank_tiles<RK_SOFTMAX>(a, stream);
+    rc = launch_rank_tiles<RK_SOFTMAX>(a, stream, ic, N);
     if (rc != GHF_OK) return rc;
     softmax_finish_kernel<<<qb, 256, 0, stream>>>(a.ws_ms, t, valid, B, a.slabs, scale, loss, lse);
     GHF_LAUNCH_CHECK();
@@ -123,6 +147,10 @@ struct SmBwdArgs {
     float* dc;                               // dc: [N, d]
     float pos_w, neg_w;                      // bce: 1 - smoothing, smoothing / N
 };
+// SUB: candidate j is row ic[j] of c, which has Nn rows (rank_sweep.h: sub_row, RankSubArgs)
+struct SmBwdSubArgs : SmBwdArgs { const int64_t* ic; int64_t Nn; };
+template <bool SUB> struct SmBwdKernelArgs { typedef SmBwdArgs type; };
+template <> struct SmBwdKernelArgs<true> { typedef SmBwdSubArgs type; };
 
 static inline size_t sb_lds_bytes(int d, int OT) {
     const int dpad = (d + 31) & ~31;
@@ -138,8 +166,8 @@ struct SmQuery {
 // the loss whose G the backward forms
 constexpr int SB_SOFTMAX = 0, SB_BCE = 1;
 
-template <int OT, int DMAX, bool DC, int LOSS>
-__global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
+template <int OT, int DMAX, bool DC, int LOSS, bool SUB = false>
+__global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwdKernelArgs<SUB>::type a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr bool BCE = LOSS == SB_BCE;
     constexpr int ST = SB_ST, NT = SB_NT, LDG = OT + 1;
@@ -177,7 +205,10 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
         const int64_t r = a.iq ? a.iq[qi] : qi;
         return r >= 0 && r < a.rows_q ? a.q + (size_t)r * d : nullptr;
     };
-    auto crow = [&](int64_t j) -> const float* { return j < a.N ? a.c + (size_t)j * d : nullptr; };
+    auto crow = [&](int64_t j) -> const float* {
+        if constexpr (SUB) return sub_row(a.c, a.ic, j, a.N, a.Nn, d);
+        else return j < a.N ? a.c + (size_t)j * d : nullptr;
+    };
     auto query = [&](int64_t qi) {
         SmQuery m = {__int_as_float(0x7FC00000), 0.f, -1, 0, 0};
         if (qi < a.B) {
@@ -394,14 +425,14 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const SmBwdArgs a) {
     }
 }
 
-template <int OT, int DMAX, int LOSS>
-static int launch_bwd_tiles(const SmBwdArgs& a, hipStream_t stream) {
+template <int OT, int DMAX, int LOSS, bool SUB = false>
+static int launch_bwd_tiles(const typename SmBwdKernelArgs<SUB>::type& a, hipStream_t stream) {
     const size_t lds = sb_lds_bytes(a.d, OT);
-    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, false, LOSS>), lds);
-    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, true, LOSS>), lds);
-    softmax_bwd_kernel<OT, DMAX, false, LOSS><<<(unsigned)(a.qtiles * a.slabs), SB_NT, lds, stream>>>(a);
+    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, false, LOSS, SUB>), lds);
+    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, true, LOSS, SUB>), lds);
+    softmax_bwd_kernel<OT, DMAX, false, LOSS, SUB><<<(unsigned)(a.qtiles * a.slabs), SB_NT, lds, stream>>>(a);
     GHF_LAUNCH_CHECK();
-    softmax_bwd_kernel<OT, DMAX, true, LOSS><<<(unsigned)cdiv(a.N, OT), SB_NT, lds, stream>>>(a);
+    softmax_bwd_kernel<OT, DMAX, true, LOSS, SUB><<<(unsigned)cdiv(a.N, OT), SB_NT, lds, stream>>>(a);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }
@@ -412,19 +443,32 @@ template <int LOSS>
 static int launch_score_loss_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* list_ptr,
                                  const int64_t* list_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                                  float smoothing, const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq,
-                                 float* dc, hipStream_t stream) {
+                                 float* dc, hipStream_t stream, const int64_t* ic, int64_t C) {
     RankArgs r;
-    int rc = score_open(LOSS == SB_BCE ? "score_bce_bwd" : "score_softmax_bwd", softmax_bwd_geom,
-                        score_softmax_bwd_workspace_bytes(B, N, d), q, c, iq, list_ptr, list_idx, nnz, rows_q, N, B, d, ws_bytes, &r);
+    const char* op = LOSS == SB_BCE ? "score_bce_bwd" : "score_softmax_bwd";
+    const int64_t M = ic ? C : N;                    // the candidates the sweeps run over: dc is [M, d]
+    GHF_REQUIRE(!ic || (C > 0 && C <= N), "%s: need 1 <= C <= N candidates", op);
+    const size_t base = score_softmax_bwd_workspace_bytes(B, M, d);
+    const size_t need = ic ? score_softmax_bwd_sub_workspace_bytes(B, C, d, nnz) : base;
+    int rc = score_open(op, softmax_bwd_geom, need, q, c, iq, list_ptr, list_idx, nnz, rows_q, M, B, d, ws_bytes, &r);
     if (rc != GHF_OK) return rc;
-    SmBwdArgs a = {};
+    SmBwdSubArgs a = {};
+    if (ic) {      // targets and lists as positions in ic; a query that a bad ic or a target outside it rules out has lse NaN
+        CandMap m;
+        rc = launch_cand_map(q, c, iq, target, LOSS != SB_BCE, list_ptr, list_idx, nnz, ic, C, rows_q, N, B, d, lse, nullptr, nullptr,
+                             nullptr, nullptr, (char*)ws + base, need > base ? need - base : 0, &m, stream);
+        if (rc != GHF_OK) return rc;
+        a.ic = ic; a.Nn = N;
+        target = LOSS == SB_BCE ? nullptr : m.tpos; lse = m.lse; r.filt_ptr = m.ptr; list_idx = m.idx;
+    }
     a.q = q; a.c = c; a.iq = iq; a.target = target;
     a.filt_ptr = r.filt_ptr; a.filt_idx = list_idx; a.nnz = nnz;
-    a.rows_q = rows_q; a.N = N; a.B = B; a.d = d; a.scale = scale; a.lse = lse; a.grad = grad_loss;
-    if (LOSS == SB_BCE) { a.pos_w = 1.f - smoothing; a.neg_w = smoothing / (float)N; }
+    a.rows_q = rows_q; a.N = M; a.B = B; a.d = d; a.scale = scale; a.lse = lse; a.grad = grad_loss;
+    if (LOSS == SB_BCE) { a.pos_w = 1.f - smoothing; a.neg_w = smoothing / (float)M; }
     a.qtiles = r.qtiles; a.slab_tiles = r.slab_tiles; a.slabs = r.slabs;
     a.dq_part = (float*)ws; a.dc = dc;
-    rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128, LOSS>(a, stream) : launch_bwd_tiles<64, 256, LOSS>(a, stream);
+    if (ic) rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128, LOSS, true>(a, stream) : launch_bwd_tiles<64, 256, LOSS, true>(a, stream);
+    else rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128, LOSS>(a, stream) : launch_bwd_tiles<64, 256, LOSS>(a, stream);
     if (rc != GHF_OK) return rc;
     return launch_ordered_sum(a.dq_part, a.slabs, B * (int64_t)d, dq, stream);
 }
@@ -432,19 +476,23 @@ static int launch_score_loss_bwd(const float* q, const float* c, const int64_t* 
 int launch_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                              const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc,
-                             hipStream_t stream) {
+                             hipStream_t stream, const int64_t* ic, int64_t C) {
     return launch_score_loss_bwd<SB_SOFTMAX>(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, 0.f, lse, grad_loss, ws,
-                                             ws_bytes, dq, dc, stream);
+                                             ws_bytes, dq, dc, stream, ic, C);
 }
 
 // the multi-label BCE loss's backward (bce.hip holds its forward): the same two sweeps and workspace, G formed for that loss
 size_t score_bce_bwd_workspace_bytes(int64_t B, int64_t N, int d) { return score_softmax_bwd_workspace_bytes(B, N, d); }
+size_t score_bce_bwd_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz) {
+    return score_softmax_bwd_sub_workspace_bytes(B, C, d, nnz);
+}
 
 int launch_score_bce_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
-                         const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc, hipStream_t stream) {
+                         const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc, hipStream_t stream,
+                         const int64_t* ic, int64_t C) {
     return launch_score_loss_bwd<SB_BCE>(q, c, iq, nullptr, pos_ptr, pos_idx, nnz, rows_q, N, B, d, scale, smoothing, loss, grad_loss,
-                                         ws, ws_bytes, dq, dc, stream);
+                                         ws, ws_bytes, dq, dc, stream, ic, C);
 }
 
 }  // namespace ghf

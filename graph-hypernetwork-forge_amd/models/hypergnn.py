@@ -713,6 +713,39 @@ class HyperGNN(nn.Module):
         return torch.where(ids < 0, ids + rows, ids)
 
     @staticmethod
+    def _candidate_ids(candidates, embs: torch.Tensor) -> torch.Tensor:
+        """``candidates=`` of the four all-node operations in the form the kernels take: node ids, strictly ascending, int64 on
+        embs' device.  Given as a 1-D int32 / int64 tensor (any order, on any device; repeats collapse, negative ids wrap as
+        in indexing, an id out of range is an IndexError) or as a bool mask of length N.  An empty set is a ValueError."""
+        N = embs.size(0)
+        if not isinstance(candidates, torch.Tensor) or candidates.dim() != 1:
+            raise ValueError(f"candidates must be a 1-D tensor of node ids or a bool mask of length N = {N}, got "
+                             f"{getattr(candidates, 'shape', type(candidates))}")
+        if candidates.dtype == torch.bool:
+            if candidates.numel() != N:
+                raise ValueError(f"a candidates mask must have length N = {N}, got {candidates.numel()}")
+            ids = torch.nonzero(candidates.to(embs.device)).flatten()
+        elif candidates.dtype in (torch.int32, torch.int64):
+            if candidates.numel():
+                lo, hi = (int(v) for v in torch.aminmax(candidates))
+                if lo < -N or hi >= N:
+                    raise IndexError(f"candidates holds ids outside [-{N}, {N}) (range {lo}..{hi})")
+            ids = candidates.to(device=embs.device, dtype=torch.int64)
+            ids = torch.unique(torch.where(ids < 0, ids + N, ids))          # sorted ascending, repeats gone
+        else:
+            raise TypeError(f"candidates must be int32, int64 or bool, got {candidates.dtype}")
+        if ids.numel() == 0:
+            raise ValueError("candidates is empty")
+        return ids.contiguous()
+
+    @staticmethod
+    def _softmax_candidates(cand: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        """The candidate set of ``softmax_loss(candidates=)``: the given ids (``_candidate_ids``' form) and every target of the
+        batch, ascending.  A query's own target has to be in its sum; the other queries' targets come in with it, as in-batch
+        negatives."""
+        return torch.unique(torch.cat([cand, target]))
+
+    @staticmethod
     def _rel_ids(ids: torch.Tensor, n: int, embs: torch.Tensor, name: str) -> torch.Tensor:
         """1-D relation ids, one per entry: int64 on embs' device.  The id space is the caller's (``plan.rel_ids``, the ids
         passed to ``forward_ids``); relation ids do not wrap: a negative one is a ValueError."""
@@ -809,7 +842,8 @@ class HyperGNN(nn.Module):
 
     def rank_candidates(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, known=None,
                         filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
-                        query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None):
+                        query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
+                        candidates: Optional[torch.Tensor] = None):
         """Where ``target[i]`` ranks among ALL nodes as a partner of ``query[i]`` under the dot-product score
         (``score_triple``): ``(greater, equal)``, int64 ``[B]`` — the nodes scoring above / exactly as the target, the target
         itself and the query's known partners (the "filtered" setting) left out.  ``known=(src, dst)`` names true edges
@@ -823,11 +857,18 @@ class HyperGNN(nn.Module):
         is used only to build the filter lists.  ``known=(src, dst, rel)`` with ``query_rel`` (``[B]`` relation ids, in the
         caller's id space, e.g. ``plan.rel_ids``) lists for query ``i`` every ``dst`` of a known edge with ``src == query[i]``
         and ``rel == query_rel[i]``.  For ``(?, relation, tail)`` queries (``direction="head"``) pass ``known=(dst, src, rel)``.
-        With both ``None`` the call is the untyped one."""
-        if not embs.is_cuda:
-            raise RuntimeError(f"rank_candidates computes on an MI355X HIP device only (input is on {embs.device})")
+        With both ``None`` the call is the untyped one.
+
+        ``candidates`` (node ids in any order, or a bool mask of length N) restricts the count to those nodes: the rank of
+        the true partner among sampled negatives, or among the nodes of one type (``ghf_score_rank_sub``).  The result is
+        that of the call on the table ``embs[sorted(candidates)]``, except that ``target`` and the lists stay node ids of
+        ``embs``: the target may be any node, a candidate or not (its score comes from its own row), and listed nodes that
+        are no candidates take no part.  The candidate rows are read in place; no ``[C, d]`` copy is made."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        cand = None if candidates is None else self._candidate_ids(candidates, embs)
+        if not embs.is_cuda:
+            raise RuntimeError(f"rank_candidates computes on an MI355X HIP device only (input is on {embs.device})")
         self._query_rows(embs, query, query_rows, "rank_candidates")
         e = embs.detach().float()
         q = self._rank_ids(query, e.size(0), e, "query")
@@ -836,21 +877,25 @@ class HyperGNN(nn.Module):
             raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
         ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx, query_rel)
         if query_rows is not None:
-            return _native.score_rank(query_rows.detach(), e, t, filt_ptr=ptr, filt_idx=idx)
-        return _native.score_rank(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx)
+            return _native.score_rank(query_rows.detach(), e, t, filt_ptr=ptr, filt_idx=idx, ic=cand)
+        return _native.score_rank(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, ic=cand)
 
     def topk_candidates(self, embs: torch.Tensor, query: torch.Tensor, k: int, *, known=None,
                         filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
-                        query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None):
+                        query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
+                        candidates: Optional[torch.Tensor] = None):
         """The ``k`` (1..128) best partners of every ``query[i]`` among ALL nodes outside its filter list (``known`` /
         ``filt_ptr, filt_idx`` as in ``rank_candidates``): ``(scores [B, k]`` fp32 descending, ``ids [B, k]`` int64``)``, ties
         towards the lower id, ``(-inf, -1)`` where fewer than k candidates remain.  The query node itself is a candidate
         unless listed.  No autograd graph.  ``query_rows`` / ``known=(src, dst, rel)`` with ``query_rel``: relation-typed
-        queries, as in ``rank_candidates``."""
-        if not embs.is_cuda:
-            raise RuntimeError(f"topk_candidates computes on an MI355X HIP device only (input is on {embs.device})")
+        queries, as in ``rank_candidates``.  ``candidates`` (ids or a bool mask, as in ``rank_candidates``): the k best among
+        those nodes only, e.g. the cities for ``(person, born in, ?)``; the ids returned are node ids of ``embs``, ties still go
+        to the lower node id, and ``(-inf, -1)`` fills up where fewer than k candidates remain outside the list."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        cand = None if candidates is None else self._candidate_ids(candidates, embs)
+        if not embs.is_cuda:
+            raise RuntimeError(f"topk_candidates computes on an MI355X HIP device only (input is on {embs.device})")
         self._query_rows(embs, query, query_rows, "topk_candidates")
         if not 1 <= int(k) <= 128:
             raise ValueError(f"k = {k} outside 1..128")
@@ -858,12 +903,13 @@ class HyperGNN(nn.Module):
         q = self._rank_ids(query, e.size(0), e, "query")
         ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx, query_rel)
         if query_rows is not None:
-            return _native.score_topk(query_rows.detach(), e, int(k), filt_ptr=ptr, filt_idx=idx)
-        return _native.score_topk(e, e, int(k), iq=q, filt_ptr=ptr, filt_idx=idx)
+            return _native.score_topk(query_rows.detach(), e, int(k), filt_ptr=ptr, filt_idx=idx, ic=cand)
+        return _native.score_topk(e, e, int(k), iq=q, filt_ptr=ptr, filt_idx=idx, ic=cand)
 
     def softmax_loss(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, scale: float = 1.0, known=None,
                      filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
-                     query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
+                     candidates: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The 1-vs-all softmax cross-entropy that ``rank_candidates``' filtered metrics measure, fp32 ``[B]``:
         ``loss[i] = logsumexp_j(scale * embs[query[i]] . embs[j]) - scale * embs[query[i]] . embs[target[i]]`` over ALL nodes
         ``j`` except ``query[i]``'s known partners (``known`` / ``filt_ptr, filt_idx`` as in ``rank_candidates``; the target
@@ -873,9 +919,19 @@ class HyperGNN(nn.Module):
         ``autograd.SoftmaxLossFn``).  Bit-reproducible.  Recorded for autograd when grad mode is on and ``embs`` requires grad.
         ``query_rows`` / ``known=(src, dst, rel)`` with ``query_rel``: relation-typed queries, as in ``rank_candidates``; the
         loss is then recorded when ``embs`` or ``query_rows`` requires grad (``autograd.SoftmaxLossFn`` with the rows: the per-query
-        gradient is ``query_rows``' own, the per-candidate one ``embs``')."""
+        gradient is ``query_rows``' own, the per-candidate one ``embs``').
+
+        ``candidates`` (ids in any order or a bool mask, as in ``rank_candidates``) turns the loss into the 1-vs-C one of
+        sampled-negative training: the sum runs over the candidates instead of all nodes, at ``C / N`` of the cost
+        (``ghf_score_softmax_fwd_sub`` / ``_bwd_sub``).  The batch's targets are ADDED to the set before the call, so every
+        query's own target is in its sum — and every other query's target is an in-batch negative for it, unless that query's
+        ``known`` lists it.  Everything else is the sub-table rule: ``target`` and the lists stay node ids, listed nodes
+        outside the set take no part, the candidate rows are read in place (no ``[C, d]`` copy, forward or backward), and
+        the gradient lands in ``embs``' own rows: rows that are neither candidates, targets nor queries get exactly zero.
+        Still bit-reproducible."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        cand = None if candidates is None else self._candidate_ids(candidates, embs)
         self._query_rows(embs, query, query_rows, "softmax_loss")
         scale = float(scale)
         if not (0.0 < scale < float("inf")):
@@ -887,21 +943,24 @@ class HyperGNN(nn.Module):
         if not embs.is_cuda:
             raise RuntimeError(f"softmax_loss computes on an MI355X HIP device only (input is on {embs.device})")
         ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
+        if cand is not None:
+            cand = self._softmax_candidates(cand, t)
         if query_rows is not None:
             if torch.is_grad_enabled() and (embs.requires_grad or query_rows.requires_grad):
                 from ..autograd import SoftmaxLossFn
-                return SoftmaxLossFn.apply(embs, query_rows, None, t, ptr, idx, scale)
+                return SoftmaxLossFn.apply(embs, query_rows, None, t, ptr, idx, scale, cand)
             return _native.score_softmax_fwd(query_rows.detach(), embs.detach().float(), t, filt_ptr=ptr, filt_idx=idx,
-                                             scale=scale)[0]
+                                             scale=scale, ic=cand)[0]
         if torch.is_grad_enabled() and embs.requires_grad:
             from ..autograd import SoftmaxLossFn
-            return SoftmaxLossFn.apply(embs, None, q, t, ptr, idx, scale)
+            return SoftmaxLossFn.apply(embs, None, q, t, ptr, idx, scale, cand)
         e = embs.detach().float()
-        return _native.score_softmax_fwd(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, scale=scale)[0]
+        return _native.score_softmax_fwd(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, scale=scale, ic=cand)[0]
 
     def bce_loss(self, embs: torch.Tensor, query: torch.Tensor, *, known=None, pos_ptr: Optional[torch.Tensor] = None,
                  pos_idx: Optional[torch.Tensor] = None, scale: float = 1.0, smoothing: float = 0.0, normalize: bool = True,
-                 query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
+                 candidates: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The multi-label 1-vs-all loss of ConvE / TuckER / CompGCN, fp32 ``[B]``: every ``query[i]`` is scored against ALL
         nodes, all of its known partners are positives at once, and the loss is binary cross-entropy with label smoothing,
         ``F.binary_cross_entropy_with_logits(scale * embs[query] @ embs.T, y, reduction="none").mean(1)`` with
@@ -912,9 +971,17 @@ class HyperGNN(nn.Module):
         set, not a mask; a repeated id counts once.  ``normalize=False`` returns the sum over the candidates instead of their
         mean.  ``0 <= smoothing < 1``.  Bit-reproducible.  Recorded for autograd when grad mode is on and ``embs`` requires grad.
         ``query_rows``: relation-typed queries, as in ``softmax_loss``; the loss is then recorded when ``embs`` or ``query_rows``
-        requires grad (``autograd.BceLossFn`` with the rows)."""
+        requires grad (``autograd.BceLossFn`` with the rows).
+
+        ``candidates`` (ids in any order or a bool mask, as in ``rank_candidates``): the loss over those ``C`` nodes alone
+        (``ghf_score_bce_fwd_sub`` / ``_bwd_sub``): the positives are the partners that are candidates, the labels
+        ``(1 - smoothing) * [partner] + smoothing / C``, and ``normalize=True`` divides by ``C``.  A partner outside the set
+        takes no part, as a label or as a logit — so when sampling negatives, INCLUDE the batch's positives in ``candidates``
+        (nothing is added here: unlike ``softmax_loss`` there is no single target to add).  The candidate rows are read in
+        place; rows of ``embs`` that are neither candidates nor queries get exactly zero gradient."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        cand = None if candidates is None else self._candidate_ids(candidates, embs)
         self._query_rows(embs, query, query_rows, "bce_loss")
         scale, smoothing = float(scale), float(smoothing)
         if not (0.0 < scale < float("inf")):
@@ -929,17 +996,17 @@ class HyperGNN(nn.Module):
         if query_rows is not None:
             if torch.is_grad_enabled() and (embs.requires_grad or query_rows.requires_grad):
                 from ..autograd import BceLossFn
-                loss = BceLossFn.apply(embs, query_rows, None, ptr, idx, scale, smoothing)
+                loss = BceLossFn.apply(embs, query_rows, None, ptr, idx, scale, smoothing, cand)
             else:
                 loss = _native.score_bce_fwd(query_rows.detach(), embs.detach().float(), pos_ptr=ptr, pos_idx=idx, scale=scale,
-                                             smoothing=smoothing)
+                                             smoothing=smoothing, ic=cand)
         elif torch.is_grad_enabled() and embs.requires_grad:
             from ..autograd import BceLossFn
-            loss = BceLossFn.apply(embs, None, q, ptr, idx, scale, smoothing)
+            loss = BceLossFn.apply(embs, None, q, ptr, idx, scale, smoothing, cand)
         else:
             e = embs.detach().float()
-            loss = _native.score_bce_fwd(e, e, iq=q, pos_ptr=ptr, pos_idx=idx, scale=scale, smoothing=smoothing)
-        return loss * (1.0 / embs.size(0)) if normalize else loss
+            loss = _native.score_bce_fwd(e, e, iq=q, pos_ptr=ptr, pos_idx=idx, scale=scale, smoothing=smoothing, ic=cand)
+        return loss * (1.0 / (embs.size(0) if cand is None else cand.numel())) if normalize else loss
 
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self.parameters() if p.requires_grad)

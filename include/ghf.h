@@ -592,6 +592,55 @@ int ghf_score_bce_bwd(const float* q, const float* c, const int64_t* iq, const i
                       int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
                       const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* dc, void* stream);
 
+/* ---- the same four operations against a candidate subset (csrc/candidates.hip) --------------------------
+ * Sampled or in-batch negatives for the two losses, type-constrained ranking for the two evaluations.  Every call above has
+ * a _sub form that takes, beside the same arguments, the candidates as node ids:
+ *   ic int64 [C], STRICTLY ascending, every id in [0, N);  1 <= C <= N (GHF_EINVAL otherwise).
+ * With P the set of ids in ic, the result is that of the call above on the table c[ic] — except that every id that goes in
+ * (target, the lists) or comes out (top-k ids) stays a row id of c, and list entries outside P take no part:
+ *   ghf_score_rank_sub         counts j in P outside query i's list and other than target[i].  The target may be ANY row of
+ *                              c, a candidate or not: t_i comes from its own row.
+ *   ghf_score_topk_sub         the k best of P outside the list, ties towards the lower id, (-inf, -1) where fewer remain.
+ *   ghf_score_softmax_fwd_sub  J_i = (P minus query i's list) plus target[i], and the target must be in P: a query whose
+ *                              target is not (or is out of range) has loss = lse = NaN and takes no part in the backward.
+ *   ghf_score_bce_fwd_sub      the loss over P alone: positives are the listed ids inside P, y_ij = (1 - smoothing) [listed]
+ *                              + smoothing / C, sums over j in P; a mean over the candidates is the caller's division by C.
+ *   the two backwards          dq [B, d] as above; dc is [C, d], row j the gradient of row ic[j] of c, every row written.
+ * No [C, d] copy of the candidate rows is made: the sweeps read candidate j at c + ic[j] d.  Geometry (slabs, partial sums)
+ * is that of the calls above for N := C, so the bits of a subset call equal those of the call above on a contiguous copy
+ * c[ic] with renumbered ids, a query's bits do not depend on its batch, and everything stays bit-reproducible (no
+ * floating-point atomics).  A list id outside [0, N) makes its query invalid, as above.  An ic that is not strictly
+ * ascending or leaves [0, N) makes EVERY query invalid (counts and ids -1, scores / losses NaN, dq and dc zero); no row
+ * outside c is read or written whatever ic holds.  workspace: the matching _sub_workspace_bytes query, which also takes nnz
+ * (the renumbered lists live there); 0 = bad sizes; 256-byte aligned.  Nothing allocates or synchronises. */
+size_t ghf_score_rank_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
+int ghf_score_rank_sub(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                       const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, const int64_t* ic,
+                       int64_t C, void* workspace, size_t workspace_bytes, int64_t* greater, int64_t* equal, void* stream);
+size_t ghf_score_topk_sub_workspace_bytes(int64_t B, int64_t C, int d, int k, int64_t nnz);
+int ghf_score_topk_sub(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
+                       int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, const int64_t* ic, int64_t C,
+                       void* workspace, size_t workspace_bytes, float* scores, int64_t* ids, void* stream);
+size_t ghf_score_softmax_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
+int ghf_score_softmax_fwd_sub(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                              const int64_t* ic, int64_t C, void* workspace, size_t workspace_bytes, float* loss, float* lse,
+                              void* stream);
+size_t ghf_score_softmax_bwd_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
+int ghf_score_softmax_bwd_sub(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                              const float* lse, const float* grad_loss, const int64_t* ic, int64_t C, void* workspace,
+                              size_t workspace_bytes, float* dq, float* dc, void* stream);
+size_t ghf_score_bce_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
+int ghf_score_bce_fwd_sub(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
+                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const int64_t* ic,
+                          int64_t C, void* workspace, size_t workspace_bytes, float* loss, void* stream);
+size_t ghf_score_bce_bwd_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
+int ghf_score_bce_bwd_sub(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
+                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
+                          const float* grad_loss, const int64_t* ic, int64_t C, void* workspace, size_t workspace_bytes, float* dq,
+                          float* dc, void* stream);
+
 /* ---- relation-typed query rows (csrc/relation.hip) ----------------------------------------------------
  * No counterpart in the reference, whose score_triple (models/hypergnn.py:304-318) ignores the relation.  The query side of
  * a (head, relation, ?) score: every query row multiplied by ITS relation's matrix, without gathering a matrix per query
@@ -673,6 +722,10 @@ int ghf_rows_unpack(const void* packed, const int64_t* idx, int64_t n, int64_t n
  * itself.  idx entries distinct within one call (no atomics; callers add the peers' messages one call after another, in
  * rank order); entries outside [0, nrows) skipped.  d a multiple of 4, 16-byte aligned buffers.  One fp32 add per element. */
 int ghf_rows_accumulate(const float* packed, const int64_t* idx, int64_t n, int64_t nrows, float* rows, int d, void* stream);
+/* The same sum for rows of ANY width d > 0 and buffers aligned to 4 bytes: where d is a multiple of 4 and both buffers are
+ * 16-byte aligned it is the call above, bit for bit; otherwise one float per lane.  The losses' candidate subsets put their
+ * [C, d] gradient back into the table's rows with it: they take every d <= 256, not only whole float4s. */
+int ghf_rows_accumulate_any(const float* packed, const int64_t* idx, int64_t n, int64_t nrows, float* rows, int d, void* stream);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,7 @@
 them — embs[q] @ embs.T in query chunks sized to 1 GB of scores, then compare-and-count (resp. torch.topk) — at the sizes of
 BASELINE configs 3 and 2.  Prints one JSON line.
 
-    python tools/rank_time.py [--configs c3,c2] [--batches 1024,16384] [--reps 5] [--no-torch]
+    python tools/rank_time.py [--configs c3,c2] [--batches 1024,16384] [--reps 5] [--no-torch] [--candidates C[,C...]]
 
 Per config and B in (1,024, 16,384): medians of device-event windows (ms, warm) of the two calls without filter lists, of
 the two calls with a filter list per query built from `known` edges (10 per query), and of the torch formulation; the ratio
@@ -10,7 +10,12 @@ torch / ours; the achieved fraction of the fp32 matrix peak, 2 B N d / time / 15
 random rows of the config's [N, d] (what the model's last layer emits): the time does not depend on their values beyond the
 insertion rate of the top-k lists, which random rows set at its expected k ln(N / k).  --no-torch leaves the torch
 formulation out (a counter collection of the kernels alone: tools/pmc.sh <prefix> rank_tile_kernel -- python tools/rank_time.py
---configs c3 --batches 1024 --no-torch)."""
+--configs c3 --batches 1024 --no-torch).
+
+--candidates 16384,131072,N adds, per C, the two calls with lists against a sorted random subset of C nodes (candidates=;
+"N" = every node, through the subset entry points): their times, C / N x the all-node time of the same call beside them, and,
+so that the two can be told apart from noise, the all-node calls timed a second time after them (`*_again_ms`: the same code
+twice in one command)."""
 
 from __future__ import annotations
 
@@ -67,7 +72,17 @@ def torch_topk(embs, q, k):
     return torch.cat([p.values for p in parts]), torch.cat([p.indices for p in parts])
 
 
-def run_config(name, reps, batches, with_torch):
+def candidate_sets(spec, N, dev, seed):
+    """{label: sorted int64 ids on the device} for a --candidates list ("N" = all nodes)"""
+    sets = {}
+    for item in [s for s in spec.split(",") if s]:
+        C = N if item.upper() == "N" else int(item)
+        gen = torch.Generator(device=dev).manual_seed(seed + C)
+        sets[item.upper()] = torch.sort(torch.randperm(N, device=dev, generator=gen)[:C]).values if C < N else torch.arange(N, device=dev)
+    return sets
+
+
+def run_config(name, reps, batches, with_torch, candidates=""):
     cfg = CONFIGS[name]
     dev = torch.device("cuda:0")
     N, d = cfg["N"], cfg["d"]
@@ -98,6 +113,18 @@ def run_config(name, reps, batches, with_torch):
             r["topk_speedup"] = r["torch_topk_ms"] / r["topk_ms"]
         r["rank_fraction_of_fp32_matrix_peak"] = flops / (r["rank_ms"] * 1e-3) / (FP32_MATRIX_PEAK_TF * 1e12)
         r["topk_fraction_of_fp32_matrix_peak"] = flops / (r["topk_ms"] * 1e-3) / (FP32_MATRIX_PEAK_TF * 1e12)
+        for label, cand in candidate_sets(candidates, N, dev, cfg["seed"]).items():
+            C = cand.numel()
+            tc = cand[torch.from_numpy(rng.integers(0, C, B)).to(dev)]      # targets among the candidates
+            s = {"C": C}
+            s["rank_known_ms"], _ = timed(lambda: model.rank_candidates(embs, q, tc, known=known, candidates=cand), reps)
+            s["topk_known_ms"], _ = timed(lambda: model.topk_candidates(embs, q, 10, known=known, candidates=cand), reps)
+            s["rank_known_scaled_all_node_ms"] = r["rank_known_ms"] * C / N
+            s["topk_known_scaled_all_node_ms"] = r["topk_known_ms"] * C / N
+            r[f"candidates_{label}"] = s
+        if candidates:
+            r["rank_known_again_ms"], _ = timed(lambda: model.rank_candidates(embs, q, t, known=known), reps)
+            r["topk_known_again_ms"], _ = timed(lambda: model.topk_candidates(embs, q, 10, known=known), reps)
         res[f"B{B}"] = r
     return res
 
@@ -108,12 +135,13 @@ def main():
     ap.add_argument("--batches", default="1024,16384")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--candidates", default="", help="C[,C...] or N: also time the calls against a sorted random subset")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rank_time.py measures on an MI355X; no HIP device here")
     out = {"tool": "rank_time", "device": torch.cuda.get_device_name(0)}
     for name in args.configs.split(","):
-        out[name] = run_config(name, args.reps, [int(b) for b in args.batches.split(",")], not args.no_torch)
+        out[name] = run_config(name, args.reps, [int(b) for b in args.batches.split(",")], not args.no_torch, args.candidates)
     print(json.dumps(out))
 
 

@@ -3,7 +3,7 @@ has without it — embs[q] @ embs.T in query chunks sized to 1 GB of scores, mas
 chunk — at the sizes of BASELINE configs 3 and 2, with rank_candidates' time on the same box beside them.  Prints one JSON
 line.
 
-    python tools/softmax_time.py [--configs c3,c2] [--batches 1024,16384] [--reps 5] [--no-torch]
+    python tools/softmax_time.py [--configs c3,c2] [--batches 1024,16384] [--reps 5] [--no-torch] [--candidates C[,C...]]
 
 Per config and B in (1,024, 16,384): medians of device-event windows (ms, warm) of the forward (no autograd graph), of the
 forward plus backward down to d embs (both with a filter list per query built from `known` edges, 10 per query, and the
@@ -11,7 +11,13 @@ forward also without lists), and of the torch formulation; the peak memory each 
 (torch.cuda.max_memory_allocated); the achieved fraction of the fp32 matrix peak, counting one B x N x d product forward
 and four backward.  The torch formulation reports "does not fit" where it raises an out-of-memory error.  --no-torch leaves
 it out (a counter collection of the kernels alone: tools/pmc.sh <prefix> softmax_bwd_kernel -- python tools/softmax_time.py
---configs c3 --batches 1024 --no-torch)."""
+--configs c3 --batches 1024 --no-torch).
+
+--candidates 16384,131072,N adds, per C, softmax_loss forward and forward + backward and bce_loss forward + backward (all
+with lists) against a sorted random subset of C nodes (candidates=; "N" = every node, through the subset entry points; the
+targets are drawn from the subset, so softmax_loss adds none): their times with C / N x the all-node time of the same call
+beside them — bce_loss' all-node forward + backward is then timed as well — and, so that the two can be told apart from
+noise, the all-node calls timed a second time after them (`*_again_ms`: the same code twice in one command)."""
 
 from __future__ import annotations
 
@@ -76,7 +82,17 @@ def torch_loss(embs, q, t, ptr, idx, scale, backward):
     return torch.cat(out), e.grad
 
 
-def run_config(name, reps, batches, with_torch):
+def candidate_sets(spec, N, dev, seed):
+    """{label: sorted int64 ids on the device} for a --candidates list ("N" = all nodes)"""
+    sets = {}
+    for item in [s for s in spec.split(",") if s]:
+        C = N if item.upper() == "N" else int(item)
+        gen = torch.Generator(device=dev).manual_seed(seed + C)
+        sets[item.upper()] = torch.sort(torch.randperm(N, device=dev, generator=gen)[:C]).values if C < N else torch.arange(N, device=dev)
+    return sets
+
+
+def run_config(name, reps, batches, with_torch, candidates=""):
     cfg = CONFIGS[name]
     dev = torch.device("cuda:0")
     N, d = cfg["N"], cfg["d"]
@@ -110,6 +126,32 @@ def run_config(name, reps, batches, with_torch):
         r["fwd_fraction_of_fp32_matrix_peak"] = flops / (r["fwd_known_ms"] * 1e-3) / (FP32_MATRIX_PEAK_TF * 1e12)
         r["bwd_fraction_of_fp32_matrix_peak"] = (4 * flops / ((r["fwd_bwd_known_ms"] - r["fwd_known_ms"]) * 1e-3)
                                                  / (FP32_MATRIX_PEAK_TF * 1e12))
+        def loss_step(kind, tt, cand):
+            e = embs.detach().requires_grad_(True)
+            if kind == "softmax":
+                loss = model.softmax_loss(e, q, tt, scale=scale, filt_ptr=ptr, filt_idx=idx, candidates=cand)
+            else:
+                loss = model.bce_loss(e, q, pos_ptr=ptr, pos_idx=idx, scale=scale, smoothing=0.1, candidates=cand)
+            loss.mean().backward()
+            return loss.detach(), e.grad
+
+        if candidates:
+            r["bce_fwd_bwd_known_ms"], _, _ = timed(lambda: loss_step("bce", t, None), reps)
+        for label, cand in candidate_sets(candidates, N, dev, cfg["seed"]).items():
+            C = cand.numel()
+            tc = cand[torch.from_numpy(rng.integers(0, C, B)).to(dev)]      # targets among the candidates: none is added
+            s = {"C": C}
+            s["fwd_known_ms"], _, _ = timed(lambda: model.softmax_loss(embs, q, tc, scale=scale, filt_ptr=ptr, filt_idx=idx,
+                                                                       candidates=cand), reps)
+            s["fwd_bwd_known_ms"], s["fwd_bwd_peak_bytes"], _ = timed(lambda: loss_step("softmax", tc, cand), reps)
+            s["bce_fwd_bwd_known_ms"], _, _ = timed(lambda: loss_step("bce", tc, cand), reps)
+            for key in ("fwd_known_ms", "fwd_bwd_known_ms", "bce_fwd_bwd_known_ms"):
+                s[key.replace("_ms", "_scaled_all_node_ms")] = r[key] * C / N
+            r[f"candidates_{label}"] = s
+        if candidates:
+            r["fwd_known_again_ms"], _, _ = timed(lambda: model.softmax_loss(embs, q, t, scale=scale, filt_ptr=ptr, filt_idx=idx), reps)
+            r["fwd_bwd_known_again_ms"], _, _ = timed(step, reps)
+            r["bce_fwd_bwd_known_again_ms"], _, _ = timed(lambda: loss_step("bce", t, None), reps)
         if with_torch:
             for key, backward in (("torch_fwd", False), ("torch_fwd_bwd", True)):
                 try:
@@ -134,12 +176,13 @@ def main():
     ap.add_argument("--batches", default="1024,16384")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--candidates", default="", help="C[,C...] or N: also time the losses against a sorted random subset")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("softmax_time.py measures on an MI355X; no HIP device here")
     out = {"tool": "softmax_time", "device": torch.cuda.get_device_name(0)}
     for name in args.configs.split(","):
-        out[name] = run_config(name, args.reps, [int(b) for b in args.batches.split(",")], not args.no_torch)
+        out[name] = run_config(name, args.reps, [int(b) for b in args.batches.split(",")], not args.no_torch, args.candidates)
     print(json.dumps(out))
 
 
