@@ -7,7 +7,11 @@ kernels — so a retuned kernel gets the cases of its new geometry, and `realise
 claims (a block "at exactly split_chunks + 1 chunks" that has another count).
 
 The graphs stay within 3 * block_nodes + 1 nodes, except the hub cases and the two graphs that line up blocks with 0..7
-chunks in one launch (eight blocks)."""
+chunks in one launch (eight blocks).
+
+The CSR catalogue is instantiated at every width of the relation-stationary layer (RS_WIDTHS).  For those widths the file
+also restates the range guard's rule on the rows that layer cuts (cut_rows_margin: what the guard word must be after a
+forward and after a backward) and the two-layer chain of test_wide_rows_gpu.py."""
 
 from __future__ import annotations
 
@@ -33,7 +37,11 @@ class Case(NamedTuple):
 # (geometry key, case name) -> seed of the layer inputs, where the default seed makes the case ill-conditioned (a LayerNorm
 # row with next to no variance, a ReLU kink): test_edge_graphs_host.py checks that the seed named here is admissible
 SEED = 7100
-SEED_OVERRIDES: dict = {("bx128", "split_exactly_sc_chunks"): 7103, ("bx128", "split_sc_plus_1_chunks"): 7104}
+SEED_OVERRIDES: dict = {("bx128", "split_exactly_sc_chunks"): 7103, ("bx128", "split_sc_plus_1_chunks"): 7104,
+                        ("csr512", "csr_hubs_around_hub_rows"): 7103, ("csr640", "csr_hubs_around_hub_rows"): 7105,
+                        ("csr768", "csr_hubs_around_hub_rows"): 7102, ("csr896", "csr_hubs_around_hub_rows"): 7102,
+                        ("csr1024", "csr_hubs_around_hub_rows"): 7101}
+RS_WIDTHS = (128, 256, 384, 512, 640, 768, 896, 1024)       # every width ghf_message_rs_supported accepts
 
 
 def seed_for(geometry: str, name: str) -> int:
@@ -42,13 +50,15 @@ def seed_for(geometry: str, name: str) -> int:
 
 def geometries():
     """[(key, d, block_nodes, chunk_rows, split_chunks, rows per helper wave)]: the plans of the tuned kernels and the CSR
-    plan at the two widths that run on it (relation-stationary layer, generic kernel).  Needs the library, no GPU."""
+    plan at every width that runs on it (the relation-stationary layer's eight widths; the generic kernel at 20).  Needs the
+    library, no GPU."""
     from graph_hypernetwork_forge_amd import _native
     from graph_hypernetwork_forge_amd.plan import CSR_CONFIG
     bx128, bx64, pp128, pp64 = (_native.message_config(128), _native.message_config(64), _native.message_config(128, "pp"),
                                 _native.exact_config(64))
     out = [("bx128", 128, bx128, bx128[0] // 4), ("bx64", 64, bx64, bx64[0] // 4), ("pp128", 128, pp128, 0), ("pp64", 64, pp64, 0),
            ("csr256", 256, CSR_CONFIG, 0), ("csr20", 20, CSR_CONFIG, 0)]
+    out += [(f"csr{d}", d, CSR_CONFIG, 0) for d in RS_WIDTHS if d != 256]
     return [(k, d, c[0], c[2], c[3], npw) for k, d, c, npw in out]
 
 
@@ -248,11 +258,16 @@ def _csr_cases(seed: int) -> List[Case]:
 # ---- the layer in float64 ----------------------------------------------------------------------------------------------
 
 def layer_inputs(case: Case, d: int, seed: int):
-    """(h, W_msg, W_self, bias, gamma, beta) float32, at the scales of test_hip_parity._layer_inputs."""
+    """(h, W_msg, W_self, bias, gamma, beta) float32, at the scales of test_hip_parity._layer_inputs up to d = 256.  Beyond,
+    the weights are scaled by sqrt(256 / d): at a fixed std the aggregate grows like sqrt(2 d) and its absolute error with
+    it, and the float32 oracle itself leaves half of assert_close's bounds (test_edge_graphs_host.py); scaled, the
+    aggregate keeps the magnitude it has at 256 and the same bounds hold at every width."""
     N, R = case.N, case.R
     h = synth.normal(seed, "h", (N, d))
     Wm = synth.normal(seed, "Wm", (R, d, d), std=0.15)
     Ws = synth.normal(seed, "Ws", (R, d, d), std=0.15)
+    if d > 256:
+        Wm, Ws = (W * np.float32(np.sqrt(256.0 / d)) for W in (Wm, Ws))
     b = synth.normal(seed, "b", (R, d), std=0.3)
     gamma = (1.0 + 0.2 * synth.normal(seed, "g", (d,))).astype(np.float32)
     beta = (0.2 * synth.normal(seed, "bt", (d,))).astype(np.float32)
@@ -281,6 +296,84 @@ def layer_ref64(h, edge_index, rel, W_msg, W_self, bias, gamma, beta, eps: float
     mu = x.mean(axis=1, keepdims=True)
     var = ((x - mu) ** 2).mean(axis=1, keepdims=True)
     return out, (x - mu) / np.sqrt(var + eps) * gamma + beta
+
+
+RANGE_ROWS = 1                                             # include/ghf.h: GHF_RANGE_ROWS
+RS_TRAIN_WIDTHS = (256, 384, 512, 768, 1024)               # widths whose per-edge route test_edge_graphs_gpu.py differentiates
+
+
+def cut_rows_margin(case: Case, h, agg, gamma, gout, eps: float = LN_EPS) -> dict:
+    """How close the rows the relation-stationary layer cuts into fp16 pieces come to raising GHF_RANGE_ROWS (csrc/common.h:
+    the bit is raised when tiny > 0 and tiny * 8 >= nonzero): the largest tiny * 8 / nonzero over
+        "forward"   the rows of h and the sums of every (destination, relation) run's source rows (pass 0 of a run plan),
+        "backward"  the rows the two gradient passes gather, G_v = dpre_v / max(indeg_v, 1) — dpre the gradient at the
+                    aggregate, from `gout` at h' through LayerNorm and ReLU in float64 — and the run sums of G on the plan and
+                    on the reversed plan, each where build_rs(runs=None) chooses a run plan (rows <= RS_RUNS_MAX_SHARE * E).
+    Runs are cut into rows of RS_RUN_MAX edges in the stable order of the case's edge list (the plan's own order inside a
+    run may differ: that moves which sources share a row of a run longer than RS_RUN_MAX, not what kind of rows they are).
+    The backward of a graph with hubs is NOT of ordinary range by itself: on the reversed plan a run that mixes a hub's row
+    of G (divided by thousands) with a leaf's has the hub's entries 2^-12 down wherever the ReLU masks the leaf's — the
+    guard's rule is met or missed by a few entries, and `predicted_range_word` says which."""
+    from _rows_cases import guard_counts
+    from graph_hypernetwork_forge_amd.plan import RS_RUN_MAX, RS_RUNS_MAX_SHARE
+    h64, agg, gamma, g = (np.asarray(a, dtype=np.float64) for a in (h, agg, gamma, gout))
+    src, dst, rel = case.edge_index[0], case.edge_index[1], case.rel
+    pre = agg + h64
+    x = np.maximum(pre, 0.0)
+    mu = x.mean(axis=1, keepdims=True)
+    rstd = 1.0 / np.sqrt(((x - mu) ** 2).mean(axis=1, keepdims=True) + eps)
+    xhat, dxh = (x - mu) * rstd, g * gamma
+    dx = rstd * (dxh - dxh.mean(axis=1, keepdims=True) - xhat * (dxh * xhat).mean(axis=1, keepdims=True))
+    Gm = (dx * (pre > 0) / np.maximum(np.bincount(dst, minlength=case.N), 1)[:, None]).astype(np.float32)
+
+    def worst(rows):
+        out = 0.0
+        for row in rows:
+            tiny, nz = guard_counts(row)
+            out = max(out, tiny * 8 / nz if nz else 0.0)
+        return out
+
+    def run_rows(to, frm):
+        """(the source lists of the rows of two or more edges, rows in all) of the run plan keyed by (`to`, relation)."""
+        key = to * case.R + rel
+        order = np.argsort(key, kind="stable")
+        ks, ss = key[order], frm[order]
+        heads = np.nonzero(np.concatenate([[True], ks[1:] != ks[:-1]]))[0].tolist() + [ks.size]
+        rows = [ss[a:min(a + RS_RUN_MAX, q)] for p, q in zip(heads[:-1], heads[1:]) for a in range(p, q, RS_RUN_MAX)]
+        return [r for r in rows if r.size > 1], len(rows)
+
+    def sums(X, rows):
+        return (X[r].sum(axis=0, dtype=np.float32) for r in rows)
+
+    h32 = np.asarray(h, dtype=np.float32)
+    fwd_rows, n_fwd = run_rows(dst, src)
+    rev_rows, n_rev = run_rows(src, dst)
+    E = rel.size
+    bwd = [worst(Gm)]
+    bwd += [worst(sums(Gm, fwd_rows))] if n_fwd <= RS_RUNS_MAX_SHARE * E else []
+    bwd += [worst(sums(Gm, rev_rows))] if n_rev <= RS_RUNS_MAX_SHARE * E else []
+    return {"forward": max(worst(h32), worst(sums(h32, fwd_rows))), "backward": max(bwd)}
+
+
+def predicted_range_word(margin: float) -> int:
+    """The guard word a pass leaves whose rows reach `margin` of the rule (cut_rows_margin): it fires from 1 on.  Within 0.03
+    of 1 the prediction is not made: the kernels' fp32 rows differ from the restatement's in their last bits, which can move
+    a handful of entries standing at the "tiny" threshold — 3 % of a row's nonzero entries (ten and more from d = 384) is
+    far more than that.  test_edge_graphs_host.py keeps every differentiated case outside the band."""
+    assert abs(margin - 1.0) > 0.03, f"margin {margin:.3f}: too close to the guard's rule to call"
+    return RANGE_ROWS if margin >= 1.0 else 0
+
+
+def two_layer_inputs(case: Case, d: int, seed: int):
+    """(layer 1: h, W_msg, W_self, bias, gamma, beta; layer 2: W_msg, W_self, bias, gamma, beta) for two layers on one graph:
+    layer 2's parameters are layer_inputs' of another seed."""
+    return layer_inputs(case, d, seed), layer_inputs(case, d, seed + 1000)[1:]
+
+
+def two_layer_ref64(case: Case, ins1, ins2) -> np.ndarray:
+    """h'' of two layers (layer_ref64 twice) in float64."""
+    _, h1 = layer_ref64(ins1[0], case.edge_index, case.rel, *ins1[1:])
+    return layer_ref64(h1, case.edge_index, case.rel, *ins2)[1]
 
 
 def layer_ref64_torch(h, edge_index, rel, W_msg, W_self, bias, gamma, beta, eps: float = LN_EPS):

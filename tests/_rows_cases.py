@@ -17,7 +17,7 @@ import numpy as np
 
 BIG, EDGE, FAR = np.float32(1.0), np.float32(2.0 ** -14), np.float32(2.0 ** -20)
 KINDS = ("fires", "holds")
-WIDTHS = (32, 64, 100, 128, 192, 256, 384)          # every row width a case of test_rows_bits_gpu.py cuts
+WIDTHS = (32, 64, 100, 128, 192, 256, 384, 512, 640, 768, 896, 1024)   # every row width a case of test_rows_bits_gpu.py cuts
 
 
 def threshold_row(d: int, kind: str, signed: bool = False) -> np.ndarray:

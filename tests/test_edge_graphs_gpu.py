@@ -1,7 +1,16 @@
 """The crafted edge-case graphs of _edge_graphs.py through every tuned message kernel, forward and backward, against the
 float64 reference; and the reference's own small graphs through the whole model at the hidden sizes of the tuned kernels.
 
-Run one route at a time (`-k "bx128-"`, ...): some of these shapes are launched by no other test."""
+Run one route at a time (`-k "bx128-"`, ...): some of these shapes are launched by no other test.
+
+The relation-stationary layer runs at every width it declares itself correct for (ghf_message_rs_supported: 128 .. 1024 in
+steps of 128).  The width is no passive loop bound there: d % 256 == 0 runs the LDS-DMA ring (256-column tiles, d / 16 steps
+over three buffers: 256 and 1024 leave d / 16 % 3 == 1, 512 leaves 2, 768 leaves 0), the other widths the register-staged
+kernel (128-column tiles: 384, 640, 896 divide the grid index by 3, 5, 7); passes 0 and 2 hold d / 64 columns per lane.  384,
+512, 768 and 1024 run all four kinds (both pass-1 kernels, every ring residue, the largest column count) and train; 128, 640
+and 896 run the two-piece kernel on per-edge rows."""
+
+import functools
 
 import numpy as np
 import pytest
@@ -30,6 +39,13 @@ ROUTES = {
     "rs32_runs": (256, "rs32", "csr256", "rs", True, False),
     "generic": (20, None, "csr20", "generic", None, True),
 }
+for _d in (384, 512, 768, 1024):                                 # (a width's routes side by side: they share its references)
+    ROUTES.update({f"rs_edges{_d}": (_d, None, f"csr{_d}", "rs", False, True), f"rs_runs{_d}": (_d, None, f"csr{_d}", "rs", True, False),
+                   f"rs32_edges{_d}": (_d, "rs32", f"csr{_d}", "rs", False, False),
+                   f"rs32_runs{_d}": (_d, "rs32", f"csr{_d}", "rs", True, False)})
+for _d in (128, 640, 896):                                       # (128: the block kernel's width — the plan is forced onto CSR)
+    ROUTES[f"rs_edges{_d}"] = (_d, None, f"csr{_d}", "rs", False, False)
+assert {v[0] for v in ROUTES.values() if v[3] == "rs" and v[5]} == set(G.RS_TRAIN_WIDTHS)      # (the host file proves these)
 GEO = {g[0]: g for g in G.geometries()}
 CASES = {key: {c.name: c for c in G.edge_cases(*GEO[key][2:], GEO[key][1])} for key in GEO}
 FWD = [(r, n) for r, v in ROUTES.items() for n in CASES[v[2]]]
@@ -41,6 +57,21 @@ def _rel_l2(got, ref):
     return float(np.linalg.norm(got - ref) / max(np.linalg.norm(ref), 1e-30))
 
 
+@functools.lru_cache(maxsize=None)
+def _reference(key, name):
+    """(aggregate, h') of the float64 reference, computed once per (geometry, case) and shared by its routes; read-only."""
+    case, (h, *rest) = CASES[key][name], _inputs(key, name)
+    ref = G.layer_ref64(h, case.edge_index, case.rel, *rest)
+    for a in ref:
+        a.flags.writeable = False
+    return ref
+
+
+@functools.lru_cache(maxsize=7)                                  # (one width's cases: the weights of a case are up to 50 MB)
+def _inputs(key, name):
+    return G.layer_inputs(CASES[key][name], GEO[key][1], G.seed_for(key, name))
+
+
 def _setup(route, name, monkeypatch):
     d, env, key, kind, runs, _ = ROUTES[route]
     if env:
@@ -49,7 +80,7 @@ def _setup(route, name, monkeypatch):
         monkeypatch.delenv("GHF_KERNEL", raising=False)
     case = CASES[key][name]
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)                       # noqa: E731
-    plan = build_plan(t(case.edge_index), t(case.rel), [""] * case.R, case.N, d, DEV)
+    plan = build_plan(t(case.edge_index), t(case.rel), [""] * case.R, case.N, d, DEV, force_generic=(kind == "rs" and d == 128))
     _, _, bn, cr, sc, npw = GEO[key]
     want = {"bx128": lambda: _native.message_config(128), "bx64": lambda: _native.message_config(64),
             "pp128": lambda: _native.message_config(128, "pp"), "pp64": lambda: _native.exact_config(64)}.get(key)
@@ -74,22 +105,28 @@ def test_forward(route, name, monkeypatch):
         assert np.array_equal(plan.blk_chunk_off.cpu().numpy(), res["blk_chunk_off"]), "blk_chunk_off"
         assert np.array_equal(np.asarray(plan.item_off_host), res["item_off"]), "item_off_host"
         assert plan.n_slots == int(res["items_per_block"][res["items_per_block"] > 1].sum())
-    h, Wm, Ws, b, gamma, beta = G.layer_inputs(case, d, seed)
-    ref_agg, ref_out = G.layer_ref64(h, case.edge_index, case.rel, Wm, Ws, b, gamma, beta)
+    h, Wm, Ws, b, gamma, beta = _inputs(key, name)
+    ref_agg, ref_out = _reference(key, name)
     h_d, b_d, g_d, bt_d = t(h), t(b), t(gamma), t(beta)
+    sub = None                               # the row range launched on its own: (first row, rows)
     if kind == "rs":
         rs = build_rs(plan, runs=runs)
         assert (rs.run_start is not None) == bool(runs)
         Y = torch.full((max(rs.rows, 1), d), float("nan"), device=DEV)
+        Wm_d, Ws_d = t(Wm), t(Ws)
+        if N >= 4:
+            sub = (N // 3, max(N // 4, 1))
 
-        def launch(out, no_tail, row0=0, rows=None):
-            _native.edge_transform_fwd(h_d, rs, t(Wm), t(Ws), b_d, Y)
+        def launch(out, no_tail, row0=0, rows=None, flags=_native.GHF_FLAG_NO_TAIL):
+            _native.edge_transform_fwd(h_d, rs, Wm_d, Ws_d, b_d, Y)
             if no_tail:
-                _native.segment_tail_fwd(Y, rs, None, None, None, 0.0, out, row0=row0, rows=rows, flags=_native.GHF_FLAG_NO_TAIL)
+                _native.segment_tail_fwd(Y, rs, None, None, None, 0.0, out, row0=row0, rows=rows, flags=flags)
             else:
                 _native.segment_tail_fwd(Y, rs, h_d, g_d, bt_d, 1e-5, out, row0=row0, rows=rows)
     else:
         W, W2 = _layer_weights(plan, t(Wm), t(Ws), transpose=False)
+        if kind == "block" and N > bn:
+            sub = (bn, min(2 * bn, N) - bn)
 
         def launch(out, no_tail, row0=0, rows=None):
             _native.message_layer_fwd(h_d, plan, W, W2, b_d, plan.wlayout, None if no_tail else g_d, None if no_tail else bt_d,
@@ -104,12 +141,22 @@ def test_forward(route, name, monkeypatch):
         again = torch.full_like(h_d, float("nan"))
         launch(again, no_tail)
         assert torch.equal(out, again), "a second launch gives other bits"
-        if kind == "block" and N > bn:
-            hi = min(2 * bn, N)
+        if sub is not None:
+            lo, hi = sub[0], sub[0] + sub[1]
             part = torch.full_like(h_d, 7.0)
-            launch(part, no_tail, row0=bn, rows=hi - bn)
-            assert torch.equal(part[bn:hi], out[bn:hi]), "the row range [bn, 2 bn) differs from the full launch"
-            assert bool((part[:bn] == 7.0).all()) and bool((part[hi:] == 7.0).all()), "rows outside the range were written"
+            launch(part, no_tail, row0=lo, rows=hi - lo)
+            assert torch.equal(part[lo:hi], out[lo:hi]), f"the row range [{lo}, {hi}) differs from the full launch"
+            assert bool((part[:lo] == 7.0).all()) and bool((part[hi:] == 7.0).all()), "rows outside the range were written"
+    if kind == "rs":
+        # GHF_FLAG_RAW_SUM (what the backward's passes run under): the sum the mean divides, left undivided.  Held to the
+        # aggregate's bounds per unit of the divisor: raw / max(indeg, 1) against the reference aggregate (the division is
+        # done here in float64; the kernel's own fp32 sum is the one both outputs start from).
+        raw = torch.full_like(h_d, float("nan"))
+        launch(raw, True, flags=_native.GHF_FLAG_NO_TAIL | _native.GHF_FLAG_RAW_SUM)
+        div = np.maximum(res["indeg"], 1).astype(np.float64)[:, None]
+        got = raw.cpu().numpy().astype(np.float64) / div
+        print(f"FIG fwd {route} {name} raw_sum rel_l2={_rel_l2(got, ref_agg):.3e} max_abs={np.nanmax(np.abs(got - ref_agg)):.3e}")
+        assert_close(got, ref_agg, f"{route} {name} raw sum / max(indeg, 1)")
     assert int(flag.item()) == 0, f"range guard word {int(flag.item())} on inputs of ordinary dynamic range"
 
 
@@ -122,7 +169,7 @@ def test_backward(route, name, monkeypatch):
     tp = build_train_plan(t(case.edge_index), t(case.rel), plan, d, DEV)
     if name == "sources_hub_with_sc_plus_1_chunks_of_out_edges":
         assert tp.rev.n_slots > 0, "the hub source must be a split block of the reversed plan"
-    ins = G.layer_inputs(case, d, seed)
+    ins = _inputs(key, name)
     gout = synth.normal(77, "gout", (case.N, d))
     th = torch.from_numpy
     ref_in = [th(a).double().requires_grad_(True) for a in ins]
@@ -132,6 +179,7 @@ def test_backward(route, name, monkeypatch):
     for _ in range(2):
         args = [t(a).requires_grad_(True) for a in ins]
         out = MessageLayerFn.apply(*args, 1e-5, tp)
+        assert int(flag.item()) == 0 or len(runs_), f"range guard word {int(flag.item())} after the training forward"
         out.backward(t(gout))
         runs_.append((out.detach(), [a.grad for a in args]))
     assert_close(runs_[0][0].cpu().numpy(), ref.detach().numpy(), f"{route} {name} training forward")
@@ -143,7 +191,16 @@ def test_backward(route, name, monkeypatch):
             f"d{n}: max abs err {np.abs(gg - gw).max():.3e} at scale {scale:.3e}"
         assert _rel_l2(gg, gw) < 2e-5, f"d{n}: relative L2 {_rel_l2(gg, gw):.3e}"
         assert torch.equal(got, again), f"d{n}: a second backward gives other bits"
-    assert int(flag.item()) == 0, f"range guard word {int(flag.item())} on inputs of ordinary dynamic range"
+    # The rows the gradient passes cut are not the test's inputs: on the wide-row layer a graph with hubs sums rows of G that
+    # lie 2^-12 apart (the hubs' are divided by their in-degree) and meets the guard's rule by itself at some widths.  The
+    # word is held to what the rule gives on the float64 rows (_edge_graphs.cut_rows_margin; test_edge_graphs_host.py shows
+    # that every case here can be called): 0 wherever they are of ordinary range, GHF_RANGE_ROWS where they are not.
+    want_word = 0
+    if kind == "rs":
+        margin = G.cut_rows_margin(case, ins[0], _reference(key, name)[0], ins[4], gout)
+        want_word = G.predicted_range_word(margin["backward"])
+        print(f"FIG bwd {route} {name} guard margin fwd={margin['forward']:.3f} bwd={margin['backward']:.3f} word={int(flag.item())}")
+    assert int(flag.item()) == want_word, f"range guard word {int(flag.item())}, the rows' own range gives {want_word}"
 
 
 # ---- the reference's own small graphs through the whole model at hidden 64 / 128 / 256 ----------------------------------

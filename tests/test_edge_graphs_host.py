@@ -93,3 +93,12 @@ def test_reference_equals_the_oracle_and_the_case_is_admissible(geo, name):
         scale = float(np.abs(want).max())
         ok, rel = _within(a, want, 1e-4, 1e-5 * max(scale, 1.0), 1e-5)
         assert ok, f"{key} {name} seed {seed}: float32 autograd d{n} misses half the bound (relative L2 {rel:.3e}): another seed"
+    # the range word: the forward's rows must stay far from the guard's rule (the tests assert 0 there); the backward's may
+    # meet it — graphs with hubs do, see _edge_graphs.cut_rows_margin — but never so narrowly that the word cannot be predicted
+    if geo[2] == 1 and d % 128 == 0:
+        margin = G.cut_rows_margin(case, h, agg_np, gamma, G.synth.normal(77, "gout", (case.N, d)))
+        assert margin["forward"] <= 0.5, f"{key} {name} seed {seed}: rows of h reach {margin['forward']:.3f} of the range guard's rule"
+        if d in G.RS_TRAIN_WIDTHS:
+            word = G.predicted_range_word(margin["backward"])           # (asserts that it can be called)
+            assert word == (G.RANGE_ROWS if margin["backward"] >= 1 else 0)
+            assert name == "csr_hubs_around_hub_rows" or margin["backward"] <= 0.5, f"{key} {name}: {margin['backward']:.3f}"

@@ -25,7 +25,8 @@ Cases:
   wide rows    d = 128 (CPL 2, the four-wave pass 1), 256 (the eight-wave pass 1), 384 (not a power of two): a graph of 12
                nodes whose node 0 is a hub (hub_of >= 0: RS_HUB_ROWS lowered to 8), node 1 has one row, node 2 none, node 3 a
                run of several edges (RS_RUN_MAX lowered to 2, so that run_rows_kernel runs): tail, NO_TAIL, NO_TAIL | RAW_SUM, a
-               row sub-range, and the threshold rows for pass 0 (run_rows) and pass 2 (segment_tail).
+               row sub-range, and the threshold rows for pass 0 (run_rows) and pass 2 (segment_tail).  The guard tests at the
+               end of this file (no fixture) run the same threshold rows at every width of the layer, 128 .. 1024.
   split blocks d = 64, 128, kernels bx and pp: a block of 5 rows (not a multiple of the rows per pass) with more than
                split_chunks chunks, and the last-round split of _plan_cases.value_cases: tail, NO_TAIL, NO_TAIL | RAW_SUM;
                bx also h_split_out + agg_out, NO_TAIL | ADD_H and the threshold rows (the split block's rows alone are launched,
@@ -394,14 +395,17 @@ def test_guard_input_proj_pieces_rows_of_x(d, F, kind):
     assert int(flag) == guard(kind)
 
 
-@pytest.mark.parametrize("d", (128, 256, 384))
+WIDE = (128, 256, 384, 512, 640, 768, 896, 1024)    # every width of the relation-stationary layer (the fixture records three)
+
+
+@pytest.mark.parametrize("d", WIDE)
 @pytest.mark.parametrize("kind", KINDS)
 def test_guard_run_rows(d, kind):
     Y, X, flag1, out, split, flag2 = case_rs(d, "run_" + kind)
     assert int(flag1) == guard(kind) and int(flag2) == 0
 
 
-@pytest.mark.parametrize("d", (128, 256, 384))
+@pytest.mark.parametrize("d", WIDE)
 @pytest.mark.parametrize("kind", KINDS)
 def test_guard_segment_tail(d, kind):
     Y, X, flag1, out, split, flag2 = case_rs(d, kind)
