@@ -11,7 +11,10 @@ chunks in one launch (eight blocks).
 
 The CSR catalogue is instantiated at every width of the relation-stationary layer (RS_WIDTHS).  For those widths the file
 also restates the range guard's rule on the rows that layer cuts (cut_rows_margin: what the guard word must be after a
-forward and after a backward) and the two-layer chain of test_wide_rows_gpu.py."""
+forward and after a backward) and the two-layer chain of test_wide_rows_gpu.py.
+
+The same catalogue, less its hub case, runs the any-width route (message_generic_kernel) at the widths of ANY_FWD_WIDTHS:
+test_any_width_host.py and test_any_width_gpu.py take their width tables and the kernels' thread geometry from here."""
 
 from __future__ import annotations
 
@@ -42,6 +45,67 @@ SEED_OVERRIDES: dict = {("bx128", "split_exactly_sc_chunks"): 7103, ("bx128", "s
                         ("csr768", "csr_hubs_around_hub_rows"): 7102, ("csr896", "csr_hubs_around_hub_rows"): 7102,
                         ("csr1024", "csr_hubs_around_hub_rows"): 7101}
 RS_WIDTHS = (128, 256, 384, 512, 640, 768, 896, 1024)       # every width ghf_message_rs_supported accepts
+
+# ---- the any-width route (test_any_width_host.py / test_any_width_gpu.py) ---------------------------------------------
+# message_generic_kernel and tail_kernel (csrc/message_generic.hip): GEN_TPB threads, thread t holds column t + GEN_TPB c for
+# c < GEN_MAX_D / GEN_TPB, block_sum over GEN_TPB / 64 waves.  The widths: one live wave (1, 2, 3, 63), a second wave with one
+# live lane (65), part-filled waves (100, 192, 255), a last column group with exactly one live thread (257, 513, 769), every
+# column group with a dead last thread (1023).  Seeds of these widths' cases are recorded under the key f"any{d}".
+GEN_TPB, GEN_MAX_D, WAVE = 256, 1024, 64
+ANY_FWD_WIDTHS = (1, 2, 3, 63, 65, 100, 192, 255, 257, 513, 769, 1023)
+ANY_BWD_WIDTHS = (3, 65, 100, 257, 513, 1023)             # (LayerNorm over one or two values has no well-conditioned gradient)
+ANY_NO_HUBS = "csr_hubs_around_hub_rows"                  # cut around a threshold of the relation-stationary layer: not run here
+SEED_OVERRIDES.update({("any3", "csr_n1_self_loop"): 7101})
+
+# the fp32 input projection (csrc/input_proj.hip): input_proj_mfma_kernel<NT> at d = 16 NT, column tiles in groups of TG;
+# W_in staged in LDS (WLDS) when cdiv(N, IP_ROWS_PER_BLOCK) >= IP_WLDS_MIN_BLOCKS and d (F + 4) 4 <= IP_WLDS_MAX_BYTES
+IP_NT = tuple(range(1, 17))
+IP_F = (16, 48, 80)
+IP_N = (77, 8200)
+IP_ROWS_PER_BLOCK, IP_WLDS_MIN_BLOCKS, IP_WLDS_MAX_BYTES = 128, 64, 72 * 1024
+IP_SIMPLE = ((10, 72), (16, 200), (48, 320), (7, 1023))    # (F, d) of the vector-ALU fallback: F % 16, d % 16 or d > 256
+MODEL_WIDTHS = (72, 96, 200)                               # the whole model: d % 16 != 0; MFMA projection at NT = 6; neither
+
+
+def any_width_cases(seed: int = 7100) -> List["Case"]:
+    """The CSR catalogue without the hub case, in the catalogue's order."""
+    return [c for c in _csr_cases(seed) if c.name != ANY_NO_HUBS]
+
+
+def dropout_mask(N: int, d: int, seed: int = 78) -> np.ndarray:
+    """A layer's dropout mask at p = 0.25, scaled by 1 / (1 - p): [N, d] float32, the same on every machine."""
+    return ((synth.uniform01(seed, "drop", N * d) < 0.75) / 0.75).astype(np.float32).reshape(N, d)
+
+
+def tail_ref64(agg, h, gamma, beta, drop=None, eps: float = 1e-5) -> np.ndarray:
+    """LayerNorm(ReLU(agg + h) * drop) in numpy float64 (biased variance)."""
+    agg, h, gamma, beta = (np.asarray(a, dtype=np.float64) for a in (agg, h, gamma, beta))
+    x = np.maximum(agg + h, 0.0) * (1.0 if drop is None else np.asarray(drop, dtype=np.float64))
+    mu = x.mean(axis=1, keepdims=True)
+    var = ((x - mu) ** 2).mean(axis=1, keepdims=True)
+    return (x - mu) / np.sqrt(var + eps) * gamma + beta
+
+
+def generic_geometry(d: int) -> dict:
+    """How message_generic_kernel's 256 threads cover d columns: live waves (waves with a column in group 0), column groups
+    used, live threads of the last group."""
+    assert 1 <= d <= GEN_MAX_D
+    groups = -(-d // GEN_TPB)
+    return dict(live_waves=-(-min(d, GEN_TPB) // WAVE), groups=groups, last_group_threads=d - GEN_TPB * (groups - 1))
+
+
+def ip_tile_group(NT: int) -> int:
+    """TG of input_proj_mfma_kernel<NT>: column tiles whose MFMAs are interleaved."""
+    return 4 if NT % 4 == 0 else (2 if NT % 2 == 0 else 1)
+
+
+def ip_route(N: int, F: int, d: int) -> str:
+    """The kernel launch_input_proj picks for 16-byte aligned operands and no h_split below N = 1024: "mfma_wlds", "mfma"
+    (W_in's fragments from L2) or "simple" (the vector ALU)."""
+    if F % 16 or d % 16 or d > 256:
+        return "simple"
+    wlds = d * (F + 4) * 4 <= IP_WLDS_MAX_BYTES and -(-N // IP_ROWS_PER_BLOCK) >= IP_WLDS_MIN_BLOCKS
+    return "mfma_wlds" if wlds else "mfma"
 
 
 def seed_for(geometry: str, name: str) -> int:
