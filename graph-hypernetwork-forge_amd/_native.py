@@ -1242,16 +1242,24 @@ def split_row_scales(split: torch.Tensor, N: int, d: int) -> torch.Tensor:
 
 def edge_outer(h: torch.Tensor, G: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, slice_tab: torch.Tensor,
                slice_off: torch.Tensor, R: int, exact: bool = False, h_scales: Optional[torch.Tensor] = None,
-               G_scales: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None):
+               G_scales: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None,
+               workspace: Optional[torch.Tensor] = None):
     """(dW [R, 2d, d] = dW_msg stacked on dW_self, db [R, d]) of include/ghf.h: ghf_edge_outer (exact: the fp32 chain at
     every d — a step that fell back to the exact kernels).  h_scales / G_scales: the row scales of the two tensors' split
     forms (split_row_scales), when the caller holds them: ghf_edge_outer_scaled, same bits without the pass over h and G.
-    order [S] int32: the launch order of the slices (ghf.h; the same bits in any order)."""
+    order [S] int32: the launch order of the slices (ghf.h; the same bits in any order).  workspace: the call's scratch, for a
+    caller that reads it afterwards (ghf.h: the range guard's counters) — float32, at least S (2 D D + D) + 64 elements, D =
+    min(d, 128); allocated here when absent."""
     lib = load()
     h, G = _req(h, torch.float32, "h"), _req(G, torch.float32, "G")
     d, ns = h.size(1), slice_tab.size(0)
     D = min(d, 128)
-    ws = torch.empty(ns * (2 * D * D + D) + 64, dtype=torch.float32, device=h.device)
+    if workspace is None:
+        ws = torch.empty(ns * (2 * D * D + D) + 64, dtype=torch.float32, device=h.device)
+    else:
+        ws = _req(workspace, torch.float32, "workspace")
+        if ws.numel() < ns * (2 * D * D + D) + 64 or ws.device != h.device:
+            raise ValueError("edge_outer: workspace of at least S (2 D D + D) + 64 floats on the tensors' device expected")
     dW = torch.empty(R, 2 * d, d, dtype=torch.float32, device=h.device)
     db = torch.empty(R, d, dtype=torch.float32, device=h.device)
     tabs = (_ptr(_req(src, torch.int64, "src")), _ptr(_req(dst, torch.int64, "dst")), _ptr(_req(slice_tab, torch.int64, "slice_tab")),

@@ -70,22 +70,33 @@ def build_train_plan(edge_index: torch.Tensor, rel_ids: torch.Tensor, fwd: Graph
     tp = TrainPlan(fwd=fwd, rev=rev, src_by_rel=ei[0].index_select(0, perm).contiguous(),
                    dst_by_rel=ei[1].index_select(0, perm).contiguous(), goff=goff, carry=_SplitCarry())
     if _native.load().ghf_edge_outer_supported(d):
-        off = goff.cpu().tolist()                             # (one host sync per plan)
-        tab, soff = [], [0]
-        for r in range(fwd.R):
-            tab += [(r, a, min(a + SLICE_EDGES, off[r + 1])) for a in range(off[r], off[r + 1], SLICE_EDGES)]
-            soff.append(len(tab))
+        tab, soff, order = _slice_tables(goff.cpu().tolist(), fwd.R)   # (one host sync per plan)
         if tab:
             tp.slice_tab = torch.tensor(tab, dtype=torch.int64).to(device)
             tp.slice_off = torch.tensor(soff, dtype=torch.int64).to(device)
-            # Destinations ascend inside a relation, so a slice's place in its relation (as a fraction of the relation's
-            # slices) says which band of destination rows it reads.  Launched band by band — every relation's slice of the
-            # band together — the workgroups in flight share that band's rows of h and G (Infinity Cache) instead of each
-            # relation sweeping all N rows alone.  Same bits: ghf.h, ghf_edge_outer.
-            place = [((k + 0.5) / (soff[r + 1] - soff[r]), r) for r in range(fwd.R) for k in range(soff[r + 1] - soff[r])]
-            order = sorted(range(len(tab)), key=place.__getitem__)
             tp.slice_order = torch.tensor(order, dtype=torch.int32).to(device)
     return tp
+
+
+def _slice_tables(off, R: int):
+    """ghf_edge_outer's work list for relation offsets `off` [R+1]: (slice_tab rows (relation, first edge, end edge) of at most
+    SLICE_EDGES edges, slice_off [R+1], the slices in launch order) as host lists."""
+    tab, soff = [], [0]
+    for r in range(R):
+        tab += [(r, a, min(a + SLICE_EDGES, off[r + 1])) for a in range(off[r], off[r + 1], SLICE_EDGES)]
+        soff.append(len(tab))
+    # Destinations ascend inside a relation, so a slice's place in its relation (as a fraction of the relation's
+    # slices) says which band of destination rows it reads.  Launched band by band — every relation's slice of the
+    # band together — the workgroups in flight share that band's rows of h and G (Infinity Cache) instead of each
+    # relation sweeping all N rows alone.  Same bits: ghf.h, ghf_edge_outer.
+    place = [((k + 0.5) / (soff[r + 1] - soff[r]), r) for r in range(R) for k in range(soff[r + 1] - soff[r])]
+    return tab, soff, sorted(range(len(tab)), key=place.__getitem__)
+
+
+def _ident_slices(N: int):
+    """The same work list for InputProjFn's weight gradient: the "edges" v -> v of one relation, v < N."""
+    step = min(SLICE_EDGES, max(256, (N // 1024 + 31) // 32 * 32))           # ~1,000 slices: all CUs also at 10^5 rows
+    return [(0, a, min(a + step, N)) for a in range(0, N, step)]
 
 
 def _layer_weights(plan: GraphPlan, Wm: Optional[torch.Tensor], Ws: Optional[torch.Tensor], transpose: bool):
@@ -344,8 +355,7 @@ class InputProjFn(torch.autograd.Function):
             # arithmetic and one-scale-per-tensor contract as the layers' weight gradients (ghf.h); the exact chain when the
             # step fell back to the exact kernels.
             if tp.ident is None or tp.ident[0].numel() != N:
-                step = min(SLICE_EDGES, max(256, (N // 1024 + 31) // 32 * 32))       # ~1,000 slices: all CUs also at 10^5 rows
-                tab = [(0, a, min(a + step, N)) for a in range(0, N, step)]
+                tab = _ident_slices(N)
                 tp.ident = (torch.arange(N, dtype=torch.int64, device=x.device), torch.tensor(tab, dtype=torch.int64).to(x.device),
                             torch.tensor([0, len(tab)], dtype=torch.int64).to(x.device))
             ids, tab, soff = tp.ident
