@@ -130,6 +130,21 @@ SIGNATURES = {
     "ghf_score_bce_bwd_sub_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
     "ghf_score_bce_bwd_sub": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _i64, _vp, _sz, _vp,
                                      _vp, _vp]),
+    "ghf_score_rank_b_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i64]),
+    "ghf_score_rank_b": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "ghf_score_topk_b_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i32, _i64]),
+    "ghf_score_topk_b": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "ghf_score_softmax_b_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i64]),
+    "ghf_score_softmax_fwd_b": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _i64, _vp, _vp, _sz, _vp, _vp,
+                                       _vp]),
+    "ghf_score_softmax_bwd_b_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i64]),
+    "ghf_score_softmax_bwd_b": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _i64, _vp, _vp, _sz,
+                                       _vp, _vp, _vp, _vp]),
+    "ghf_score_bce_b_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i64]),
+    "ghf_score_bce_fwd_b": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _vp, _i64, _vp, _vp, _sz, _vp, _vp]),
+    "ghf_score_bce_bwd_b_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i64]),
+    "ghf_score_bce_bwd_b": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _i64, _vp, _vp, _sz,
+                                   _vp, _vp, _vp, _vp]),
     "ghf_relation_rows_workspace_bytes": (_sz, [_i64, _i32]),
     "ghf_relation_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
     "ghf_relation_scores": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp]),
@@ -683,6 +698,43 @@ def _ic_arg(ic: Optional[torch.Tensor], c: torch.Tensor, what: str) -> Optional[
     return ic
 
 
+def _bias_arg(bias: Optional[torch.Tensor], c: torch.Tensor, what: str) -> Optional[torch.Tensor]:
+    """The per-candidate bias of the ghf_score_*_b calls (include/ghf.h): fp32 [N], one entry per row of c, on c's device.  Only
+    metadata is looked at; the values are the device's business."""
+    if bias is None:
+        return None
+    N = c.size(0)
+    if (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or bias.dim() != 1 or bias.numel() != N
+            or bias.device != c.device):
+        got = f"{tuple(bias.shape)} {bias.dtype} on {bias.device}" if isinstance(bias, torch.Tensor) else type(bias).__name__
+        raise ValueError(f"{what}: the bias must be a float32 tensor of shape [N = {N}] on {c.device}, got {got}")
+    return bias.detach().contiguous()
+
+
+def score_rank_b_workspace_bytes(B: int, N: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_rank_b_workspace_bytes(B, N, C, d, nnz))
+
+
+def score_topk_b_workspace_bytes(B: int, N: int, C: int, d: int, k: int, nnz: int) -> int:
+    return int(load().ghf_score_topk_b_workspace_bytes(B, N, C, d, k, nnz))
+
+
+def score_softmax_b_workspace_bytes(B: int, N: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_softmax_b_workspace_bytes(B, N, C, d, nnz))
+
+
+def score_softmax_bwd_b_workspace_bytes(B: int, N: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_softmax_bwd_b_workspace_bytes(B, N, C, d, nnz))
+
+
+def score_bce_b_workspace_bytes(B: int, N: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_bce_b_workspace_bytes(B, N, C, d, nnz))
+
+
+def score_bce_bwd_b_workspace_bytes(B: int, N: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_bce_bwd_b_workspace_bytes(B, N, C, d, nnz))
+
+
 def score_rank_workspace_bytes(B: int, N: int, d: int) -> int:
     return int(load().ghf_score_rank_workspace_bytes(B, N, d))
 
@@ -702,19 +754,25 @@ def score_topk_workspace_bytes(B: int, N: int, d: int, k: int) -> int:
 def score_rank(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optional[torch.Tensor] = None,
                filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-               ic: Optional[torch.Tensor] = None):
+               ic: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
     """(greater, equal) int64 [B]: how many rows of c score above / the same as row target[i] against query q[iq[i]], the
     target and the query's filter list (CSR, each list sorted ascending) left out.  Nothing of size B x N is stored.  With
     `workspace` (uint8, score_rank_workspace_bytes) and `out` given the call allocates nothing (graph capture).  `ic` (int64
     [C], strictly ascending node ids): only those rows of c are counted (ghf_score_rank_sub; the workspace is then
-    score_rank_sub_workspace_bytes'); target and lists stay node ids, the target need not be a candidate."""
+    score_rank_sub_workspace_bytes'); target and lists stay node ids, the target need not be a candidate.  `bias` (fp32 [N], one
+    entry per row of c): every score, the target's too, is s + bias[row] (ghf_score_rank_b; workspace:
+    score_rank_b_workspace_bytes with C = 0 for every node)."""
     q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, "score_rank")
     target = _req(target, torch.int64, "target")
     if target.dim() != 1 or target.numel() != B or target.device != q.device:
         raise ValueError(f"score_rank: target must be [B = {B}] on {q.device}, got {tuple(target.shape)} on {target.device}")
     N, d = c.size(0), c.size(1)
     ic = _ic_arg(ic, c, "score_rank")
-    if ic is None:
+    bias = _bias_arg(bias, c, "score_rank")
+    C = 0 if ic is None else ic.numel()
+    if bias is not None:
+        ws = _workspace(workspace, score_rank_b_workspace_bytes, q.device, "score_rank", B=B, N=N, C=C, d=d, nnz=nnz)
+    elif ic is None:
         ws = _workspace(workspace, score_rank_workspace_bytes, q.device, "score_rank", B=B, N=N, d=d)
     else:
         ws = _workspace(workspace, score_rank_sub_workspace_bytes, q.device, "score_rank", B=B, C=ic.numel(), d=d, nnz=nnz)
@@ -725,6 +783,11 @@ def score_rank(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optio
         greater, equal = (_req(t, torch.int64, "out") for t in out)
         if greater.numel() != B or equal.numel() != B or not (out[0].is_contiguous() and out[1].is_contiguous()):
             raise ValueError(f"score_rank: out must be two contiguous int64 [{B}] tensors")
+    if bias is not None:
+        _check(load().ghf_score_rank_b(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d,
+                                       _ptr(ic), C, _ptr(bias), _ptr(ws), ws.numel(), _ptr(greater), _ptr(equal), _stream()),
+               "ghf_score_rank_b")
+        return greater, equal
     if ic is not None:
         _check(load().ghf_score_rank_sub(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
                                          d, _ptr(ic), ic.numel(), _ptr(ws), ws.numel(), _ptr(greater), _ptr(equal), _stream()),
@@ -738,17 +801,22 @@ def score_rank(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optio
 def score_topk(q: torch.Tensor, c: torch.Tensor, k: int, iq: Optional[torch.Tensor] = None,
                filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-               ic: Optional[torch.Tensor] = None):
+               ic: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
     """(scores [B, k] fp32 descending, ids [B, k] int64): the k best rows of c for every query, ties towards the lower id,
     (-inf, -1) where fewer than k candidates remain outside the query's filter list.  `ic` (int64 [C], strictly ascending node
-    ids): the k best among those rows only (ghf_score_topk_sub); the ids returned are node ids."""
+    ids): the k best among those rows only (ghf_score_topk_sub); the ids returned are node ids.  `bias` (fp32 [N]): the scores
+    compared and returned are s + bias[row] (ghf_score_topk_b); -inf there means "never this row"."""
     q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, "score_topk")
     k = int(k)
     if not 1 <= k <= 128:
         raise ValueError(f"score_topk: k = {k} outside 1..128")
     N, d = c.size(0), c.size(1)
     ic = _ic_arg(ic, c, "score_topk")
-    if ic is None:
+    bias = _bias_arg(bias, c, "score_topk")
+    C = 0 if ic is None else ic.numel()
+    if bias is not None:
+        ws = _workspace(workspace, score_topk_b_workspace_bytes, q.device, "score_topk", B=B, N=N, C=C, d=d, k=k, nnz=nnz)
+    elif ic is None:
         ws = _workspace(workspace, score_topk_workspace_bytes, q.device, "score_topk", B=B, N=N, d=d, k=k)
     else:
         ws = _workspace(workspace, score_topk_sub_workspace_bytes, q.device, "score_topk", B=B, C=ic.numel(), d=d, k=k, nnz=nnz)
@@ -759,6 +827,10 @@ def score_topk(q: torch.Tensor, c: torch.Tensor, k: int, iq: Optional[torch.Tens
         scores, ids = _req(out[0], torch.float32, "out[0]"), _req(out[1], torch.int64, "out[1]")
         if tuple(scores.shape) != (B, k) or tuple(ids.shape) != (B, k) or not (out[0].is_contiguous() and out[1].is_contiguous()):
             raise ValueError(f"score_topk: out must be contiguous fp32 and int64 [{B}, {k}] tensors")
+    if bias is not None:
+        _check(load().ghf_score_topk_b(_ptr(q), _ptr(c), _ptr(iq), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d, k, _ptr(ic),
+                                       C, _ptr(bias), _ptr(ws), ws.numel(), _ptr(scores), _ptr(ids), _stream()), "ghf_score_topk_b")
+        return scores, ids
     if ic is not None:
         _check(load().ghf_score_topk_sub(_ptr(q), _ptr(c), _ptr(iq), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d, k,
                                          _ptr(ic), ic.numel(), _ptr(ws), ws.numel(), _ptr(scores), _ptr(ids), _stream()),
@@ -818,17 +890,26 @@ def _scale_arg(scale, what: str) -> float:
 def score_softmax_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optional[torch.Tensor] = None,
                       filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0,
                       workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
-                      ic: Optional[torch.Tensor] = None):
+                      ic: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
     """(loss, lse) fp32 [B]: lse[i] = log sum_j exp(scale q[iq[i]] . c[j]) over every row j of c outside query i's filter
     list (CSR, each list sorted ascending; the target always stays in), loss[i] = lse[i] - scale q[iq[i]] . c[target[i]].
     Nothing of size B x N is stored.  With `workspace` (uint8, score_softmax_workspace_bytes) and `out` given the call
     allocates nothing.  `ic` (int64 [C], strictly ascending node ids): the sum runs over those rows of c only
     (ghf_score_softmax_fwd_sub; workspace: score_softmax_sub_workspace_bytes); a query whose target is not among them gets
-    NaN."""
+    NaN.  `bias` (fp32 [N]): every logit is fmaf(scale, q . c[j], bias[j]), the bias not scaled (ghf_score_softmax_fwd_b;
+    workspace: score_softmax_b_workspace_bytes with C = 0 for every node)."""
     q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, "score_softmax_fwd")
     N, d = c.size(0), c.size(1)
     ic = _ic_arg(ic, c, "score_softmax_fwd")
     loss, lse = _f32_out_pair(out, (B,), (B,), q.device, "score_softmax_fwd")
+    bias = _bias_arg(bias, c, "score_softmax_fwd")
+    if bias is not None:
+        C = 0 if ic is None else ic.numel()
+        ws = _workspace(workspace, score_softmax_b_workspace_bytes, q.device, "score_softmax_fwd", B=B, N=N, C=C, d=d, nnz=nnz)
+        _check(load().ghf_score_softmax_fwd_b(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0),
+                                              N, B, d, scale, _ptr(ic), C, _ptr(bias), _ptr(ws), ws.numel(), _ptr(loss), _ptr(lse),
+                                              _stream()), "ghf_score_softmax_fwd_b")
+        return loss, lse
     if ic is not None:
         ws = _workspace(workspace, score_softmax_sub_workspace_bytes, q.device, "score_softmax_fwd", B=B, C=ic.numel(), d=d, nnz=nnz)
         _check(load().ghf_score_softmax_fwd_sub(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0),
@@ -844,16 +925,29 @@ def score_softmax_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq
 def score_softmax_bwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, lse: torch.Tensor, grad_loss: torch.Tensor,
                       iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
                       filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0, workspace: Optional[torch.Tensor] = None,
-                      out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ic: Optional[torch.Tensor] = None):
+                      out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ic: Optional[torch.Tensor] = None,
+                      bias: Optional[torch.Tensor] = None, want_db: bool = True):
     """(dq [B, d], dc [N, d]) fp32 of include/ghf.h: ghf_score_softmax_bwd — dq per query (not scattered through iq), every
     row of dc written.  `lse` is the forward's.  With `ic` (the forward's): ghf_score_softmax_bwd_sub, dc is [C, d], row j the
-    gradient of row ic[j] of c."""
+    gradient of row ic[j] of c.  With `bias` (the forward's): ghf_score_softmax_bwd_b, and the result is (dq, dc, db), db fp32
+    [N] ([C] with ic, entry j belonging to node ic[j]) the bias's gradient, None when `want_db` is False."""
     q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, "score_softmax_bwd")
     lse, grad_loss = _req(lse, torch.float32, "lse"), _req(grad_loss, torch.float32, "grad_loss")
     if lse.numel() != B or grad_loss.numel() != B:
         raise ValueError(f"score_softmax_bwd: lse and grad_loss must hold B = {B} values")
     N, d = c.size(0), c.size(1)
     ic = _ic_arg(ic, c, "score_softmax_bwd")
+    bias = _bias_arg(bias, c, "score_softmax_bwd")
+    if bias is not None:
+        C = 0 if ic is None else ic.numel()
+        M = C if C else N
+        ws = _workspace(workspace, score_softmax_bwd_b_workspace_bytes, q.device, "score_softmax_bwd", B=B, N=N, C=C, d=d, nnz=nnz)
+        dq, dc = _f32_out_pair(out, (B, d), (M, d), q.device, "score_softmax_bwd")
+        db = torch.empty(M, dtype=torch.float32, device=q.device) if want_db else None
+        _check(load().ghf_score_softmax_bwd_b(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0),
+                                              N, B, d, scale, _ptr(lse), _ptr(grad_loss), _ptr(ic), C, _ptr(bias), _ptr(ws),
+                                              ws.numel(), _ptr(dq), _ptr(dc), _ptr(db), _stream()), "ghf_score_softmax_bwd_b")
+        return dq, dc, db
     if ic is not None:
         C = ic.numel()
         ws = _workspace(workspace, score_softmax_bwd_sub_workspace_bytes, q.device, "score_softmax_bwd", B=B, C=C, d=d, nnz=nnz)
@@ -898,16 +992,25 @@ def _bce_args(q, c, iq, pos_ptr, pos_idx, scale, smoothing, what: str):
 def score_bce_fwd(q: torch.Tensor, c: torch.Tensor, iq: Optional[torch.Tensor] = None, pos_ptr: Optional[torch.Tensor] = None,
                   pos_idx: Optional[torch.Tensor] = None, scale: float = 1.0, smoothing: float = 0.0,
                   workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                  ic: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  ic: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """loss fp32 [B]: binary_cross_entropy_with_logits(scale q[iq[i]] . c[j], y_ij, reduction="sum") over every row j of c, with
     y_ij = (1 - smoothing) [j in query i's list] + smoothing / N (CSR lists, each sorted ascending, a repeated id counting once).
     Nothing of size B x N is stored.  With `workspace` (uint8, score_bce_workspace_bytes) and `out` given the call allocates
     nothing.  `ic` (int64 [C], strictly ascending node ids): the loss over those rows of c alone, smoothing / C, listed ids
-    that are no candidates taking no part (ghf_score_bce_fwd_sub; workspace: score_bce_sub_workspace_bytes)."""
+    that are no candidates taking no part (ghf_score_bce_fwd_sub; workspace: score_bce_sub_workspace_bytes).  `bias` (fp32 [N],
+    finite): every logit is fmaf(scale, q . c[j], bias[j]) (ghf_score_bce_fwd_b; workspace: score_bce_b_workspace_bytes)."""
     q, c, iq, pos_ptr, pos_idx, B, nnz, scale, smoothing = _bce_args(q, c, iq, pos_ptr, pos_idx, scale, smoothing, "score_bce_fwd")
     N, d = c.size(0), c.size(1)
     ic = _ic_arg(ic, c, "score_bce_fwd")
     loss = _f32_out(out, (B,), q.device, "score_bce_fwd")
+    bias = _bias_arg(bias, c, "score_bce_fwd")
+    if bias is not None:
+        C = 0 if ic is None else ic.numel()
+        ws = _workspace(workspace, score_bce_b_workspace_bytes, q.device, "score_bce_fwd", B=B, N=N, C=C, d=d, nnz=nnz)
+        _check(load().ghf_score_bce_fwd_b(_ptr(q), _ptr(c), _ptr(iq), _ptr(pos_ptr), _ptr(pos_idx), nnz, q.size(0), N, B, d, scale,
+                                          smoothing, _ptr(ic), C, _ptr(bias), _ptr(ws), ws.numel(), _ptr(loss), _stream()),
+               "ghf_score_bce_fwd_b")
+        return loss
     if ic is not None:
         ws = _workspace(workspace, score_bce_sub_workspace_bytes, q.device, "score_bce_fwd", B=B, C=ic.numel(), d=d, nnz=nnz)
         _check(load().ghf_score_bce_fwd_sub(_ptr(q), _ptr(c), _ptr(iq), _ptr(pos_ptr), _ptr(pos_idx), nnz, q.size(0), N, B, d, scale,
@@ -923,16 +1026,29 @@ def score_bce_fwd(q: torch.Tensor, c: torch.Tensor, iq: Optional[torch.Tensor] =
 def score_bce_bwd(q: torch.Tensor, c: torch.Tensor, loss: torch.Tensor, grad_loss: torch.Tensor, iq: Optional[torch.Tensor] = None,
                   pos_ptr: Optional[torch.Tensor] = None, pos_idx: Optional[torch.Tensor] = None, scale: float = 1.0,
                   smoothing: float = 0.0, workspace: Optional[torch.Tensor] = None,
-                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ic: Optional[torch.Tensor] = None):
+                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ic: Optional[torch.Tensor] = None,
+                  bias: Optional[torch.Tensor] = None, want_db: bool = True):
     """(dq [B, d], dc [N, d]) fp32 of include/ghf.h: ghf_score_bce_bwd — dq per query (not scattered through iq), every row
     of dc written.  `loss` is the forward's (a NaN entry: that query takes no part).  With `ic` (the forward's):
-    ghf_score_bce_bwd_sub, dc is [C, d], row j the gradient of row ic[j] of c."""
+    ghf_score_bce_bwd_sub, dc is [C, d], row j the gradient of row ic[j] of c.  With `bias` (the forward's): ghf_score_bce_bwd_b,
+    and the result is (dq, dc, db) as score_softmax_bwd's."""
     q, c, iq, pos_ptr, pos_idx, B, nnz, scale, smoothing = _bce_args(q, c, iq, pos_ptr, pos_idx, scale, smoothing, "score_bce_bwd")
     loss, grad_loss = _req(loss, torch.float32, "loss"), _req(grad_loss, torch.float32, "grad_loss")
     if loss.numel() != B or grad_loss.numel() != B:
         raise ValueError(f"score_bce_bwd: loss and grad_loss must hold B = {B} values")
     N, d = c.size(0), c.size(1)
     ic = _ic_arg(ic, c, "score_bce_bwd")
+    bias = _bias_arg(bias, c, "score_bce_bwd")
+    if bias is not None:
+        C = 0 if ic is None else ic.numel()
+        M = C if C else N
+        ws = _workspace(workspace, score_bce_bwd_b_workspace_bytes, q.device, "score_bce_bwd", B=B, N=N, C=C, d=d, nnz=nnz)
+        dq, dc = _f32_out_pair(out, (B, d), (M, d), q.device, "score_bce_bwd")
+        db = torch.empty(M, dtype=torch.float32, device=q.device) if want_db else None
+        _check(load().ghf_score_bce_bwd_b(_ptr(q), _ptr(c), _ptr(iq), _ptr(pos_ptr), _ptr(pos_idx), nnz, q.size(0), N, B, d, scale,
+                                          smoothing, _ptr(loss), _ptr(grad_loss), _ptr(ic), C, _ptr(bias), _ptr(ws), ws.numel(),
+                                          _ptr(dq), _ptr(dc), _ptr(db), _stream()), "ghf_score_bce_bwd_b")
+        return dq, dc, db
     if ic is not None:
         C = ic.numel()
         ws = _workspace(workspace, score_bce_bwd_sub_workspace_bytes, q.device, "score_bce_bwd", B=B, C=C, d=d, nnz=nnz)

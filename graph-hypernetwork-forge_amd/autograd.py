@@ -426,11 +426,24 @@ def _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand=None):
     added into a zeroed [N, d] gradient at the rows `cand` names (ghf_rows_accumulate_any — ghf_rows_accumulate for every
     row width the losses take —: the ids are distinct, one add per element, so reproducible too); every other row of it
     stays exactly zero.  Nothing of size [N, d] is made when embs needs no gradient."""
+    if rows is None and not ctx.needs_input_grad[0]:        # recorded for the bias alone: embs is data
+        return None, None
     if cand is not None and (rows is None or ctx.needs_input_grad[0]):
         dc = _native.rows_accumulate(torch.zeros_like(embs), cand, dc, any_width=True)
     if rows is None:
         return _native.add3(dc, _fold_rows(dq, query, embs.size(0)), out=dc), None
     return (dc if ctx.needs_input_grad[0] else None), (dq if ctx.needs_input_grad[1] else None)
+
+
+def _bias_grad(ctx, pos: int, db, bias, cand):
+    """The [N] gradient of a loss's per-candidate bias (input number `pos`) from its backward call's db: db itself for an
+    all-node call; over a candidate subset db is [C], entry j belonging to node cand[j] — the ids are distinct, so one copy
+    into a zeroed [N] places it, and every other node's entry stays exactly zero."""
+    if bias is None or not ctx.needs_input_grad[pos]:
+        return None
+    if cand is None:
+        return db
+    return torch.zeros_like(bias).index_copy_(0, cand, db)
 
 
 class SoftmaxLossFn(torch.autograd.Function):
@@ -440,26 +453,34 @@ class SoftmaxLossFn(torch.autograd.Function):
     exist neither here nor in the backward, which recomputes them tile by tile from the saved lse (ghf_score_softmax_bwd);
     _all_node_loss_grads turns its (dq, dc) into the gradients.  `cand` (ascending node ids, HyperGNN._candidate_ids' form with
     the targets added) restricts the sum to those nodes (ghf_score_softmax_fwd_sub / _bwd_sub): dc is then one row per
-    candidate and is added into embs' own rows."""
+    candidate and is added into embs' own rows.  `bias` (fp32 [N], one entry per node): the logits are fmaf(scale, q_i . embs[j],
+    bias[j]) (ghf_score_softmax_fwd_b / _bwd_b; None runs exactly the calls above); its gradient is the backward's db
+    (_bias_grad)."""
 
     @staticmethod
-    def forward(ctx, embs, rows, query, target, ptr, idx, scale: float, cand=None):
+    def forward(ctx, embs, rows, query, target, ptr, idx, scale: float, cand=None, bias=None):
         assert (rows is None) != (query is None)
         embs = embs.contiguous().float()
         rows = None if rows is None else rows.contiguous().float()
+        bias = None if bias is None else bias.contiguous()
         loss, lse = _native.score_softmax_fwd(embs if rows is None else rows, embs, target, iq=query, filt_ptr=ptr, filt_idx=idx,
-                                              scale=scale, ic=cand)
-        ctx.save_for_backward(embs, rows, query, target, ptr, idx, lse, cand)
+                                              scale=scale, ic=cand, bias=bias)
+        ctx.save_for_backward(embs, rows, query, target, ptr, idx, lse, cand, bias)
         ctx.scale = scale
         return loss
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        embs, rows, query, target, ptr, idx, lse, cand = ctx.saved_tensors
-        dq, dc = _native.score_softmax_bwd(embs if rows is None else rows, embs, target, lse, g.contiguous().float(), iq=query,
-                                           filt_ptr=ptr, filt_idx=idx, scale=ctx.scale, ic=cand)
-        return _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand) + (None,) * 6
+        embs, rows, query, target, ptr, idx, lse, cand, bias = ctx.saved_tensors
+        if bias is None:
+            dq, dc = _native.score_softmax_bwd(embs if rows is None else rows, embs, target, lse, g.contiguous().float(), iq=query,
+                                               filt_ptr=ptr, filt_idx=idx, scale=ctx.scale, ic=cand)
+            return _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand) + (None,) * 7
+        dq, dc, db = _native.score_softmax_bwd(embs if rows is None else rows, embs, target, lse, g.contiguous().float(), iq=query,
+                                               filt_ptr=ptr, filt_idx=idx, scale=ctx.scale, ic=cand, bias=bias,
+                                               want_db=ctx.needs_input_grad[8])
+        return _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand) + (None,) * 6 + (_bias_grad(ctx, 8, db, bias, cand),)
 
 
 class BceLossFn(torch.autograd.Function):
@@ -467,26 +488,34 @@ class BceLossFn(torch.autograd.Function):
     + smoothing / N (HyperGNN.bce_loss; include/ghf.h: ghf_score_bce_fwd), q_i and the pair `rows` / `query` as in
     SoftmaxLossFn.  Neither the [B, N] logits nor the labels exist, here or in the backward, which recomputes the logits tile
     by tile (ghf_score_bce_bwd); _all_node_loss_grads turns its (dq, dc) into the gradients.  `cand` (ascending node ids): the
-    loss over those C nodes alone, smoothing / C (ghf_score_bce_fwd_sub / _bwd_sub), dc one row per candidate."""
+    loss over those C nodes alone, smoothing / C (ghf_score_bce_fwd_sub / _bwd_sub), dc one row per candidate.  `bias` (fp32 [N],
+    finite): the learned entity bias of the 1-N models, logits fmaf(scale, q_i . embs[j], bias[j]) (ghf_score_bce_fwd_b /
+    _bwd_b; None runs exactly the calls above); its gradient is the backward's db (_bias_grad)."""
 
     @staticmethod
-    def forward(ctx, embs, rows, query, ptr, idx, scale: float, smoothing: float, cand=None):
+    def forward(ctx, embs, rows, query, ptr, idx, scale: float, smoothing: float, cand=None, bias=None):
         assert (rows is None) != (query is None)
         embs = embs.contiguous().float()
         rows = None if rows is None else rows.contiguous().float()
+        bias = None if bias is None else bias.contiguous()
         loss = _native.score_bce_fwd(embs if rows is None else rows, embs, iq=query, pos_ptr=ptr, pos_idx=idx, scale=scale,
-                                     smoothing=smoothing, ic=cand)
-        ctx.save_for_backward(embs, rows, query, ptr, idx, loss, cand)
+                                     smoothing=smoothing, ic=cand, bias=bias)
+        ctx.save_for_backward(embs, rows, query, ptr, idx, loss, cand, bias)
         ctx.scale, ctx.smoothing = scale, smoothing
         return loss
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        embs, rows, query, ptr, idx, loss, cand = ctx.saved_tensors
-        dq, dc = _native.score_bce_bwd(embs if rows is None else rows, embs, loss, g.contiguous().float(), iq=query, pos_ptr=ptr,
-                                       pos_idx=idx, scale=ctx.scale, smoothing=ctx.smoothing, ic=cand)
-        return _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand) + (None,) * 6
+        embs, rows, query, ptr, idx, loss, cand, bias = ctx.saved_tensors
+        if bias is None:
+            dq, dc = _native.score_bce_bwd(embs if rows is None else rows, embs, loss, g.contiguous().float(), iq=query, pos_ptr=ptr,
+                                           pos_idx=idx, scale=ctx.scale, smoothing=ctx.smoothing, ic=cand)
+            return _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand) + (None,) * 7
+        dq, dc, db = _native.score_bce_bwd(embs if rows is None else rows, embs, loss, g.contiguous().float(), iq=query, pos_ptr=ptr,
+                                           pos_idx=idx, scale=ctx.scale, smoothing=ctx.smoothing, ic=cand, bias=bias,
+                                           want_db=ctx.needs_input_grad[8])
+        return _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand) + (None,) * 6 + (_bias_grad(ctx, 8, db, bias, cand),)
 
 
 class ScorePairsFn(torch.autograd.Function):

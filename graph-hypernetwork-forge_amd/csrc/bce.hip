@@ -34,6 +34,13 @@ size_t score_bce_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz) {
     return base && map ? base + map : 0;
 }
 
+// with a per-candidate bias: C = 0 is the all-node call (no id map), C > 0 adds the subset's gathered bias [C]
+size_t score_bce_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    if (C <= 0) return score_bce_workspace_bytes(B, N, d);
+    const size_t base = score_bce_sub_workspace_bytes(B, C, d, nnz);
+    return base ? base + rk_align((size_t)C * 4) : 0;
+}
+
 __global__ __launch_bounds__(256) void bce_finish_kernel(const float* __restrict__ part, const int* __restrict__ valid, int64_t B,
                                                          int64_t slabs, float pos_w, float neg_w, float* __restrict__ loss) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -50,14 +57,22 @@ __global__ __launch_bounds__(256) void bce_finish_kernel(const float* __restrict
 
 int launch_score_bce_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, void* ws,
-                         size_t ws_bytes, float* loss, hipStream_t stream, const int64_t* ic, int64_t C) {
+                         size_t ws_bytes, float* loss, hipStream_t stream, const int64_t* ic, int64_t C, const float* bias) {
     RankArgs a;
     const int64_t M = ic ? C : N;                    // the candidates the sweep runs over, and the labels' smoothing / M
     GHF_REQUIRE(!ic || (C > 0 && C <= N), "score_bce_fwd: need 1 <= C <= N candidates");
     const size_t base = score_bce_workspace_bytes(B, M, d);
-    const size_t need = ic ? score_bce_sub_workspace_bytes(B, C, d, nnz) : base;
-    int rc = score_open("score_bce_fwd", softmax_geom, need, q, c, iq, pos_ptr, pos_idx, nnz, rows_q, M, B, d, ws_bytes, &a);
+    const size_t need = ic ? score_bce_sub_workspace_bytes(B, C, d, nnz) : base;      // with a bias over a subset: + its [C] floats
+    const size_t need_b = bias && ic && need ? need + rk_align((size_t)C * 4) : need;
+    int rc = score_open("score_bce_fwd", softmax_geom, need_b, q, c, iq, pos_ptr, pos_idx, nnz, rows_q, M, B, d, ws_bytes, &a);
     if (rc != GHF_OK) return rc;
+    const float* bias_c = bias;                      // the bias in the sweep's candidate space
+    if (bias && ic) {
+        GHF_REQUIRE(need > 0, "candidates: B or nnz out of range");
+        bias_c = (float*)((char*)ws + need);
+        rc = launch_cand_bias(bias, ic, C, N, (float*)((char*)ws + need), stream);
+        if (rc != GHF_OK) return rc;
+    }
     int* valid = (int*)ws;
     const unsigned qb = (unsigned)cdiv(B, 256);
     if (ic) {
@@ -76,7 +91,7 @@ int launch_score_bce_fwd(const float* q, const float* c, const int64_t* iq, cons
         }
     }
     a.scale = scale; a.ws_bce = (float*)((char*)ws + rk_align((size_t)B * 4));
-    rc = launch_rank_tiles<RK_BCE>(a, stream, ic, N);
+    rc = launch_rank_tiles<RK_BCE>(a, stream, ic, N, bias_c);
     if (rc != GHF_OK) return rc;
     bce_finish_kernel<<<qb, 256, 0, stream>>>(a.ws_bce, valid, B, a.slabs, 1.f - smoothing, smoothing / (float)M, loss);
     GHF_LAUNCH_CHECK();

@@ -124,6 +124,23 @@ __global__ __launch_bounds__(256) void cand_compact_kernel(const int64_t* __rest
     }
 }
 
+// one thread per candidate: the bias of node ic[j] at position j, where the BIAS sweeps read it; an id outside
+// the table reads nothing (cand_check_kernel reports such a list, and every query is then invalid)
+__global__ __launch_bounds__(256) void cand_bias_kernel(const float* __restrict__ bias, const int64_t* __restrict__ ic, int64_t C,
+                                                        int64_t N, float* __restrict__ out) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= C) return;
+    const int64_t id = ic[j];
+    out[j] = id >= 0 && id < N ? bias[id] : 0.f;
+}
+
+int launch_cand_bias(const float* bias, const int64_t* ic, int64_t C, int64_t N, float* out, hipStream_t stream) {
+    GHF_REQUIRE(bias && ic && out && C > 0 && C <= N, "candidates: bias gather needs 1 <= C <= N ids");
+    cand_bias_kernel<<<(unsigned)cdiv(C, 256), 256, 0, stream>>>(bias, ic, C, N, out);
+    GHF_LAUNCH_CHECK();
+    return GHF_OK;
+}
+
 int launch_cand_map(const float* q, const float* c, const int64_t* iq, const int64_t* target, bool target_in,
                     const int64_t* list_ptr, const int64_t* list_idx, int64_t nnz, const int64_t* ic, int64_t C, int64_t rows_q,
                     int64_t N, int64_t B, int d, const float* lse, float* t, int* valid, int64_t* greater, int64_t* equal, void* ws,

@@ -808,6 +808,108 @@ int ghf_score_bce_bwd_sub(const float* q, const float* c, const int64_t* iq, con
 
 #undef GHF_SUB_CHECK
 
+// the same six with a per-candidate bias (include/ghf.h): ic = NULL with C = 0 is every node, otherwise the
+// subset's rules; the bias itself is required
+#define GHF_BIAS_CHECK(op)                                                                              \
+    do {                                                                                                \
+        GHF_REQUIRE(bias, op ": null bias");                                                            \
+        GHF_REQUIRE(ic ? (C > 0 && C <= N) : C == 0, op ": need ic and 1 <= C <= N, or ic = NULL and C = 0"); \
+    } while (0)
+
+size_t ghf_score_rank_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    return score_rank_b_workspace_bytes(B, N, C, d, nnz);
+}
+
+int ghf_score_rank_b(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                     const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, const int64_t* ic,
+                     int64_t C, const float* bias, void* workspace, size_t workspace_bytes, int64_t* greater, int64_t* equal,
+                     void* stream) {
+    const int rc = score_entry_check("score_rank_b", "filter", q && c && target && greater && equal, filt_ptr, filt_idx, nnz, 1.f,
+                                     0.f, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_BIAS_CHECK("score_rank_b");
+    return launch_score_rank(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, workspace, workspace_bytes, greater, equal,
+                             (hipStream_t)stream, ic, C, bias);
+}
+
+size_t ghf_score_topk_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int k, int64_t nnz) {
+    return score_topk_b_workspace_bytes(B, N, C, d, k, nnz);
+}
+
+int ghf_score_topk_b(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
+                     int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, const int64_t* ic, int64_t C,
+                     const float* bias, void* workspace, size_t workspace_bytes, float* scores, int64_t* ids, void* stream) {
+    const int rc = score_entry_check("score_topk_b", "filter", q && c && scores && ids, filt_ptr, filt_idx, nnz, 1.f, 0.f, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_BIAS_CHECK("score_topk_b");
+    return launch_score_topk(q, c, iq, filt_ptr, filt_idx, nnz, rows_q, N, B, d, k, workspace, workspace_bytes, scores, ids,
+                             (hipStream_t)stream, ic, C, bias);
+}
+
+size_t ghf_score_softmax_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    return score_softmax_b_workspace_bytes(B, N, C, d, nnz);
+}
+
+int ghf_score_softmax_fwd_b(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                            const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                            const int64_t* ic, int64_t C, const float* bias, void* workspace, size_t workspace_bytes, float* loss,
+                            float* lse, void* stream) {
+    const int rc = score_entry_check("score_softmax_fwd_b", "filter", q && c && target && loss && lse, filt_ptr, filt_idx, nnz, scale,
+                                     0.f, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_BIAS_CHECK("score_softmax_fwd_b");
+    return launch_score_softmax_fwd(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, workspace, workspace_bytes,
+                                    loss, lse, (hipStream_t)stream, ic, C, bias);
+}
+
+size_t ghf_score_softmax_bwd_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    return score_softmax_bwd_b_workspace_bytes(B, N, C, d, nnz);
+}
+
+int ghf_score_softmax_bwd_b(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                            const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                            const float* lse, const float* grad_loss, const int64_t* ic, int64_t C, const float* bias,
+                            void* workspace, size_t workspace_bytes, float* dq, float* dc, float* db, void* stream) {
+    const int rc = score_entry_check("score_softmax_bwd_b", "filter", q && c && target && lse && grad_loss && dq && dc, filt_ptr,
+                                     filt_idx, nnz, scale, 0.f, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_BIAS_CHECK("score_softmax_bwd_b");
+    return launch_score_softmax_bwd(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, lse, grad_loss, workspace,
+                                    workspace_bytes, dq, dc, (hipStream_t)stream, ic, C, bias, db);
+}
+
+size_t ghf_score_bce_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    return score_bce_b_workspace_bytes(B, N, C, d, nnz);
+}
+
+int ghf_score_bce_fwd_b(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
+                        int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const int64_t* ic,
+                        int64_t C, const float* bias, void* workspace, size_t workspace_bytes, float* loss, void* stream) {
+    const int rc = score_entry_check("score_bce_fwd_b", "positive", q && c && loss, pos_ptr, pos_idx, nnz, scale, smoothing, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_BIAS_CHECK("score_bce_fwd_b");
+    return launch_score_bce_fwd(q, c, iq, pos_ptr, pos_idx, nnz, rows_q, N, B, d, scale, smoothing, workspace, workspace_bytes, loss,
+                                (hipStream_t)stream, ic, C, bias);
+}
+
+size_t ghf_score_bce_bwd_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    return score_bce_bwd_b_workspace_bytes(B, N, C, d, nnz);
+}
+
+int ghf_score_bce_bwd_b(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
+                        int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
+                        const float* grad_loss, const int64_t* ic, int64_t C, const float* bias, void* workspace,
+                        size_t workspace_bytes, float* dq, float* dc, float* db, void* stream) {
+    const int rc = score_entry_check("score_bce_bwd_b", "positive", q && c && loss && grad_loss && dq && dc, pos_ptr, pos_idx, nnz,
+                                     scale, smoothing, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_BIAS_CHECK("score_bce_bwd_b");
+    return launch_score_bce_bwd(q, c, iq, pos_ptr, pos_idx, nnz, rows_q, N, B, d, scale, smoothing, loss, grad_loss, workspace,
+                                workspace_bytes, dq, dc, (hipStream_t)stream, ic, C, bias, db);
+}
+
+#undef GHF_BIAS_CHECK
+
 size_t ghf_relation_rows_workspace_bytes(int64_t B, int R) { return relation_rows_workspace_bytes(B, R); }
 
 int ghf_relation_rows(const float* x, const int64_t* ix, const int64_t* rel, const float* W, const float* bias,

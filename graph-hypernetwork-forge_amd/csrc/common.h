@@ -172,35 +172,48 @@ size_t score_rank_workspace_bytes(int64_t B, int64_t N, int d);
 size_t score_topk_workspace_bytes(int64_t B, int64_t N, int d, int k);
 size_t score_rank_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
 size_t score_topk_sub_workspace_bytes(int64_t B, int64_t C, int d, int k, int64_t nnz);
+// With `bias` [N] fp32 a launch adds bias[j] to every score of node j; the *_b_workspace_bytes are those
+// calls' (C = 0: every node).  The two backwards write db ([N], or [C] over a subset) where it is given.
+size_t score_rank_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+size_t score_topk_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int k, int64_t nnz);
 int launch_score_rank(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                       const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, void* ws,
-                      size_t ws_bytes, int64_t* greater, int64_t* equal, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0);
+                      size_t ws_bytes, int64_t* greater, int64_t* equal, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0,
+                      const float* bias = nullptr);
 int launch_score_topk(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
                       int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, void* ws, size_t ws_bytes, float* scores,
-                      int64_t* ids, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0);
+                      int64_t* ids, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0, const float* bias = nullptr);
 // softmax.hip
 size_t score_softmax_workspace_bytes(int64_t B, int64_t N, int d);
 size_t score_softmax_bwd_workspace_bytes(int64_t B, int64_t N, int d);
 size_t score_softmax_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
 size_t score_softmax_bwd_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
+size_t score_softmax_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+size_t score_softmax_bwd_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
 int launch_score_softmax_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
-                             void* ws, size_t ws_bytes, float* loss, float* lse, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0);
+                             void* ws, size_t ws_bytes, float* loss, float* lse, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0,
+                             const float* bias = nullptr);
 int launch_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                              const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc,
-                             hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0);
+                             hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0, const float* bias = nullptr,
+                             float* db = nullptr);
 // bce.hip (forward) and softmax.hip (backward: softmax_bwd_kernel's second loss)
 size_t score_bce_workspace_bytes(int64_t B, int64_t N, int d);
 size_t score_bce_bwd_workspace_bytes(int64_t B, int64_t N, int d);
 size_t score_bce_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
 size_t score_bce_bwd_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz);
+size_t score_bce_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+size_t score_bce_bwd_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
 int launch_score_bce_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, void* ws,
-                         size_t ws_bytes, float* loss, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0);
+                         size_t ws_bytes, float* loss, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0,
+                         const float* bias = nullptr);
 int launch_score_bce_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
-                         const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0);
+                         const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc, hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0,
+                         const float* bias = nullptr, float* db = nullptr);
 // relation.hip
 size_t relation_rows_workspace_bytes(int64_t B, int R);
 int launch_relation_rows(const float* x, const int64_t* ix, const int64_t* rel, const float* W, const float* bias,

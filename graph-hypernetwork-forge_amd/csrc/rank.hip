@@ -70,15 +70,31 @@ size_t score_topk_sub_workspace_bytes(int64_t B, int64_t C, int d, int k, int64_
     return base && map ? base + map : 0;
 }
 
+// with a per-candidate bias: C = 0 is the all-node call (no id map), C > 0 adds the subset's gathered bias [C]
+size_t score_rank_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    if (C <= 0) return score_rank_workspace_bytes(B, N, d);
+    const size_t base = score_rank_sub_workspace_bytes(B, C, d, nnz);
+    return base ? base + rk_align((size_t)C * 4) : 0;
+}
+
+size_t score_topk_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int k, int64_t nnz) {
+    if (C <= 0) return score_topk_workspace_bytes(B, N, d, k);
+    const size_t base = score_topk_sub_workspace_bytes(B, C, d, k, nnz);
+    return base ? base + rk_align((size_t)C * 4) : 0;
+}
+
 // ---- rank: the small kernels around the sweep -----------------------------------------------------------------------------
 // one thread per filter entry: an id out of range marks its query; any other entry's score is recomputed and taken out of the
 // count it went into (lists are sorted: a repeat is the entry before; the target is taken out by rank_finish)
-__global__ __launch_bounds__(256) void rank_filter_kernel(const float* __restrict__ q, const float* __restrict__ c,
-                                                          const int64_t* __restrict__ iq, const int64_t* __restrict__ target,
-                                                          const int64_t* __restrict__ filt_ptr, const int64_t* __restrict__ filt_idx,
-                                                          int64_t nnz, int64_t N, int64_t B, int d, const float* __restrict__ t,
-                                                          int* valid, unsigned long long* __restrict__ greater,
-                                                          unsigned long long* __restrict__ equal, const int64_t* __restrict__ ic) {
+// (BIAS: the entry's score is the sweep's, s + bias[j], bias in the sweep's candidate space)
+template <bool BIAS>
+__device__ __forceinline__ void rank_filter_body(const float* __restrict__ q, const float* __restrict__ c,
+                                                 const int64_t* __restrict__ iq, const int64_t* __restrict__ target,
+                                                 const int64_t* __restrict__ filt_ptr, const int64_t* __restrict__ filt_idx,
+                                                 int64_t nnz, int64_t N, int64_t B, int d, const float* __restrict__ t,
+                                                 int* valid, unsigned long long* __restrict__ greater,
+                                                 unsigned long long* __restrict__ equal, const int64_t* __restrict__ ic,
+                                                 const float* __restrict__ bias) {
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= nnz) return;
     int64_t i;
@@ -92,10 +108,40 @@ __global__ __launch_bounds__(256) void rank_filter_kernel(const float* __restric
     if (j == target[i] || (e > filt_ptr[i] && filt_idx[e - 1] == j)) return;
     const int64_t r = iq ? iq[i] : i;                // in range: score_prep_kernel said so (valid[i] was 1)
     // over a candidate subset j and target[] are positions in ic (candidates.hip, which has checked ic)
-    const float s = dot_chain(q + (size_t)r * d, c + (size_t)(ic ? ic[j] : j) * d, d, rows_vec(q, d) && rows_vec(c, d));
+    float s = dot_chain(q + (size_t)r * d, c + (size_t)(ic ? ic[j] : j) * d, d, rows_vec(q, d) && rows_vec(c, d));
+    if constexpr (BIAS) s += bias[j];
     const float ti = t[i];
     if (s > ti) atomicAdd(&greater[i], ~0ull);
     else if (s == ti) atomicAdd(&equal[i], ~0ull);
+}
+
+__global__ __launch_bounds__(256) void rank_filter_kernel(const float* __restrict__ q, const float* __restrict__ c,
+                                                          const int64_t* __restrict__ iq, const int64_t* __restrict__ target,
+                                                          const int64_t* __restrict__ filt_ptr, const int64_t* __restrict__ filt_idx,
+                                                          int64_t nnz, int64_t N, int64_t B, int d, const float* __restrict__ t,
+                                                          int* valid, unsigned long long* __restrict__ greater,
+                                                          unsigned long long* __restrict__ equal, const int64_t* __restrict__ ic) {
+    rank_filter_body<false>(q, c, iq, target, filt_ptr, filt_idx, nnz, N, B, d, t, valid, greater, equal, ic, nullptr);
+}
+
+__global__ __launch_bounds__(256) void rank_filter_bias_kernel(const float* __restrict__ q, const float* __restrict__ c,
+                                                               const int64_t* __restrict__ iq, const int64_t* __restrict__ target,
+                                                               const int64_t* __restrict__ filt_ptr,
+                                                               const int64_t* __restrict__ filt_idx, int64_t nnz, int64_t N, int64_t B,
+                                                               int d, const float* __restrict__ t, int* valid,
+                                                               unsigned long long* __restrict__ greater,
+                                                               unsigned long long* __restrict__ equal,
+                                                               const int64_t* __restrict__ ic, const float* __restrict__ bias) {
+    rank_filter_body<true>(q, c, iq, target, filt_ptr, filt_idx, nnz, N, B, d, t, valid, greater, equal, ic, bias);
+}
+
+// one thread per query, behind the prep pass of a call with a bias: the target's score gets its own node's bias entry (the
+// target need not be a candidate, so `bias` and `target` are the caller's, in node ids).  A query that is not valid keeps NaN.
+__global__ __launch_bounds__(256) void rank_bias_target_kernel(const int64_t* __restrict__ target, const float* __restrict__ bias,
+                                                               const int* __restrict__ valid, int64_t B, float* __restrict__ t) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B || !valid[i]) return;
+    t[i] += bias[target[i]];
 }
 
 __global__ __launch_bounds__(256) void rank_finish_kernel(const float* __restrict__ t, const int* __restrict__ valid, int64_t B,
@@ -162,17 +208,27 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint64_t* __restr
 // ---- launches -------------------------------------------------------------------------------------------------------------
 int launch_score_rank(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                       const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, void* ws,
-                      size_t ws_bytes, int64_t* greater, int64_t* equal, hipStream_t stream, const int64_t* ic, int64_t C) {
+                      size_t ws_bytes, int64_t* greater, int64_t* equal, hipStream_t stream, const int64_t* ic, int64_t C,
+                      const float* bias) {
     RankArgs a;
     const int64_t M = ic ? C : N;                    // the candidates the sweep runs over
     GHF_REQUIRE(!ic || (C > 0 && C <= N), "score_rank: need 1 <= C <= N candidates");
     const size_t base = score_rank_workspace_bytes(B, M, d);
-    const size_t need = ic ? score_rank_sub_workspace_bytes(B, C, d, nnz) : base;
-    int rc = score_open("score_rank", rank_geom_rank, need, q, c, iq, filt_ptr, filt_idx, nnz, rows_q, M, B, d, ws_bytes, &a);
+    const size_t need = ic ? score_rank_sub_workspace_bytes(B, C, d, nnz) : base;      // with a bias over a subset: + its [C] floats
+    const size_t need_b = bias && ic && need ? need + rk_align((size_t)C * 4) : need;
+    int rc = score_open("score_rank", rank_geom_rank, need_b, q, c, iq, filt_ptr, filt_idx, nnz, rows_q, M, B, d, ws_bytes, &a);
     if (rc != GHF_OK) return rc;
     float* t = (float*)ws;
     int* valid = (int*)((char*)ws + rk_align((size_t)B * 4));
     const unsigned qb = (unsigned)cdiv(B, 256);
+    const float* bias_c = bias;                      // the bias in the sweep's candidate space
+    if (bias && ic) {
+        GHF_REQUIRE(need > 0, "candidates: B or nnz out of range");
+        bias_c = (float*)((char*)ws + need);
+        rc = launch_cand_bias(bias, ic, C, N, (float*)((char*)ws + need), stream);
+        if (rc != GHF_OK) return rc;
+    }
+    const int64_t* target_nodes = target;
     CandMap m = {};
     if (ic) {
         rc = launch_cand_map(q, c, iq, target, false, filt_ptr, filt_idx, nnz, ic, C, rows_q, N, B, d, nullptr, t, valid, greater,
@@ -184,10 +240,18 @@ int launch_score_rank(const float* q, const float* c, const int64_t* iq, const i
         score_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, target, rows_q, N, B, d, t, valid, (long long*)greater, (long long*)equal);
         GHF_LAUNCH_CHECK();
     }
+    if (bias) {
+        rank_bias_target_kernel<<<qb, 256, 0, stream>>>(target_nodes, bias, valid, B, t);
+        GHF_LAUNCH_CHECK();
+    }
     a.t = t; a.greater = (unsigned long long*)greater; a.equal = (unsigned long long*)equal;
-    rc = launch_rank_tiles<RK_RANK>(a, stream, ic, N);
+    rc = launch_rank_tiles<RK_RANK>(a, stream, ic, N, bias_c);
     if (rc != GHF_OK) return rc;
-    if (nnz > 0) {
+    if (nnz > 0 && bias) {
+        rank_filter_bias_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(q, c, iq, target, filt_ptr, filt_idx, nnz, M, B, d, t,
+                                                                             valid, a.greater, a.equal, ic, bias_c);
+        GHF_LAUNCH_CHECK();
+    } else if (nnz > 0) {
         rank_filter_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(q, c, iq, target, filt_ptr, filt_idx, nnz, M, B, d, t, valid,
                                                                         a.greater, a.equal, ic);
         GHF_LAUNCH_CHECK();
@@ -199,15 +263,23 @@ int launch_score_rank(const float* q, const float* c, const int64_t* iq, const i
 
 int launch_score_topk(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
                       int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, void* ws, size_t ws_bytes, float* scores,
-                      int64_t* ids, hipStream_t stream, const int64_t* ic, int64_t C) {
+                      int64_t* ids, hipStream_t stream, const int64_t* ic, int64_t C, const float* bias) {
     RankArgs a;
     const int64_t M = ic ? C : N;
     GHF_REQUIRE(k >= 1 && k <= TOPK_MAX_K, "score_topk: k = %d outside 1..%d", k, TOPK_MAX_K);
     GHF_REQUIRE(!ic || (C > 0 && C <= N), "score_topk: need 1 <= C <= N candidates");
     const size_t base = score_topk_workspace_bytes(B, M, d, k);
     const size_t need = ic ? score_topk_sub_workspace_bytes(B, C, d, k, nnz) : base;
-    int rc = score_open("score_topk", rank_geom_topk, need, q, c, iq, filt_ptr, filt_idx, nnz, rows_q, M, B, d, ws_bytes, &a);
+    const size_t need_b = bias && ic && need ? need + rk_align((size_t)C * 4) : need;
+    int rc = score_open("score_topk", rank_geom_topk, need_b, q, c, iq, filt_ptr, filt_idx, nnz, rows_q, M, B, d, ws_bytes, &a);
     if (rc != GHF_OK) return rc;
+    const float* bias_c = bias;
+    if (bias && ic) {
+        GHF_REQUIRE(need > 0, "candidates: B or nnz out of range");
+        bias_c = (float*)((char*)ws + need);
+        rc = launch_cand_bias(bias, ic, C, N, (float*)((char*)ws + need), stream);
+        if (rc != GHF_OK) return rc;
+    }
     int* valid = (int*)ws;
     a.k = k; a.cap = topk_cap(d, k); a.ws_key = (uint64_t*)((char*)ws + rk_align((size_t)B * 4));
     if (ic) {
@@ -224,7 +296,7 @@ int launch_score_topk(const float* q, const float* c, const int64_t* iq, const i
             GHF_LAUNCH_CHECK();
         }
     }
-    rc = launch_rank_tiles<RK_TOPK>(a, stream, ic, N);
+    rc = launch_rank_tiles<RK_TOPK>(a, stream, ic, N, bias_c);
     if (rc != GHF_OK) return rc;
     topk_merge_kernel<<<(unsigned)cdiv(B, 4), 256, 0, stream>>>(a.ws_key, valid, B, a.slabs, a.cap, k, scores, (long long*)ids, ic);
     GHF_LAUNCH_CHECK();

@@ -2,7 +2,9 @@
 // softmax.hip (1-vs-all softmax loss) and bce.hip (multi-label 1-vs-all BCE loss) share: geometry, the VALU form of the
 // accumulator's chain, the LDS layout and rank_tile_kernel with its four epilogues, and the host side around it: the two
 // kernels that validate ids ahead of a sweep, the checks that open a launch (score_open) and the choice of the instantiation
-// (launch_rank_tiles).  rank.hip's header comment describes the sweep.
+// (launch_rank_tiles).  rank.hip's header comment describes the sweep.  Two template flags select a variant of it, each with an
+// argument struct of its own so that the others keep theirs: SUB (a candidate subset, candidates.hip) and BIAS (a per-candidate
+// fp32 term on every score).
 #pragma once
 #include "common.h"
 
@@ -197,8 +199,15 @@ struct RankArgs {
 // N, the lists and the targets are then the count of, and positions in, ic.  A type of its own, so that the all-node
 // instantiations keep their argument block, and with it their code, as they are.
 struct RankSubArgs : RankArgs { const int64_t* ic; int64_t Nn; };
-template <bool SUB> struct RankKernelArgs { typedef RankArgs type; };
-template <> struct RankKernelArgs<true> { typedef RankSubArgs type; };
+template <bool SUB, bool BIAS = false> struct RankKernelArgs { typedef RankArgs type; };
+template <> struct RankKernelArgs<true, false> { typedef RankSubArgs type; };
+
+// a per-candidate bias (the BIAS instantiations): bias[j] is the fp32 term of the
+// sweep's candidate j, i.e. of node j in an all-node sweep (ic and Nn are then unused) and of node ic[j] over a subset, where
+// candidates.hip has gathered it into position space ahead of the sweep.  Rank and top-k compare s(i, j) + bias[j], the two
+// losses use fmaf(scale, s(i, j), bias[j]).  Again a type of its own: every other instantiation keeps its argument block.
+struct RankBiasArgs : RankSubArgs { const float* bias; };
+template <bool SUB> struct RankKernelArgs<SUB, true> { typedef RankBiasArgs type; };
 
 // row j of a sweep over the candidate subset ic [C] of a table of `rows` rows: absent past C or when the id is outside the
 // table (candidates.hip reports such a list; the sweep only has to read nothing outside c)
@@ -285,13 +294,14 @@ static __global__ __launch_bounds__(256) void score_prep_kernel(const float* __r
     valid[i] = ok ? 1 : 0;
 }
 
-static inline size_t rank_lds_bytes(int d, int BK, int CT) {
+// `bias`: the two buffers of CT bias values behind the counters (the BIAS instantiations)
+static inline size_t rank_lds_bytes(int d, int BK, int CT, bool bias = false) {
     const int dpad = (d + 7) & ~7;
-    return ((size_t)RK_TILE * (dpad + 4) + 2 * (size_t)CT * (BK + 4) + 2 * RK_TILE) * 4;
+    return ((size_t)RK_TILE * (dpad + 4) + 2 * (size_t)CT * (BK + 4) + 2 * RK_TILE + (bias ? 2 * CT : 0)) * 4;
 }
 
-template <int BK, int CT, int MODE, bool SUB = false>
-__global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKernelArgs<SUB>::type a) {
+template <int BK, int CT, int MODE, bool SUB = false, bool BIAS = false>
+__global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKernelArgs<SUB, BIAS>::type a) {
     constexpr bool TOPK = MODE == RK_TOPK, RANK = MODE == RK_RANK, SOFTMAX = MODE == RK_SOFTMAX, BCE = MODE == RK_BCE;
     constexpr bool CURSOR = SOFTMAX || BCE;             // the lists are walked by a cursor, in step with the sweep
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -305,6 +315,9 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
     int* sm0 = (int*)(Cs + 2 * CT * LDC);      // rank: greater counts; top-k: entry counts
     int* sm1 = sm0 + RK_TILE;                       // rank: equal counts;   top-k: thresholds (float bits)
     float* thrS = (float*)sm1;
+    // BIAS: the bias of the tile being multiplied and of the next one, CT values each; a tile's values are requested with its
+    // first chunk of rows (a register per thread of the first CT) and stored with it, so the epilogue reads them from LDS
+    float* Bs = (float*)(sm1 + RK_TILE);
 
     // Workgroups are dealt to the 8 XCDs round-robin; number them so that the ones an XCD runs at the same time are
     // neighbours, i.e. the query tiles of ONE candidate slab: the slab then comes from that XCD's L2 for all but the first.
@@ -401,6 +414,15 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
         }
     };
 
+    float bpre = 0.f;
+    int bb = 0;                                         // the bias buffer of the tile being multiplied
+    auto fetch_bias = [&](int64_t tile) {               // a candidate past N: 0 (the epilogues leave it out themselves)
+        if constexpr (BIAS) {
+            const int64_t cand = tile * CT + tid;
+            if (tid < CT) bpre = cand < a.N ? a.bias[cand] : 0.f;
+        }
+    };
+
     f32x16 acc[2][2];
 #pragma unroll
     for (int x = 0; x < 2; ++x)
@@ -413,8 +435,12 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
         load_ids(tile0, cid);
         load_ids(tile0 + 1, nid);
     }
+    if constexpr (BIAS) fetch_bias(tile0);
     fetch(tile0, 0);
     stash(0);
+    if constexpr (BIAS) {
+        if (tid < CT) Bs[tid] = bpre;
+    }
     __syncthreads();
 
     int64_t tile = tile0;
@@ -430,6 +456,9 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
                 for (int i = 0; i < NL; ++i) cid[i] = nid[i];
                 load_ids(ntile + 1, nid);
             }
+        }
+        if constexpr (BIAS) {
+            if (more && nkc == 0) fetch_bias(ntile);
         }
         if (more) fetch(ntile, nkc);
 
@@ -456,6 +485,26 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
         if (tile_done) {
             const int64_t base = tile * CT + wm * 64 + 4 * lh;     // + 32 tm + (r & 3) + 8 (r >> 2): the register's candidate
             const bool full = tile * CT + CT <= a.N;
+            // BIAS: the bias of the lane's 32 candidates (the same for both query columns), register e = 16 tm + r, read from
+            // LDS four at a time where it is used.  Rank and top-k add it to the scores where they stand; the losses fuse it
+            // into the multiply by scale.
+            auto bias4 = [&](int g) -> f32x4 {          // registers e = 4 g .. 4 g + 3
+                return *(const f32x4*)(Bs + bb * CT + wm * 64 + 4 * lh + 32 * (g >> 2) + 8 * (g & 3));
+            };
+            if constexpr (BIAS && (RANK || TOPK)) {
+#pragma unroll
+                for (int g = 0; g < 8; ++g) {
+                    const f32x4 b4 = bias4(g);
+#pragma unroll
+                    for (int tn = 0; tn < 2; ++tn)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) acc[g >> 2][tn][4 * (g & 3) + i] += b4[i];
+                }
+            }
+            auto logit = [&](int tn, int e) -> float {
+                if constexpr (BIAS) return fmaf(a.scale, acc[e >> 4][tn][e & 15], bias4(e >> 2)[e & 3]);
+                else return a.scale * acc[e >> 4][tn][e & 15];
+            };
             if (SOFTMAX) {
                 // online softmax: once per finished tile, a column's 32 registers enter its running (max, sum).  A tile whose
                 // id range holds none of the query's listed ids (the cursor says so) takes the plain path; the others look
@@ -466,13 +515,13 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
                     float v[32];
                     if (full && nxt[tn] >= tile_end) {
 #pragma unroll
-                        for (int e = 0; e < 32; ++e) v[e] = a.scale * acc[e >> 4][tn][e & 15];
+                        for (int e = 0; e < 32; ++e) v[e] = logit(tn, e);
                     } else {
 #pragma unroll
                         for (int e = 0; e < 32; ++e) {
                             const int64_t cand = base + 32 * (e >> 4) + (e & 3) + 8 * ((e & 15) >> 2);
                             const bool out = cand >= a.N || (cand != tgt[tn] && in_filter(a.filt_idx, f0[tn], f1[tn], cand));
-                            v[e] = out ? -INFINITY : a.scale * acc[e >> 4][tn][e & 15];
+                            v[e] = out ? -INFINITY : logit(tn, e);
                         }
                         while (nxt[tn] < tile_end) {
                             ++f0[tn];
@@ -501,7 +550,7 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
                     if (full && nxt[tn] >= tile_end) {
 #pragma unroll
                         for (int e = 0; e < 32; ++e) {
-                            const float z = a.scale * acc[e >> 4][tn][e & 15];
+                            const float z = logit(tn, e);
                             tsp += softplus(z);
                             tsz += z;
                         }
@@ -510,7 +559,7 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
 #pragma unroll
                         for (int e = 0; e < 32; ++e) {
                             const int64_t cand = base + 32 * (e >> 4) + (e & 3) + 8 * ((e & 15) >> 2);
-                            const float z = a.scale * acc[e >> 4][tn][e & 15];
+                            const float z = logit(tn, e);
                             const bool in = cand < a.N;
                             tsp += in ? softplus(z) : 0.f;
                             tsz += in ? z : 0.f;
@@ -573,6 +622,10 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
         }
 
         if (more) stash(buf ^ 1);
+        if constexpr (BIAS) {
+            if (more && nkc == 0 && tid < CT) Bs[(bb ^ 1) * CT + tid] = bpre;
+            if (tile_done) bb ^= 1;
+        }
         __syncthreads();
         if (TOPK && tile_done && more) {
             // a query whose buffer could overflow in the next tile keeps its k best now (wave w: queries w, w + 4, ...)
@@ -653,10 +706,26 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
 // ---- the host side every operation shares ---------------------------------------------------------------------------------
 // the sweep with epilogue MODE over a.qtiles x a.slabs workgroups: the one place that picks the instantiation.  With `ic`
 // (node ids of the a.N candidates, rows of a table of Nn rows) the sweep over that subset.
+// With `bias` (one value per candidate of the sweep: per node, or gathered through ic) the BIAS instantiations.
 template <int MODE>
-static int launch_rank_tiles(const RankArgs& a, hipStream_t stream, const int64_t* ic = nullptr, int64_t Nn = 0) {
+static int launch_rank_tiles(const RankArgs& a, hipStream_t stream, const int64_t* ic = nullptr, int64_t Nn = 0,
+                             const float* bias = nullptr) {
     const unsigned grid = (unsigned)(a.qtiles * a.slabs);
-    if (ic) {                                           // the same two shapes, rows through ic
+    if (bias) {
+        RankBiasArgs s;
+        static_cast<RankArgs&>(s) = a;
+        s.ic = ic; s.Nn = Nn; s.bias = bias;
+        const bool wide = rank_ctile(a.d) == 256;
+        const size_t lds = wide ? rank_lds_bytes(a.d, 32, 256, true) : rank_lds_bytes(a.d, 16, 128, true);
+#define GHF_RANK_BIAS_LAUNCH(BK, CT, SUBSET)                                                  \
+    do {                                                                                       \
+        GHF_SET_MAX_LDS((rank_tile_kernel<BK, CT, MODE, SUBSET, true>), lds);                  \
+        rank_tile_kernel<BK, CT, MODE, SUBSET, true><<<grid, CT * 2, lds, stream>>>(s);        \
+    } while (0)
+        if (wide) { if (ic) GHF_RANK_BIAS_LAUNCH(32, 256, true); else GHF_RANK_BIAS_LAUNCH(32, 256, false); }
+        else { if (ic) GHF_RANK_BIAS_LAUNCH(16, 128, true); else GHF_RANK_BIAS_LAUNCH(16, 128, false); }
+#undef GHF_RANK_BIAS_LAUNCH
+    } else if (ic) {                                           // the same two shapes, rows through ic
         RankSubArgs s;
         static_cast<RankArgs&>(s) = a;
         s.ic = ic; s.Nn = Nn;
@@ -717,5 +786,7 @@ int launch_cand_map(const float* q, const float* c, const int64_t* iq, const int
                     const int64_t* list_ptr, const int64_t* list_idx, int64_t nnz, const int64_t* ic, int64_t C, int64_t rows_q,
                     int64_t N, int64_t B, int d, const float* lse, float* t, int* valid, int64_t* greater, int64_t* equal, void* ws,
                     size_t ws_bytes, CandMap* m, hipStream_t stream);
+// out[j] = bias[ic[j]], j < C: a per-node bias in the position space of a sweep over ic (0 where ic[j] is outside [0, N))
+int launch_cand_bias(const float* bias, const int64_t* ic, int64_t C, int64_t N, float* out, hipStream_t stream);
 
 }  // namespace ghf

@@ -35,6 +35,11 @@
 //   G_ij = grad[i] scale (sigma(scale s(i,j)) - smoothing / N - (1 - smoothing) [j listed]),
 // the lists naming positives, not masks: the dq sweep's cursor says which steps hold listed ids, and the dc sweep's collected
 // pairs SUBTRACT grad scale (1 - smoothing) from their entries of G instead of zeroing them.
+//
+// A per-candidate bias (BIAS instantiations; include/ghf.h: the _b calls): every logit is fmaf(scale, s(i,j), b_j),
+// forward (rank_sweep.h) and backward, where the softmax forms p_ij = exp(fmaf(scale, s, b_j - lse[i])) so that a zero bias keeps
+// the bits.  The dq sweep stages the 64 bias values of a step with its streamed rows, the dc sweep loads its owner rows' once;
+// db[j] = sum_i G_ij / scale falls out of the dc sweep's second product, whose A operand is G itself (ascending query order).
 #include "common.h"
 #include "rank_sweep.h"
 
@@ -84,6 +89,19 @@ size_t score_softmax_bwd_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_
     return base && map ? base + map : 0;
 }
 
+// with a per-candidate bias: C = 0 is the all-node call (no id map), C > 0 adds the subset's gathered bias [C]
+size_t score_softmax_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    if (C <= 0) return score_softmax_workspace_bytes(B, N, d);
+    const size_t base = score_softmax_sub_workspace_bytes(B, C, d, nnz);
+    return base ? base + rk_align((size_t)C * 4) : 0;
+}
+
+size_t score_softmax_bwd_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    if (C <= 0) return score_softmax_bwd_workspace_bytes(B, N, d);
+    const size_t base = score_softmax_bwd_sub_workspace_bytes(B, C, d, nnz);
+    return base ? base + rk_align((size_t)C * 4) : 0;
+}
+
 // ---- forward: the sweep between score_prep_kernel / list_range_kernel (rank_sweep.h) and the merge over the slabs ---------
 __global__ __launch_bounds__(256) void softmax_finish_kernel(const f32x2* __restrict__ ms, const float* __restrict__ t,
                                                              const int* __restrict__ valid, int64_t B, int64_t slabs, float scale,
@@ -97,17 +115,43 @@ __global__ __launch_bounds__(256) void softmax_finish_kernel(const f32x2* __rest
     loss[i] = l - scale * t[i];
 }
 
+// with a bias: the target's logit is fmaf(scale, t, bias[target]), as the sweep forms it (target and bias in node ids; a query
+// that is not valid may hold any target)
+__global__ __launch_bounds__(256) void softmax_finish_bias_kernel(const f32x2* __restrict__ ms, const float* __restrict__ t,
+                                                                  const int* __restrict__ valid, int64_t B, int64_t slabs,
+                                                                  float scale, const int64_t* __restrict__ target,
+                                                                  const float* __restrict__ bias, float* __restrict__ loss,
+                                                                  float* __restrict__ lse) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B) return;
+    f32x2 m = ms[(size_t)i * slabs];
+    for (int64_t s = 1; s < slabs; ++s) m = lse_merge(m, ms[(size_t)i * slabs + s]);
+    const bool ok = valid[i] != 0;
+    const float l = ok ? m[0] + logf(m[1]) : __int_as_float(0x7FC00000);
+    lse[i] = l;
+    loss[i] = ok ? l - fmaf(scale, t[i], bias[target[i]]) : l;
+}
+
 int launch_score_softmax_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                              void* ws, size_t ws_bytes, float* loss, float* lse, hipStream_t stream, const int64_t* ic,
-                             int64_t C) {
+                             int64_t C, const float* bias) {
     RankArgs a;
     const int64_t M = ic ? C : N;                    // the candidates the sweep runs over
     GHF_REQUIRE(!ic || (C > 0 && C <= N), "score_softmax_fwd: need 1 <= C <= N candidates");
     const size_t base = score_softmax_workspace_bytes(B, M, d);
-    const size_t need = ic ? score_softmax_sub_workspace_bytes(B, C, d, nnz) : base;
-    int rc = score_open("score_softmax_fwd", softmax_geom, need, q, c, iq, filt_ptr, filt_idx, nnz, rows_q, M, B, d, ws_bytes, &a);
+    const size_t need = ic ? score_softmax_sub_workspace_bytes(B, C, d, nnz) : base;      // with a bias over a subset: + its [C] floats
+    const size_t need_b = bias && ic && need ? need + rk_align((size_t)C * 4) : need;
+    int rc = score_open("score_softmax_fwd", softmax_geom, need_b, q, c, iq, filt_ptr, filt_idx, nnz, rows_q, M, B, d, ws_bytes, &a);
     if (rc != GHF_OK) return rc;
+    const float* bias_c = bias;                      // the bias in the sweep's candidate space
+    if (bias && ic) {
+        GHF_REQUIRE(need > 0, "candidates: B or nnz out of range");
+        bias_c = (float*)((char*)ws + need);
+        rc = launch_cand_bias(bias, ic, C, N, (float*)((char*)ws + need), stream);
+        if (rc != GHF_OK) return rc;
+    }
+    const int64_t* target_nodes = target;
     float* t = (float*)ws;
     int* valid = (int*)((char*)ws + rk_align((size_t)B * 4));
     const unsigned qb = (unsigned)cdiv(B, 256);
@@ -127,9 +171,10 @@ int launch_score_softmax_fwd(const float* q, const float* c, const int64_t* iq, 
         }
     }
     a.target = target; a.scale = scale; a.ws_ms = (f32x2*)((char*)ws + 2 * rk_align((size_t)B * 4));
-    rc = launch_rank_tiles<RK_SOFTMAX>(a, stream, ic, N);
+    rc = launch_rank_tiles<RK_SOFTMAX>(a, stream, ic, N, bias_c);
     if (rc != GHF_OK) return rc;
-    softmax_finish_kernel<<<qb, 256, 0, stream>>>(a.ws_ms, t, valid, B, a.slabs, scale, loss, lse);
+    if (bias) softmax_finish_bias_kernel<<<qb, 256, 0, stream>>>(a.ws_ms, t, valid, B, a.slabs, scale, target_nodes, bias, loss, lse);
+    else softmax_finish_kernel<<<qb, 256, 0, stream>>>(a.ws_ms, t, valid, B, a.slabs, scale, loss, lse);
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }
@@ -149,12 +194,17 @@ struct SmBwdArgs {
 };
 // SUB: candidate j is row ic[j] of c, which has Nn rows (rank_sweep.h: sub_row, RankSubArgs)
 struct SmBwdSubArgs : SmBwdArgs { const int64_t* ic; int64_t Nn; };
-template <bool SUB> struct SmBwdKernelArgs { typedef SmBwdArgs type; };
-template <> struct SmBwdKernelArgs<true> { typedef SmBwdSubArgs type; };
+template <bool SUB, bool BIAS = false> struct SmBwdKernelArgs { typedef SmBwdArgs type; };
+template <> struct SmBwdKernelArgs<true, false> { typedef SmBwdSubArgs type; };
+// BIAS: bias[j] is the term of the sweeps' candidate j (rank_sweep.h: RankBiasArgs),
+// the logit fmaf(scale, s, bias[j]); db [N] (may be NULL) gets sum_i G_ij / scale from the dc pass
+struct SmBwdBiasArgs : SmBwdSubArgs { const float* bias; float* db; };
+template <bool SUB> struct SmBwdKernelArgs<SUB, true> { typedef SmBwdBiasArgs type; };
 
-static inline size_t sb_lds_bytes(int d, int OT) {
+constexpr int SB_BIAS = 128;                 // backward: bias values in LDS (the owner tile's, or the streamed tile's)
+static inline size_t sb_lds_bytes(int d, int OT, bool bias = false) {
     const int dpad = (d + 31) & ~31;
-    return ((size_t)(OT + SB_ST) * (dpad + 4) + (size_t)SB_ST * (OT + 1)) * 4 + (size_t)SB_HCAP * 8 + 16;
+    return ((size_t)(OT + SB_ST) * (dpad + 4) + (size_t)SB_ST * (OT + 1)) * 4 + (size_t)SB_HCAP * 8 + 16 + (bias ? SB_BIAS * 4 : 0);
 }
 
 // what a lane knows of the query in its accumulator column
@@ -166,8 +216,8 @@ struct SmQuery {
 // the loss whose G the backward forms
 constexpr int SB_SOFTMAX = 0, SB_BCE = 1;
 
-template <int OT, int DMAX, bool DC, int LOSS, bool SUB = false>
-__global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwdKernelArgs<SUB>::type a) {
+template <int OT, int DMAX, bool DC, int LOSS, bool SUB = false, bool BIAS = false>
+__global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwdKernelArgs<SUB, BIAS>::type a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr bool BCE = LOSS == SB_BCE;
     constexpr int ST = SB_ST, NT = SB_NT, LDG = OT + 1;
@@ -182,6 +232,8 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
     float* Gs = Ys + ST * LDX;                   // G of the step: [streamed row][owner row]
     long long* hits = (long long*)(Gs + ST * LDG);
     int* hcnt = (int*)(hits + SB_HCAP);
+    // BIAS: the bias of the step's candidates — dc: the owner tile's, loaded once; dq: the streamed tile's, staged with it
+    float* Bs = (float*)(hcnt + 4);
     const bool vq = rows_vec(a.q, d), vc = rows_vec(a.c, d);
 
     int64_t own0, tile0, tile1, slab = 0;
@@ -235,6 +287,9 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
         const float* src = DC ? crow(own0 + row) : qrow(own0 + row);
         store_perm(Xs + row * LDX, c4, load_k4(src, c4 * 4, d, DC ? vc : vq));
     }
+    if constexpr (BIAS && DC) {
+        if (tid < OT) Bs[tid] = own0 + tid < a.N ? a.bias[own0 + tid] : 0.f;
+    }
 
     // dc: the listed (query, candidate) pairs inside this candidate tile, the targets' own left out.  bce: the pairs of the
     // queries that take part, an id that repeats its predecessor in the list left out (a positive counts once)
@@ -274,6 +329,7 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
     }
 
     f32x4 pre[NL];
+    float bpre = 0.f, dbacc = 0.f;
     auto fetch = [&](int64_t tile) {
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
@@ -284,6 +340,9 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
                 pre[i] = load_k4(src, c4 * 4, d, DC ? vq : vc);
             }
         }
+        if constexpr (BIAS && !DC) {
+            if (tid < ST) bpre = tile * ST + tid < a.N ? a.bias[tile * ST + tid] : 0.f;
+        }
     };
     auto stash = [&]() {
 #pragma unroll
@@ -293,6 +352,9 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
                 const int row = idx / nf4, c4 = idx - row * nf4;
                 store_perm(Ys + row * LDX, c4, pre[i]);
             }
+        }
+        if constexpr (BIAS && !DC) {
+            if (tid < ST) Bs[tid] = bpre;
         }
     };
 
@@ -349,7 +411,12 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
             look = nxt < cand0 + CR;
         }
 #pragma unroll
-        for (int t = 0; t < NTW; ++t)
+        for (int t = 0; t < NTW; ++t) {
+            f32x4 bq[4];                             // BIAS: the bias of the lane's 16 candidates of this tile, bq[r >> 2][r & 3]
+            if constexpr (BIAS) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) bq[g] = *(const f32x4*)(Bs + (rt0 + t) * 32 + 8 * g + 4 * lh);
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int cl = (rt0 + t) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
@@ -358,18 +425,25 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
                 if (live && cand < a.N) {
                     if (BCE) {
                         // sigma(z) from e = exp(-|z|) in (0, 1]: 1 / (1 + e) for z >= 0, e / (1 + e) below
-                        const float z = a.scale * s[t][r], e = __expf(-fabsf(z)), rcp = __builtin_amdgcn_rcpf(1.f + e);
+                        float z;
+                        if constexpr (BIAS) z = fmaf(a.scale, s[t][r], bq[r >> 2][r & 3]);
+                        else z = a.scale * s[t][r];
+                        const float e = __expf(-fabsf(z)), rcp = __builtin_amdgcn_rcpf(1.f + e);
                         const float p = z >= 0.f ? rcp : e * rcp;
                         const bool listed = look && in_filter(a.filt_idx, cur.f0, cur.f1, cand);
                         gv = cur.gs * ((p - a.neg_w) - (listed ? a.pos_w : 0.f));
                     } else {
                         const bool masked = look && cand != cur.tgt && in_filter(a.filt_idx, cur.f0, cur.f1, cand);
-                        const float p = masked ? 0.f : __expf(fmaf(a.scale, s[t][r], -cur.lse));
+                        // BIAS: bias - lse first, so that a zero bias leaves the one rounding of the line below it
+                        float p;
+                        if constexpr (BIAS) p = masked ? 0.f : __expf(fmaf(a.scale, s[t][r], bq[r >> 2][r & 3] - cur.lse));
+                        else p = masked ? 0.f : __expf(fmaf(a.scale, s[t][r], -cur.lse));
                         gv = cur.gs * (p - (cand == cur.tgt ? 1.f : 0.f));
                     }
                 }
                 Gs[DC ? ql * LDG + cl : cl * LDG + ql] = gv;
             }
+        }
         if (!DC) {
             while (nxt < cand0 + CR) {
                 ++cur.f0;
@@ -396,6 +470,13 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
 #pragma unroll 4
         for (int k = 0; k < ST; k += 2) {
             const float av = gA[k * LDG];
+            if constexpr (BIAS && DC) {
+                // db falls out of the operand this loop loads anyway: av is G[query k + lh][owner row rt2 * 32 + lr], so the
+                // lower half-wave adds its own entry (query k), then the upper one's (query k + 1, fetched by one 32-lane
+                // swap): every owner column sums its G over the queries in ascending order, in the shadow of the MFMAs
+                const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(av), __float_as_uint(av), false, false);
+                dbacc = (dbacc + av) + __uint_as_float(sw[1]);
+            }
 #pragma unroll
             for (int c = 0; c < NC; ++c)
                 if ((cb + c) * 32 < d) out[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, yB[k * LDX + (cb + c) * 32], out[c], 0, 0, 0);
@@ -423,6 +504,12 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
             }
         }
     }
+    if constexpr (BIAS && DC) {
+        // the lower half-waves of the waves with the first column block hold one owner row each; G carries grad * scale and
+        // the bias enters the logit unscaled
+        const int64_t row = own0 + rt2 * 32 + lr;
+        if (a.db && cb == 0 && lh == 0 && row < a.N) a.db[row] = dbacc / a.scale;
+    }
 }
 
 template <int OT, int DMAX, int LOSS, bool SUB = false>
@@ -437,22 +524,42 @@ static int launch_bwd_tiles(const typename SmBwdKernelArgs<SUB>::type& a, hipStr
     return GHF_OK;
 }
 
+template <int OT, int DMAX, int LOSS, bool SUB>
+static int launch_bwd_bias_tiles(const SmBwdBiasArgs& a, hipStream_t stream) {
+    const size_t lds = sb_lds_bytes(a.d, OT, true);
+    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, false, LOSS, SUB, true>), lds);
+    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, true, LOSS, SUB, true>), lds);
+    softmax_bwd_kernel<OT, DMAX, false, LOSS, SUB, true><<<(unsigned)(a.qtiles * a.slabs), SB_NT, lds, stream>>>(a);
+    GHF_LAUNCH_CHECK();
+    softmax_bwd_kernel<OT, DMAX, true, LOSS, SUB, true><<<(unsigned)cdiv(a.N, OT), SB_NT, lds, stream>>>(a);
+    GHF_LAUNCH_CHECK();
+    return GHF_OK;
+}
+
 // both losses' backward: the lists are the softmax's filter lists or the BCE's positives, `lse` the forward's lse or (BCE, of
 // which only the NaNs are read) its loss; target and smoothing belong to one loss each
 template <int LOSS>
 static int launch_score_loss_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* list_ptr,
                                  const int64_t* list_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                                  float smoothing, const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq,
-                                 float* dc, hipStream_t stream, const int64_t* ic, int64_t C) {
+                                 float* dc, hipStream_t stream, const int64_t* ic, int64_t C, const float* bias, float* db) {
     RankArgs r;
     const char* op = LOSS == SB_BCE ? "score_bce_bwd" : "score_softmax_bwd";
     const int64_t M = ic ? C : N;                    // the candidates the sweeps run over: dc is [M, d]
     GHF_REQUIRE(!ic || (C > 0 && C <= N), "%s: need 1 <= C <= N candidates", op);
     const size_t base = score_softmax_bwd_workspace_bytes(B, M, d);
-    const size_t need = ic ? score_softmax_bwd_sub_workspace_bytes(B, C, d, nnz) : base;
-    int rc = score_open(op, softmax_bwd_geom, need, q, c, iq, list_ptr, list_idx, nnz, rows_q, M, B, d, ws_bytes, &r);
+    const size_t need = ic ? score_softmax_bwd_sub_workspace_bytes(B, C, d, nnz) : base;      // with a bias over a subset: + [C] floats
+    const size_t need_b = bias && ic && need ? need + rk_align((size_t)C * 4) : need;
+    int rc = score_open(op, softmax_bwd_geom, need_b, q, c, iq, list_ptr, list_idx, nnz, rows_q, M, B, d, ws_bytes, &r);
     if (rc != GHF_OK) return rc;
-    SmBwdSubArgs a = {};
+    SmBwdBiasArgs a = {};
+    a.bias = bias; a.db = db;
+    if (bias && ic) {
+        GHF_REQUIRE(need > 0, "candidates: B or nnz out of range");
+        a.bias = (float*)((char*)ws + need);
+        rc = launch_cand_bias(bias, ic, C, N, (float*)((char*)ws + need), stream);
+        if (rc != GHF_OK) return rc;
+    }
     if (ic) {      // targets and lists as positions in ic; a query that a bad ic or a target outside it rules out has lse NaN
         CandMap m;
         rc = launch_cand_map(q, c, iq, target, LOSS != SB_BCE, list_ptr, list_idx, nnz, ic, C, rows_q, N, B, d, lse, nullptr, nullptr,
@@ -467,7 +574,9 @@ static int launch_score_loss_bwd(const float* q, const float* c, const int64_t* 
     if (LOSS == SB_BCE) { a.pos_w = 1.f - smoothing; a.neg_w = smoothing / (float)M; }
     a.qtiles = r.qtiles; a.slab_tiles = r.slab_tiles; a.slabs = r.slabs;
     a.dq_part = (float*)ws; a.dc = dc;
-    if (ic) rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128, LOSS, true>(a, stream) : launch_bwd_tiles<64, 256, LOSS, true>(a, stream);
+    if (bias && ic) rc = sb_otile(d) == 128 ? launch_bwd_bias_tiles<128, 128, LOSS, true>(a, stream) : launch_bwd_bias_tiles<64, 256, LOSS, true>(a, stream);
+    else if (bias) rc = sb_otile(d) == 128 ? launch_bwd_bias_tiles<128, 128, LOSS, false>(a, stream) : launch_bwd_bias_tiles<64, 256, LOSS, false>(a, stream);
+    else if (ic) rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128, LOSS, true>(a, stream) : launch_bwd_tiles<64, 256, LOSS, true>(a, stream);
     else rc = sb_otile(d) == 128 ? launch_bwd_tiles<128, 128, LOSS>(a, stream) : launch_bwd_tiles<64, 256, LOSS>(a, stream);
     if (rc != GHF_OK) return rc;
     return launch_ordered_sum(a.dq_part, a.slabs, B * (int64_t)d, dq, stream);
@@ -476,9 +585,9 @@ static int launch_score_loss_bwd(const float* q, const float* c, const int64_t* 
 int launch_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                              const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc,
-                             hipStream_t stream, const int64_t* ic, int64_t C) {
+                             hipStream_t stream, const int64_t* ic, int64_t C, const float* bias, float* db) {
     return launch_score_loss_bwd<SB_SOFTMAX>(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, 0.f, lse, grad_loss, ws,
-                                             ws_bytes, dq, dc, stream, ic, C);
+                                             ws_bytes, dq, dc, stream, ic, C, bias, db);
 }
 
 // the multi-label BCE loss's backward (bce.hip holds its forward): the same two sweeps and workspace, G formed for that loss
@@ -486,13 +595,16 @@ size_t score_bce_bwd_workspace_bytes(int64_t B, int64_t N, int d) { return score
 size_t score_bce_bwd_sub_workspace_bytes(int64_t B, int64_t C, int d, int64_t nnz) {
     return score_softmax_bwd_sub_workspace_bytes(B, C, d, nnz);
 }
+size_t score_bce_bwd_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    return score_softmax_bwd_b_workspace_bytes(B, N, C, d, nnz);
+}
 
 int launch_score_bce_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
                          int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
                          const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc, hipStream_t stream,
-                         const int64_t* ic, int64_t C) {
+                         const int64_t* ic, int64_t C, const float* bias, float* db) {
     return launch_score_loss_bwd<SB_BCE>(q, c, iq, nullptr, pos_ptr, pos_idx, nnz, rows_q, N, B, d, scale, smoothing, loss, grad_loss,
-                                         ws, ws_bytes, dq, dc, stream, ic, C);
+                                         ws, ws_bytes, dq, dc, stream, ic, C, bias, db);
 }
 
 }  // namespace ghf

@@ -739,6 +739,21 @@ class HyperGNN(nn.Module):
         return ids.contiguous()
 
     @staticmethod
+    def _candidate_bias(candidate_bias, embs: torch.Tensor) -> Optional[torch.Tensor]:
+        """``candidate_bias=`` of the four all-node operations: a 1-D fp32 tensor with one entry per NODE (length ``N``, also
+        with ``candidates=``) on ``embs``' device, made contiguous.  Only metadata is looked at — no device work, no
+        synchronisation; what the values may be (``-inf`` removes a node, NaN is outside the contract) is the kernels' rule."""
+        if candidate_bias is None:
+            return None
+        N = embs.size(0)
+        b = candidate_bias
+        if (not isinstance(b, torch.Tensor) or b.dim() != 1 or b.numel() != N or b.dtype != torch.float32
+                or b.device != embs.device):
+            got = f"{tuple(b.shape)} {b.dtype} on {b.device}" if isinstance(b, torch.Tensor) else type(b).__name__
+            raise ValueError(f"candidate_bias must be a float32 tensor of shape [N] = [{N}] on {embs.device}, got {got}")
+        return b.contiguous()
+
+    @staticmethod
     def _softmax_candidates(cand: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         """The candidate set of ``softmax_loss(candidates=)``: the given ids (``_candidate_ids``' form) and every target of the
         batch, ascending.  A query's own target has to be in its sum; the other queries' targets come in with it, as in-batch
@@ -843,7 +858,7 @@ class HyperGNN(nn.Module):
     def rank_candidates(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, known=None,
                         filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                         query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
-                        candidates: Optional[torch.Tensor] = None):
+                        candidates: Optional[torch.Tensor] = None, candidate_bias: Optional[torch.Tensor] = None):
         """Where ``target[i]`` ranks among ALL nodes as a partner of ``query[i]`` under the dot-product score
         (``score_triple``): ``(greater, equal)``, int64 ``[B]`` — the nodes scoring above / exactly as the target, the target
         itself and the query's known partners (the "filtered" setting) left out.  ``known=(src, dst)`` names true edges
@@ -863,9 +878,16 @@ class HyperGNN(nn.Module):
         the true partner among sampled negatives, or among the nodes of one type (``ghf_score_rank_sub``).  The result is
         that of the call on the table ``embs[sorted(candidates)]``, except that ``target`` and the lists stay node ids of
         ``embs``: the target may be any node, a candidate or not (its score comes from its own row), and listed nodes that
-        are no candidates take no part.  The candidate rows are read in place; no ``[C, d]`` copy is made."""
+        are no candidates take no part.  The candidate rows are read in place; no ``[C, d]`` copy is made.
+
+        ``candidate_bias`` (fp32 ``[N]``, one entry per node, also with ``candidates``): every score becomes
+        ``embs[query[i]] . embs[j] + candidate_bias[j]`` — one fp32 add behind the dot product — and the target's score is
+        formed the same way from its own entry (``ghf_score_rank_b``): a trained entity bias, a popularity prior, a type
+        penalty.  ``-inf`` on a node that is no query's target takes it out of both counts.  A bias of zeros returns the
+        counts of the call without the keyword."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        bias = self._candidate_bias(candidate_bias, embs)
         cand = None if candidates is None else self._candidate_ids(candidates, embs)
         if not embs.is_cuda:
             raise RuntimeError(f"rank_candidates computes on an MI355X HIP device only (input is on {embs.device})")
@@ -877,22 +899,26 @@ class HyperGNN(nn.Module):
             raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
         ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx, query_rel)
         if query_rows is not None:
-            return _native.score_rank(query_rows.detach(), e, t, filt_ptr=ptr, filt_idx=idx, ic=cand)
-        return _native.score_rank(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, ic=cand)
+            return _native.score_rank(query_rows.detach(), e, t, filt_ptr=ptr, filt_idx=idx, ic=cand, bias=bias)
+        return _native.score_rank(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, ic=cand, bias=bias)
 
     def topk_candidates(self, embs: torch.Tensor, query: torch.Tensor, k: int, *, known=None,
                         filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                         query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
-                        candidates: Optional[torch.Tensor] = None):
+                        candidates: Optional[torch.Tensor] = None, candidate_bias: Optional[torch.Tensor] = None):
         """The ``k`` (1..128) best partners of every ``query[i]`` among ALL nodes outside its filter list (``known`` /
         ``filt_ptr, filt_idx`` as in ``rank_candidates``): ``(scores [B, k]`` fp32 descending, ``ids [B, k]`` int64``)``, ties
         towards the lower id, ``(-inf, -1)`` where fewer than k candidates remain.  The query node itself is a candidate
         unless listed.  No autograd graph.  ``query_rows`` / ``known=(src, dst, rel)`` with ``query_rel``: relation-typed
         queries, as in ``rank_candidates``.  ``candidates`` (ids or a bool mask, as in ``rank_candidates``): the k best among
         those nodes only, e.g. the cities for ``(person, born in, ?)``; the ids returned are node ids of ``embs``, ties still go
-        to the lower node id, and ``(-inf, -1)`` fills up where fewer than k candidates remain outside the list."""
+        to the lower node id, and ``(-inf, -1)`` fills up where fewer than k candidates remain outside the list.
+        ``candidate_bias`` (fp32 ``[N]``, as in ``rank_candidates``): nodes are ordered by, and ``scores`` holds,
+        ``embs[query[i]] . embs[j] + candidate_bias[j]`` (``ghf_score_topk_b``); a node whose entry is ``-inf`` is never
+        returned — "never propose this node" without a filter list per query."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        bias = self._candidate_bias(candidate_bias, embs)
         cand = None if candidates is None else self._candidate_ids(candidates, embs)
         if not embs.is_cuda:
             raise RuntimeError(f"topk_candidates computes on an MI355X HIP device only (input is on {embs.device})")
@@ -903,13 +929,13 @@ class HyperGNN(nn.Module):
         q = self._rank_ids(query, e.size(0), e, "query")
         ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx, query_rel)
         if query_rows is not None:
-            return _native.score_topk(query_rows.detach(), e, int(k), filt_ptr=ptr, filt_idx=idx, ic=cand)
-        return _native.score_topk(e, e, int(k), iq=q, filt_ptr=ptr, filt_idx=idx, ic=cand)
+            return _native.score_topk(query_rows.detach(), e, int(k), filt_ptr=ptr, filt_idx=idx, ic=cand, bias=bias)
+        return _native.score_topk(e, e, int(k), iq=q, filt_ptr=ptr, filt_idx=idx, ic=cand, bias=bias)
 
     def softmax_loss(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, scale: float = 1.0, known=None,
                      filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                      query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
-                     candidates: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     candidates: Optional[torch.Tensor] = None, candidate_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The 1-vs-all softmax cross-entropy that ``rank_candidates``' filtered metrics measure, fp32 ``[B]``:
         ``loss[i] = logsumexp_j(scale * embs[query[i]] . embs[j]) - scale * embs[query[i]] . embs[target[i]]`` over ALL nodes
         ``j`` except ``query[i]``'s known partners (``known`` / ``filt_ptr, filt_idx`` as in ``rank_candidates``; the target
@@ -928,9 +954,20 @@ class HyperGNN(nn.Module):
         ``known`` lists it.  Everything else is the sub-table rule: ``target`` and the lists stay node ids, listed nodes
         outside the set take no part, the candidate rows are read in place (no ``[C, d]`` copy, forward or backward), and
         the gradient lands in ``embs``' own rows: rows that are neither candidates, targets nor queries get exactly zero.
-        Still bit-reproducible."""
+        Still bit-reproducible.
+
+        ``candidate_bias`` (fp32 ``[N]``, one entry per node, also with ``candidates``): the logits become
+        ``fma(scale, embs[query[i]] . embs[j], candidate_bias[j])`` — the bias is not multiplied by ``scale`` — in the
+        log-sum and in the target's term (``ghf_score_softmax_fwd_b`` / ``_bwd_b``).  With negatives drawn with probability
+        ``p[j]``, ``candidate_bias=-torch.log(p)`` is the log-Q correction that makes the sampled loss an estimate of the full
+        one.  ``-inf`` on a node that is no query's target adds nothing to any sum and leaves its gradients exactly zero.  When
+        the bias requires grad it receives ``[N]``: ``sum_i grad[i] (p_ij - [j = target_i])``, exactly zero for nodes outside
+        the candidate set; the loss is recorded for autograd also when only the bias requires grad.  A bias of zeros gives the
+        bits of the call without the keyword."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        bias = self._candidate_bias(candidate_bias, embs)
+        bias_grad = bias is not None and bias.requires_grad
         cand = None if candidates is None else self._candidate_ids(candidates, embs)
         self._query_rows(embs, query, query_rows, "softmax_loss")
         scale = float(scale)
@@ -946,21 +983,21 @@ class HyperGNN(nn.Module):
         if cand is not None:
             cand = self._softmax_candidates(cand, t)
         if query_rows is not None:
-            if torch.is_grad_enabled() and (embs.requires_grad or query_rows.requires_grad):
+            if torch.is_grad_enabled() and (embs.requires_grad or query_rows.requires_grad or bias_grad):
                 from ..autograd import SoftmaxLossFn
-                return SoftmaxLossFn.apply(embs, query_rows, None, t, ptr, idx, scale, cand)
+                return SoftmaxLossFn.apply(embs, query_rows, None, t, ptr, idx, scale, cand, bias)
             return _native.score_softmax_fwd(query_rows.detach(), embs.detach().float(), t, filt_ptr=ptr, filt_idx=idx,
-                                             scale=scale, ic=cand)[0]
-        if torch.is_grad_enabled() and embs.requires_grad:
+                                             scale=scale, ic=cand, bias=bias)[0]
+        if torch.is_grad_enabled() and (embs.requires_grad or bias_grad):
             from ..autograd import SoftmaxLossFn
-            return SoftmaxLossFn.apply(embs, None, q, t, ptr, idx, scale, cand)
+            return SoftmaxLossFn.apply(embs, None, q, t, ptr, idx, scale, cand, bias)
         e = embs.detach().float()
-        return _native.score_softmax_fwd(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, scale=scale, ic=cand)[0]
+        return _native.score_softmax_fwd(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, scale=scale, ic=cand, bias=bias)[0]
 
     def bce_loss(self, embs: torch.Tensor, query: torch.Tensor, *, known=None, pos_ptr: Optional[torch.Tensor] = None,
                  pos_idx: Optional[torch.Tensor] = None, scale: float = 1.0, smoothing: float = 0.0, normalize: bool = True,
                  query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
-                 candidates: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 candidates: Optional[torch.Tensor] = None, candidate_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The multi-label 1-vs-all loss of ConvE / TuckER / CompGCN, fp32 ``[B]``: every ``query[i]`` is scored against ALL
         nodes, all of its known partners are positives at once, and the loss is binary cross-entropy with label smoothing,
         ``F.binary_cross_entropy_with_logits(scale * embs[query] @ embs.T, y, reduction="none").mean(1)`` with
@@ -978,9 +1015,18 @@ class HyperGNN(nn.Module):
         ``(1 - smoothing) * [partner] + smoothing / C``, and ``normalize=True`` divides by ``C``.  A partner outside the set
         takes no part, as a label or as a logit — so when sampling negatives, INCLUDE the batch's positives in ``candidates``
         (nothing is added here: unlike ``softmax_loss`` there is no single target to add).  The candidate rows are read in
-        place; rows of ``embs`` that are neither candidates nor queries get exactly zero gradient."""
+        place; rows of ``embs`` that are neither candidates nor queries get exactly zero gradient.
+
+        ``candidate_bias`` (fp32 ``[N]``, finite, one entry per node, also with ``candidates``): the per-entity bias ``b_t`` of
+        those models' ``f(h, r) . e_t + b_t`` — the logits are ``fma(scale, embs[query[i]] . embs[j], candidate_bias[j])``
+        (``ghf_score_bce_fwd_b`` / ``_bwd_b``).  Pass an ``nn.Parameter``: when it requires grad it receives ``[N]``,
+        ``sum_i grad[i] (sigmoid(z_ij) - y_ij)`` (already divided by the candidate count under ``normalize=True``), exactly zero
+        for nodes outside ``candidates``; the loss is recorded also when only the bias requires grad.  A bias of zeros gives the
+        bits of the call without the keyword."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        bias = self._candidate_bias(candidate_bias, embs)
+        bias_grad = bias is not None and bias.requires_grad
         cand = None if candidates is None else self._candidate_ids(candidates, embs)
         self._query_rows(embs, query, query_rows, "bce_loss")
         scale, smoothing = float(scale), float(smoothing)
@@ -994,18 +1040,19 @@ class HyperGNN(nn.Module):
             raise RuntimeError(f"bce_loss computes on an MI355X HIP device only (input is on {embs.device})")
         ptr, idx = self._filter_lists(embs, q, known, pos_ptr, pos_idx, query_rel)
         if query_rows is not None:
-            if torch.is_grad_enabled() and (embs.requires_grad or query_rows.requires_grad):
+            if torch.is_grad_enabled() and (embs.requires_grad or query_rows.requires_grad or bias_grad):
                 from ..autograd import BceLossFn
-                loss = BceLossFn.apply(embs, query_rows, None, ptr, idx, scale, smoothing, cand)
+                loss = BceLossFn.apply(embs, query_rows, None, ptr, idx, scale, smoothing, cand, bias)
             else:
                 loss = _native.score_bce_fwd(query_rows.detach(), embs.detach().float(), pos_ptr=ptr, pos_idx=idx, scale=scale,
-                                             smoothing=smoothing, ic=cand)
-        elif torch.is_grad_enabled() and embs.requires_grad:
+                                             smoothing=smoothing, ic=cand, bias=bias)
+        elif torch.is_grad_enabled() and (embs.requires_grad or bias_grad):
             from ..autograd import BceLossFn
-            loss = BceLossFn.apply(embs, None, q, ptr, idx, scale, smoothing, cand)
+            loss = BceLossFn.apply(embs, None, q, ptr, idx, scale, smoothing, cand, bias)
         else:
             e = embs.detach().float()
-            loss = _native.score_bce_fwd(e, e, iq=q, pos_ptr=ptr, pos_idx=idx, scale=scale, smoothing=smoothing, ic=cand)
+            loss = _native.score_bce_fwd(e, e, iq=q, pos_ptr=ptr, pos_idx=idx, scale=scale, smoothing=smoothing, ic=cand,
+                                         bias=bias)
         return loss * (1.0 / (embs.size(0) if cand is None else cand.numel())) if normalize else loss
 
     def num_parameters(self) -> int:

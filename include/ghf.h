@@ -641,6 +641,60 @@ int ghf_score_bce_bwd_sub(const float* q, const float* c, const int64_t* iq, con
                           const float* grad_loss, const int64_t* ic, int64_t C, void* workspace, size_t workspace_bytes, float* dq,
                           float* dc, void* stream);
 
+/* ---- the same four operations with a per-candidate bias (csrc/rank_sweep.h) -----------------------------
+ * A log-Q correction for sampled negatives, a learned entity bias (the b_t of ConvE / TuckER / CompGCN's f(h, r) . e_t + b_t),
+ * a prior or soft mask at evaluation.  Every call above has a _b form that takes the arguments of its _sub form plus
+ *   bias fp32 [N], one entry per ROW of c (a node id, also when ic is given);  NULL is GHF_EINVAL.
+ *   ic = NULL with C = 0 means every node (the result of the plain call with the bias); otherwise ic as for the _sub calls.
+ * With s(i, j) the chain above, unchanged:
+ *   ghf_score_rank_b, ghf_score_topk_b   s_b(i, j) = fl32(s(i, j) + bias[j]): ONE fp32 add behind the chain.  t_i is formed the
+ *                              same way from the target's own row and its own bias entry, a candidate or not.  Top-k returns
+ *                              the biased scores.  Ties, (-inf, -1) padding and the lists as above.
+ *   ghf_score_softmax_fwd_b, ghf_score_bce_fwd_b   z_ij = fmaf(scale, s(i, j), bias[j]) wherever the calls above use
+ *                              scale s(i, j): the lse, loss = lse - z_it, BCE's three sums.  The bias is NOT multiplied by scale;
+ *                              labels and smoothing / N as above.
+ *   the two backwards          G_ij as above with the biased z (the softmax forms p_ij = exp(fmaf(scale, s, bias[j] - lse[i])));
+ *                              dq and dc as above, and db [N] ([C] with ic, entry j belonging to node ic[j]; NULL = not wanted):
+ *                              db[j] = sum_i grad_loss[i] (p_ij - [j = target[i]])      softmax
+ *                              db[j] = sum_i grad_loss[i] (sigma(z_ij) - y_ij)          BCE
+ *                              computed as (sum_i G_ij) / scale over the queries in ascending order by the dc pass: every entry
+ *                              written, no floating-point atomics, bit-reproducible.
+ * bias[j] = -inf on a candidate that is no query's target takes it out: rank counts it in neither count, top-k never returns
+ * it, the softmax adds 0 for it and its dc row and db entry are exactly 0.  For the BCE loss the bias must be finite.  A NaN
+ * entry is outside the contract but faults nothing.  No value is checked on the host.  A bias of zeros returns the bits of
+ * the call without one (fmaf(scale, s, 0) = fl(scale s), s + 0 = s).  Errors as above: a bad id makes its query invalid, a bad
+ * ic every query (db is then zero).  workspace: the matching _b_workspace_bytes query (B, N, C, ...; C = 0: every node), which
+ * with C > 0 holds the _sub workspace and the bias gathered through ic, [C] floats; 0 = bad sizes; 256-byte aligned.  Nothing
+ * allocates or synchronises. */
+size_t ghf_score_rank_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+int ghf_score_rank_b(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                     const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, const int64_t* ic,
+                     int64_t C, const float* bias, void* workspace, size_t workspace_bytes, int64_t* greater, int64_t* equal,
+                     void* stream);
+size_t ghf_score_topk_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int k, int64_t nnz);
+int ghf_score_topk_b(const float* q, const float* c, const int64_t* iq, const int64_t* filt_ptr, const int64_t* filt_idx,
+                     int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, int k, const int64_t* ic, int64_t C,
+                     const float* bias, void* workspace, size_t workspace_bytes, float* scores, int64_t* ids, void* stream);
+size_t ghf_score_softmax_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+int ghf_score_softmax_fwd_b(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                            const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                            const int64_t* ic, int64_t C, const float* bias, void* workspace, size_t workspace_bytes, float* loss,
+                            float* lse, void* stream);
+size_t ghf_score_softmax_bwd_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+int ghf_score_softmax_bwd_b(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                            const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                            const float* lse, const float* grad_loss, const int64_t* ic, int64_t C, const float* bias,
+                            void* workspace, size_t workspace_bytes, float* dq, float* dc, float* db, void* stream);
+size_t ghf_score_bce_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+int ghf_score_bce_fwd_b(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
+                        int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const int64_t* ic,
+                        int64_t C, const float* bias, void* workspace, size_t workspace_bytes, float* loss, void* stream);
+size_t ghf_score_bce_bwd_b_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+int ghf_score_bce_bwd_b(const float* q, const float* c, const int64_t* iq, const int64_t* pos_ptr, const int64_t* pos_idx,
+                        int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float smoothing, const float* loss,
+                        const float* grad_loss, const int64_t* ic, int64_t C, const float* bias, void* workspace,
+                        size_t workspace_bytes, float* dq, float* dc, float* db, void* stream);
+
 /* ---- relation-typed query rows (csrc/relation.hip) ----------------------------------------------------
  * No counterpart in the reference, whose score_triple (models/hypergnn.py:304-318) ignores the relation.  The query side of
  * a (head, relation, ?) score: every query row multiplied by ITS relation's matrix, without gathering a matrix per query

@@ -3,14 +3,18 @@ same B in the same process and against the formulation a user has without it —
 of logits, dense labels, binary_cross_entropy_with_logits, autograd backward chunk by chunk — at the sizes of BASELINE
 configs 3 and 2.  Prints one JSON line.
 
-    python tools/bce_time.py [--configs c3,c2] [--batches 1024,16384] [--reps 5] [--no-torch]
+    python tools/bce_time.py [--configs c3,c2] [--batches 1024,16384] [--reps 5] [--no-torch] [--bias]
 
 Per config and B in (1,024, 16,384), ten positives per query, smoothing 0.1, scale d^-1/2: medians of device-event windows
 (ms, warm) of the forward (no autograd graph; also without lists), of the forward plus backward down to d embs, of
 softmax_loss on the same queries and lists (a random target), and of the torch formulation; the ratios bce / softmax; the
 peak memory each allocates beyond the embeddings; the achieved fraction of the fp32 matrix peak, counting one B x N x d
 product forward and four backward.  The torch formulation reports "does not fit" where it raises an out-of-memory error.
---no-torch leaves it out (a counter collection of the kernels alone)."""
+--no-torch leaves it out (a counter collection of the kernels alone).
+
+--bias adds bce_loss forward and forward + backward with a random candidate_bias= (a learned entity bias: N(0, 1), one entry
+per node, requiring its gradient in the backward; `bias` holds the times), then times the two calls without the keyword
+again (`fwd_again_ms`, `fwd_bwd_again_ms`: the same code twice in one command, i.e. the spread)."""
 
 from __future__ import annotations
 
@@ -76,7 +80,7 @@ def torch_loss(embs, q, ptr, idx, scale, backward):
     return torch.cat(out), e.grad
 
 
-def run_config(name, reps, batches, with_torch):
+def run_config(name, reps, batches, with_torch, bias=False):
     cfg = CONFIGS[name]
     dev = torch.device("cuda:0")
     N, d = cfg["N"], cfg["d"]
@@ -118,6 +122,21 @@ def run_config(name, reps, batches, with_torch):
         r["bwd_over_softmax"] = (r["fwd_bwd_ms"] - r["fwd_ms"]) / (r["softmax_fwd_bwd_ms"] - r["softmax_fwd_ms"])
         r["fwd_fraction_of_fp32_matrix_peak"] = flops / (r["fwd_ms"] * 1e-3) / (FP32_MATRIX_PEAK_TF * 1e12)
         r["bwd_fraction_of_fp32_matrix_peak"] = (4 * flops / ((r["fwd_bwd_ms"] - r["fwd_ms"]) * 1e-3) / (FP32_MATRIX_PEAK_TF * 1e12))
+        if bias:
+            b = torch.randn(N, device=dev, generator=torch.Generator(device=dev).manual_seed(cfg["seed"] + B))
+
+            def bias_step():
+                e, p = embs.detach().requires_grad_(True), b.detach().requires_grad_(True)
+                loss = model.bce_loss(e, q, candidate_bias=p, **kw)
+                loss.mean().backward()
+                return loss.detach(), e.grad, p.grad
+
+            s = {}
+            s["fwd_ms"], _, _ = timed(lambda: model.bce_loss(embs, q, candidate_bias=b, **kw), reps)
+            s["fwd_bwd_ms"], s["fwd_bwd_peak_bytes"], _ = timed(bias_step, reps)
+            r["bias"] = s
+            r["fwd_again_ms"], _, _ = timed(lambda: model.bce_loss(embs, q, **kw), reps)
+            r["fwd_bwd_again_ms"], _, _ = timed(step, reps)
         if with_torch:
             for key, backward in (("torch_fwd", False), ("torch_fwd_bwd", True)):
                 try:
@@ -142,12 +161,13 @@ def main():
     ap.add_argument("--batches", default="1024,16384")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--bias", action="store_true", help="also time the loss with a random candidate_bias=, then the plain calls again")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bce_time.py measures on an MI355X; no HIP device here")
     out = {"tool": "bce_time", "device": torch.cuda.get_device_name(0)}
     for name in args.configs.split(","):
-        out[name] = run_config(name, args.reps, [int(b) for b in args.batches.split(",")], not args.no_torch)
+        out[name] = run_config(name, args.reps, [int(b) for b in args.batches.split(",")], not args.no_torch, args.bias)
     print(json.dumps(out))
 
 

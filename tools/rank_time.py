@@ -2,7 +2,7 @@
 them — embs[q] @ embs.T in query chunks sized to 1 GB of scores, then compare-and-count (resp. torch.topk) — at the sizes of
 BASELINE configs 3 and 2.  Prints one JSON line.
 
-    python tools/rank_time.py [--configs c3,c2] [--batches 1024,16384] [--reps 5] [--no-torch] [--candidates C[,C...]]
+    python tools/rank_time.py [--configs c3,c2] [--batches 1024,16384] [--reps 5] [--no-torch] [--candidates C[,C...]] [--bias]
 
 Per config and B in (1,024, 16,384): medians of device-event windows (ms, warm) of the two calls without filter lists, of
 the two calls with a filter list per query built from `known` edges (10 per query), and of the torch formulation; the ratio
@@ -15,7 +15,11 @@ formulation out (a counter collection of the kernels alone: tools/pmc.sh <prefix
 --candidates 16384,131072,N adds, per C, the two calls with lists against a sorted random subset of C nodes (candidates=;
 "N" = every node, through the subset entry points): their times, C / N x the all-node time of the same call beside them, and,
 so that the two can be told apart from noise, the all-node calls timed a second time after them (`*_again_ms`: the same code
-twice in one command)."""
+twice in one command).
+
+--bias adds the two calls with lists and a random candidate_bias= (N(0, 1), one entry per node): `bias` holds their times,
+after which the calls without the keyword are timed again (`*_again_ms`, as above: the same-code spread of this command);
+with --candidates also the biased calls against every subset (`candidates_<C>` inside `bias`)."""
 
 from __future__ import annotations
 
@@ -82,7 +86,7 @@ def candidate_sets(spec, N, dev, seed):
     return sets
 
 
-def run_config(name, reps, batches, with_torch, candidates=""):
+def run_config(name, reps, batches, with_torch, candidates="", bias=False):
     cfg = CONFIGS[name]
     dev = torch.device("cuda:0")
     N, d = cfg["N"], cfg["d"]
@@ -122,7 +126,18 @@ def run_config(name, reps, batches, with_torch, candidates=""):
             s["rank_known_scaled_all_node_ms"] = r["rank_known_ms"] * C / N
             s["topk_known_scaled_all_node_ms"] = r["topk_known_ms"] * C / N
             r[f"candidates_{label}"] = s
-        if candidates:
+        if bias:
+            b = torch.randn(N, device=dev, generator=torch.Generator(device=dev).manual_seed(cfg["seed"] + B))
+            s = {}
+            s["rank_known_ms"], _ = timed(lambda: model.rank_candidates(embs, q, t, known=known, candidate_bias=b), reps)
+            s["topk_known_ms"], _ = timed(lambda: model.topk_candidates(embs, q, 10, known=known, candidate_bias=b), reps)
+            for label, cand in candidate_sets(candidates, N, dev, cfg["seed"]).items():
+                tc = cand[torch.from_numpy(np.random.default_rng(B + 1).integers(0, cand.numel(), B)).to(dev)]
+                s[f"candidates_{label}"] = {
+                    "rank_known_ms": timed(lambda: model.rank_candidates(embs, q, tc, known=known, candidates=cand, candidate_bias=b), reps)[0],
+                    "topk_known_ms": timed(lambda: model.topk_candidates(embs, q, 10, known=known, candidates=cand, candidate_bias=b), reps)[0]}
+            r["bias"] = s
+        if candidates or bias:
             r["rank_known_again_ms"], _ = timed(lambda: model.rank_candidates(embs, q, t, known=known), reps)
             r["topk_known_again_ms"], _ = timed(lambda: model.topk_candidates(embs, q, 10, known=known), reps)
         res[f"B{B}"] = r
@@ -136,12 +151,13 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--candidates", default="", help="C[,C...] or N: also time the calls against a sorted random subset")
+    ap.add_argument("--bias", action="store_true", help="also time the calls with a random candidate_bias=, then the plain calls again")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rank_time.py measures on an MI355X; no HIP device here")
     out = {"tool": "rank_time", "device": torch.cuda.get_device_name(0)}
     for name in args.configs.split(","):
-        out[name] = run_config(name, args.reps, [int(b) for b in args.batches.split(",")], not args.no_torch, args.candidates)
+        out[name] = run_config(name, args.reps, [int(b) for b in args.batches.split(",")], not args.no_torch, args.candidates, args.bias)
     print(json.dumps(out))
 
 

@@ -3,7 +3,7 @@ has without it — embs[q] @ embs.T in query chunks sized to 1 GB of scores, mas
 chunk — at the sizes of BASELINE configs 3 and 2, with rank_candidates' time on the same box beside them.  Prints one JSON
 line.
 
-    python tools/softmax_time.py [--configs c3,c2] [--batches 1024,16384] [--reps 5] [--no-torch] [--candidates C[,C...]]
+    python tools/softmax_time.py [--configs c3,c2] [--batches 1024,16384] [--reps 5] [--no-torch] [--candidates C[,C...]] [--bias]
 
 Per config and B in (1,024, 16,384): medians of device-event windows (ms, warm) of the forward (no autograd graph), of the
 forward plus backward down to d embs (both with a filter list per query built from `known` edges, 10 per query, and the
@@ -17,7 +17,11 @@ it out (a counter collection of the kernels alone: tools/pmc.sh <prefix> softmax
 with lists) against a sorted random subset of C nodes (candidates=; "N" = every node, through the subset entry points; the
 targets are drawn from the subset, so softmax_loss adds none): their times with C / N x the all-node time of the same call
 beside them — bce_loss' all-node forward + backward is then timed as well — and, so that the two can be told apart from
-noise, the all-node calls timed a second time after them (`*_again_ms`: the same code twice in one command)."""
+noise, the all-node calls timed a second time after them (`*_again_ms`: the same code twice in one command).
+
+--bias adds the same three calls (softmax_loss forward and forward + backward, bce_loss forward + backward, with lists) with a
+random candidate_bias= (N(0, 1), one entry per node, requiring its gradient in the backward): `bias` holds their times, with
+--candidates also against every subset; the calls without the keyword are then timed again (`*_again_ms`, as above)."""
 
 from __future__ import annotations
 
@@ -92,7 +96,7 @@ def candidate_sets(spec, N, dev, seed):
     return sets
 
 
-def run_config(name, reps, batches, with_torch, candidates=""):
+def run_config(name, reps, batches, with_torch, candidates="", bias=False):
     cfg = CONFIGS[name]
     dev = torch.device("cuda:0")
     N, d = cfg["N"], cfg["d"]
@@ -126,16 +130,17 @@ def run_config(name, reps, batches, with_torch, candidates=""):
         r["fwd_fraction_of_fp32_matrix_peak"] = flops / (r["fwd_known_ms"] * 1e-3) / (FP32_MATRIX_PEAK_TF * 1e12)
         r["bwd_fraction_of_fp32_matrix_peak"] = (4 * flops / ((r["fwd_bwd_known_ms"] - r["fwd_known_ms"]) * 1e-3)
                                                  / (FP32_MATRIX_PEAK_TF * 1e12))
-        def loss_step(kind, tt, cand):
+        def loss_step(kind, tt, cand, b=None):
             e = embs.detach().requires_grad_(True)
+            b = None if b is None else b.detach().requires_grad_(True)
             if kind == "softmax":
-                loss = model.softmax_loss(e, q, tt, scale=scale, filt_ptr=ptr, filt_idx=idx, candidates=cand)
+                loss = model.softmax_loss(e, q, tt, scale=scale, filt_ptr=ptr, filt_idx=idx, candidates=cand, candidate_bias=b)
             else:
-                loss = model.bce_loss(e, q, pos_ptr=ptr, pos_idx=idx, scale=scale, smoothing=0.1, candidates=cand)
+                loss = model.bce_loss(e, q, pos_ptr=ptr, pos_idx=idx, scale=scale, smoothing=0.1, candidates=cand, candidate_bias=b)
             loss.mean().backward()
             return loss.detach(), e.grad
 
-        if candidates:
+        if candidates or bias:
             r["bce_fwd_bwd_known_ms"], _, _ = timed(lambda: loss_step("bce", t, None), reps)
         for label, cand in candidate_sets(candidates, N, dev, cfg["seed"]).items():
             C = cand.numel()
@@ -148,7 +153,22 @@ def run_config(name, reps, batches, with_torch, candidates=""):
             for key in ("fwd_known_ms", "fwd_bwd_known_ms", "bce_fwd_bwd_known_ms"):
                 s[key.replace("_ms", "_scaled_all_node_ms")] = r[key] * C / N
             r[f"candidates_{label}"] = s
-        if candidates:
+        if bias:
+            b = torch.randn(N, device=dev, generator=torch.Generator(device=dev).manual_seed(cfg["seed"] + B))
+            s = {}
+            s["fwd_known_ms"], _, _ = timed(lambda: model.softmax_loss(embs, q, t, scale=scale, filt_ptr=ptr, filt_idx=idx,
+                                                                       candidate_bias=b), reps)
+            s["fwd_bwd_known_ms"], s["fwd_bwd_peak_bytes"], _ = timed(lambda: loss_step("softmax", t, None, b), reps)
+            s["bce_fwd_bwd_known_ms"], _, _ = timed(lambda: loss_step("bce", t, None, b), reps)
+            for label, cand in candidate_sets(candidates, N, dev, cfg["seed"]).items():
+                tc = cand[torch.from_numpy(np.random.default_rng(B + 1).integers(0, cand.numel(), B)).to(dev)]
+                s[f"candidates_{label}"] = {
+                    "fwd_known_ms": timed(lambda: model.softmax_loss(embs, q, tc, scale=scale, filt_ptr=ptr, filt_idx=idx, candidates=cand,
+                                                                     candidate_bias=b), reps)[0],
+                    "fwd_bwd_known_ms": timed(lambda: loss_step("softmax", tc, cand, b), reps)[0],
+                    "bce_fwd_bwd_known_ms": timed(lambda: loss_step("bce", tc, cand, b), reps)[0]}
+            r["bias"] = s
+        if candidates or bias:
             r["fwd_known_again_ms"], _, _ = timed(lambda: model.softmax_loss(embs, q, t, scale=scale, filt_ptr=ptr, filt_idx=idx), reps)
             r["fwd_bwd_known_again_ms"], _, _ = timed(step, reps)
             r["bce_fwd_bwd_known_again_ms"], _, _ = timed(lambda: loss_step("bce", t, None), reps)
@@ -177,12 +197,13 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--candidates", default="", help="C[,C...] or N: also time the losses against a sorted random subset")
+    ap.add_argument("--bias", action="store_true", help="also time the losses with a random candidate_bias=, then the plain calls again")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("softmax_time.py measures on an MI355X; no HIP device here")
     out = {"tool": "softmax_time", "device": torch.cuda.get_device_name(0)}
     for name in args.configs.split(","):
-        out[name] = run_config(name, args.reps, [int(b) for b in args.batches.split(",")], not args.no_torch, args.candidates)
+        out[name] = run_config(name, args.reps, [int(b) for b in args.batches.split(",")], not args.no_torch, args.candidates, args.bias)
     print(json.dumps(out))
 
 
