@@ -145,6 +145,12 @@ SIGNATURES = {
     "ghf_score_bce_bwd_b_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i64]),
     "ghf_score_bce_bwd_b": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _vp, _vp, _vp, _i64, _vp, _vp, _sz,
                                    _vp, _vp, _vp, _vp]),
+    "ghf_score_negsamp_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i64]),
+    "ghf_score_negsamp_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _f32, _vp, _i64, _vp, _vp, _sz,
+                                     _vp, _vp, _vp]),
+    "ghf_score_negsamp_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i64]),
+    "ghf_score_negsamp_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _f32, _vp, _vp, _vp, _i64, _vp,
+                                     _vp, _sz, _vp, _vp, _vp, _vp]),
     "ghf_relation_rows_workspace_bytes": (_sz, [_i64, _i32]),
     "ghf_relation_rows": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
     "ghf_relation_scores": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp]),
@@ -1063,6 +1069,78 @@ def score_bce_bwd(q: torch.Tensor, c: torch.Tensor, loss: torch.Tensor, grad_los
                                     smoothing, _ptr(loss), _ptr(grad_loss), _ptr(ws), ws.numel(), _ptr(dq), _ptr(dc), _stream()),
            "ghf_score_bce_bwd")
     return dq, dc
+
+
+# ---- negative-sampling loss with self-adversarial weighting (include/ghf.h: ghf_score_negsamp_fwd / _bwd, csrc/negsamp.hip) ----
+def score_negsamp_workspace_bytes(B: int, N: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_negsamp_workspace_bytes(B, N, C, d, nnz))
+
+
+def score_negsamp_bwd_workspace_bytes(B: int, N: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_negsamp_bwd_workspace_bytes(B, N, C, d, nnz))
+
+
+def _negsamp_args(q, c, target, iq, filt_ptr, filt_idx, scale, margin, adversarial_temperature, what: str):
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, what)
+    margin, alpha = float(margin), float(adversarial_temperature)
+    if not (float("-inf") < margin < float("inf")):
+        raise ValueError(f"{what}: margin must be finite, got {margin}")
+    if not (0.0 <= alpha < float("inf")):
+        raise ValueError(f"{what}: adversarial_temperature must be finite and not negative, got {alpha}")
+    return q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, alpha
+
+
+def score_negsamp_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optional[torch.Tensor] = None,
+                      filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0,
+                      margin: float = 0.0, adversarial_temperature: float = 0.0, workspace: Optional[torch.Tensor] = None,
+                      out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ic: Optional[torch.Tensor] = None,
+                      bias: Optional[torch.Tensor] = None):
+    """(loss, lw) fp32 [B] of include/ghf.h: ghf_score_negsamp_fwd.  With z_ij = scale q[iq[i]] . c[j] (+ bias[j]) and J_i the
+    rows of c (of c[ic] with `ic`) outside query i's filter list other than target[i]: lw[i] = log sum_{J_i} exp(alpha z_ij)
+    (-inf: no negatives), loss[i] = softplus(-(z_it + margin)) + sum_{J_i} exp(alpha z_ij - lw[i]) softplus(z_ij + margin), alpha
+    the adversarial temperature.  Nothing of size B x N is stored.  With `workspace` (uint8, score_negsamp_workspace_bytes, C = 0
+    for every node) and `out` given the call allocates nothing.  With `ic` a query whose target is not among the candidates
+    gets NaN."""
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, alpha = _negsamp_args(
+        q, c, target, iq, filt_ptr, filt_idx, scale, margin, adversarial_temperature, "score_negsamp_fwd")
+    N, d = c.size(0), c.size(1)
+    ic = _ic_arg(ic, c, "score_negsamp_fwd")
+    loss, lw = _f32_out_pair(out, (B,), (B,), q.device, "score_negsamp_fwd")
+    bias = _bias_arg(bias, c, "score_negsamp_fwd")
+    C = 0 if ic is None else ic.numel()
+    ws = _workspace(workspace, score_negsamp_workspace_bytes, q.device, "score_negsamp_fwd", B=B, N=N, C=C, d=d, nnz=nnz)
+    _check(load().ghf_score_negsamp_fwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
+                                        d, scale, margin, alpha, _ptr(ic), C, _ptr(bias), _ptr(ws), ws.numel(), _ptr(loss), _ptr(lw),
+                                        _stream()), "ghf_score_negsamp_fwd")
+    return loss, lw
+
+
+def score_negsamp_bwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, lw: torch.Tensor, grad_loss: torch.Tensor,
+                      iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
+                      filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0, margin: float = 0.0,
+                      adversarial_temperature: float = 0.0, workspace: Optional[torch.Tensor] = None,
+                      out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ic: Optional[torch.Tensor] = None,
+                      bias: Optional[torch.Tensor] = None, want_db: bool = True):
+    """(dq [B, d], dc [N, d]) fp32 of include/ghf.h: ghf_score_negsamp_bwd, the weights constants — dq per query (not scattered
+    through iq), every row of dc written.  `lw` is the forward's.  With `ic` (the forward's) dc is [C, d], row j the gradient
+    of row ic[j] of c.  With `bias` (the forward's) the result is (dq, dc, db) as score_softmax_bwd's."""
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, alpha = _negsamp_args(
+        q, c, target, iq, filt_ptr, filt_idx, scale, margin, adversarial_temperature, "score_negsamp_bwd")
+    lw, grad_loss = _req(lw, torch.float32, "lw"), _req(grad_loss, torch.float32, "grad_loss")
+    if lw.numel() != B or grad_loss.numel() != B:
+        raise ValueError(f"score_negsamp_bwd: lw and grad_loss must hold B = {B} values")
+    N, d = c.size(0), c.size(1)
+    ic = _ic_arg(ic, c, "score_negsamp_bwd")
+    bias = _bias_arg(bias, c, "score_negsamp_bwd")
+    C = 0 if ic is None else ic.numel()
+    M = C if C else N
+    ws = _workspace(workspace, score_negsamp_bwd_workspace_bytes, q.device, "score_negsamp_bwd", B=B, N=N, C=C, d=d, nnz=nnz)
+    dq, dc = _f32_out_pair(out, (B, d), (M, d), q.device, "score_negsamp_bwd")
+    db = torch.empty(M, dtype=torch.float32, device=q.device) if bias is not None and want_db else None
+    _check(load().ghf_score_negsamp_bwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
+                                        d, scale, margin, alpha, _ptr(lw), _ptr(grad_loss), _ptr(ic), C, _ptr(bias), _ptr(ws),
+                                        ws.numel(), _ptr(dq), _ptr(dc), _ptr(db), _stream()), "ghf_score_negsamp_bwd")
+    return (dq, dc) if bias is None else (dq, dc, db)
 
 
 # ---- relation-typed query rows (include/ghf.h: ghf_relation_rows, csrc/relation.hip) ------------------------------------

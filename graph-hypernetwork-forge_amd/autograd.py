@@ -518,6 +518,38 @@ class BceLossFn(torch.autograd.Function):
         return _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand) + (None,) * 6 + (_bias_grad(ctx, 8, db, bias, cand),)
 
 
+class NegSamplingLossFn(torch.autograd.Function):
+    """loss_i = softplus(-(z_it + margin)) + sum_{j in J_i} w_ij softplus(z_ij + margin), z_ij = scale q_i . embs[j] (+ bias[j]),
+    J_i every node (every candidate of `cand`) outside query i's filter list other than its target, w_ij = softmax_j(alpha z_ij)
+    over J_i taken as a CONSTANT, as in RotatE and PyKEEN's NSSALoss (HyperGNN.negative_sampling_loss; include/ghf.h:
+    ghf_score_negsamp_fwd); q_i and the pair `rows` / `query` as in SoftmaxLossFn.  Saved is lw_i = log sum_{J_i} exp(alpha
+    z_ij), from which the backward recomputes the weights tile by tile (ghf_score_negsamp_bwd); _all_node_loss_grads and
+    _bias_grad turn its (dq, dc, db) into the gradients exactly as for the softmax loss."""
+
+    @staticmethod
+    def forward(ctx, embs, rows, query, target, ptr, idx, scale: float, margin: float, alpha: float, cand=None, bias=None):
+        assert (rows is None) != (query is None)
+        embs = embs.contiguous().float()
+        rows = None if rows is None else rows.contiguous().float()
+        bias = None if bias is None else bias.contiguous()
+        loss, lw = _native.score_negsamp_fwd(embs if rows is None else rows, embs, target, iq=query, filt_ptr=ptr, filt_idx=idx,
+                                             scale=scale, margin=margin, adversarial_temperature=alpha, ic=cand, bias=bias)
+        ctx.save_for_backward(embs, rows, query, target, ptr, idx, lw, cand, bias)
+        ctx.scale, ctx.margin, ctx.alpha = scale, margin, alpha
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        embs, rows, query, target, ptr, idx, lw, cand, bias = ctx.saved_tensors
+        res = _native.score_negsamp_bwd(embs if rows is None else rows, embs, target, lw, g.contiguous().float(), iq=query,
+                                        filt_ptr=ptr, filt_idx=idx, scale=ctx.scale, margin=ctx.margin,
+                                        adversarial_temperature=ctx.alpha, ic=cand, bias=bias,
+                                        want_db=bias is not None and ctx.needs_input_grad[10])
+        db = res[2] if bias is not None else None
+        return _all_node_loss_grads(ctx, embs, rows, query, res[0], res[1], cand) + (None,) * 8 + (_bias_grad(ctx, 10, db, bias, cand),)
+
+
 class ScorePairsFn(torch.autograd.Function):
     """s_i = a_i . b_i (reference score_triple, hypergnn.py:304-318)."""
 

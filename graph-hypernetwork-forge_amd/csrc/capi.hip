@@ -910,6 +910,51 @@ int ghf_score_bce_bwd_b(const float* q, const float* c, const int64_t* iq, const
 
 #undef GHF_BIAS_CHECK
 
+// the negative-sampling loss (include/ghf.h): one general form per call — ic = NULL with C = 0 is every node,
+// bias = NULL none.  score_entry_check, then its own two floats and the pairing of ic and C.
+#define GHF_NEGSAMP_CHECK(op)                                                                                       \
+    do {                                                                                                            \
+        GHF_REQUIRE(margin >= -3.402823466e38f && margin <= 3.402823466e38f, op ": margin must be finite");         \
+        GHF_REQUIRE(adv_temperature >= 0.f && adv_temperature <= 3.402823466e38f,                                    \
+                    op ": adv_temperature must be finite and not negative");                                        \
+        GHF_REQUIRE(ic ? (C > 0 && C <= N) : C == 0, op ": need ic and 1 <= C <= N, or ic = NULL and C = 0");        \
+    } while (0)
+
+size_t ghf_score_negsamp_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    return score_negsamp_workspace_bytes(B, N, C, d, nnz);
+}
+
+int ghf_score_negsamp_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                          const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                          float margin, float adv_temperature, const int64_t* ic, int64_t C, const float* bias, void* workspace,
+                          size_t workspace_bytes, float* loss, float* lw, void* stream) {
+    const int rc = score_entry_check("score_negsamp_fwd", "filter", q && c && target && loss && lw, filt_ptr, filt_idx, nnz, scale, 0.f,
+                                     workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_NEGSAMP_CHECK("score_negsamp_fwd");
+    return launch_score_negsamp_fwd(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, adv_temperature, ic, C,
+                                    bias, workspace, workspace_bytes, loss, lw, (hipStream_t)stream);
+}
+
+size_t ghf_score_negsamp_bwd_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    return score_negsamp_bwd_workspace_bytes(B, N, C, d, nnz);
+}
+
+int ghf_score_negsamp_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                          const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                          float margin, float adv_temperature, const float* lw, const float* grad_loss, const int64_t* ic,
+                          int64_t C, const float* bias, void* workspace, size_t workspace_bytes, float* dq, float* dc, float* db,
+                          void* stream) {
+    const int rc = score_entry_check("score_negsamp_bwd", "filter", q && c && target && lw && grad_loss && dq && dc, filt_ptr,
+                                     filt_idx, nnz, scale, 0.f, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_NEGSAMP_CHECK("score_negsamp_bwd");
+    return launch_score_negsamp_bwd(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, adv_temperature, lw,
+                                    grad_loss, ic, C, bias, workspace, workspace_bytes, dq, dc, bias ? db : nullptr, (hipStream_t)stream);
+}
+
+#undef GHF_NEGSAMP_CHECK
+
 size_t ghf_relation_rows_workspace_bytes(int64_t B, int R) { return relation_rows_workspace_bytes(B, R); }
 
 int ghf_relation_rows(const float* x, const int64_t* ix, const int64_t* rel, const float* W, const float* bias,

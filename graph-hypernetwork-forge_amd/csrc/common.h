@@ -199,6 +199,17 @@ int launch_score_softmax_bwd(const float* q, const float* c, const int64_t* iq, 
                              const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc,
                              hipStream_t stream, const int64_t* ic = nullptr, int64_t C = 0, const float* bias = nullptr,
                              float* db = nullptr);
+// negsamp.hip (forward) and softmax.hip (backward: softmax_bwd_kernel's third loss); C = 0 with ic = NULL: every node
+size_t score_negsamp_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+size_t score_negsamp_bwd_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+int launch_score_negsamp_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                             const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                             float margin, float alpha, const int64_t* ic, int64_t C, const float* bias, void* ws, size_t ws_bytes,
+                             float* loss, float* lw, hipStream_t stream);
+int launch_score_negsamp_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                             const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                             float margin, float alpha, const float* lw, const float* grad_loss, const int64_t* ic, int64_t C,
+                             const float* bias, void* ws, size_t ws_bytes, float* dq, float* dc, float* db, hipStream_t stream);
 // bce.hip (forward) and softmax.hip (backward: softmax_bwd_kernel's second loss)
 size_t score_bce_workspace_bytes(int64_t B, int64_t N, int d);
 size_t score_bce_bwd_workspace_bytes(int64_t B, int64_t N, int d);

@@ -1,6 +1,7 @@
 // rank_sweep.h — the tiled q . c^T sweep on the exact fp32 matrix instruction that rank.hip (rank counts, top-k),
 // softmax.hip (1-vs-all softmax loss) and bce.hip (multi-label 1-vs-all BCE loss) share: geometry, the VALU form of the
-// accumulator's chain, the LDS layout and rank_tile_kernel with its four epilogues, and the host side around it: the two
+// accumulator's chain, the LDS layout and rank_tile_kernel with its five epilogues (the fifth: negsamp.hip's negative-sampling
+// loss, with an argument struct of its own for its two extra floats), and the host side around it: the two
 // kernels that validate ids ahead of a sweep, the checks that open a launch (score_open) and the choice of the instantiation
 // (launch_rank_tiles).  rank.hip's header comment describes the sweep.  Two template flags select a variant of it, each with an
 // argument struct of its own so that the others keep theirs: SUB (a candidate subset, candidates.hip) and BIAS (a per-candidate
@@ -199,7 +200,7 @@ struct RankArgs {
 // N, the lists and the targets are then the count of, and positions in, ic.  A type of its own, so that the all-node
 // instantiations keep their argument block, and with it their code, as they are.
 struct RankSubArgs : RankArgs { const int64_t* ic; int64_t Nn; };
-template <bool SUB, bool BIAS = false> struct RankKernelArgs { typedef RankArgs type; };
+template <bool SUB, bool BIAS = false, bool NEG = false> struct RankKernelArgs { typedef RankArgs type; };
 template <> struct RankKernelArgs<true, false> { typedef RankSubArgs type; };
 
 // a per-candidate bias (the BIAS instantiations): bias[j] is the fp32 term of the
@@ -208,6 +209,12 @@ template <> struct RankKernelArgs<true, false> { typedef RankSubArgs type; };
 // losses use fmaf(scale, s(i, j), bias[j]).  Again a type of its own: every other instantiation keeps its argument block.
 struct RankBiasArgs : RankSubArgs { const float* bias; };
 template <bool SUB> struct RankKernelArgs<SUB, true> { typedef RankBiasArgs type; };
+
+// the negative-sampling loss (the RK_NEGSAMP instantiations; negsamp.hip): its margin and adversarial
+// temperature.  One type for its four (SUB, BIAS) variants (ic / Nn / bias unused where the flag is off), and a type of its
+// own once more: every other instantiation keeps its argument block.
+struct RankNegArgs : RankBiasArgs { float margin, alpha; };
+template <bool SUB, bool BIAS> struct RankKernelArgs<SUB, BIAS, true> { typedef RankNegArgs type; };
 
 // row j of a sweep over the candidate subset ic [C] of a table of `rows` rows: absent past C or when the id is outside the
 // table (candidates.hip reports such a list; the sweep only has to read nothing outside c)
@@ -219,7 +226,7 @@ __device__ __forceinline__ const float* sub_row(const float* __restrict__ c, con
 }
 
 // the epilogue of rank_tile_kernel
-constexpr int RK_RANK = 0, RK_TOPK = 1, RK_SOFTMAX = 2, RK_BCE = 3;
+constexpr int RK_RANK = 0, RK_TOPK = 1, RK_SOFTMAX = 2, RK_BCE = 3, RK_NEGSAMP = 4;
 
 // first entry of the sorted list [lo, hi) that is not below `first`
 __device__ __forceinline__ int64_t filter_lower_bound(const int64_t* __restrict__ idx, int64_t lo, int64_t hi, int64_t first) {
@@ -235,6 +242,16 @@ __device__ __forceinline__ f32x2 lse_merge(f32x2 x, f32x2 y) {
     const float m = fmaxf(x[0], y[0]);
     if (!(m > -INFINITY)) return m == m ? f32x2{-INFINITY, 0.f} : f32x2{m, m};     // both empty, or a NaN on its way out
     return f32x2{m, x[1] * expf(x[0] - m) + y[1] * expf(y[0] - m)};
+}
+
+// (max, S, T) of two disjoint sets of negatives (RK_NEGSAMP): max of a = alpha z, S = sum exp(a - max), T = sum exp(a - max)
+// softplus(z + margin); (-inf, 0, 0) is the empty set
+struct NegTriple { float m, s, t; };
+__device__ __forceinline__ NegTriple neg_merge(NegTriple x, NegTriple y) {
+    const float m = fmaxf(x.m, y.m);
+    if (!(m > -INFINITY)) return m == m ? NegTriple{-INFINITY, 0.f, 0.f} : NegTriple{m, m, m};
+    const float ex = expf(x.m - m), ey = expf(y.m - m);
+    return NegTriple{m, x.s * ex + y.s * ey, x.t * ex + y.t * ey};
 }
 
 // log(1 + t) for t = exp(-|z|) in (0, 1].  Forming 1 + t rounds t to a multiple of 2^-24: 4e-6 of the result at t = 2^-6,
@@ -301,9 +318,10 @@ static inline size_t rank_lds_bytes(int d, int BK, int CT, bool bias = false) {
 }
 
 template <int BK, int CT, int MODE, bool SUB = false, bool BIAS = false>
-__global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKernelArgs<SUB, BIAS>::type a) {
+__global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKernelArgs<SUB, BIAS, MODE == RK_NEGSAMP>::type a) {
     constexpr bool TOPK = MODE == RK_TOPK, RANK = MODE == RK_RANK, SOFTMAX = MODE == RK_SOFTMAX, BCE = MODE == RK_BCE;
-    constexpr bool CURSOR = SOFTMAX || BCE;             // the lists are walked by a cursor, in step with the sweep
+    constexpr bool NEGSAMP = MODE == RK_NEGSAMP;
+    constexpr bool CURSOR = SOFTMAX || BCE || NEGSAMP;  // the lists are walked by a cursor, in step with the sweep
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int NT = CT * 2, NW = NT / 64;            // a wave per 64 candidates x 64 queries
     constexpr int LDC = BK + 4, F4 = BK / 4, NL = CT * F4 / NT;
@@ -358,13 +376,16 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
     int64_t tgt[2] = {-1, -1}, nxt[2] = {INT64_MAX, INT64_MAX};
     // bce: running sums of softplus(z), of z, and of z over the column's listed candidates (its positives)
     float bsp[2] = {0.f, 0.f}, bsz[2] = {0.f, 0.f}, bpos[2] = {0.f, 0.f};
+    // negsamp: rm / rs are the running max of alpha z and the sum S of exp(alpha z - max) over the column's negatives, nT the
+    // same sum weighted by softplus(z + margin); tgt and the cursor as for the softmax
+    float nT[2] = {0.f, 0.f};
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn) {
         const int64_t qi = q0 + wn * 64 + tn * 32 + lr;
         tq[tn] = __int_as_float(0x7FC00000);
         if (qi < a.B) {
             if (RANK) tq[tn] = a.t[qi];
-            if (SOFTMAX) tgt[tn] = a.target[qi];
+            if (SOFTMAX || NEGSAMP) tgt[tn] = a.target[qi];
             if (!RANK && a.filt_ptr) {
                 int64_t lo = a.filt_ptr[qi], hi = a.filt_ptr[qi + 1];
                 lo = lo < 0 ? 0 : (lo > a.nnz ? a.nnz : lo);
@@ -574,6 +595,50 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
                     bsz[tn] += tsz;
                     bpos[tn] += tpos;
                 }
+            } else if constexpr (NEGSAMP) {
+                // no contraction in this arm: z is rounded once before the margin is added, with a bias (fmaf(scale, s, b)) as
+                // without (scale * s), so that a bias of zeros keeps the bits
+#pragma clang fp contract(off)
+                // The column's negatives of this tile enter (max, S, T) in two passes over its 32 registers: the max of
+                // alpha z (and, where the tile's id range holds a listed id, the target or the end of the candidates, a bit
+                // per register that is no negative), then the two sums.  A register left out adds +0 to both.
+                const int64_t tile_end = tile * CT + CT;
+#pragma unroll
+                for (int tn = 0; tn < 2; ++tn) {
+                    uint32_t outm = 0;
+                    float mx = rm[tn];
+                    if (full && nxt[tn] >= tile_end && (tgt[tn] < tile * CT || tgt[tn] >= tile_end)) {
+#pragma unroll
+                        for (int e = 0; e < 32; ++e) mx = fmaxf(mx, a.alpha * logit(tn, e));
+                    } else {
+                        const bool look = nxt[tn] < tile_end;
+#pragma unroll
+                        for (int e = 0; e < 32; ++e) {
+                            const int64_t cand = base + 32 * (e >> 4) + (e & 3) + 8 * ((e & 15) >> 2);
+                            const bool out = cand >= a.N || cand == tgt[tn] || (look && in_filter(a.filt_idx, f0[tn], f1[tn], cand));
+                            outm |= out ? 1u << e : 0u;
+                            mx = out ? mx : fmaxf(mx, a.alpha * logit(tn, e));
+                        }
+                        while (nxt[tn] < tile_end) {
+                            ++f0[tn];
+                            nxt[tn] = f0[tn] < f1[tn] ? a.filt_idx[f0[tn]] : INT64_MAX;
+                        }
+                    }
+                    if (mx > -INFINITY) {
+                        const float r = __expf(rm[tn] - mx);
+                        float S = rs[tn] * r, T = nT[tn] * r;
+#pragma unroll
+                        for (int e = 0; e < 32; ++e) {
+                            const float z = logit(tn, e);
+                            const float w = (outm >> e) & 1 ? 0.f : __expf(fmaf(a.alpha, z, -mx));
+                            S += w;
+                            T = fmaf(w, softplus(z + a.margin), T);
+                        }
+                        rs[tn] = S;
+                        nT[tn] = T;
+                        rm[tn] = mx;
+                    }
+                }
             } else if (RANK) {
 #pragma unroll
                 for (int tm = 0; tm < 2; ++tm)
@@ -680,6 +745,27 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
             w[1] = pos;
             w[2] = sz;
         }
+    } else if constexpr (NEGSAMP) {
+        // as the BCE's partials: the column's NP triples through LDS, merged in that fixed order, one per (query, slab)
+        constexpr int NP = NW;
+        float* part = Cs;
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) {
+            float* p = part + ((wn * 64 + tn * 32 + lr) * NP + wm * 2 + lh) * 3;
+            p[0] = rm[tn];
+            p[1] = rs[tn];
+            p[2] = nT[tn];
+        }
+        __syncthreads();
+        if (tid < RK_TILE && q0 + tid < a.B) {
+            NegTriple m = {part[tid * NP * 3], part[tid * NP * 3 + 1], part[tid * NP * 3 + 2]};
+            for (int p = 1; p < NP; ++p)
+                m = neg_merge(m, NegTriple{part[(tid * NP + p) * 3], part[(tid * NP + p) * 3 + 1], part[(tid * NP + p) * 3 + 2]});
+            float* w = a.ws_bce + ((size_t)(q0 + tid) * a.slabs + slab) * 3;
+            w[0] = m.m;
+            w[1] = m.s;
+            w[2] = m.t;
+        }
     } else if (RANK) {
 #pragma unroll
         for (int tn = 0; tn < 2; ++tn) {
@@ -707,11 +793,33 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
 // the sweep with epilogue MODE over a.qtiles x a.slabs workgroups: the one place that picks the instantiation.  With `ic`
 // (node ids of the a.N candidates, rows of a table of Nn rows) the sweep over that subset.
 // With `bias` (one value per candidate of the sweep: per node, or gathered through ic) the BIAS instantiations.
+// RK_NEGSAMP: the same 2 x 2 x 2 choice among its own instantiations, which all take RankNegArgs (margin, alpha).
 template <int MODE>
 static int launch_rank_tiles(const RankArgs& a, hipStream_t stream, const int64_t* ic = nullptr, int64_t Nn = 0,
-                             const float* bias = nullptr) {
+                             const float* bias = nullptr, float margin = 0.f, float alpha = 0.f) {
     const unsigned grid = (unsigned)(a.qtiles * a.slabs);
-    if (bias) {
+    if constexpr (MODE == RK_NEGSAMP) {
+        RankNegArgs s;
+        static_cast<RankArgs&>(s) = a;
+        s.ic = ic; s.Nn = Nn; s.bias = bias; s.margin = margin; s.alpha = alpha;
+        const bool wide = rank_ctile(a.d) == 256;
+        const size_t lds = wide ? rank_lds_bytes(a.d, 32, 256, bias != nullptr) : rank_lds_bytes(a.d, 16, 128, bias != nullptr);
+#define GHF_RANK_NEG_LAUNCH(BK, CT, SUBSET, BIASED)                                              \
+    do {                                                                                          \
+        GHF_SET_MAX_LDS((rank_tile_kernel<BK, CT, MODE, SUBSET, BIASED>), lds);                   \
+        rank_tile_kernel<BK, CT, MODE, SUBSET, BIASED><<<grid, CT * 2, lds, stream>>>(s);         \
+    } while (0)
+#define GHF_RANK_NEG_SHAPE(BK, CT)                                                                \
+    do {                                                                                          \
+        if (ic && bias) GHF_RANK_NEG_LAUNCH(BK, CT, true, true);                                  \
+        else if (ic) GHF_RANK_NEG_LAUNCH(BK, CT, true, false);                                    \
+        else if (bias) GHF_RANK_NEG_LAUNCH(BK, CT, false, true);                                  \
+        else GHF_RANK_NEG_LAUNCH(BK, CT, false, false);                                           \
+    } while (0)
+        if (wide) GHF_RANK_NEG_SHAPE(32, 256); else GHF_RANK_NEG_SHAPE(16, 128);
+#undef GHF_RANK_NEG_SHAPE
+#undef GHF_RANK_NEG_LAUNCH
+    } else if (bias) {
         RankBiasArgs s;
         static_cast<RankArgs&>(s) = a;
         s.ic = ic; s.Nn = Nn; s.bias = bias;

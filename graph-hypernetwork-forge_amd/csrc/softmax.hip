@@ -36,6 +36,11 @@
 // the lists naming positives, not masks: the dq sweep's cursor says which steps hold listed ids, and the dc sweep's collected
 // pairs SUBTRACT grad scale (1 - smoothing) from their entries of G instead of zeroing them.
 //
+// The self-adversarial negative-sampling loss (negsamp.hip) is the kernel's third loss (LOSS = SB_NEGSAMP), the
+// saved per-query value being lw = log sum_{j in J_i} exp(alpha z_ij) (-inf: no negatives) and the weights constants:
+//   G_ij = grad[i] scale exp(alpha z_ij - lw[i]) sigma(z_ij + margin) on J_i,   G_it = -grad[i] scale sigma(-(z_it + margin)),
+// 0 at a listed candidate; lists, cursor and the dc sweep's zeroed pairs are the softmax's, the target never a negative.
+//
 // A per-candidate bias (BIAS instantiations; include/ghf.h: the _b calls): every logit is fmaf(scale, s(i,j), b_j),
 // forward (rank_sweep.h) and backward, where the softmax forms p_ij = exp(fmaf(scale, s, b_j - lse[i])) so that a zero bias keeps
 // the bits.  The dq sweep stages the 64 bias values of a step with its streamed rows, the dc sweep loads its owner rows' once;
@@ -190,7 +195,7 @@ struct SmBwdArgs {
     int64_t qtiles, slab_tiles, slabs;       // dq
     float* dq_part;                          // dq: [slabs, B, d]
     float* dc;                               // dc: [N, d]
-    float pos_w, neg_w;                      // bce: 1 - smoothing, smoothing / N
+    float pos_w, neg_w;                      // bce: 1 - smoothing, smoothing / N; negsamp: the margin, the adversarial temperature
 };
 // SUB: candidate j is row ic[j] of c, which has Nn rows (rank_sweep.h: sub_row, RankSubArgs)
 struct SmBwdSubArgs : SmBwdArgs { const int64_t* ic; int64_t Nn; };
@@ -214,12 +219,12 @@ struct SmQuery {
 };
 
 // the loss whose G the backward forms
-constexpr int SB_SOFTMAX = 0, SB_BCE = 1;
+constexpr int SB_SOFTMAX = 0, SB_BCE = 1, SB_NEGSAMP = 2;
 
 template <int OT, int DMAX, bool DC, int LOSS, bool SUB = false, bool BIAS = false>
 __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwdKernelArgs<SUB, BIAS>::type a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr bool BCE = LOSS == SB_BCE;
+    constexpr bool BCE = LOSS == SB_BCE, NEG = LOSS == SB_NEGSAMP;
     constexpr int ST = SB_ST, NT = SB_NT, LDG = OT + 1;
     constexpr int QR = DC ? ST : OT, CR = DC ? OT : ST;             // query / candidate rows of a step's score tile
     constexpr int QT = QR / 32, NTW = QT * (CR / 32) / 4;           // a wave: one query column tile, NTW candidate row tiles
@@ -423,7 +428,24 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
                 const int64_t cand = cand0 + cl;
                 float gv = 0.f;
                 if (live && cand < a.N) {
-                    if (BCE) {
+                    if constexpr (NEG) {
+#pragma clang fp contract(off)                           // z is rounded before the margin is added, as in the forward
+                        // sigma(y), y = z + margin, from e = exp(-|y|) as the BCE's; the target's entry is -gs sigma(-y), a
+                        // negative's gs w sigma(y) with w = exp(alpha z - lw), 0 for a query without negatives (lw = -inf)
+                        float z;
+                        if constexpr (BIAS) z = fmaf(a.scale, s[t][r], bq[r >> 2][r & 3]);
+                        else z = a.scale * s[t][r];
+                        const float y = z + a.pos_w;
+                        const float e = __expf(-fabsf(y)), rcp = __builtin_amdgcn_rcpf(1.f + e);
+                        const float hi = rcp, lo = e * rcp;              // sigma(|y|), sigma(-|y|)
+                        if (cand == cur.tgt) {
+                            gv = -cur.gs * (y >= 0.f ? lo : hi);
+                        } else {
+                            const bool masked = look && in_filter(a.filt_idx, cur.f0, cur.f1, cand);
+                            const float w = cur.lse > -INFINITY ? __expf(fmaf(a.neg_w, z, -cur.lse)) : 0.f;
+                            gv = masked ? 0.f : cur.gs * (w * (y >= 0.f ? hi : lo));
+                        }
+                    } else if (BCE) {
                         // sigma(z) from e = exp(-|z|) in (0, 1]: 1 / (1 + e) for z >= 0, e / (1 + e) below
                         float z;
                         if constexpr (BIAS) z = fmaf(a.scale, s[t][r], bq[r >> 2][r & 3]);
@@ -536,15 +558,17 @@ static int launch_bwd_bias_tiles(const SmBwdBiasArgs& a, hipStream_t stream) {
     return GHF_OK;
 }
 
-// both losses' backward: the lists are the softmax's filter lists or the BCE's positives, `lse` the forward's lse or (BCE, of
-// which only the NaNs are read) its loss; target and smoothing belong to one loss each
+// the three losses' backward: the lists are the softmax's / negsamp's filter lists or the BCE's positives, `lse` the forward's
+// lse, (negsamp) its lw or (BCE, of which only the NaNs are read) its loss; target, smoothing and (margin, alpha) belong to
+// one loss each
 template <int LOSS>
 static int launch_score_loss_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* list_ptr,
                                  const int64_t* list_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                                  float smoothing, const float* lse, const float* grad_loss, void* ws, size_t ws_bytes, float* dq,
-                                 float* dc, hipStream_t stream, const int64_t* ic, int64_t C, const float* bias, float* db) {
+                                 float* dc, hipStream_t stream, const int64_t* ic, int64_t C, const float* bias, float* db,
+                                 float margin = 0.f, float alpha = 0.f) {
     RankArgs r;
-    const char* op = LOSS == SB_BCE ? "score_bce_bwd" : "score_softmax_bwd";
+    const char* op = LOSS == SB_BCE ? "score_bce_bwd" : LOSS == SB_NEGSAMP ? "score_negsamp_bwd" : "score_softmax_bwd";
     const int64_t M = ic ? C : N;                    // the candidates the sweeps run over: dc is [M, d]
     GHF_REQUIRE(!ic || (C > 0 && C <= N), "%s: need 1 <= C <= N candidates", op);
     const size_t base = score_softmax_bwd_workspace_bytes(B, M, d);
@@ -572,6 +596,7 @@ static int launch_score_loss_bwd(const float* q, const float* c, const int64_t* 
     a.filt_ptr = r.filt_ptr; a.filt_idx = list_idx; a.nnz = nnz;
     a.rows_q = rows_q; a.N = M; a.B = B; a.d = d; a.scale = scale; a.lse = lse; a.grad = grad_loss;
     if (LOSS == SB_BCE) { a.pos_w = 1.f - smoothing; a.neg_w = smoothing / (float)M; }
+    if (LOSS == SB_NEGSAMP) { a.pos_w = margin; a.neg_w = alpha; }
     a.qtiles = r.qtiles; a.slab_tiles = r.slab_tiles; a.slabs = r.slabs;
     a.dq_part = (float*)ws; a.dc = dc;
     if (bias && ic) rc = sb_otile(d) == 128 ? launch_bwd_bias_tiles<128, 128, LOSS, true>(a, stream) : launch_bwd_bias_tiles<64, 256, LOSS, true>(a, stream);
@@ -605,6 +630,20 @@ int launch_score_bce_bwd(const float* q, const float* c, const int64_t* iq, cons
                          const int64_t* ic, int64_t C, const float* bias, float* db) {
     return launch_score_loss_bwd<SB_BCE>(q, c, iq, nullptr, pos_ptr, pos_idx, nnz, rows_q, N, B, d, scale, smoothing, loss, grad_loss,
                                          ws, ws_bytes, dq, dc, stream, ic, C, bias, db);
+}
+
+// the negative-sampling loss's backward (negsamp.hip holds its forward): the same two sweeps; the workspace is the softmax's
+// general form (a subset's always with room for its gathered bias)
+size_t score_negsamp_bwd_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    return C > N ? 0 : score_softmax_bwd_b_workspace_bytes(B, N, C, d, nnz);
+}
+
+int launch_score_negsamp_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                             const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                             float margin, float alpha, const float* lw, const float* grad_loss, const int64_t* ic, int64_t C,
+                             const float* bias, void* ws, size_t ws_bytes, float* dq, float* dc, float* db, hipStream_t stream) {
+    return launch_score_loss_bwd<SB_NEGSAMP>(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, 0.f, lw, grad_loss, ws,
+                                             ws_bytes, dq, dc, stream, ic, C, bias, db, margin, alpha);
 }
 
 }  // namespace ghf

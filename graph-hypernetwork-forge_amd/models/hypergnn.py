@@ -994,6 +994,69 @@ class HyperGNN(nn.Module):
         e = embs.detach().float()
         return _native.score_softmax_fwd(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, scale=scale, ic=cand, bias=bias)[0]
 
+    def negative_sampling_loss(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, scale: float = 1.0,
+                               margin: float = 0.0, adversarial_temperature: float = 0.0, known=None,
+                               filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+                               query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
+                               candidates: Optional[torch.Tensor] = None,
+                               candidate_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The negative-sampling loss with self-adversarial weighting (RotatE; PyKEEN's ``NSSALoss``; the DGL-KE and OGB
+        ``wikikg2`` / ``biokg`` baselines) on one shared set of negatives, fp32 ``[B]``.  With ``z[i, j] = scale * embs[query[i]]
+        . embs[j]`` and the negatives ``J_i`` = every node (every candidate) except ``query[i]``'s known partners (``known`` /
+        ``filt_ptr, filt_idx`` as in ``rank_candidates``) and except ``target[i]`` itself::
+
+            w[i, j] = softmax over J_i of (adversarial_temperature * z[i, j])          # a constant: detached
+            loss[i] = softplus(-(z[i, target[i]] + margin)) + sum_{j in J_i} w[i, j] * softplus(z[i, j] + margin)
+
+        i.e. ``-logsigmoid(margin + pos) - sum_j w_j logsigmoid(-(margin + neg_j))``.  ``adversarial_temperature=0`` is the
+        uniform mean over the negatives (TransE / word2vec negative sampling).  The value per query is the positive term plus
+        the weighted negative term: PyKEEN's ``/ 2`` and the batch mean are the caller's.  A query without negatives has the
+        positive term alone.  Neither the ``[B, C]`` logits, the weights nor the ``[C, d]`` gather exist, forward or backward:
+        one sweep on the fp32 matrix cores with an online softmax-weighted sum in its epilogue (``ghf_score_negsamp_fwd``), and
+        a backward that recomputes the weights from the saved log-sum (``ghf_score_negsamp_bwd``,
+        ``autograd.NegSamplingLossFn``), the weights taken as constants as those libraries do.  Bit-reproducible.  ``margin``
+        finite, ``adversarial_temperature`` finite and ``>= 0``, ``scale`` finite and ``> 0`` (``ValueError`` otherwise).
+
+        Recording, ``query_rows`` / ``known=(src, dst, rel)`` with ``query_rel``, ``candidates`` and ``candidate_bias`` follow
+        ``softmax_loss``: with ``candidates`` the batch's targets are added to the set, so another query's target is an
+        in-batch negative unless that query's ``known`` lists it; rows of ``embs`` that are neither candidates, targets nor
+        queries get exactly zero gradient; the logits become ``fma(scale, ., candidate_bias[j])`` with a finite bias, which
+        receives its ``[N]`` gradient when it requires grad; a bias of zeros gives the bits of the call without the keyword."""
+        if embs.dim() != 2:
+            raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        bias = self._candidate_bias(candidate_bias, embs)
+        bias_grad = bias is not None and bias.requires_grad
+        cand = None if candidates is None else self._candidate_ids(candidates, embs)
+        self._query_rows(embs, query, query_rows, "negative_sampling_loss")
+        scale, margin, alpha = float(scale), float(margin), float(adversarial_temperature)
+        if not (0.0 < scale < float("inf")):
+            raise ValueError(f"scale must be finite and positive, got {scale}")
+        if not (float("-inf") < margin < float("inf")):
+            raise ValueError(f"margin must be finite, got {margin}")
+        if not (0.0 <= alpha < float("inf")):
+            raise ValueError(f"adversarial_temperature must be finite and not negative, got {alpha}")
+        q = self._rank_ids(query, embs.size(0), embs, "query")
+        t = self._rank_ids(target, embs.size(0), embs, "target")
+        if q.numel() != t.numel():
+            raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
+        if not embs.is_cuda:
+            raise RuntimeError(f"negative_sampling_loss computes on an MI355X HIP device only (input is on {embs.device})")
+        ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
+        if cand is not None:
+            cand = self._softmax_candidates(cand, t)
+        if query_rows is not None:
+            if torch.is_grad_enabled() and (embs.requires_grad or query_rows.requires_grad or bias_grad):
+                from ..autograd import NegSamplingLossFn
+                return NegSamplingLossFn.apply(embs, query_rows, None, t, ptr, idx, scale, margin, alpha, cand, bias)
+            return _native.score_negsamp_fwd(query_rows.detach(), embs.detach().float(), t, filt_ptr=ptr, filt_idx=idx, scale=scale,
+                                             margin=margin, adversarial_temperature=alpha, ic=cand, bias=bias)[0]
+        if torch.is_grad_enabled() and (embs.requires_grad or bias_grad):
+            from ..autograd import NegSamplingLossFn
+            return NegSamplingLossFn.apply(embs, None, q, t, ptr, idx, scale, margin, alpha, cand, bias)
+        e = embs.detach().float()
+        return _native.score_negsamp_fwd(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, scale=scale, margin=margin,
+                                         adversarial_temperature=alpha, ic=cand, bias=bias)[0]
+
     def bce_loss(self, embs: torch.Tensor, query: torch.Tensor, *, known=None, pos_ptr: Optional[torch.Tensor] = None,
                  pos_idx: Optional[torch.Tensor] = None, scale: float = 1.0, smoothing: float = 0.0, normalize: bool = True,
                  query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,

@@ -695,6 +695,47 @@ int ghf_score_bce_bwd_b(const float* q, const float* c, const int64_t* iq, const
                         const float* grad_loss, const int64_t* ic, int64_t C, const float* bias, void* workspace,
                         size_t workspace_bytes, float* dq, float* dc, float* db, void* stream);
 
+/* ---- negative-sampling loss with self-adversarial weighting (csrc/negsamp.hip, csrc/softmax.hip) -----------
+ * The objective of RotatE, PyKEEN's NSSALoss, DGL-KE and the OGB wikikg2 / biokg baselines on one shared set of negatives;
+ * adv_temperature = 0 is the uniform negative-sampling loss of TransE / word2vec.  One general form per call: q, c, iq,
+ * target, the filter lists, rows_q, N, B, d and the limits exactly as ghf_score_softmax_fwd; ic [C] as for the _sub calls, or
+ * ic = NULL with C = 0 for every node; bias [N] as for the _b calls, or NULL for none (GHF_EINVAL for any other pairing of ic
+ * and C).  s(i, j) is the same chain, z_ij = scale s(i, j), or fmaf(scale, s(i, j), bias[j]) with a bias (NOT multiplied by
+ * scale).  scale: finite, > 0; margin: finite; adv_temperature (alpha): finite, >= 0; GHF_EINVAL otherwise.  The bias must be
+ * finite, as for the BCE loss.  With P the candidates (every row of c, or ic) and J_i = P minus query i's list minus
+ * target[i] — known partners are filtered out, the target is never its own negative:
+ *   lw[i]   = log sum_{j in J_i} exp(alpha z_ij)                                  fp32 [B]; -inf when J_i is empty
+ *   w_ij    = exp(alpha z_ij - lw[i])                                             sums to 1 over J_i; alpha = 0: 1 / |J_i|
+ *   loss[i] = softplus(-(z_it + margin)) + sum_{j in J_i} w_ij softplus(z_ij + margin)                       fp32 [B]
+ * "positive term + weighted negative term": PyKEEN's / 2 and the mean over the batch are the caller's.  A query without
+ * negatives has the positive term alone.  softplus as for the BCE loss.
+ * ghf_score_negsamp_bwd: given grad_loss [B] and the forward's lw, THE WEIGHTS ARE CONSTANTS (detached, as in RotatE and
+ * PyKEEN; part of the contract):
+ *   G_ij = grad_loss[i] scale w_ij sigmoid(z_ij + margin)  on J_i,   G_it = -grad_loss[i] scale sigmoid(-(z_it + margin)),
+ *   G_ij = 0 at a listed j;   dq[i] = sum_j G_ij c[j]  [B, d] (NOT scattered through iq),   dc[j] = sum_i G_ij q[iq[i]]
+ *   ([N, d], or [C, d] with ic, row j the gradient of row ic[j] of c; every row written),   db[j] = (sum_i G_ij) / scale  ([N] or
+ *   [C]; NULL = not wanted; ignored without a bias).
+ * With ic the target must be in P: a query whose target is not, or whose iq / target / list id is out of range, has loss = lw
+ * = NaN and takes no part in the backward, which reads a NaN lw[i] as "no part" and an lw[i] of -inf as "the target entry
+ * alone".  An ic that is not strictly ascending or leaves [0, N) makes every query invalid.  No id faults.  All sums run in a
+ * fixed order, no floating-point atomics: loss, lw, dq, dc and db are bit-reproducible; the slabs depend on the candidate
+ * count and d alone, so a query's bits do not depend on its batch, and a subset call has the bits of the all-node call on a
+ * contiguous copy c[ic].  A bias of zeros gives the bits of the call without one.  workspace: the matching _workspace_bytes
+ * query (C = 0: every node; 0 = bad sizes, d > 256 included), 256-byte aligned: O(B) plus 12 bytes per (query, candidate
+ * slab) forward, the softmax backward's backward, plus the id map and C floats with C > 0.  d > 256 is GHF_EUNSUPPORTED.
+ * Nothing allocates or synchronises. */
+size_t ghf_score_negsamp_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+int ghf_score_negsamp_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                          const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                          float margin, float adv_temperature, const int64_t* ic, int64_t C, const float* bias, void* workspace,
+                          size_t workspace_bytes, float* loss, float* lw, void* stream);
+size_t ghf_score_negsamp_bwd_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+int ghf_score_negsamp_bwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                          const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                          float margin, float adv_temperature, const float* lw, const float* grad_loss, const int64_t* ic,
+                          int64_t C, const float* bias, void* workspace, size_t workspace_bytes, float* dq, float* dc, float* db,
+                          void* stream);
+
 /* ---- relation-typed query rows (csrc/relation.hip) ----------------------------------------------------
  * No counterpart in the reference, whose score_triple (models/hypergnn.py:304-318) ignores the relation.  The query side of
  * a (head, relation, ?) score: every query row multiplied by ITS relation's matrix, without gathering a matrix per query
