@@ -606,7 +606,7 @@ class RelationRowsFn(torch.autograd.Function):
             if ix is not None:
                 dx = _fold_rows(dx, ix, rows)
             elif rows > B:                                   # rows beyond the B queries took no part
-                dx = torch.cat([dx, dx.new_zeros(rows - B, dx.size(1))])
+                dx = torch.cat([dx, torch.zeros(rows - B, dx.size(1), dtype=dx.dtype, device=dx.device)])
         if ctx.needs_input_grad[3]:
             dA = _native.group_outer(x, perm if ix is None else ix.index_select(0, perm), g, perm, goff)
         if ctx.has_bias and ctx.needs_input_grad[4]:

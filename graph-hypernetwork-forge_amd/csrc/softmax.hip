@@ -573,7 +573,9 @@ static int launch_score_loss_bwd(const float* q, const float* c, const int64_t* 
     GHF_REQUIRE(!ic || (C > 0 && C <= N), "%s: need 1 <= C <= N candidates", op);
     const size_t base = score_softmax_bwd_workspace_bytes(B, M, d);
     const size_t need = ic ? score_softmax_bwd_sub_workspace_bytes(B, C, d, nnz) : base;      // with a bias over a subset: + [C] floats
-    const size_t need_b = bias && ic && need ? need + rk_align((size_t)C * 4) : need;
+    // (ghf_score_negsamp_bwd_workspace_bytes is one size per shape: a subset's workspace holds the gathered bias's room, asked
+    // for or not, and the call refuses less)
+    const size_t need_b = (bias || LOSS == SB_NEGSAMP) && ic && need ? need + rk_align((size_t)C * 4) : need;
     int rc = score_open(op, softmax_bwd_geom, need_b, q, c, iq, list_ptr, list_idx, nnz, rows_q, M, B, d, ws_bytes, &r);
     if (rc != GHF_OK) return rc;
     SmBwdBiasArgs a = {};

@@ -133,6 +133,8 @@ int ghf_plan_build(const int64_t* edge_index /* [2,E] row 0 = src, row 1 = dst *
  *   ghf_subgraph_nodes: from dist: node_list [N] int64, whose first m[k] entries are the nodes with dist <= k ordered by
  *                       (dist, node id) (the rest is not written); new_id [N] int64: v's position in node_list, -1 beyond
  *                       k hops; m [k+1] int64: m[j] = the number of nodes with dist <= j — they are the first m[j] entries.
+ *                       It is not told E and uses the head of the shared workspace only: what it requires, and refuses to
+ *                       run below, is ghf_subgraph_workspace_bytes(N, 0, k).
  *   ghf_subgraph_edges: the edges whose destination has dist <= k - 1 (their sources have dist <= k), in the plan's sorted
  *                       order (a stable compaction): edge_out [2, E] int64 (row stride E): edge_out[p] = new_id[src],
  *                       edge_out[E + p] = new_id[dst]; rel_out [E] int64: the relation id, p < E'; num_edges [1] int64 = E'.
