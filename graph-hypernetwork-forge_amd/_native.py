@@ -166,10 +166,30 @@ SIGNATURES = {
     "ghf_set_range_flag": (_i32, [_vp]),
 }
 
+# include/ghf_negatives.h (per-query negative sets, csrc/negatives.hip): a table of its own — SIGNATURES is include/ghf.h's
+NEG_SIGNATURES = {
+    "ghf_neg_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "ghf_neg_rank": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "ghf_neg_softmax_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _i64, _vp, _vp, _sz, _vp, _vp,
+                                   _vp]),
+    "ghf_neg_negsamp_fwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _f32, _vp, _i64, _vp, _vp, _sz,
+                                   _vp, _vp, _vp]),
+    "ghf_neg_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _f32, _vp, _i64, _vp, _vp, _vp,
+                           _vp, _sz, _vp, _vp, _vp]),
+}
+NEG_SOFTMAX, NEG_NEGSAMP = 0, 1          # ghf_neg_bwd's mode
+
 
 def header_symbols() -> List[str]:
     """Function names declared in include/ghf.h (for the export test)."""
     with open(os.path.join(_build.INCLUDE, "ghf.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(ghf_[a-z_0-9]+)\s*\(", text)))
+
+
+def negatives_header_symbols() -> List[str]:
+    """Function names declared in include/ghf_negatives.h."""
+    with open(os.path.join(_build.INCLUDE, "ghf_negatives.h")) as f:
         text = f.read()
     return sorted(set(re.findall(r"\b(ghf_[a-z_0-9]+)\s*\(", text)))
 
@@ -195,7 +215,7 @@ def load() -> C.CDLL:
                     f"libghf_hip.so is missing at {path} and could not be built ({exc}). "
                     "This package has no CPU/PyTorch fallback: run __graft_entry__.build() first.") from exc
         lib = C.CDLL(path)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(NEG_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1141,6 +1161,118 @@ def score_negsamp_bwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, lw
                                         d, scale, margin, alpha, _ptr(lw), _ptr(grad_loss), _ptr(ic), C, _ptr(bias), _ptr(ws),
                                         ws.numel(), _ptr(dq), _ptr(dc), _ptr(db), _stream()), "ghf_score_negsamp_bwd")
     return (dq, dc) if bias is None else (dq, dc, db)
+
+
+# ---- per-query negative sets (include/ghf_negatives.h, csrc/negatives.hip) ------------------------------------------------
+def neg_workspace_bytes(B: int, K: int, d: int, nnz: int) -> int:
+    return int(load().ghf_neg_workspace_bytes(B, K, d, nnz))
+
+
+def _neg_arg(neg: torch.Tensor, B: int, c: torch.Tensor, what: str) -> torch.Tensor:
+    """The negatives of the ghf_neg_* calls: int64 [B, K], K >= 1, on c's device.  What the entries are (-1, a node id, or
+    neither: that query is invalid) is the device's check."""
+    neg = _req(neg, torch.int64, "neg")
+    if neg.dim() != 2 or neg.size(0) != B or neg.size(1) < 1:
+        raise ValueError(f"{what}: neg must be [B = {B}, K >= 1], got {tuple(neg.shape)}")
+    if neg.device != c.device:
+        raise RuntimeError(f"{what}: neg is on {neg.device}, the embeddings on {c.device}")
+    return neg
+
+
+def score_neg_rank(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor, iq: Optional[torch.Tensor] = None,
+                   filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+                   workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                   bias: Optional[torch.Tensor] = None):
+    """(greater, equal) int64 [B] of include/ghf_negatives.h: ghf_neg_rank — how many of query i's OWN negatives neg[i, :]
+    (node ids, -1 = no entry, repeats count) score above / the same as row target[i], positions that hold the target or a
+    listed id left out.  `bias` (fp32 [N]): every score is s + bias[row].  With `workspace` (uint8, neg_workspace_bytes) and
+    `out` given the call allocates nothing."""
+    q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, "score_neg_rank")
+    target = _req(target, torch.int64, "target")
+    if target.dim() != 1 or target.numel() != B or target.device != q.device:
+        raise ValueError(f"score_neg_rank: target must be [B = {B}] on {q.device}, got {tuple(target.shape)} on {target.device}")
+    neg = _neg_arg(neg, B, c, "score_neg_rank")
+    N, d, K = c.size(0), c.size(1), neg.size(1)
+    bias = _bias_arg(bias, c, "score_neg_rank")
+    ws = _workspace(workspace, neg_workspace_bytes, q.device, "score_neg_rank", B=B, K=K, d=d, nnz=nnz)
+    if out is None:
+        greater = torch.empty(B, dtype=torch.int64, device=q.device)
+        equal = torch.empty(B, dtype=torch.int64, device=q.device)
+    else:
+        greater, equal = (_req(t, torch.int64, "out") for t in out)
+        if greater.numel() != B or equal.numel() != B or not (out[0].is_contiguous() and out[1].is_contiguous()):
+            raise ValueError(f"score_neg_rank: out must be two contiguous int64 [{B}] tensors")
+    _check(load().ghf_neg_rank(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d,
+                               _ptr(neg), K, _ptr(bias), _ptr(ws), ws.numel(), _ptr(greater), _ptr(equal), _stream()), "ghf_neg_rank")
+    return greater, equal
+
+
+def score_neg_softmax_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
+                          iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
+                          filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0, workspace: Optional[torch.Tensor] = None,
+                          out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, bias: Optional[torch.Tensor] = None):
+    """(loss, lse) fp32 [B] of include/ghf_negatives.h: ghf_neg_softmax_fwd — lse[i] = log(exp(z_it) + sum over query i's own
+    negatives neg[i, :] outside its list other than the target of exp(z_ij)), z = scale q . c[row] (+ bias[row]), loss = lse -
+    z_it; exactly 0 for a query without negatives."""
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale,
+                                                                        "score_neg_softmax_fwd")
+    neg = _neg_arg(neg, B, c, "score_neg_softmax_fwd")
+    N, d, K = c.size(0), c.size(1), neg.size(1)
+    loss, lse = _f32_out_pair(out, (B,), (B,), q.device, "score_neg_softmax_fwd")
+    bias = _bias_arg(bias, c, "score_neg_softmax_fwd")
+    ws = _workspace(workspace, neg_workspace_bytes, q.device, "score_neg_softmax_fwd", B=B, K=K, d=d, nnz=nnz)
+    _check(load().ghf_neg_softmax_fwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d,
+                                      scale, _ptr(neg), K, _ptr(bias), _ptr(ws), ws.numel(), _ptr(loss), _ptr(lse), _stream()),
+           "ghf_neg_softmax_fwd")
+    return loss, lse
+
+
+def score_neg_negsamp_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
+                          iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
+                          filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0, margin: float = 0.0,
+                          adversarial_temperature: float = 0.0, workspace: Optional[torch.Tensor] = None,
+                          out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, bias: Optional[torch.Tensor] = None):
+    """(loss, lw) fp32 [B] of include/ghf_negatives.h: ghf_neg_negsamp_fwd — score_negsamp_fwd's formulas with J_i the positions
+    of query i's own negatives neg[i, :] outside its list other than the target; lw = -inf and the positive term alone where
+    there are none."""
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, alpha = _negsamp_args(
+        q, c, target, iq, filt_ptr, filt_idx, scale, margin, adversarial_temperature, "score_neg_negsamp_fwd")
+    neg = _neg_arg(neg, B, c, "score_neg_negsamp_fwd")
+    N, d, K = c.size(0), c.size(1), neg.size(1)
+    loss, lw = _f32_out_pair(out, (B,), (B,), q.device, "score_neg_negsamp_fwd")
+    bias = _bias_arg(bias, c, "score_neg_negsamp_fwd")
+    ws = _workspace(workspace, neg_workspace_bytes, q.device, "score_neg_negsamp_fwd", B=B, K=K, d=d, nnz=nnz)
+    _check(load().ghf_neg_negsamp_fwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d,
+                                      scale, margin, alpha, _ptr(neg), K, _ptr(bias), _ptr(ws), ws.numel(), _ptr(loss), _ptr(lw),
+                                      _stream()), "ghf_neg_negsamp_fwd")
+    return loss, lw
+
+
+def score_neg_bwd(mode: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor, saved: torch.Tensor,
+                  grad_loss: torch.Tensor, iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
+                  filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0, margin: float = 0.0,
+                  adversarial_temperature: float = 0.0, workspace: Optional[torch.Tensor] = None,
+                  out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, bias: Optional[torch.Tensor] = None):
+    """(dq [B, d], coef [B, K + 1]) fp32 of include/ghf_negatives.h: ghf_neg_bwd, `mode` NEG_SOFTMAX or NEG_NEGSAMP and `saved`
+    that forward's lse / lw.  coef[i, j] is the gradient of the loss sum with respect to the score of position j of query i (0
+    where the position takes no part), coef[i, K] the target's; dq[i] = sum_j coef[i, j] c[neg[i, j]] + coef[i, K] c[target[i]],
+    per query (not scattered through iq).  The gradient of c is a grouped sum over coef (autograd.NegativesLossFn)."""
+    if mode not in (NEG_SOFTMAX, NEG_NEGSAMP):
+        raise ValueError(f"score_neg_bwd: mode must be NEG_SOFTMAX or NEG_NEGSAMP, got {mode}")
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, alpha = _negsamp_args(
+        q, c, target, iq, filt_ptr, filt_idx, scale, margin, adversarial_temperature, "score_neg_bwd")
+    neg = _neg_arg(neg, B, c, "score_neg_bwd")
+    saved, grad_loss = _req(saved, torch.float32, "saved"), _req(grad_loss, torch.float32, "grad_loss")
+    if saved.numel() != B or grad_loss.numel() != B:
+        raise ValueError(f"score_neg_bwd: saved and grad_loss must hold B = {B} values")
+    N, d, K = c.size(0), c.size(1), neg.size(1)
+    bias = _bias_arg(bias, c, "score_neg_bwd")
+    ws = _workspace(workspace, neg_workspace_bytes, q.device, "score_neg_bwd", B=B, K=K, d=d, nnz=nnz)
+    dq, coef = _f32_out_pair(out, (B, d), (B, K + 1), q.device, "score_neg_bwd")
+    _check(load().ghf_neg_bwd(mode, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d,
+                              scale, margin, alpha, _ptr(neg), K, _ptr(bias), _ptr(saved), _ptr(grad_loss), _ptr(ws), ws.numel(),
+                              _ptr(dq), _ptr(coef), _stream()), "ghf_neg_bwd")
+    return dq, coef
 
 
 # ---- relation-typed query rows (include/ghf.h: ghf_relation_rows, csrc/relation.hip) ------------------------------------

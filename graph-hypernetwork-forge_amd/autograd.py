@@ -550,6 +550,66 @@ class NegSamplingLossFn(torch.autograd.Function):
         return _all_node_loss_grads(ctx, embs, rows, query, res[0], res[1], cand) + (None,) * 8 + (_bias_grad(ctx, 10, db, bias, cand),)
 
 
+class NegativesLossFn(torch.autograd.Function):
+    """The softmax loss (mode = _native.NEG_SOFTMAX) or the negative-sampling loss (NEG_NEGSAMP) of every query against ITS OWN
+    negatives `neg` [B, K] (node ids, -1 = no entry, a multiset in the given order; HyperGNN.softmax_loss /
+    negative_sampling_loss with ``negatives=``; include/ghf_negatives.h), q_i and the pair `rows` / `query` as in
+    SoftmaxLossFn.  Saved is the forward's lse / lw; the backward (ghf_neg_bwd) recomputes the logits, returns dq per query
+    and the coefficients coef [B, K + 1] — one per position, the target's last.  d embs is the sum of coef q_i over the
+    entries that name a node: the B (K + 1) node ids grouped by node (ghf_group_edges, stable; an entry that is padding
+    stands under its query's target with coefficient 0) and summed per node in that order (ghf_segment_axpy), as
+    ScoreEdgesFn does — reproducible, and a row that is no one's negative, target or query gets exactly zero.  The
+    grouping depends on the ids alone: it is made in the forward and saved.  d bias is the same sum over a column of ones,
+    over scale.  Nothing of size [N, d] is made when embs needs no gradient."""
+
+    @staticmethod
+    def forward(ctx, embs, rows, query, target, ptr, idx, neg, mode: int, scale: float, margin: float, alpha: float, bias=None):
+        assert (rows is None) != (query is None)
+        embs = embs.contiguous().float()
+        rows = None if rows is None else rows.contiguous().float()
+        bias = None if bias is None else bias.contiguous()
+        q = embs if rows is None else rows
+        if mode == _native.NEG_SOFTMAX:
+            loss, saved = _native.score_neg_softmax_fwd(q, embs, target, neg, iq=query, filt_ptr=ptr, filt_idx=idx, scale=scale,
+                                                        bias=bias)
+        else:
+            loss, saved = _native.score_neg_negsamp_fwd(q, embs, target, neg, iq=query, filt_ptr=ptr, filt_idx=idx, scale=scale,
+                                                        margin=margin, adversarial_temperature=alpha, bias=bias)
+        perm = off = None
+        if ctx.needs_input_grad[0] or (bias is not None and ctx.needs_input_grad[11]):
+            N = embs.size(0)
+            keys = torch.cat([torch.where(neg < 0, target.unsqueeze(1), neg), target.unsqueeze(1)], 1).reshape(-1).clamp_(0, N - 1)
+            perm, off = _native.group_edges(keys, N)
+        ctx.save_for_backward(embs, rows, query, target, ptr, idx, neg, saved, bias, perm, off)
+        ctx.mode, ctx.scale, ctx.margin, ctx.alpha = mode, scale, margin, alpha
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        embs, rows, query, target, ptr, idx, neg, saved, bias, perm, off = ctx.saved_tensors
+        q = embs if rows is None else rows
+        dq, coef = _native.score_neg_bwd(ctx.mode, q, embs, target, neg, saved, g.contiguous().float(), iq=query, filt_ptr=ptr,
+                                         filt_idx=idx, scale=ctx.scale, margin=ctx.margin, adversarial_temperature=ctx.alpha,
+                                         bias=bias)
+        K1 = neg.size(1) + 1
+        w = coef.reshape(-1)
+        d_embs = d_rows = d_bias = None
+        if ctx.needs_input_grad[0]:
+            owner = torch.div(perm, K1, rounding_mode="floor")                 # the query of every grouped entry
+            if query is not None:
+                owner = query.index_select(0, owner)
+            d_embs = _native.segment_axpy(w, perm, q, owner.clamp_(0, q.size(0) - 1), off)
+            if rows is None:
+                d_embs = _native.add3(d_embs, _fold_rows(dq, query, embs.size(0)), out=d_embs)
+        if rows is not None and ctx.needs_input_grad[1]:
+            d_rows = dq
+        if bias is not None and ctx.needs_input_grad[11]:
+            one = torch.ones(1, 1, dtype=torch.float32, device=embs.device)
+            d_bias = _native.segment_axpy(w, perm, one, torch.zeros_like(perm), off).reshape(-1).mul_(1.0 / ctx.scale)
+        return (d_embs, d_rows) + (None,) * 9 + (d_bias,)
+
+
 class ScorePairsFn(torch.autograd.Function):
     """s_i = a_i . b_i (reference score_triple, hypergnn.py:304-318)."""
 

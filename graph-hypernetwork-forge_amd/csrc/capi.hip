@@ -1,5 +1,6 @@
 // capi.hip — the extern "C" surface declared in include/ghf.h.
 #include "common.h"
+#include "negatives.h"
 #include <vector>
 #include <thread>
 #include <algorithm>
@@ -954,6 +955,71 @@ int ghf_score_negsamp_bwd(const float* q, const float* c, const int64_t* iq, con
 }
 
 #undef GHF_NEGSAMP_CHECK
+
+// per-query negative sets (include/ghf_negatives.h; csrc/negatives.hip): score_entry_check, then the set itself
+#define GHF_NEG_CHECK(op) GHF_REQUIRE(neg && K > 0, op ": need neg [B, K] with K >= 1")
+
+size_t ghf_neg_workspace_bytes(int64_t B, int64_t K, int d, int64_t nnz) { return neg_workspace_bytes(B, K, d, nnz); }
+
+int ghf_neg_rank(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                 const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, const int64_t* neg, int64_t K,
+                 const float* bias, void* workspace, size_t workspace_bytes, int64_t* greater, int64_t* equal, void* stream) {
+    const int rc = score_entry_check("neg_rank", "filter", q && c && target && greater && equal, filt_ptr, filt_idx, nnz, 1.f, 0.f,
+                                     workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_NEG_CHECK("neg_rank");
+    return launch_neg_rank(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, neg, K, bias, workspace, workspace_bytes,
+                           greater, equal, (hipStream_t)stream);
+}
+
+int ghf_neg_softmax_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                        const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                        const int64_t* neg, int64_t K, const float* bias, void* workspace, size_t workspace_bytes, float* loss,
+                        float* lse, void* stream) {
+    const int rc = score_entry_check("neg_softmax_fwd", "filter", q && c && target && loss && lse, filt_ptr, filt_idx, nnz, scale, 0.f,
+                                     workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_NEG_CHECK("neg_softmax_fwd");
+    return launch_neg_loss_fwd(GHF_NEG_SOFTMAX, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, 0.f, 0.f, neg, K,
+                               bias, workspace, workspace_bytes, loss, lse, (hipStream_t)stream);
+}
+
+#define GHF_NEG_FLOATS(op)                                                                                          \
+    do {                                                                                                            \
+        GHF_REQUIRE(margin >= -3.402823466e38f && margin <= 3.402823466e38f, op ": margin must be finite");         \
+        GHF_REQUIRE(adv_temperature >= 0.f && adv_temperature <= 3.402823466e38f,                                    \
+                    op ": adv_temperature must be finite and not negative");                                        \
+    } while (0)
+
+int ghf_neg_negsamp_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                        const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
+                        float margin, float adv_temperature, const int64_t* neg, int64_t K, const float* bias, void* workspace,
+                        size_t workspace_bytes, float* loss, float* lw, void* stream) {
+    const int rc = score_entry_check("neg_negsamp_fwd", "filter", q && c && target && loss && lw, filt_ptr, filt_idx, nnz, scale, 0.f,
+                                     workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_NEG_FLOATS("neg_negsamp_fwd");
+    GHF_NEG_CHECK("neg_negsamp_fwd");
+    return launch_neg_loss_fwd(GHF_NEG_NEGSAMP, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin,
+                               adv_temperature, neg, K, bias, workspace, workspace_bytes, loss, lw, (hipStream_t)stream);
+}
+
+int ghf_neg_bwd(int mode, const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float margin,
+                float adv_temperature, const int64_t* neg, int64_t K, const float* bias, const float* lse_or_lw,
+                const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* coef, void* stream) {
+    const int rc = score_entry_check("neg_bwd", "filter", q && c && target && lse_or_lw && grad_loss && dq && coef, filt_ptr, filt_idx,
+                                     nnz, scale, 0.f, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_REQUIRE(mode == GHF_NEG_SOFTMAX || mode == GHF_NEG_NEGSAMP, "neg_bwd: mode must be GHF_NEG_SOFTMAX or GHF_NEG_NEGSAMP");
+    if (mode == GHF_NEG_NEGSAMP) GHF_NEG_FLOATS("neg_bwd");
+    GHF_NEG_CHECK("neg_bwd");
+    return launch_neg_bwd(mode, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, adv_temperature, neg, K,
+                          bias, lse_or_lw, grad_loss, workspace, workspace_bytes, dq, coef, (hipStream_t)stream);
+}
+
+#undef GHF_NEG_FLOATS
+#undef GHF_NEG_CHECK
 
 size_t ghf_relation_rows_workspace_bytes(int64_t B, int R) { return relation_rows_workspace_bytes(B, R); }
 

@@ -699,14 +699,15 @@ class HyperGNN(nn.Module):
 
     # -- link prediction against every node (csrc/rank.hip; no counterpart in the reference, whose demo stops at the loss) --
     @staticmethod
-    def _rank_ids(ids: torch.Tensor, rows: int, embs: torch.Tensor, name: str) -> torch.Tensor:
-        """1-D node ids checked as indexing checks them (IndexError), negative ids wrapped: int64 on embs' device."""
+    def _rank_ids(ids: torch.Tensor, rows: int, embs: torch.Tensor, name: str, bounds=None) -> torch.Tensor:
+        """1-D node ids checked as indexing checks them (IndexError), negative ids wrapped: int64 on embs' device.  `bounds`:
+        the ids' (smallest, largest), where the caller has read them already."""
         if not isinstance(ids, torch.Tensor) or ids.dim() != 1:
             raise ValueError(f"{name} must be a 1-D tensor of node ids, got {getattr(ids, 'shape', type(ids))}")
         if ids.dtype not in (torch.int32, torch.int64):
             raise TypeError(f"{name} must be int32 or int64, got {ids.dtype}")
         if ids.numel():
-            lo, hi = (int(v) for v in torch.aminmax(ids))
+            lo, hi = bounds if bounds is not None else (int(v) for v in torch.aminmax(ids))
             if lo < -rows or hi >= rows:
                 raise IndexError(f"{name} holds ids outside [-{rows}, {rows}) (range {lo}..{hi})")
         ids = ids.to(device=embs.device, dtype=torch.int64)
@@ -737,6 +738,50 @@ class HyperGNN(nn.Module):
         if ids.numel() == 0:
             raise ValueError("candidates is empty")
         return ids.contiguous()
+
+    @staticmethod
+    def _negative_ids(negatives, B: int, embs: torch.Tensor, bounds=None) -> torch.Tensor:
+        """``negatives=`` of ``rank_candidates``, ``softmax_loss`` and ``negative_sampling_loss`` in the form the kernels take:
+        int64 ``[B, K]``, ``K >= 1``, contiguous, on embs' device; row ``i`` is query ``i``'s own set.  An entry is a node id in
+        ``[0, N)`` or exactly ``-1``, "no entry" (padding for ragged sets).  Negative ids do NOT wrap here, unlike everywhere
+        else in this class, because ``-1`` is the padding: an id outside ``{-1} | [0, N)`` is an IndexError (one ``aminmax``, as
+        ``_candidate_ids``; `bounds` = its result where the caller has it).  Nothing is sorted or de-duplicated: a row is a
+        multiset in the given order."""
+        N = embs.size(0)
+        if not isinstance(negatives, torch.Tensor) or negatives.dim() != 2 or negatives.size(0) != B or negatives.size(1) < 1:
+            raise ValueError(f"negatives must be a 2-D tensor [B = {B}, K >= 1] of node ids (-1 = no entry), got "
+                             f"{getattr(negatives, 'shape', type(negatives))}")
+        if negatives.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"negatives must be int32 or int64, got {negatives.dtype}")
+        lo, hi = bounds if bounds is not None else ((int(v) for v in torch.aminmax(negatives)) if negatives.numel() else (0, 0))
+        if lo < -1 or hi >= N:
+            raise IndexError(f"negatives holds ids outside [0, {N}) other than the padding -1 (range {lo}..{hi}; negative ids do "
+                             "not wrap here)")
+        return negatives.to(device=embs.device, dtype=torch.int64).contiguous()
+
+    @classmethod
+    def _negatives_arg(cls, negatives, candidates, query, target, embs: torch.Tensor):
+        """``negatives=`` with the queries and targets it belongs to, checked without a device and ahead of every device
+        check: None without the keyword, else ``(negatives, query, target)`` in the kernels' form.  Not together with
+        ``candidates``; ``query`` and ``target`` go through ``_rank_ids`` exactly as without the keyword (the same forms
+        accepted, the same errors), ``negatives`` through ``_negative_ids``.  Each of the three checks needs the smallest and
+        largest id, and reading a device value costs a synchronisation — three of them were 0.14 ms of a 0.33 ms call at
+        B = 1,024 x K = 1,000 — so where the three tensors share a device the six values are read at once."""
+        if negatives is None:
+            return None
+        if candidates is not None:
+            raise ValueError("pass either negatives= (a set per query) or candidates= (one set for all queries), not both")
+        N, bounds = embs.size(0), (None, None, None)
+        ids = (query, target, negatives)
+        if (all(isinstance(x, torch.Tensor) and x.dtype in (torch.int32, torch.int64) and x.numel() for x in ids)
+                and query.device == target.device == negatives.device):
+            v = torch.stack([m.to(torch.int64) for x in ids for m in torch.aminmax(x)]).tolist()
+            bounds = ((v[0], v[1]), (v[2], v[3]), (v[4], v[5]))
+        q = cls._rank_ids(query, N, embs, "query", bounds[0])
+        t = cls._rank_ids(target, N, embs, "target", bounds[1])
+        if q.numel() != t.numel():
+            raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
+        return cls._negative_ids(negatives, q.numel(), embs, bounds[2]), q, t
 
     @staticmethod
     def _candidate_bias(candidate_bias, embs: torch.Tensor) -> Optional[torch.Tensor]:
@@ -858,7 +903,8 @@ class HyperGNN(nn.Module):
     def rank_candidates(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, known=None,
                         filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                         query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
-                        candidates: Optional[torch.Tensor] = None, candidate_bias: Optional[torch.Tensor] = None):
+                        candidates: Optional[torch.Tensor] = None, candidate_bias: Optional[torch.Tensor] = None,
+                        negatives: Optional[torch.Tensor] = None):
         """Where ``target[i]`` ranks among ALL nodes as a partner of ``query[i]`` under the dot-product score
         (``score_triple``): ``(greater, equal)``, int64 ``[B]`` — the nodes scoring above / exactly as the target, the target
         itself and the query's known partners (the "filtered" setting) left out.  ``known=(src, dst)`` names true edges
@@ -884,20 +930,39 @@ class HyperGNN(nn.Module):
         ``embs[query[i]] . embs[j] + candidate_bias[j]`` — one fp32 add behind the dot product — and the target's score is
         formed the same way from its own entry (``ghf_score_rank_b``): a trained entity bias, a popularity prior, a type
         penalty.  ``-inf`` on a node that is no query's target takes it out of both counts.  A bias of zeros returns the
-        counts of the call without the keyword."""
+        counts of the call without the keyword.
+
+        ``negatives`` (int32 / int64 ``[B, K]``, not together with ``candidates``): query ``i`` is ranked against ITS OWN set,
+        row ``i`` — the protocol of OGB ``wikikg2`` / ``biokg`` / ``citation2``, whose test triples come with their 500 /
+        1,000 negatives.  An entry is a node id in ``[0, N)`` or exactly ``-1`` for "no entry" (padding for ragged sets);
+        negative ids do NOT wrap here, an id outside ``{-1} | [0, N)`` is an IndexError.  A row is a multiset in the given
+        order: an id that occurs three times counts three times, nothing is sorted or de-duplicated.  Positions that hold
+        the target or one of the query's ``known`` partners take no part.  A gather-and-dot kernel, one wave per query
+        (``ghf_neg_rank``, ``include/ghf_negatives.h``): each candidate row is read once, the query row once per query.  The
+        scores are fp32 dot products in an order that depends on ``d`` alone; they agree with the all-node sweep's to
+        rounding.  ``query_rows``, typed ``known`` and ``candidate_bias`` work as above."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
         bias = self._candidate_bias(candidate_bias, embs)
+        pre = self._negatives_arg(negatives, candidates, query, target, embs)
         cand = None if candidates is None else self._candidate_ids(candidates, embs)
         if not embs.is_cuda:
             raise RuntimeError(f"rank_candidates computes on an MI355X HIP device only (input is on {embs.device})")
         self._query_rows(embs, query, query_rows, "rank_candidates")
         e = embs.detach().float()
-        q = self._rank_ids(query, e.size(0), e, "query")
-        t = self._rank_ids(target, e.size(0), e, "target")
-        if q.numel() != t.numel():
-            raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
+        if pre is not None:
+            neg, q, t = pre
+        else:
+            neg = None
+            q = self._rank_ids(query, e.size(0), e, "query")
+            t = self._rank_ids(target, e.size(0), e, "target")
+            if q.numel() != t.numel():
+                raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
         ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx, query_rel)
+        if neg is not None:
+            if query_rows is not None:
+                return _native.score_neg_rank(query_rows.detach(), e, t, neg, filt_ptr=ptr, filt_idx=idx, bias=bias)
+            return _native.score_neg_rank(e, e, t, neg, iq=q, filt_ptr=ptr, filt_idx=idx, bias=bias)
         if query_rows is not None:
             return _native.score_rank(query_rows.detach(), e, t, filt_ptr=ptr, filt_idx=idx, ic=cand, bias=bias)
         return _native.score_rank(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, ic=cand, bias=bias)
@@ -935,7 +1000,8 @@ class HyperGNN(nn.Module):
     def softmax_loss(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, scale: float = 1.0, known=None,
                      filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                      query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
-                     candidates: Optional[torch.Tensor] = None, candidate_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     candidates: Optional[torch.Tensor] = None, candidate_bias: Optional[torch.Tensor] = None,
+                     negatives: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The 1-vs-all softmax cross-entropy that ``rank_candidates``' filtered metrics measure, fp32 ``[B]``:
         ``loss[i] = logsumexp_j(scale * embs[query[i]] . embs[j]) - scale * embs[query[i]] . embs[target[i]]`` over ALL nodes
         ``j`` except ``query[i]``'s known partners (``known`` / ``filt_ptr, filt_idx`` as in ``rank_candidates``; the target
@@ -963,23 +1029,40 @@ class HyperGNN(nn.Module):
         one.  ``-inf`` on a node that is no query's target adds nothing to any sum and leaves its gradients exactly zero.  When
         the bias requires grad it receives ``[N]``: ``sum_i grad[i] (p_ij - [j = target_i])``, exactly zero for nodes outside
         the candidate set; the loss is recorded for autograd also when only the bias requires grad.  A bias of zeros gives the
-        bits of the call without the keyword."""
+        bits of the call without the keyword.
+
+        ``negatives`` (int32 / int64 ``[B, K]``, not together with ``candidates``; ids in ``[0, N)`` or exactly ``-1`` for "no
+        entry"; negative ids do NOT wrap here; a multiset in the given order, as in ``rank_candidates``): the sampled softmax
+        with a set PER QUERY, ``F.cross_entropy`` over ``[z_target | z_negatives]``: ``loss[i] = log(exp(z_it) + sum_j
+        exp(z_ij)) - z_it`` over the positions ``j`` of row ``i`` that hold neither ``-1``, the target nor a known partner.  The
+        target enters exactly once and always; a query without negatives has loss exactly 0.  Nothing is added to the sets.
+        One wave per query gathers its rows (``ghf_neg_softmax_fwd`` / ``ghf_neg_bwd``, ``autograd.NegativesLossFn``); the
+        gradient of ``embs`` sums, per node, over every position that names it — a repeated id gets a term per occurrence —
+        and rows that are no one's negative, target or query get exactly zero.  Bit-reproducible, and a query's loss does
+        not depend on the batch it is in.  ``query_rows``, typed ``known`` and ``candidate_bias`` work as above."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
         bias = self._candidate_bias(candidate_bias, embs)
         bias_grad = bias is not None and bias.requires_grad
+        pre = self._negatives_arg(negatives, candidates, query, target, embs)
         cand = None if candidates is None else self._candidate_ids(candidates, embs)
         self._query_rows(embs, query, query_rows, "softmax_loss")
         scale = float(scale)
         if not (0.0 < scale < float("inf")):
             raise ValueError(f"scale must be finite and positive, got {scale}")
-        q = self._rank_ids(query, embs.size(0), embs, "query")
-        t = self._rank_ids(target, embs.size(0), embs, "target")
-        if q.numel() != t.numel():
-            raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
+        if pre is not None:
+            neg, q, t = pre
+        else:
+            neg = None
+            q = self._rank_ids(query, embs.size(0), embs, "query")
+            t = self._rank_ids(target, embs.size(0), embs, "target")
+            if q.numel() != t.numel():
+                raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
         if not embs.is_cuda:
             raise RuntimeError(f"softmax_loss computes on an MI355X HIP device only (input is on {embs.device})")
         ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
+        if neg is not None:
+            return self._negatives_loss(_native.NEG_SOFTMAX, embs, q, t, ptr, idx, neg, scale, 0.0, 0.0, query_rows, bias)
         if cand is not None:
             cand = self._softmax_candidates(cand, t)
         if query_rows is not None:
@@ -999,7 +1082,8 @@ class HyperGNN(nn.Module):
                                filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                                query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
                                candidates: Optional[torch.Tensor] = None,
-                               candidate_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+                               candidate_bias: Optional[torch.Tensor] = None,
+                               negatives: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The negative-sampling loss with self-adversarial weighting (RotatE; PyKEEN's ``NSSALoss``; the DGL-KE and OGB
         ``wikikg2`` / ``biokg`` baselines) on one shared set of negatives, fp32 ``[B]``.  With ``z[i, j] = scale * embs[query[i]]
         . embs[j]`` and the negatives ``J_i`` = every node (every candidate) except ``query[i]``'s known partners (``known`` /
@@ -1021,11 +1105,20 @@ class HyperGNN(nn.Module):
         ``softmax_loss``: with ``candidates`` the batch's targets are added to the set, so another query's target is an
         in-batch negative unless that query's ``known`` lists it; rows of ``embs`` that are neither candidates, targets nor
         queries get exactly zero gradient; the logits become ``fma(scale, ., candidate_bias[j])`` with a finite bias, which
-        receives its ``[N]`` gradient when it requires grad; a bias of zeros gives the bits of the call without the keyword."""
+        receives its ``[N]`` gradient when it requires grad; a bias of zeros gives the bits of the call without the keyword.
+
+        ``negatives`` (int32 / int64 ``[B, K]``, not together with ``candidates``; ids in ``[0, N)`` or exactly ``-1`` for "no
+        entry"; negative ids do NOT wrap here; a multiset in the given order, as in ``rank_candidates``): ``K`` negatives PER
+        QUERY, as RotatE's training loop and PyKEEN's default sampler draw them.  ``J_i`` is then the set of positions of row
+        ``i`` that hold neither ``-1``, the target nor a known partner, and the formulas above run over it, the weights
+        detached; a query whose ``J_i`` is empty has the positive term alone.  Nothing is added to the sets.  One wave per
+        query (``ghf_neg_negsamp_fwd`` / ``ghf_neg_bwd``, ``autograd.NegativesLossFn``); gradients, reproducibility and the
+        other keywords as for ``softmax_loss(negatives=)``."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
         bias = self._candidate_bias(candidate_bias, embs)
         bias_grad = bias is not None and bias.requires_grad
+        pre = self._negatives_arg(negatives, candidates, query, target, embs)
         cand = None if candidates is None else self._candidate_ids(candidates, embs)
         self._query_rows(embs, query, query_rows, "negative_sampling_loss")
         scale, margin, alpha = float(scale), float(margin), float(adversarial_temperature)
@@ -1035,13 +1128,19 @@ class HyperGNN(nn.Module):
             raise ValueError(f"margin must be finite, got {margin}")
         if not (0.0 <= alpha < float("inf")):
             raise ValueError(f"adversarial_temperature must be finite and not negative, got {alpha}")
-        q = self._rank_ids(query, embs.size(0), embs, "query")
-        t = self._rank_ids(target, embs.size(0), embs, "target")
-        if q.numel() != t.numel():
-            raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
+        if pre is not None:
+            neg, q, t = pre
+        else:
+            neg = None
+            q = self._rank_ids(query, embs.size(0), embs, "query")
+            t = self._rank_ids(target, embs.size(0), embs, "target")
+            if q.numel() != t.numel():
+                raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
         if not embs.is_cuda:
             raise RuntimeError(f"negative_sampling_loss computes on an MI355X HIP device only (input is on {embs.device})")
         ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
+        if neg is not None:
+            return self._negatives_loss(_native.NEG_NEGSAMP, embs, q, t, ptr, idx, neg, scale, margin, alpha, query_rows, bias)
         if cand is not None:
             cand = self._softmax_candidates(cand, t)
         if query_rows is not None:
@@ -1056,6 +1155,23 @@ class HyperGNN(nn.Module):
         e = embs.detach().float()
         return _native.score_negsamp_fwd(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, scale=scale, margin=margin,
                                          adversarial_temperature=alpha, ic=cand, bias=bias)[0]
+
+    @staticmethod
+    def _negatives_loss(mode: int, embs, q, t, ptr, idx, neg, scale: float, margin: float, alpha: float, query_rows, bias):
+        """``softmax_loss`` / ``negative_sampling_loss`` with ``negatives=`` once every argument is checked: recorded
+        (``autograd.NegativesLossFn``) under the rules of the calls without the keyword, else the forward alone."""
+        grad = embs.requires_grad or (bias is not None and bias.requires_grad) or (query_rows is not None and query_rows.requires_grad)
+        if torch.is_grad_enabled() and grad:
+            from ..autograd import NegativesLossFn
+            if query_rows is not None:
+                return NegativesLossFn.apply(embs, query_rows, None, t, ptr, idx, neg, mode, scale, margin, alpha, bias)
+            return NegativesLossFn.apply(embs, None, q, t, ptr, idx, neg, mode, scale, margin, alpha, bias)
+        e = embs.detach().float()
+        qm, iq = (e, q) if query_rows is None else (query_rows.detach(), None)
+        if mode == _native.NEG_SOFTMAX:
+            return _native.score_neg_softmax_fwd(qm, e, t, neg, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale, bias=bias)[0]
+        return _native.score_neg_negsamp_fwd(qm, e, t, neg, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale, margin=margin,
+                                             adversarial_temperature=alpha, bias=bias)[0]
 
     def bce_loss(self, embs: torch.Tensor, query: torch.Tensor, *, known=None, pos_ptr: Optional[torch.Tensor] = None,
                  pos_idx: Optional[torch.Tensor] = None, scale: float = 1.0, smoothing: float = 0.0, normalize: bool = True,
