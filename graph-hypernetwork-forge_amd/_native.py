@@ -179,6 +179,21 @@ NEG_SIGNATURES = {
 }
 NEG_SOFTMAX, NEG_NEGSAMP = 0, 1          # ghf_neg_bwd's mode
 
+# include/ghf_distance.h (distance scores for per-query negative sets, csrc/distance.hip): the third table
+DIST_SIGNATURES = {
+    "ghf_dist_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "ghf_dist_rank": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _sz, _vp, _vp, _vp]),
+    "ghf_dist_softmax_fwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _i64, _vp, _sz, _vp, _vp,
+                                    _vp]),
+    "ghf_dist_negsamp_fwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _f32, _vp, _i64, _vp, _sz,
+                                    _vp, _vp, _vp]),
+    "ghf_dist_bwd": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _f32, _vp, _i64, _vp, _vp,
+                            _vp, _sz, _vp, _vp, _vp]),
+    "ghf_dist_rows_grad": (_i32, [_i32, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
+}
+DIST_L1, DIST_L2, DIST_COMPLEX = 1, 2, 3  # the metric of the ghf_dist_* calls
+DIST_METRICS = {"l1": DIST_L1, "l2": DIST_L2, "complex": DIST_COMPLEX}
+
 
 def header_symbols() -> List[str]:
     """Function names declared in include/ghf.h (for the export test)."""
@@ -190,6 +205,13 @@ def header_symbols() -> List[str]:
 def negatives_header_symbols() -> List[str]:
     """Function names declared in include/ghf_negatives.h."""
     with open(os.path.join(_build.INCLUDE, "ghf_negatives.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(ghf_[a-z_0-9]+)\s*\(", text)))
+
+
+def distance_header_symbols() -> List[str]:
+    """Function names declared in include/ghf_distance.h."""
+    with open(os.path.join(_build.INCLUDE, "ghf_distance.h")) as f:
         text = f.read()
     return sorted(set(re.findall(r"\b(ghf_[a-z_0-9]+)\s*\(", text)))
 
@@ -215,7 +237,7 @@ def load() -> C.CDLL:
                     f"libghf_hip.so is missing at {path} and could not be built ({exc}). "
                     "This package has no CPU/PyTorch fallback: run __graft_entry__.build() first.") from exc
         lib = C.CDLL(path)
-        for name, (res, args) in list(SIGNATURES.items()) + list(NEG_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(DIST_SIGNATURES.items()):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1273,6 +1295,134 @@ def score_neg_bwd(mode: int, q: torch.Tensor, c: torch.Tensor, target: torch.Ten
                               scale, margin, alpha, _ptr(neg), K, _ptr(bias), _ptr(saved), _ptr(grad_loss), _ptr(ws), ws.numel(),
                               _ptr(dq), _ptr(coef), _stream()), "ghf_neg_bwd")
     return dq, coef
+
+
+# ---- distance scores for per-query negative sets (include/ghf_distance.h, csrc/distance.hip) ----------------------------
+def dist_workspace_bytes(B: int, K: int, d: int, nnz: int) -> int:
+    return int(load().ghf_dist_workspace_bytes(B, K, d, nnz))
+
+
+def _metric_arg(metric: int, d: int, what: str) -> int:
+    if metric not in (DIST_L1, DIST_L2, DIST_COMPLEX):
+        raise ValueError(f"{what}: metric must be DIST_L1, DIST_L2 or DIST_COMPLEX, got {metric}")
+    if metric == DIST_COMPLEX and d % 2:
+        raise ValueError(f"{what}: DIST_COMPLEX reads the rows as interleaved re / im pairs and needs an even d, got {d}")
+    return int(metric)
+
+
+def score_dist_rank(metric: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
+                    iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
+                    filt_idx: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                    out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """(greater, equal) int64 [B] of include/ghf_distance.h: ghf_dist_rank — score_neg_rank with the score -D(q_i, c[row]),
+    `metric` DIST_L1, DIST_L2 or DIST_COMPLEX: how many of query i's own negatives lie closer to q_i than / exactly as far as
+    row target[i]."""
+    q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, "score_dist_rank")
+    target = _req(target, torch.int64, "target")
+    if target.dim() != 1 or target.numel() != B or target.device != q.device:
+        raise ValueError(f"score_dist_rank: target must be [B = {B}] on {q.device}, got {tuple(target.shape)} on {target.device}")
+    neg = _neg_arg(neg, B, c, "score_dist_rank")
+    N, d, K = c.size(0), c.size(1), neg.size(1)
+    metric = _metric_arg(metric, d, "score_dist_rank")
+    ws = _workspace(workspace, dist_workspace_bytes, q.device, "score_dist_rank", B=B, K=K, d=d, nnz=nnz)
+    if out is None:
+        greater = torch.empty(B, dtype=torch.int64, device=q.device)
+        equal = torch.empty(B, dtype=torch.int64, device=q.device)
+    else:
+        greater, equal = (_req(t, torch.int64, "out") for t in out)
+        if greater.numel() != B or equal.numel() != B or not (out[0].is_contiguous() and out[1].is_contiguous()):
+            raise ValueError(f"score_dist_rank: out must be two contiguous int64 [{B}] tensors")
+    _check(load().ghf_dist_rank(metric, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
+                                d, _ptr(neg), K, _ptr(ws), ws.numel(), _ptr(greater), _ptr(equal), _stream()), "ghf_dist_rank")
+    return greater, equal
+
+
+def score_dist_softmax_fwd(metric: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
+                           iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
+                           filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0, workspace: Optional[torch.Tensor] = None,
+                           out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """(loss, lse) fp32 [B] of include/ghf_distance.h: ghf_dist_softmax_fwd — score_neg_softmax_fwd with z = -scale D(q_i,
+    c[row])."""
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale,
+                                                                        "score_dist_softmax_fwd")
+    neg = _neg_arg(neg, B, c, "score_dist_softmax_fwd")
+    N, d, K = c.size(0), c.size(1), neg.size(1)
+    metric = _metric_arg(metric, d, "score_dist_softmax_fwd")
+    loss, lse = _f32_out_pair(out, (B,), (B,), q.device, "score_dist_softmax_fwd")
+    ws = _workspace(workspace, dist_workspace_bytes, q.device, "score_dist_softmax_fwd", B=B, K=K, d=d, nnz=nnz)
+    _check(load().ghf_dist_softmax_fwd(metric, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0),
+                                       N, B, d, scale, _ptr(neg), K, _ptr(ws), ws.numel(), _ptr(loss), _ptr(lse), _stream()),
+           "ghf_dist_softmax_fwd")
+    return loss, lse
+
+
+def score_dist_negsamp_fwd(metric: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
+                           iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
+                           filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0, margin: float = 0.0,
+                           adversarial_temperature: float = 0.0, workspace: Optional[torch.Tensor] = None,
+                           out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """(loss, lw) fp32 [B] of include/ghf_distance.h: ghf_dist_negsamp_fwd — score_neg_negsamp_fwd with z = -scale D(q_i,
+    c[row]); at scale = 1 and margin = gamma the positive term is -log sigmoid(gamma - D_t), RotatE's."""
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, alpha = _negsamp_args(
+        q, c, target, iq, filt_ptr, filt_idx, scale, margin, adversarial_temperature, "score_dist_negsamp_fwd")
+    neg = _neg_arg(neg, B, c, "score_dist_negsamp_fwd")
+    N, d, K = c.size(0), c.size(1), neg.size(1)
+    metric = _metric_arg(metric, d, "score_dist_negsamp_fwd")
+    loss, lw = _f32_out_pair(out, (B,), (B,), q.device, "score_dist_negsamp_fwd")
+    ws = _workspace(workspace, dist_workspace_bytes, q.device, "score_dist_negsamp_fwd", B=B, K=K, d=d, nnz=nnz)
+    _check(load().ghf_dist_negsamp_fwd(metric, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0),
+                                       N, B, d, scale, margin, alpha, _ptr(neg), K, _ptr(ws), ws.numel(), _ptr(loss), _ptr(lw),
+                                       _stream()), "ghf_dist_negsamp_fwd")
+    return loss, lw
+
+
+def score_dist_bwd(metric: int, mode: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
+                   saved: torch.Tensor, grad_loss: torch.Tensor, iq: Optional[torch.Tensor] = None,
+                   filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0,
+                   margin: float = 0.0, adversarial_temperature: float = 0.0, workspace: Optional[torch.Tensor] = None,
+                   out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+    """(dq [B, d], coef [B, K + 1]) fp32 of include/ghf_distance.h: ghf_dist_bwd, `mode` NEG_SOFTMAX or NEG_NEGSAMP and `saved`
+    that forward's lse / lw.  coef means what score_neg_bwd's means (the gradient with respect to the score s = -D of every
+    position, the target's last); dq[i] = -(sum_j coef[i, j] g(i, neg[i, j]) + coef[i, K] g(i, target[i])), g = dD / dq.  The
+    gradient of c is dist_rows_grad over coef (autograd.DistanceLossFn)."""
+    if mode not in (NEG_SOFTMAX, NEG_NEGSAMP):
+        raise ValueError(f"score_dist_bwd: mode must be NEG_SOFTMAX or NEG_NEGSAMP, got {mode}")
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, alpha = _negsamp_args(
+        q, c, target, iq, filt_ptr, filt_idx, scale, margin, adversarial_temperature, "score_dist_bwd")
+    neg = _neg_arg(neg, B, c, "score_dist_bwd")
+    saved, grad_loss = _req(saved, torch.float32, "saved"), _req(grad_loss, torch.float32, "grad_loss")
+    if saved.numel() != B or grad_loss.numel() != B:
+        raise ValueError(f"score_dist_bwd: saved and grad_loss must hold B = {B} values")
+    N, d, K = c.size(0), c.size(1), neg.size(1)
+    metric = _metric_arg(metric, d, "score_dist_bwd")
+    ws = _workspace(workspace, dist_workspace_bytes, q.device, "score_dist_bwd", B=B, K=K, d=d, nnz=nnz)
+    dq, coef = _f32_out_pair(out, (B, d), (B, K + 1), q.device, "score_dist_bwd")
+    _check(load().ghf_dist_bwd(metric, mode, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N,
+                               B, d, scale, margin, alpha, _ptr(neg), K, _ptr(saved), _ptr(grad_loss), _ptr(ws), ws.numel(),
+                               _ptr(dq), _ptr(coef), _stream()), "ghf_dist_bwd")
+    return dq, coef
+
+
+def dist_rows_grad(metric: int, q: torch.Tensor, c: torch.Tensor, coef: torch.Tensor, perm: torch.Tensor, off: torch.Tensor,
+                   iq: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dc [N, d] fp32 of include/ghf_distance.h: ghf_dist_rows_grad — the gradient of the candidate rows under a distance:
+    dc[v] = sum_{e in off[v] .. off[v + 1]} coef[perm[e]] g(query perm[e] // (K + 1), v), e ascending, `coef` [B, K + 1]
+    score_dist_bwd's and (perm, off) group_edges' for the B (K + 1) node ids [neg | target]; exact zeros for a node nobody
+    names."""
+    q, c, iq, _, _, B, _ = _rank_args(q, c, iq, None, None, "dist_rows_grad")
+    coef = _req(coef, torch.float32, "coef")
+    perm, off = _req(perm, torch.int64, "perm"), _req(off, torch.int64, "off")
+    N, d = c.size(0), c.size(1)
+    metric = _metric_arg(metric, d, "dist_rows_grad")
+    if coef.dim() != 2 or coef.size(0) != B or coef.size(1) < 2:
+        raise ValueError(f"dist_rows_grad: coef must be [B = {B}, K + 1], got {tuple(coef.shape)}")
+    if perm.numel() != coef.numel() or off.numel() != N + 1:
+        raise ValueError(f"dist_rows_grad: perm must hold B (K + 1) = {coef.numel()} entries and off N + 1 = {N + 1}, got "
+                         f"{perm.numel()} and {off.numel()}")
+    dc = _f32_out(out, (N, d), q.device, "dist_rows_grad")
+    _check(load().ghf_dist_rows_grad(metric, _ptr(q), _ptr(c), _ptr(iq), q.size(0), N, B, d, coef.size(1) - 1, _ptr(coef), _ptr(perm),
+                                     _ptr(off), _ptr(dc), _stream()), "ghf_dist_rows_grad")
+    return dc
 
 
 # ---- relation-typed query rows (include/ghf.h: ghf_relation_rows, csrc/relation.hip) ------------------------------------

@@ -610,6 +610,54 @@ class NegativesLossFn(torch.autograd.Function):
         return (d_embs, d_rows) + (None,) * 9 + (d_bias,)
 
 
+class DistanceLossFn(torch.autograd.Function):
+    """NegativesLossFn under a distance score, s = -D(q_i, embs[v]) with `metric` _native.DIST_L1 / DIST_L2 / DIST_COMPLEX
+    (``distance=`` of HyperGNN.softmax_loss / negative_sampling_loss; include/ghf_distance.h).  Saved is the forward's lse / lw
+    and the grouping of the B (K + 1) node ids by node (ghf_group_edges, stable; padding stands under its query's target with
+    coefficient 0), made in the forward.  The backward (ghf_dist_bwd) returns dq per query and coef [B, K + 1]; the gradient
+    of a candidate row under a distance is no multiple of the query's row, so d embs is ghf_dist_rows_grad over coef — per
+    node, its entries in order — plus dq folded through `query` when the queries are embs' own rows.  Reproducible; rows that
+    are no one's negative, target or query get exactly zero; nothing of size [N, d] is made when embs needs no gradient."""
+
+    @staticmethod
+    def forward(ctx, embs, rows, query, target, ptr, idx, neg, metric: int, mode: int, scale: float, margin: float, alpha: float):
+        assert (rows is None) != (query is None)
+        embs = embs.contiguous().float()
+        rows = None if rows is None else rows.contiguous().float()
+        q = embs if rows is None else rows
+        if mode == _native.NEG_SOFTMAX:
+            loss, saved = _native.score_dist_softmax_fwd(metric, q, embs, target, neg, iq=query, filt_ptr=ptr, filt_idx=idx,
+                                                         scale=scale)
+        else:
+            loss, saved = _native.score_dist_negsamp_fwd(metric, q, embs, target, neg, iq=query, filt_ptr=ptr, filt_idx=idx,
+                                                         scale=scale, margin=margin, adversarial_temperature=alpha)
+        perm = off = None
+        if ctx.needs_input_grad[0]:
+            N = embs.size(0)
+            keys = torch.cat([torch.where(neg < 0, target.unsqueeze(1), neg), target.unsqueeze(1)], 1).reshape(-1).clamp_(0, N - 1)
+            perm, off = _native.group_edges(keys, N)
+        ctx.save_for_backward(embs, rows, query, target, ptr, idx, neg, saved, perm, off)
+        ctx.metric, ctx.mode, ctx.scale, ctx.margin, ctx.alpha = metric, mode, scale, margin, alpha
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        embs, rows, query, target, ptr, idx, neg, saved, perm, off = ctx.saved_tensors
+        q = embs if rows is None else rows
+        dq, coef = _native.score_dist_bwd(ctx.metric, ctx.mode, q, embs, target, neg, saved, g.contiguous().float(), iq=query,
+                                          filt_ptr=ptr, filt_idx=idx, scale=ctx.scale, margin=ctx.margin,
+                                          adversarial_temperature=ctx.alpha)
+        d_embs = d_rows = None
+        if ctx.needs_input_grad[0]:
+            d_embs = _native.dist_rows_grad(ctx.metric, q, embs, coef, perm, off, iq=query)
+            if rows is None:
+                d_embs = _native.add3(d_embs, _fold_rows(dq, query, embs.size(0)), out=d_embs)
+        if rows is not None and ctx.needs_input_grad[1]:
+            d_rows = dq
+        return (d_embs, d_rows) + (None,) * 10
+
+
 class ScorePairsFn(torch.autograd.Function):
     """s_i = a_i . b_i (reference score_triple, hypergnn.py:304-318)."""
 

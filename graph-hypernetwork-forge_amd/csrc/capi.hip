@@ -1,6 +1,7 @@
 // capi.hip — the extern "C" surface declared in include/ghf.h.
 #include "common.h"
 #include "negatives.h"
+#include "distance.h"
 #include <vector>
 #include <thread>
 #include <algorithm>
@@ -1018,6 +1019,79 @@ int ghf_neg_bwd(int mode, const float* q, const float* c, const int64_t* iq, con
                           bias, lse_or_lw, grad_loss, workspace, workspace_bytes, dq, coef, (hipStream_t)stream);
 }
 
+// distance scores for per-query negative sets (include/ghf_distance.h; csrc/distance.hip): the metric first —
+// an unknown one is refused whatever else the call holds — then the checks of the ghf_neg_* calls
+#define GHF_DIST_METRIC(op, dd)                                                                                              \
+    do {                                                                                                                     \
+        GHF_REQUIRE(metric == GHF_DIST_L1 || metric == GHF_DIST_L2 || metric == GHF_DIST_COMPLEX,                            \
+                    op ": metric must be GHF_DIST_L1, GHF_DIST_L2 or GHF_DIST_COMPLEX");                                     \
+        GHF_REQUIRE(metric != GHF_DIST_COMPLEX || ((dd) & 1) == 0, op ": GHF_DIST_COMPLEX needs an even d (re / im interleaved)"); \
+    } while (0)
+
+size_t ghf_dist_workspace_bytes(int64_t B, int64_t K, int d, int64_t nnz) { return dist_workspace_bytes(B, K, d, nnz); }
+
+int ghf_dist_rank(int metric, const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                  const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, const int64_t* neg, int64_t K,
+                  void* workspace, size_t workspace_bytes, int64_t* greater, int64_t* equal, void* stream) {
+    GHF_DIST_METRIC("dist_rank", d);
+    const int rc = score_entry_check("dist_rank", "filter", q && c && target && greater && equal, filt_ptr, filt_idx, nnz, 1.f, 0.f,
+                                     workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_NEG_CHECK("dist_rank");
+    return launch_dist_rank(metric, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, neg, K, workspace, workspace_bytes,
+                            greater, equal, (hipStream_t)stream);
+}
+
+int ghf_dist_softmax_fwd(int metric, const float* q, const float* c, const int64_t* iq, const int64_t* target,
+                         const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
+                         float scale, const int64_t* neg, int64_t K, void* workspace, size_t workspace_bytes, float* loss,
+                         float* lse, void* stream) {
+    GHF_DIST_METRIC("dist_softmax_fwd", d);
+    const int rc = score_entry_check("dist_softmax_fwd", "filter", q && c && target && loss && lse, filt_ptr, filt_idx, nnz, scale, 0.f,
+                                     workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_NEG_CHECK("dist_softmax_fwd");
+    return launch_dist_loss_fwd(metric, GHF_DIST_SOFTMAX, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, 0.f, 0.f,
+                                neg, K, workspace, workspace_bytes, loss, lse, (hipStream_t)stream);
+}
+
+int ghf_dist_negsamp_fwd(int metric, const float* q, const float* c, const int64_t* iq, const int64_t* target,
+                         const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
+                         float scale, float margin, float adv_temperature, const int64_t* neg, int64_t K, void* workspace,
+                         size_t workspace_bytes, float* loss, float* lw, void* stream) {
+    GHF_DIST_METRIC("dist_negsamp_fwd", d);
+    const int rc = score_entry_check("dist_negsamp_fwd", "filter", q && c && target && loss && lw, filt_ptr, filt_idx, nnz, scale, 0.f,
+                                     workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_NEG_FLOATS("dist_negsamp_fwd");
+    GHF_NEG_CHECK("dist_negsamp_fwd");
+    return launch_dist_loss_fwd(metric, GHF_DIST_NEGSAMP, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin,
+                                adv_temperature, neg, K, workspace, workspace_bytes, loss, lw, (hipStream_t)stream);
+}
+
+int ghf_dist_bwd(int metric, int mode, const float* q, const float* c, const int64_t* iq, const int64_t* target,
+                 const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
+                 float scale, float margin, float adv_temperature, const int64_t* neg, int64_t K, const float* lse_or_lw,
+                 const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* coef, void* stream) {
+    GHF_DIST_METRIC("dist_bwd", d);
+    const int rc = score_entry_check("dist_bwd", "filter", q && c && target && lse_or_lw && grad_loss && dq && coef, filt_ptr, filt_idx,
+                                     nnz, scale, 0.f, workspace);
+    if (rc != GHF_OK) return rc;
+    GHF_REQUIRE(mode == GHF_DIST_SOFTMAX || mode == GHF_DIST_NEGSAMP, "dist_bwd: mode must be GHF_DIST_SOFTMAX or GHF_DIST_NEGSAMP");
+    if (mode == GHF_DIST_NEGSAMP) GHF_NEG_FLOATS("dist_bwd");
+    GHF_NEG_CHECK("dist_bwd");
+    return launch_dist_bwd(metric, mode, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, adv_temperature,
+                           neg, K, lse_or_lw, grad_loss, workspace, workspace_bytes, dq, coef, (hipStream_t)stream);
+}
+
+int ghf_dist_rows_grad(int metric, const float* q, const float* c, const int64_t* iq, int64_t rows_q, int64_t N, int64_t B, int d,
+                       int64_t K, const float* coef, const int64_t* perm, const int64_t* off, float* dc, void* stream) {
+    GHF_DIST_METRIC("dist_rows_grad", d);
+    GHF_REQUIRE(q && c && coef && perm && off && dc, "dist_rows_grad: null pointer argument");
+    return launch_dist_rows_grad(metric, q, c, iq, rows_q, N, B, d, K, coef, perm, off, dc, (hipStream_t)stream);
+}
+
+#undef GHF_DIST_METRIC
 #undef GHF_NEG_FLOATS
 #undef GHF_NEG_CHECK
 

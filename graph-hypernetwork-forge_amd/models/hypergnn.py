@@ -784,6 +784,24 @@ class HyperGNN(nn.Module):
         return cls._negative_ids(negatives, q.numel(), embs, bounds[2]), q, t
 
     @staticmethod
+    def _distance_arg(distance, negatives, candidates, candidate_bias, embs: torch.Tensor) -> Optional[int]:
+        """``distance=`` of ``rank_candidates``, ``softmax_loss`` and ``negative_sampling_loss``: None without the keyword, else
+        the metric of the ``ghf_dist_*`` calls (``include/ghf_distance.h``).  Only metadata is looked at, ahead of every device
+        check.  The keyword goes with ``negatives=`` alone: the all-node and shared-set sweeps are matrix-core tiles and score
+        by dot product, and no distance call takes a per-candidate bias."""
+        if distance is None:
+            return None
+        metric = _native.DIST_METRICS.get(distance) if isinstance(distance, str) else None
+        if metric is None:
+            raise ValueError(f"distance must be one of {sorted(_native.DIST_METRICS)} or None, got {distance!r}")
+        if negatives is None or candidates is not None or candidate_bias is not None:
+            raise ValueError("distance= needs negatives= (a set per query) and goes with neither candidates= nor candidate_bias=: "
+                             "the all-node and shared-set sweeps score by dot product")
+        if metric == _native.DIST_COMPLEX and embs.size(1) % 2:
+            raise ValueError(f'distance="complex" reads a row as interleaved re / im pairs and needs an even d, got {embs.size(1)}')
+        return metric
+
+    @staticmethod
     def _candidate_bias(candidate_bias, embs: torch.Tensor) -> Optional[torch.Tensor]:
         """``candidate_bias=`` of the four all-node operations: a 1-D fp32 tensor with one entry per NODE (length ``N``, also
         with ``candidates=``) on ``embs``' device, made contiguous.  Only metadata is looked at — no device work, no
@@ -904,7 +922,7 @@ class HyperGNN(nn.Module):
                         filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                         query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
                         candidates: Optional[torch.Tensor] = None, candidate_bias: Optional[torch.Tensor] = None,
-                        negatives: Optional[torch.Tensor] = None):
+                        negatives: Optional[torch.Tensor] = None, distance: Optional[str] = None):
         """Where ``target[i]`` ranks among ALL nodes as a partner of ``query[i]`` under the dot-product score
         (``score_triple``): ``(greater, equal)``, int64 ``[B]`` — the nodes scoring above / exactly as the target, the target
         itself and the query's known partners (the "filtered" setting) left out.  ``known=(src, dst)`` names true edges
@@ -940,9 +958,17 @@ class HyperGNN(nn.Module):
         the target or one of the query's ``known`` partners take no part.  A gather-and-dot kernel, one wave per query
         (``ghf_neg_rank``, ``include/ghf_negatives.h``): each candidate row is read once, the query row once per query.  The
         scores are fp32 dot products in an order that depends on ``d`` alone; they agree with the all-node sweep's to
-        rounding.  ``query_rows``, typed ``known`` and ``candidate_bias`` work as above."""
+        rounding.  ``query_rows``, typed ``known`` and ``candidate_bias`` work as above.
+
+        ``distance`` (``"l1"``, ``"l2"`` or ``"complex"``; with ``negatives`` only, and not with ``candidate_bias``): the score
+        becomes ``-D(row_i, embs[j])``, the distance of TransE (``"l1"`` / ``"l2"`` of ``row_i - embs[j]``) or of RotatE
+        (``"complex"``: the sum of the moduli of the ``d / 2`` interleaved re / im pairs, ``d`` even), so a candidate ranks
+        above the target when it lies CLOSER to the query's row (``ghf_dist_rank``, ``include/ghf_distance.h``).  The
+        translated or rotated query rows are the caller's, through ``query_rows``.  The all-node and shared-set sweeps score by
+        dot product: without ``negatives`` the keyword is a ``ValueError``."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        metric = self._distance_arg(distance, negatives, candidates, candidate_bias, embs)
         bias = self._candidate_bias(candidate_bias, embs)
         pre = self._negatives_arg(negatives, candidates, query, target, embs)
         cand = None if candidates is None else self._candidate_ids(candidates, embs)
@@ -959,6 +985,10 @@ class HyperGNN(nn.Module):
             if q.numel() != t.numel():
                 raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
         ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx, query_rel)
+        if metric is not None:
+            if query_rows is not None:
+                return _native.score_dist_rank(metric, query_rows.detach(), e, t, neg, filt_ptr=ptr, filt_idx=idx)
+            return _native.score_dist_rank(metric, e, e, t, neg, iq=q, filt_ptr=ptr, filt_idx=idx)
         if neg is not None:
             if query_rows is not None:
                 return _native.score_neg_rank(query_rows.detach(), e, t, neg, filt_ptr=ptr, filt_idx=idx, bias=bias)
@@ -1001,7 +1031,7 @@ class HyperGNN(nn.Module):
                      filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                      query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
                      candidates: Optional[torch.Tensor] = None, candidate_bias: Optional[torch.Tensor] = None,
-                     negatives: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     negatives: Optional[torch.Tensor] = None, distance: Optional[str] = None) -> torch.Tensor:
         """The 1-vs-all softmax cross-entropy that ``rank_candidates``' filtered metrics measure, fp32 ``[B]``:
         ``loss[i] = logsumexp_j(scale * embs[query[i]] . embs[j]) - scale * embs[query[i]] . embs[target[i]]`` over ALL nodes
         ``j`` except ``query[i]``'s known partners (``known`` / ``filt_ptr, filt_idx`` as in ``rank_candidates``; the target
@@ -1039,9 +1069,17 @@ class HyperGNN(nn.Module):
         One wave per query gathers its rows (``ghf_neg_softmax_fwd`` / ``ghf_neg_bwd``, ``autograd.NegativesLossFn``); the
         gradient of ``embs`` sums, per node, over every position that names it — a repeated id gets a term per occurrence —
         and rows that are no one's negative, target or query get exactly zero.  Bit-reproducible, and a query's loss does
-        not depend on the batch it is in.  ``query_rows``, typed ``known`` and ``candidate_bias`` work as above."""
+        not depend on the batch it is in.  ``query_rows``, typed ``known`` and ``candidate_bias`` work as above.
+
+        ``distance`` (``"l1"``, ``"l2"`` or ``"complex"``, as in ``rank_candidates``; with ``negatives`` only, and not with
+        ``candidate_bias``): the logits become ``z = -scale * D(row_i, embs[j])`` (``ghf_dist_softmax_fwd`` / ``ghf_dist_bwd`` /
+        ``ghf_dist_rows_grad``, ``autograd.DistanceLossFn``).  The gradient of ``embs`` and of ``query_rows`` follows the
+        distance: ``sign(delta)`` under ``"l1"``, ``delta / D`` under ``"l2"``, ``delta / |pair|`` under ``"complex"``, each
+        exactly 0 where its denominator is 0 (a candidate equal to the query's row).  Still bit-reproducible, no ``[B, K, d]``
+        tensor, forward or backward."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        metric = self._distance_arg(distance, negatives, candidates, candidate_bias, embs)
         bias = self._candidate_bias(candidate_bias, embs)
         bias_grad = bias is not None and bias.requires_grad
         pre = self._negatives_arg(negatives, candidates, query, target, embs)
@@ -1061,6 +1099,8 @@ class HyperGNN(nn.Module):
         if not embs.is_cuda:
             raise RuntimeError(f"softmax_loss computes on an MI355X HIP device only (input is on {embs.device})")
         ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
+        if metric is not None:
+            return self._distance_loss(metric, _native.NEG_SOFTMAX, embs, q, t, ptr, idx, neg, scale, 0.0, 0.0, query_rows)
         if neg is not None:
             return self._negatives_loss(_native.NEG_SOFTMAX, embs, q, t, ptr, idx, neg, scale, 0.0, 0.0, query_rows, bias)
         if cand is not None:
@@ -1083,7 +1123,7 @@ class HyperGNN(nn.Module):
                                query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
                                candidates: Optional[torch.Tensor] = None,
                                candidate_bias: Optional[torch.Tensor] = None,
-                               negatives: Optional[torch.Tensor] = None) -> torch.Tensor:
+                               negatives: Optional[torch.Tensor] = None, distance: Optional[str] = None) -> torch.Tensor:
         """The negative-sampling loss with self-adversarial weighting (RotatE; PyKEEN's ``NSSALoss``; the DGL-KE and OGB
         ``wikikg2`` / ``biokg`` baselines) on one shared set of negatives, fp32 ``[B]``.  With ``z[i, j] = scale * embs[query[i]]
         . embs[j]`` and the negatives ``J_i`` = every node (every candidate) except ``query[i]``'s known partners (``known`` /
@@ -1113,9 +1153,15 @@ class HyperGNN(nn.Module):
         ``i`` that hold neither ``-1``, the target nor a known partner, and the formulas above run over it, the weights
         detached; a query whose ``J_i`` is empty has the positive term alone.  Nothing is added to the sets.  One wave per
         query (``ghf_neg_negsamp_fwd`` / ``ghf_neg_bwd``, ``autograd.NegativesLossFn``); gradients, reproducibility and the
-        other keywords as for ``softmax_loss(negatives=)``."""
+        other keywords as for ``softmax_loss(negatives=)``.
+
+        ``distance`` (``"l1"``, ``"l2"`` or ``"complex"``, as in ``softmax_loss``; with ``negatives`` only, and not with
+        ``candidate_bias``): ``z = -scale * D(row_i, embs[j])``.  At ``scale=1`` the positive term is ``-log sigmoid(margin -
+        D_target)`` and a negative's ``-log sigmoid(D_j - margin)``: the margin is the distance budget gamma of TransE's and
+        RotatE's published losses (``ghf_dist_negsamp_fwd``, ``autograd.DistanceLossFn``)."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        metric = self._distance_arg(distance, negatives, candidates, candidate_bias, embs)
         bias = self._candidate_bias(candidate_bias, embs)
         bias_grad = bias is not None and bias.requires_grad
         pre = self._negatives_arg(negatives, candidates, query, target, embs)
@@ -1139,6 +1185,8 @@ class HyperGNN(nn.Module):
         if not embs.is_cuda:
             raise RuntimeError(f"negative_sampling_loss computes on an MI355X HIP device only (input is on {embs.device})")
         ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
+        if metric is not None:
+            return self._distance_loss(metric, _native.NEG_NEGSAMP, embs, q, t, ptr, idx, neg, scale, margin, alpha, query_rows)
         if neg is not None:
             return self._negatives_loss(_native.NEG_NEGSAMP, embs, q, t, ptr, idx, neg, scale, margin, alpha, query_rows, bias)
         if cand is not None:
@@ -1172,6 +1220,23 @@ class HyperGNN(nn.Module):
             return _native.score_neg_softmax_fwd(qm, e, t, neg, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale, bias=bias)[0]
         return _native.score_neg_negsamp_fwd(qm, e, t, neg, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale, margin=margin,
                                              adversarial_temperature=alpha, bias=bias)[0]
+
+    @staticmethod
+    def _distance_loss(metric: int, mode: int, embs, q, t, ptr, idx, neg, scale: float, margin: float, alpha: float, query_rows):
+        """``softmax_loss`` / ``negative_sampling_loss`` with ``negatives=`` and ``distance=`` once every argument is checked:
+        recorded (``autograd.DistanceLossFn``) under the rules of ``_negatives_loss``, else the forward alone."""
+        grad = embs.requires_grad or (query_rows is not None and query_rows.requires_grad)
+        if torch.is_grad_enabled() and grad:
+            from ..autograd import DistanceLossFn
+            if query_rows is not None:
+                return DistanceLossFn.apply(embs, query_rows, None, t, ptr, idx, neg, metric, mode, scale, margin, alpha)
+            return DistanceLossFn.apply(embs, None, q, t, ptr, idx, neg, metric, mode, scale, margin, alpha)
+        e = embs.detach().float()
+        qm, iq = (e, q) if query_rows is None else (query_rows.detach(), None)
+        if mode == _native.NEG_SOFTMAX:
+            return _native.score_dist_softmax_fwd(metric, qm, e, t, neg, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale)[0]
+        return _native.score_dist_negsamp_fwd(metric, qm, e, t, neg, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale, margin=margin,
+                                              adversarial_temperature=alpha)[0]
 
     def bce_loss(self, embs: torch.Tensor, query: torch.Tensor, *, known=None, pos_ptr: Optional[torch.Tensor] = None,
                  pos_idx: Optional[torch.Tensor] = None, scale: float = 1.0, smoothing: float = 0.0, normalize: bool = True,
