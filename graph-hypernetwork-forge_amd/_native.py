@@ -194,6 +194,16 @@ DIST_SIGNATURES = {
 DIST_L1, DIST_L2, DIST_COMPLEX = 1, 2, 3  # the metric of the ghf_dist_* calls
 DIST_METRICS = {"l1": DIST_L1, "l2": DIST_L2, "complex": DIST_COMPLEX}
 
+# include/ghf_distance_sweep.h (distance scores against every node or a candidate subset, csrc/distance_sweep.hip): the fourth
+DSWEEP_SIGNATURES = {
+    "ghf_dist_sweep_rank_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "ghf_dist_sweep_rank": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _sz, _vp, _vp,
+                                   _vp]),
+    "ghf_dist_sweep_topk_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32, _i64]),
+    "ghf_dist_sweep_topk": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _sz, _vp, _vp,
+                                   _vp]),
+}
+
 
 def header_symbols() -> List[str]:
     """Function names declared in include/ghf.h (for the export test)."""
@@ -212,6 +222,13 @@ def negatives_header_symbols() -> List[str]:
 def distance_header_symbols() -> List[str]:
     """Function names declared in include/ghf_distance.h."""
     with open(os.path.join(_build.INCLUDE, "ghf_distance.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(ghf_[a-z_0-9]+)\s*\(", text)))
+
+
+def distance_sweep_header_symbols() -> List[str]:
+    """Function names declared in include/ghf_distance_sweep.h."""
+    with open(os.path.join(_build.INCLUDE, "ghf_distance_sweep.h")) as f:
         text = f.read()
     return sorted(set(re.findall(r"\b(ghf_[a-z_0-9]+)\s*\(", text)))
 
@@ -237,7 +254,8 @@ def load() -> C.CDLL:
                     f"libghf_hip.so is missing at {path} and could not be built ({exc}). "
                     "This package has no CPU/PyTorch fallback: run __graft_entry__.build() first.") from exc
         lib = C.CDLL(path)
-        for name, (res, args) in list(SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(DIST_SIGNATURES.items()):
+        for name, (res, args) in (list(SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(DIST_SIGNATURES.items())
+                                  + list(DSWEEP_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1335,6 +1353,74 @@ def score_dist_rank(metric: int, q: torch.Tensor, c: torch.Tensor, target: torch
     _check(load().ghf_dist_rank(metric, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
                                 d, _ptr(neg), K, _ptr(ws), ws.numel(), _ptr(greater), _ptr(equal), _stream()), "ghf_dist_rank")
     return greater, equal
+
+
+# ---- distance scores against every node or a candidate subset (include/ghf_distance_sweep.h, csrc/distance_sweep.hip) ---
+def dist_sweep_rank_workspace_bytes(B: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_dist_sweep_rank_workspace_bytes(B, C, d, nnz))
+
+
+def dist_sweep_topk_workspace_bytes(B: int, C: int, d: int, k: int, nnz: int) -> int:
+    return int(load().ghf_dist_sweep_topk_workspace_bytes(B, C, d, k, nnz))
+
+
+def score_dist_sweep_rank(metric: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optional[torch.Tensor] = None,
+                          filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+                          workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                          ic: Optional[torch.Tensor] = None):
+    """(greater, equal) int64 [B] of include/ghf_distance_sweep.h: ghf_dist_sweep_rank — score_rank with the score -D(q_i,
+    c[row]), `metric` DIST_L1, DIST_L2 or DIST_COMPLEX: how many rows of c (of c[ic] with `ic`, int64 [C] strictly ascending
+    node ids) lie closer to query q[iq[i]] than / exactly as far as row target[i], the target and the query's filter list
+    left out.  Nothing of size B x N is stored.  With `workspace` (uint8, dist_sweep_rank_workspace_bytes) and `out` given
+    the call allocates nothing."""
+    q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, "score_dist_sweep_rank")
+    N, d = c.size(0), c.size(1)
+    metric = _metric_arg(metric, d, "score_dist_sweep_rank")
+    target = _req(target, torch.int64, "target")
+    if target.dim() != 1 or target.numel() != B or target.device != q.device:
+        raise ValueError(f"score_dist_sweep_rank: target must be [B = {B}] on {q.device}, got {tuple(target.shape)} on {target.device}")
+    ic = _ic_arg(ic, c, "score_dist_sweep_rank")
+    C = N if ic is None else ic.numel()
+    ws = _workspace(workspace, dist_sweep_rank_workspace_bytes, q.device, "score_dist_sweep_rank", B=B, C=C, d=d, nnz=nnz)
+    if out is None:
+        greater = torch.empty(B, dtype=torch.int64, device=q.device)
+        equal = torch.empty(B, dtype=torch.int64, device=q.device)
+    else:
+        greater, equal = (_req(t, torch.int64, "out") for t in out)
+        if greater.numel() != B or equal.numel() != B or not (out[0].is_contiguous() and out[1].is_contiguous()):
+            raise ValueError(f"score_dist_sweep_rank: out must be two contiguous int64 [{B}] tensors")
+    _check(load().ghf_dist_sweep_rank(metric, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0),
+                                      N, B, d, _ptr(ic), C, _ptr(ws), ws.numel(), _ptr(greater), _ptr(equal), _stream()),
+           "ghf_dist_sweep_rank")
+    return greater, equal
+
+
+def score_dist_sweep_topk(metric: int, q: torch.Tensor, c: torch.Tensor, k: int, iq: Optional[torch.Tensor] = None,
+                          filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+                          workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                          ic: Optional[torch.Tensor] = None):
+    """(scores [B, k] fp32 = -D descending, ids [B, k] int64) of include/ghf_distance_sweep.h: ghf_dist_sweep_topk — score_topk
+    with the score -D(q_i, c[row]): the k nearest rows of c (of c[ic] with `ic`; the ids returned are node ids) for every query,
+    ties towards the lower id, (-inf, -1) where fewer than k candidates remain outside the query's filter list."""
+    q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, "score_dist_sweep_topk")
+    N, d = c.size(0), c.size(1)
+    metric = _metric_arg(metric, d, "score_dist_sweep_topk")
+    k = int(k)
+    if not 1 <= k <= 128:
+        raise ValueError(f"score_dist_sweep_topk: k = {k} outside 1..128")
+    ic = _ic_arg(ic, c, "score_dist_sweep_topk")
+    C = N if ic is None else ic.numel()
+    ws = _workspace(workspace, dist_sweep_topk_workspace_bytes, q.device, "score_dist_sweep_topk", B=B, C=C, d=d, k=k, nnz=nnz)
+    if out is None:
+        scores = torch.empty(B, k, dtype=torch.float32, device=q.device)
+        ids = torch.empty(B, k, dtype=torch.int64, device=q.device)
+    else:
+        scores, ids = _req(out[0], torch.float32, "out[0]"), _req(out[1], torch.int64, "out[1]")
+        if tuple(scores.shape) != (B, k) or tuple(ids.shape) != (B, k) or not (out[0].is_contiguous() and out[1].is_contiguous()):
+            raise ValueError(f"score_dist_sweep_topk: out must be contiguous fp32 and int64 [{B}, {k}] tensors")
+    _check(load().ghf_dist_sweep_topk(metric, _ptr(q), _ptr(c), _ptr(iq), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d, k,
+                                      _ptr(ic), C, _ptr(ws), ws.numel(), _ptr(scores), _ptr(ids), _stream()), "ghf_dist_sweep_topk")
+    return scores, ids
 
 
 def score_dist_softmax_fwd(metric: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,

@@ -796,7 +796,8 @@ class HyperGNN(nn.Module):
             raise ValueError(f"distance must be one of {sorted(_native.DIST_METRICS)} or None, got {distance!r}")
         if negatives is None or candidates is not None or candidate_bias is not None:
             raise ValueError("distance= needs negatives= (a set per query) and goes with neither candidates= nor candidate_bias=: "
-                             "the all-node and shared-set sweeps score by dot product")
+                             "the all-node and shared-set sweeps of this method score by dot product; rank_by_distance / "
+                             "topk_by_distance rank against every node, or a candidates= subset, under a distance")
         if metric == _native.DIST_COMPLEX and embs.size(1) % 2:
             raise ValueError(f'distance="complex" reads a row as interleaved re / im pairs and needs an even d, got {embs.size(1)}')
         return metric
@@ -1026,6 +1027,79 @@ class HyperGNN(nn.Module):
         if query_rows is not None:
             return _native.score_topk(query_rows.detach(), e, int(k), filt_ptr=ptr, filt_idx=idx, ic=cand, bias=bias)
         return _native.score_topk(e, e, int(k), iq=q, filt_ptr=ptr, filt_idx=idx, ic=cand, bias=bias)
+
+    # -- distance scores against every node (csrc/distance_sweep.hip): TransE / RotatE evaluation --------------------------
+    @staticmethod
+    def _sweep_metric(distance, embs: torch.Tensor) -> int:
+        """``distance`` of ``rank_by_distance`` / ``topk_by_distance``: the metric of the ``ghf_dist_sweep_*`` calls.  Only
+        metadata is looked at, ahead of every device check."""
+        if embs.dim() != 2:
+            raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        metric = _native.DIST_METRICS.get(distance) if isinstance(distance, str) else None
+        if metric is None:
+            raise ValueError(f"distance must be one of {sorted(_native.DIST_METRICS)}, got {distance!r}")
+        if metric == _native.DIST_COMPLEX and embs.size(1) % 2:
+            raise ValueError(f'distance="complex" reads a row as interleaved re / im pairs and needs an even d, got {embs.size(1)}')
+        return metric
+
+    def rank_by_distance(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, distance: str, *, known=None,
+                         filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+                         query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
+                         candidates: Optional[torch.Tensor] = None):
+        """``rank_candidates`` under a DISTANCE: where ``target[i]`` ranks among ALL nodes (or ``candidates``) when a node scores
+        ``-D(row_i, embs[j])`` — the filtered rank TransE and RotatE are reported by (FB15k-237, WN18RR).  ``distance`` is
+        ``"l1"``, ``"l2"`` (TransE) or ``"complex"`` (RotatE: the sum of the moduli of the ``d / 2`` interleaved re / im pairs,
+        ``d`` even).  ``(greater, equal)``, int64 ``[B]``: the nodes CLOSER to the query's row than / exactly as far as the
+        target, the target itself and the query's known partners left out; feed them to ``link_prediction_metrics``.
+
+        The translated or rotated query rows are the caller's, through ``query_rows`` (``[B, d]`` fp32: ``embs[h] + r`` or
+        ``embs[h] o r``); without it row ``i`` is ``embs[query[i]]``.  ``known`` / ``filt_ptr, filt_idx`` / ``query_rel`` /
+        ``candidates`` are ``rank_candidates``' keywords with the same meaning.  There is no ``candidate_bias`` and no
+        ``negatives`` here (``rank_candidates(negatives=, distance=)`` ranks against a set per query).
+
+        A register-tiled VALU sweep (``ghf_dist_sweep_rank``, ``include/ghf_distance_sweep.h``): every candidate row is read
+        once per 64 queries and the ``[B, N]`` distances are never stored.  A pair's distance is one fixed fp32 chain, so two
+        nodes at the same distance tie exactly and the same call gives the same counts whatever the batch.  No autograd graph
+        (``embs`` is read as data)."""
+        metric = self._sweep_metric(distance, embs)
+        self._known_form(known, filt_ptr, filt_idx, query_rel)
+        cand = None if candidates is None else self._candidate_ids(candidates, embs)
+        q = self._rank_ids(query, embs.size(0), embs, "query")
+        t = self._rank_ids(target, embs.size(0), embs, "target")
+        if q.numel() != t.numel():
+            raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
+        if not embs.is_cuda:
+            raise RuntimeError(f"rank_by_distance computes on an MI355X HIP device only (input is on {embs.device})")
+        self._query_rows(embs, query, query_rows, "rank_by_distance")
+        e = embs.detach().float()
+        ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx, query_rel)
+        if query_rows is not None:
+            return _native.score_dist_sweep_rank(metric, query_rows.detach(), e, t, filt_ptr=ptr, filt_idx=idx, ic=cand)
+        return _native.score_dist_sweep_rank(metric, e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, ic=cand)
+
+    def topk_by_distance(self, embs: torch.Tensor, query: torch.Tensor, k: int, distance: str, *, known=None,
+                         filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+                         query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
+                         candidates: Optional[torch.Tensor] = None):
+        """``topk_candidates`` under a DISTANCE: the ``k`` (1..128) NEAREST nodes of every query's row among all nodes (or
+        ``candidates``) outside its filter list.  ``(scores [B, k]`` fp32 ``= -D`` descending, i.e. nearest first, ``ids [B, k]``
+        int64``)``, ties towards the lower id, ``(-inf, -1)`` where fewer than k candidates remain.  ``distance`` and every
+        keyword as in ``rank_by_distance``; the query's own node is a candidate (at distance 0 without ``query_rows``) unless
+        listed.  ``ghf_dist_sweep_topk``; no autograd graph."""
+        metric = self._sweep_metric(distance, embs)
+        if not 1 <= int(k) <= 128:
+            raise ValueError(f"k = {k} outside 1..128")
+        self._known_form(known, filt_ptr, filt_idx, query_rel)
+        cand = None if candidates is None else self._candidate_ids(candidates, embs)
+        q = self._rank_ids(query, embs.size(0), embs, "query")
+        if not embs.is_cuda:
+            raise RuntimeError(f"topk_by_distance computes on an MI355X HIP device only (input is on {embs.device})")
+        self._query_rows(embs, query, query_rows, "topk_by_distance")
+        e = embs.detach().float()
+        ptr, idx = self._filter_lists(e, q, known, filt_ptr, filt_idx, query_rel)
+        if query_rows is not None:
+            return _native.score_dist_sweep_topk(metric, query_rows.detach(), e, int(k), filt_ptr=ptr, filt_idx=idx, ic=cand)
+        return _native.score_dist_sweep_topk(metric, e, e, int(k), iq=q, filt_ptr=ptr, filt_idx=idx, ic=cand)
 
     def softmax_loss(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, scale: float = 1.0, known=None,
                      filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
