@@ -205,6 +205,20 @@ DSWEEP_SIGNATURES = {
 }
 
 
+# include/ghf_distance_loss.h (the two losses under a distance against every node or a candidate subset, csrc/distance_loss.hip):
+# the fifth
+DLOSS_SIGNATURES = {
+    "ghf_dist_loss_fwd_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "ghf_dist_loss_softmax_fwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _i64, _vp, _sz, _vp,
+                                         _vp, _vp]),
+    "ghf_dist_loss_negsamp_fwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _f32, _vp, _i64, _vp,
+                                         _sz, _vp, _vp, _vp]),
+    "ghf_dist_loss_bwd_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "ghf_dist_loss_bwd": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _f32, _vp, _i64, _vp,
+                                 _vp, _vp, _sz, _vp, _vp, _vp]),
+}
+
+
 def header_symbols() -> List[str]:
     """Function names declared in include/ghf.h (for the export test)."""
     with open(os.path.join(_build.INCLUDE, "ghf.h")) as f:
@@ -233,6 +247,13 @@ def distance_sweep_header_symbols() -> List[str]:
     return sorted(set(re.findall(r"\b(ghf_[a-z_0-9]+)\s*\(", text)))
 
 
+def distance_loss_header_symbols() -> List[str]:
+    """Function names declared in include/ghf_distance_loss.h."""
+    with open(os.path.join(_build.INCLUDE, "ghf_distance_loss.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(ghf_[a-z_0-9]+)\s*\(", text)))
+
+
 def lib_path() -> str:
     return _build.LIB_PATH
 
@@ -255,7 +276,7 @@ def load() -> C.CDLL:
                     "This package has no CPU/PyTorch fallback: run __graft_entry__.build() first.") from exc
         lib = C.CDLL(path)
         for name, (res, args) in (list(SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(DIST_SIGNATURES.items())
-                                  + list(DSWEEP_SIGNATURES.items())):
+                                  + list(DSWEEP_SIGNATURES.items()) + list(DLOSS_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1421,6 +1442,86 @@ def score_dist_sweep_topk(metric: int, q: torch.Tensor, c: torch.Tensor, k: int,
     _check(load().ghf_dist_sweep_topk(metric, _ptr(q), _ptr(c), _ptr(iq), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d, k,
                                       _ptr(ic), C, _ptr(ws), ws.numel(), _ptr(scores), _ptr(ids), _stream()), "ghf_dist_sweep_topk")
     return scores, ids
+
+
+# ---- the two losses under a distance against every node or a candidate subset (include/ghf_distance_loss.h) -------------
+def dist_loss_fwd_workspace_bytes(B: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_dist_loss_fwd_workspace_bytes(B, C, d, nnz))
+
+
+def dist_loss_bwd_workspace_bytes(B: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_dist_loss_bwd_workspace_bytes(B, C, d, nnz))
+
+
+def score_dist_loss_softmax_fwd(metric: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor,
+                                iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
+                                filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0,
+                                workspace: Optional[torch.Tensor] = None,
+                                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ic: Optional[torch.Tensor] = None):
+    """(loss, lse) fp32 [B] of include/ghf_distance_loss.h: ghf_dist_loss_softmax_fwd — score_softmax_fwd with z = -scale D(q_i,
+    c[row]) over every row of c (of c[ic] with `ic`, int64 [C] strictly ascending node ids, which must hold every target).
+    Nothing of size B x C is stored; with `workspace` (uint8, dist_loss_fwd_workspace_bytes) and `out` the call allocates
+    nothing."""
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale,
+                                                                        "score_dist_loss_softmax_fwd")
+    N, d = c.size(0), c.size(1)
+    metric = _metric_arg(metric, d, "score_dist_loss_softmax_fwd")
+    ic = _ic_arg(ic, c, "score_dist_loss_softmax_fwd")
+    C = N if ic is None else ic.numel()
+    loss, lse = _f32_out_pair(out, (B,), (B,), q.device, "score_dist_loss_softmax_fwd")
+    ws = _workspace(workspace, dist_loss_fwd_workspace_bytes, q.device, "score_dist_loss_softmax_fwd", B=B, C=C, d=d, nnz=nnz)
+    _check(load().ghf_dist_loss_softmax_fwd(metric, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz,
+                                            q.size(0), N, B, d, scale, _ptr(ic), C, _ptr(ws), ws.numel(), _ptr(loss), _ptr(lse),
+                                            _stream()), "ghf_dist_loss_softmax_fwd")
+    return loss, lse
+
+
+def score_dist_loss_negsamp_fwd(metric: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor,
+                                iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
+                                filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0, margin: float = 0.0,
+                                adversarial_temperature: float = 0.0, workspace: Optional[torch.Tensor] = None,
+                                out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ic: Optional[torch.Tensor] = None):
+    """(loss, lw) fp32 [B] of include/ghf_distance_loss.h: ghf_dist_loss_negsamp_fwd — score_negsamp_fwd with z = -scale D(q_i,
+    c[row]) over every row of c (of c[ic] with `ic`); lw = -inf and the positive term alone where a query has no negatives."""
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, alpha = _negsamp_args(
+        q, c, target, iq, filt_ptr, filt_idx, scale, margin, adversarial_temperature, "score_dist_loss_negsamp_fwd")
+    N, d = c.size(0), c.size(1)
+    metric = _metric_arg(metric, d, "score_dist_loss_negsamp_fwd")
+    ic = _ic_arg(ic, c, "score_dist_loss_negsamp_fwd")
+    C = N if ic is None else ic.numel()
+    loss, lw = _f32_out_pair(out, (B,), (B,), q.device, "score_dist_loss_negsamp_fwd")
+    ws = _workspace(workspace, dist_loss_fwd_workspace_bytes, q.device, "score_dist_loss_negsamp_fwd", B=B, C=C, d=d, nnz=nnz)
+    _check(load().ghf_dist_loss_negsamp_fwd(metric, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz,
+                                            q.size(0), N, B, d, scale, margin, alpha, _ptr(ic), C, _ptr(ws), ws.numel(), _ptr(loss),
+                                            _ptr(lw), _stream()), "ghf_dist_loss_negsamp_fwd")
+    return loss, lw
+
+
+def score_dist_loss_bwd(metric: int, mode: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, saved: torch.Tensor,
+                        grad_loss: torch.Tensor, iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
+                        filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0, margin: float = 0.0,
+                        adversarial_temperature: float = 0.0, workspace: Optional[torch.Tensor] = None,
+                        out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, ic: Optional[torch.Tensor] = None):
+    """(dq [B, d], dc [C, d]) fp32 of include/ghf_distance_loss.h: ghf_dist_loss_bwd, `mode` NEG_SOFTMAX or NEG_NEGSAMP and
+    `saved` that forward's lse / lw.  dq[i] = -sum_j G_ij g(i, j) per query (not scattered through iq); dc[j] = +sum_i G_ij
+    g(i, j), row j the gradient of c[ic[j]] (of c[j] without `ic`, where C = N); every row written."""
+    if mode not in (NEG_SOFTMAX, NEG_NEGSAMP):
+        raise ValueError(f"score_dist_loss_bwd: mode must be NEG_SOFTMAX or NEG_NEGSAMP, got {mode}")
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, alpha = _negsamp_args(
+        q, c, target, iq, filt_ptr, filt_idx, scale, margin, adversarial_temperature, "score_dist_loss_bwd")
+    saved, grad_loss = _req(saved, torch.float32, "saved"), _req(grad_loss, torch.float32, "grad_loss")
+    if saved.numel() != B or grad_loss.numel() != B:
+        raise ValueError(f"score_dist_loss_bwd: saved and grad_loss must hold B = {B} values")
+    N, d = c.size(0), c.size(1)
+    metric = _metric_arg(metric, d, "score_dist_loss_bwd")
+    ic = _ic_arg(ic, c, "score_dist_loss_bwd")
+    C = N if ic is None else ic.numel()
+    ws = _workspace(workspace, dist_loss_bwd_workspace_bytes, q.device, "score_dist_loss_bwd", B=B, C=C, d=d, nnz=nnz)
+    dq, dc = _f32_out_pair(out, (B, d), (C, d), q.device, "score_dist_loss_bwd")
+    _check(load().ghf_dist_loss_bwd(metric, mode, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz,
+                                    q.size(0), N, B, d, scale, margin, alpha, _ptr(ic), C, _ptr(saved), _ptr(grad_loss), _ptr(ws),
+                                    ws.numel(), _ptr(dq), _ptr(dc), _stream()), "ghf_dist_loss_bwd")
+    return dq, dc
 
 
 def score_dist_softmax_fwd(metric: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,

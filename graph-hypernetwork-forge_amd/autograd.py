@@ -658,6 +658,41 @@ class DistanceLossFn(torch.autograd.Function):
         return (d_embs, d_rows) + (None,) * 10
 
 
+class DistanceSweepLossFn(torch.autograd.Function):
+    """The softmax (mode NEG_SOFTMAX) or negative-sampling (NEG_NEGSAMP) loss of a query against EVERY node, or the shared
+    candidate set `cand`, with z_ij = -scale D(q_i, embs[j]) under `metric` (HyperGNN.softmax_loss_by_distance /
+    negative_sampling_loss_by_distance; include/ghf_distance_loss.h).  q_i and the pair `rows` / `query` as in SoftmaxLossFn.
+    Saved is the forward's lse / lw; the backward recomputes every distance (ghf_dist_loss_bwd) and returns dq per query and dc
+    per candidate, which _all_node_loss_grads turns into the gradients exactly as for the dot-product losses: rows of embs that
+    are neither candidate, target nor query get exactly zero."""
+
+    @staticmethod
+    def forward(ctx, embs, rows, query, target, ptr, idx, metric: int, mode: int, scale: float, margin: float, alpha: float,
+                cand=None):
+        assert (rows is None) != (query is None)
+        embs = embs.contiguous().float()
+        rows = None if rows is None else rows.contiguous().float()
+        q = embs if rows is None else rows
+        if mode == _native.NEG_SOFTMAX:
+            loss, saved = _native.score_dist_loss_softmax_fwd(metric, q, embs, target, iq=query, filt_ptr=ptr, filt_idx=idx,
+                                                              scale=scale, ic=cand)
+        else:
+            loss, saved = _native.score_dist_loss_negsamp_fwd(metric, q, embs, target, iq=query, filt_ptr=ptr, filt_idx=idx,
+                                                              scale=scale, margin=margin, adversarial_temperature=alpha, ic=cand)
+        ctx.save_for_backward(embs, rows, query, target, ptr, idx, saved, cand)
+        ctx.metric, ctx.mode, ctx.scale, ctx.margin, ctx.alpha = metric, mode, scale, margin, alpha
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        embs, rows, query, target, ptr, idx, saved, cand = ctx.saved_tensors
+        dq, dc = _native.score_dist_loss_bwd(ctx.metric, ctx.mode, embs if rows is None else rows, embs, target, saved,
+                                             g.contiguous().float(), iq=query, filt_ptr=ptr, filt_idx=idx, scale=ctx.scale,
+                                             margin=ctx.margin, adversarial_temperature=ctx.alpha, ic=cand)
+        return _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand) + (None,) * 10
+
+
 class ScorePairsFn(torch.autograd.Function):
     """s_i = a_i . b_i (reference score_triple, hypergnn.py:304-318)."""
 

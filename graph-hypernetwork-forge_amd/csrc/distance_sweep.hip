@@ -15,7 +15,7 @@
 //   A workgroup owns (query tile, candidate slab); workgroups are numbered as in rank.hip so that an XCD runs the query tiles of
 //   one slab together.
 //
-// Numerics: an accumulator is bit for bit dist_chain() below — delta_k = q_k - c_k (one fp32 subtraction), then
+// Numerics: an accumulator is bit for bit dist_chain() of distance_sweep_dev.h — delta_k = q_k - c_k (one fp32 subtraction), then
 //   L1       acc = acc + |delta_k|,                          k ascending from acc = 0
 //   L2       acc = fmaf(delta_k, delta_k, acc),              k ascending, then one hardware root
 //   COMPLEX  rho_p = sqrt(fmaf(delta_2p+1, delta_2p+1, delta_2p * delta_2p)),  acc = acc + rho_p,  p ascending
@@ -33,18 +33,10 @@
 //         dsweep_merge_kernel merges the slabs' lists as topk_merge_kernel does.
 #include "common.h"
 #include "rank_sweep.h"
+#include "distance_sweep_dev.h"
 #include "../../include/ghf_distance_sweep.h"
 
 namespace ghf {
-
-constexpr int DS_TQ = 64;                    // queries per workgroup
-constexpr int DS_RQ = 16;                    // queries per wave
-constexpr int DS_RC = 4;                     // candidates per lane
-constexpr int DS_CT = 64 * DS_RC;            // candidates per step
-constexpr int DS_BK = 16;                    // columns per step
-constexpr int DS_LDC = DS_BK + 4;            // LDS row stride in floats
-constexpr int DS_NL = DS_CT * (DS_BK / 4) / 256;    // 16-byte pieces a thread fetches per step
-constexpr int DS_MIN_TILES = 4;              // tiles per slab, at the least
 
 static inline int dsweep_cap(int k) { return k + DS_CT + 64; }
 static_assert(TOPK_MAX_K + DS_CT + 64 <= TOPK_EPL * 64, "select_in_place holds a whole append buffer");
@@ -86,49 +78,6 @@ static size_t dsweep_topk_workspace_bytes(int64_t B, int64_t C, int d, int k, in
     return rk_align((size_t)B * 4) + rk_align(entries * 8) + map;         // valid [B] int32, keys, the id map's
 }
 
-// ---- the chain --------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float dsweep_sqrt(float v) { return __builtin_amdgcn_sqrtf(v); }
-
-// four consecutive k of one pair's chain: x the query's floats, y the candidate's
-template <int M>
-__device__ __forceinline__ float dist_step4(float acc, const f32x4 x, const f32x4 y) {
-#pragma clang fp contract(off)
-    const float d0 = x[0] - y[0], d1 = x[1] - y[1], d2 = x[2] - y[2], d3 = x[3] - y[3];
-    if constexpr (M == GHF_DIST_L1) {
-        acc = acc + fabsf(d0);
-        acc = acc + fabsf(d1);
-        acc = acc + fabsf(d2);
-        acc = acc + fabsf(d3);
-    } else if constexpr (M == GHF_DIST_L2) {
-        acc = fmaf(d0, d0, acc);
-        acc = fmaf(d1, d1, acc);
-        acc = fmaf(d2, d2, acc);
-        acc = fmaf(d3, d3, acc);
-    } else {
-        const float r0 = dsweep_sqrt(fmaf(d1, d1, d0 * d0));
-        acc = acc + r0;
-        const float r1 = dsweep_sqrt(fmaf(d3, d3, d2 * d2));
-        acc = acc + r1;
-    }
-    return acc;
-}
-
-template <int M>
-__device__ __forceinline__ float dist_finish(float acc) { return M == GHF_DIST_L2 ? dsweep_sqrt(acc) : acc; }
-
-template <int M>
-__device__ __forceinline__ float dist_chain_m(const float* __restrict__ x, const float* __restrict__ y, int d, bool vec) {
-    float acc = 0.f;
-    for (int k = 0; k < d; k += 4) acc = dist_step4<M>(acc, load_k4(x, k, d, vec), load_k4(y, k, d, vec));
-    return dist_finish<M>(acc);
-}
-
-// D(x, y) under `metric`: the chain every accumulator of the tile equals
-__device__ __forceinline__ float dist_chain(int metric, const float* __restrict__ x, const float* __restrict__ y, int d, bool vec) {
-    if (metric == GHF_DIST_L1) return dist_chain_m<GHF_DIST_L1>(x, y, d, vec);
-    if (metric == GHF_DIST_L2) return dist_chain_m<GHF_DIST_L2>(x, y, d, vec);
-    return dist_chain_m<GHF_DIST_COMPLEX>(x, y, d, vec);
-}
 
 // ---- the sweep --------------------------------------------------------------------------------------------------------------
 struct DsweepArgs {
@@ -143,8 +92,6 @@ struct DsweepArgs {
     int k, cap; uint64_t* ws_key;
 };
 
-typedef const float __attribute__((address_space(4))) ds_cfloat;
-typedef const f32x4 __attribute__((address_space(4))) ds_cf32x4;
 
 template <int M, bool VEC, bool TOPK>
 __global__ __launch_bounds__(256) void dsweep_tile_kernel(const DsweepArgs a) {

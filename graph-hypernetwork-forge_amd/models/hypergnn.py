@@ -1101,6 +1101,86 @@ class HyperGNN(nn.Module):
             return _native.score_dist_sweep_topk(metric, query_rows.detach(), e, int(k), filt_ptr=ptr, filt_idx=idx, ic=cand)
         return _native.score_dist_sweep_topk(metric, e, e, int(k), iq=q, filt_ptr=ptr, filt_idx=idx, ic=cand)
 
+    def _by_distance_loss(self, what: str, mode: int, embs, query, target, distance, scale, margin, alpha, known, filt_ptr,
+                          filt_idx, query_rows, query_rel, candidates) -> torch.Tensor:
+        """``softmax_loss_by_distance`` / ``negative_sampling_loss_by_distance``: every check on metadata ahead of the device
+        check, then the recorded call (``autograd.DistanceSweepLossFn``) or the forward alone."""
+        metric = self._sweep_metric(distance, embs)
+        self._known_form(known, filt_ptr, filt_idx, query_rel)
+        scale, margin, alpha = float(scale), float(margin), float(alpha)
+        if not (0.0 < scale < float("inf")):
+            raise ValueError(f"scale must be finite and positive, got {scale}")
+        if not (float("-inf") < margin < float("inf")):
+            raise ValueError(f"margin must be finite, got {margin}")
+        if not (0.0 <= alpha < float("inf")):
+            raise ValueError(f"adversarial_temperature must be finite and not negative, got {alpha}")
+        cand = None if candidates is None else self._candidate_ids(candidates, embs)
+        q = self._rank_ids(query, embs.size(0), embs, "query")
+        t = self._rank_ids(target, embs.size(0), embs, "target")
+        if q.numel() != t.numel():
+            raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
+        self._query_rows(embs, query, query_rows, what)
+        if not embs.is_cuda:
+            raise RuntimeError(f"{what} computes on an MI355X HIP device only (input is on {embs.device})")
+        ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
+        if cand is not None:
+            cand = self._softmax_candidates(cand, t)
+        grad = embs.requires_grad or (query_rows is not None and query_rows.requires_grad)
+        if torch.is_grad_enabled() and grad:
+            from ..autograd import DistanceSweepLossFn
+            if query_rows is not None:
+                return DistanceSweepLossFn.apply(embs, query_rows, None, t, ptr, idx, metric, mode, scale, margin, alpha, cand)
+            return DistanceSweepLossFn.apply(embs, None, q, t, ptr, idx, metric, mode, scale, margin, alpha, cand)
+        e = embs.detach().float()
+        qm, iq = (e, q) if query_rows is None else (query_rows.detach(), None)
+        if mode == _native.NEG_SOFTMAX:
+            return _native.score_dist_loss_softmax_fwd(metric, qm, e, t, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale, ic=cand)[0]
+        return _native.score_dist_loss_negsamp_fwd(metric, qm, e, t, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale, margin=margin,
+                                                   adversarial_temperature=alpha, ic=cand)[0]
+
+    def softmax_loss_by_distance(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, distance: str, *,
+                                 scale: float = 1.0, known=None, filt_ptr: Optional[torch.Tensor] = None,
+                                 filt_idx: Optional[torch.Tensor] = None, query_rows: Optional[torch.Tensor] = None,
+                                 query_rel: Optional[torch.Tensor] = None,
+                                 candidates: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``softmax_loss`` under a DISTANCE, fp32 ``[B]``: the 1-vs-all cross-entropy of the true tail against every node (or
+        one ``candidates`` set shared by the batch) when a node scores ``-D(row_i, embs[j])``: ``loss[i] = logsumexp_j z[i, j]
+        - z[i, target[i]]`` with ``z = -scale * D`` over the candidates outside query ``i``'s list; the target always stays in
+        the sum.  ``distance`` is ``"l1"``, ``"l2"`` (TransE) or ``"complex"`` (RotatE, ``d`` even), as in ``rank_by_distance``,
+        whose ``query_rows`` / ``known`` / ``filt_ptr, filt_idx`` / ``query_rel`` / ``candidates`` keywords mean the same here.
+        With ``candidates`` the batch's targets are added to the set, as in ``softmax_loss``.  There is no ``negatives`` (a set
+        per query is ``softmax_loss(negatives=, distance=)``) and no ``candidate_bias``.
+
+        The tile sweep of ``rank_by_distance`` with an online softmax in its epilogue (``ghf_dist_loss_softmax_fwd``,
+        ``include/ghf_distance_loss.h``): a candidate row is read once per 64 queries, and neither the ``[B, C]`` distances nor
+        the ``[B, C, d]`` differences exist, forward or backward.  Recorded for autograd when grad mode is on and ``embs`` or
+        ``query_rows`` requires grad (``autograd.DistanceSweepLossFn``, ``ghf_dist_loss_bwd``): the gradient follows the
+        distance (``sign(delta)``, ``delta / D``, ``delta / |pair|``, each 0 where its denominator is 0); rows of ``embs`` that
+        are neither candidate, target nor query get exactly zero.  Bit-reproducible, and a query's loss does not depend on its
+        batch."""
+        return self._by_distance_loss("softmax_loss_by_distance", _native.NEG_SOFTMAX, embs, query, target, distance, scale, 0.0, 0.0,
+                                      known, filt_ptr, filt_idx, query_rows, query_rel, candidates)
+
+    def negative_sampling_loss_by_distance(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, distance: str, *,
+                                           scale: float = 1.0, margin: float = 0.0, adversarial_temperature: float = 0.0,
+                                           known=None, filt_ptr: Optional[torch.Tensor] = None,
+                                           filt_idx: Optional[torch.Tensor] = None, query_rows: Optional[torch.Tensor] = None,
+                                           query_rel: Optional[torch.Tensor] = None,
+                                           candidates: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``negative_sampling_loss`` under a DISTANCE on one negative set shared by the batch (DGL-KE, the OGB ``wikikg2`` /
+        ``biokg`` baselines), fp32 ``[B]``.  With ``z[i, j] = -scale * D(row_i, embs[j])`` and ``J_i`` = every node (every
+        candidate) except query ``i``'s known partners and its target::
+
+            w[i, j] = softmax over J_i of (adversarial_temperature * z[i, j])          # a constant: detached
+            loss[i] = softplus(-(z[i, target[i]] + margin)) + sum_{j in J_i} w[i, j] * softplus(z[i, j] + margin)
+
+        At ``scale=1, margin=gamma`` the positive term is ``-log sigmoid(gamma - D_target)``: TransE's and RotatE's published
+        loss.  ``adversarial_temperature=0`` is the uniform mean; a query without negatives has the positive term alone.
+        ``distance`` and every other keyword as in ``softmax_loss_by_distance``; ``ghf_dist_loss_negsamp_fwd`` /
+        ``ghf_dist_loss_bwd``, recorded and reproducible the same way."""
+        return self._by_distance_loss("negative_sampling_loss_by_distance", _native.NEG_NEGSAMP, embs, query, target, distance, scale,
+                                      margin, adversarial_temperature, known, filt_ptr, filt_idx, query_rows, query_rel, candidates)
+
     def softmax_loss(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, scale: float = 1.0, known=None,
                      filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                      query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
