@@ -219,6 +219,19 @@ DLOSS_SIGNATURES = {
 }
 
 
+# include/ghf_pairwise.h (pairwise ranking losses on per-query negative sets, csrc/pairwise.hip): the sixth
+PAIR_SIGNATURES = {
+    "ghf_pair_workspace_bytes": (_sz, [_i64, _i64, _i32, _i64]),
+    "ghf_pair_fwd": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _i32, _vp, _i64, _vp, _vp,
+                            _sz, _vp, _vp, _vp, _vp]),
+    "ghf_pair_bwd": (_i32, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _i32, _vp, _i64, _vp, _vp,
+                            _vp, _vp, _sz, _vp, _vp, _vp]),
+}
+PAIR_DOT = 0                              # the metric of the ghf_pair_* calls: PAIR_DOT or DIST_L1 / DIST_L2 / DIST_COMPLEX
+PAIR_HINGE, PAIR_LOGISTIC = 1, 2          # their kind
+PAIR_KINDS = {"hinge": PAIR_HINGE, "logistic": PAIR_LOGISTIC}
+
+
 def header_symbols() -> List[str]:
     """Function names declared in include/ghf.h (for the export test)."""
     with open(os.path.join(_build.INCLUDE, "ghf.h")) as f:
@@ -254,6 +267,13 @@ def distance_loss_header_symbols() -> List[str]:
     return sorted(set(re.findall(r"\b(ghf_[a-z_0-9]+)\s*\(", text)))
 
 
+def pairwise_header_symbols() -> List[str]:
+    """Function names declared in include/ghf_pairwise.h."""
+    with open(os.path.join(_build.INCLUDE, "ghf_pairwise.h")) as f:
+        text = f.read()
+    return sorted(set(re.findall(r"\b(ghf_pair_[a-z_0-9]+)\s*\(", text)))
+
+
 def lib_path() -> str:
     return _build.LIB_PATH
 
@@ -276,7 +296,7 @@ def load() -> C.CDLL:
                     "This package has no CPU/PyTorch fallback: run __graft_entry__.build() first.") from exc
         lib = C.CDLL(path)
         for name, (res, args) in (list(SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(DIST_SIGNATURES.items())
-                                  + list(DSWEEP_SIGNATURES.items()) + list(DLOSS_SIGNATURES.items())):
+                                  + list(DSWEEP_SIGNATURES.items()) + list(DLOSS_SIGNATURES.items()) + list(PAIR_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1610,6 +1630,90 @@ def dist_rows_grad(metric: int, q: torch.Tensor, c: torch.Tensor, coef: torch.Te
     _check(load().ghf_dist_rows_grad(metric, _ptr(q), _ptr(c), _ptr(iq), q.size(0), N, B, d, coef.size(1) - 1, _ptr(coef), _ptr(perm),
                                      _ptr(off), _ptr(dc), _stream()), "ghf_dist_rows_grad")
     return dc
+
+
+# ---- pairwise ranking losses on per-query negative sets (include/ghf_pairwise.h, csrc/pairwise.hip) -----------------------
+def pair_workspace_bytes(B: int, K: int, d: int, nnz: int) -> int:
+    return int(load().ghf_pair_workspace_bytes(B, K, d, nnz))
+
+
+def _pair_selectors(metric: int, kind: int, d: int, what: str) -> Tuple[int, int]:
+    if metric not in (PAIR_DOT, DIST_L1, DIST_L2, DIST_COMPLEX):
+        raise ValueError(f"{what}: metric must be PAIR_DOT, DIST_L1, DIST_L2 or DIST_COMPLEX, got {metric}")
+    if metric == DIST_COMPLEX and d % 2:
+        raise ValueError(f"{what}: DIST_COMPLEX reads the rows as interleaved re / im pairs and needs an even d, got {d}")
+    if kind not in (PAIR_HINGE, PAIR_LOGISTIC):
+        raise ValueError(f"{what}: kind must be PAIR_HINGE or PAIR_LOGISTIC, got {kind}")
+    return int(metric), int(kind)
+
+
+def _pair_args(metric, kind, q, c, target, neg, iq, filt_ptr, filt_idx, scale, margin, normalize, bias, what: str):
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, what)
+    margin = float(margin)
+    if not (float("-inf") < margin < float("inf")):
+        raise ValueError(f"{what}: margin must be finite, got {margin}")
+    if not isinstance(normalize, (bool, int)) or normalize not in (0, 1):
+        raise ValueError(f"{what}: normalize must be a bool, got {normalize!r}")
+    neg = _neg_arg(neg, B, c, what)
+    metric, kind = _pair_selectors(metric, kind, c.size(1), what)
+    if bias is not None and metric != PAIR_DOT:
+        raise ValueError(f"{what}: no per-candidate bias under a distance")
+    bias = _bias_arg(bias, c, what)
+    return metric, kind, q, c, target, neg, iq, filt_ptr, filt_idx, B, nnz, scale, margin, int(normalize), bias
+
+
+def score_pair_fwd(metric: int, kind: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
+                   iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
+                   filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0, margin: float = 1.0, normalize: bool = True,
+                   workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None,
+                   bias: Optional[torch.Tensor] = None):
+    """(loss fp32 [B], count int32 [B], active int32 [B]) of include/ghf_pairwise.h: ghf_pair_fwd — the hinge (`kind`
+    PAIR_HINGE) or logistic (PAIR_LOGISTIC) pairwise loss of query i's target against ITS OWN negatives neg[i, :]: with u_ij =
+    (z_ij - z_it) + margin over the positions J_i outside the query's list other than the target, loss = sum phi(u) (over n_i =
+    count[i] with `normalize`), active = #{u_ij > 0}.  `metric` PAIR_DOT: z = scale q . c[row] (+ bias[row]); DIST_L1 / DIST_L2 /
+    DIST_COMPLEX: z = -scale D(q_i, c[row]), no bias.  With `workspace` (uint8, pair_workspace_bytes) and `out` given the call
+    allocates nothing."""
+    metric, kind, q, c, target, neg, iq, filt_ptr, filt_idx, B, nnz, scale, margin, normalize, bias = _pair_args(
+        metric, kind, q, c, target, neg, iq, filt_ptr, filt_idx, scale, margin, normalize, bias, "score_pair_fwd")
+    N, d, K = c.size(0), c.size(1), neg.size(1)
+    if out is None:
+        loss = torch.empty(B, dtype=torch.float32, device=q.device)
+        count = torch.empty(B, dtype=torch.int32, device=q.device)
+        active = torch.empty(B, dtype=torch.int32, device=q.device)
+    else:
+        loss = _f32_out(out[0], (B,), q.device, "score_pair_fwd")
+        count, active = (_req(t, torch.int32, "out") for t in out[1:])
+        if count.numel() != B or active.numel() != B or not (out[1].is_contiguous() and out[2].is_contiguous()):
+            raise ValueError(f"score_pair_fwd: out must be a contiguous fp32 [{B}] and two contiguous int32 [{B}] tensors")
+    ws = _workspace(workspace, pair_workspace_bytes, q.device, "score_pair_fwd", B=B, K=K, d=d, nnz=nnz)
+    _check(load().ghf_pair_fwd(metric, kind, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N,
+                               B, d, scale, margin, normalize, _ptr(neg), K, _ptr(bias), _ptr(ws), ws.numel(), _ptr(loss), _ptr(count),
+                               _ptr(active), _stream()), "ghf_pair_fwd")
+    return loss, count, active
+
+
+def score_pair_bwd(metric: int, kind: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
+                   count: torch.Tensor, grad_loss: torch.Tensor, iq: Optional[torch.Tensor] = None,
+                   filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0,
+                   margin: float = 1.0, normalize: bool = True, workspace: Optional[torch.Tensor] = None,
+                   out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, bias: Optional[torch.Tensor] = None):
+    """(dq [B, d], coef [B, K + 1]) fp32 of include/ghf_pairwise.h: ghf_pair_bwd, `count` the forward's.  coef[i, j] is the
+    gradient of the loss sum with respect to the score of position j of query i (0 where the position takes no part), coef[i,
+    K] the target's: minus the sum of the row's others.  dq is per query (not scattered through iq), formed from coef as
+    score_neg_bwd (PAIR_DOT) or score_dist_bwd (a distance) form it.  The gradient of c is a grouped sum over coef
+    (autograd.PairwiseLossFn)."""
+    metric, kind, q, c, target, neg, iq, filt_ptr, filt_idx, B, nnz, scale, margin, normalize, bias = _pair_args(
+        metric, kind, q, c, target, neg, iq, filt_ptr, filt_idx, scale, margin, normalize, bias, "score_pair_bwd")
+    count, grad_loss = _req(count, torch.int32, "count"), _req(grad_loss, torch.float32, "grad_loss")
+    if count.numel() != B or grad_loss.numel() != B:
+        raise ValueError(f"score_pair_bwd: count and grad_loss must hold B = {B} values")
+    N, d, K = c.size(0), c.size(1), neg.size(1)
+    ws = _workspace(workspace, pair_workspace_bytes, q.device, "score_pair_bwd", B=B, K=K, d=d, nnz=nnz)
+    dq, coef = _f32_out_pair(out, (B, d), (B, K + 1), q.device, "score_pair_bwd")
+    _check(load().ghf_pair_bwd(metric, kind, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N,
+                               B, d, scale, margin, normalize, _ptr(neg), K, _ptr(bias), _ptr(count), _ptr(grad_loss), _ptr(ws),
+                               ws.numel(), _ptr(dq), _ptr(coef), _stream()), "ghf_pair_bwd")
+    return dq, coef
 
 
 # ---- relation-typed query rows (include/ghf.h: ghf_relation_rows, csrc/relation.hip) ------------------------------------

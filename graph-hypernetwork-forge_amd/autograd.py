@@ -658,6 +658,63 @@ class DistanceLossFn(torch.autograd.Function):
         return (d_embs, d_rows) + (None,) * 10
 
 
+class PairwiseLossFn(torch.autograd.Function):
+    """The pairwise hinge (kind = _native.PAIR_HINGE) or logistic (PAIR_LOGISTIC) loss of every query's target against ITS OWN
+    negatives `neg` [B, K] (HyperGNN.pairwise_loss; include/ghf_pairwise.h), under the dot product (metric = _native.PAIR_DOT,
+    with an optional `bias`) or a distance (DIST_L1 / DIST_L2 / DIST_COMPLEX); q_i and the pair `rows` / `query` as in
+    SoftmaxLossFn.  Returns (loss, active); active — the violated pairs — carries no gradient.  Saved is the forward's count
+    and the grouping of the B (K + 1) node ids by node, made in the forward.  The backward (ghf_pair_bwd) returns dq per query
+    and coef [B, K + 1], the target's coefficient minus the sum of its row's; from there on the gradients are
+    NegativesLossFn's (dot: ghf_segment_axpy over coef, d bias the same sum over a column of ones, over scale) or
+    DistanceLossFn's (ghf_dist_rows_grad over coef), step for step."""
+
+    @staticmethod
+    def forward(ctx, embs, rows, query, target, ptr, idx, neg, metric: int, kind: int, scale: float, margin: float,
+                normalize: bool, bias=None):
+        assert (rows is None) != (query is None)
+        embs = embs.contiguous().float()
+        rows = None if rows is None else rows.contiguous().float()
+        bias = None if bias is None else bias.contiguous()
+        q = embs if rows is None else rows
+        loss, count, active = _native.score_pair_fwd(metric, kind, q, embs, target, neg, iq=query, filt_ptr=ptr, filt_idx=idx,
+                                                     scale=scale, margin=margin, normalize=normalize, bias=bias)
+        perm = off = None
+        if ctx.needs_input_grad[0] or (bias is not None and ctx.needs_input_grad[12]):
+            N = embs.size(0)
+            keys = torch.cat([torch.where(neg < 0, target.unsqueeze(1), neg), target.unsqueeze(1)], 1).reshape(-1).clamp_(0, N - 1)
+            perm, off = _native.group_edges(keys, N)
+        ctx.save_for_backward(embs, rows, query, target, ptr, idx, neg, count, bias, perm, off)
+        ctx.metric, ctx.kind, ctx.scale, ctx.margin, ctx.normalize = metric, kind, scale, margin, normalize
+        ctx.mark_non_differentiable(active)
+        return loss, active
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_active):
+        embs, rows, query, target, ptr, idx, neg, count, bias, perm, off = ctx.saved_tensors
+        q = embs if rows is None else rows
+        dq, coef = _native.score_pair_bwd(ctx.metric, ctx.kind, q, embs, target, neg, count, g.contiguous().float(), iq=query,
+                                          filt_ptr=ptr, filt_idx=idx, scale=ctx.scale, margin=ctx.margin, normalize=ctx.normalize,
+                                          bias=bias)
+        d_embs = d_rows = d_bias = None
+        if ctx.needs_input_grad[0]:
+            if ctx.metric == _native.PAIR_DOT:
+                owner = torch.div(perm, neg.size(1) + 1, rounding_mode="floor")    # the query of every grouped entry
+                if query is not None:
+                    owner = query.index_select(0, owner)
+                d_embs = _native.segment_axpy(coef.reshape(-1), perm, q, owner.clamp_(0, q.size(0) - 1), off)
+            else:
+                d_embs = _native.dist_rows_grad(ctx.metric, q, embs, coef, perm, off, iq=query)
+            if rows is None:
+                d_embs = _native.add3(d_embs, _fold_rows(dq, query, embs.size(0)), out=d_embs)
+        if rows is not None and ctx.needs_input_grad[1]:
+            d_rows = dq
+        if bias is not None and ctx.needs_input_grad[12]:
+            one = torch.ones(1, 1, dtype=torch.float32, device=embs.device)
+            d_bias = _native.segment_axpy(coef.reshape(-1), perm, one, torch.zeros_like(perm), off).reshape(-1).mul_(1.0 / ctx.scale)
+        return (d_embs, d_rows) + (None,) * 10 + (d_bias,)
+
+
 class DistanceSweepLossFn(torch.autograd.Function):
     """The softmax (mode NEG_SOFTMAX) or negative-sampling (NEG_NEGSAMP) loss of a query against EVERY node, or the shared
     candidate set `cand`, with z_ij = -scale D(q_i, embs[j]) under `metric` (HyperGNN.softmax_loss_by_distance /

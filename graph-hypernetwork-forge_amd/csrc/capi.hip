@@ -2,6 +2,7 @@
 #include "common.h"
 #include "negatives.h"
 #include "distance.h"
+#include "pairwise.h"
 #include <vector>
 #include <thread>
 #include <algorithm>
@@ -1094,6 +1095,51 @@ int ghf_dist_rows_grad(int metric, const float* q, const float* c, const int64_t
 #undef GHF_DIST_METRIC
 #undef GHF_NEG_FLOATS
 #undef GHF_NEG_CHECK
+
+// pairwise ranking losses on per-query negative sets (include/ghf_pairwise.h; csrc/pairwise.hip).  The
+// refusals stand in the header's order: the two selectors, the three scalars, the bias, and only then what the ghf_neg_* calls
+// check.  `kind` and `metric` are public values; launch_pair_* turns each into a template parameter once.
+static int pair_entry_check(const char* op, int metric, int kind, int d, float scale, float margin, int normalize,
+                            const float* bias, bool ptrs, const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz,
+                            const void* workspace, const int64_t* neg, int64_t K) {
+    GHF_REQUIRE(metric == GHF_PAIR_DOT || metric == GHF_DIST_L1 || metric == GHF_DIST_L2 || metric == GHF_DIST_COMPLEX,
+                "%s: metric must be GHF_PAIR_DOT, GHF_DIST_L1, GHF_DIST_L2 or GHF_DIST_COMPLEX", op);
+    GHF_REQUIRE(metric != GHF_DIST_COMPLEX || (d & 1) == 0, "%s: GHF_DIST_COMPLEX needs an even d (re / im interleaved)", op);
+    GHF_REQUIRE(kind == GHF_PAIR_HINGE || kind == GHF_PAIR_LOGISTIC, "%s: kind must be GHF_PAIR_HINGE or GHF_PAIR_LOGISTIC", op);
+    GHF_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, "%s: scale must be finite and positive", op);
+    GHF_REQUIRE(margin >= -3.402823466e38f && margin <= 3.402823466e38f, "%s: margin must be finite", op);
+    GHF_REQUIRE(normalize == 0 || normalize == 1, "%s: normalize must be 0 or 1", op);
+    GHF_REQUIRE(metric == GHF_PAIR_DOT || !bias, "%s: no per-candidate bias under a distance", op);
+    GHF_REQUIRE(ptrs && workspace, "%s: null pointer argument", op);
+    GHF_REQUIRE(nnz <= 0 || (filt_ptr && filt_idx), "%s: null filter list with nnz > 0", op);
+    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace not 256-byte aligned", op);
+    GHF_REQUIRE(neg && K > 0, "%s: need neg [B, K] with K >= 1", op);
+    return GHF_OK;
+}
+
+size_t ghf_pair_workspace_bytes(int64_t B, int64_t K, int d, int64_t nnz) { return pair_workspace_bytes(B, K, d, nnz); }
+
+int ghf_pair_fwd(int metric, int kind, const float* q, const float* c, const int64_t* iq, const int64_t* target,
+                 const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
+                 float scale, float margin, int normalize, const int64_t* neg, int64_t K, const float* bias, void* workspace,
+                 size_t workspace_bytes, float* loss, int32_t* count, int32_t* active, void* stream) {
+    const int rc = pair_entry_check("pair_fwd", metric, kind, d, scale, margin, normalize, bias, q && c && target && loss && count && active,
+                                    filt_ptr, filt_idx, nnz, workspace, neg, K);
+    if (rc != GHF_OK) return rc;
+    return launch_pair_fwd(metric, kind, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, normalize, neg, K,
+                           bias, workspace, workspace_bytes, loss, count, active, (hipStream_t)stream);
+}
+
+int ghf_pair_bwd(int metric, int kind, const float* q, const float* c, const int64_t* iq, const int64_t* target,
+                 const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
+                 float scale, float margin, int normalize, const int64_t* neg, int64_t K, const float* bias, const int32_t* count,
+                 const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* coef, void* stream) {
+    const int rc = pair_entry_check("pair_bwd", metric, kind, d, scale, margin, normalize, bias,
+                                    q && c && target && count && grad_loss && dq && coef, filt_ptr, filt_idx, nnz, workspace, neg, K);
+    if (rc != GHF_OK) return rc;
+    return launch_pair_bwd(metric, kind, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, normalize, neg, K,
+                           bias, count, grad_loss, workspace, workspace_bytes, dq, coef, (hipStream_t)stream);
+}
 
 size_t ghf_relation_rows_workspace_bytes(int64_t B, int R) { return relation_rows_workspace_bytes(B, R); }
 

@@ -1358,6 +1358,74 @@ class HyperGNN(nn.Module):
         return _native.score_negsamp_fwd(e, e, t, iq=q, filt_ptr=ptr, filt_idx=idx, scale=scale, margin=margin,
                                          adversarial_temperature=alpha, ic=cand, bias=bias)[0]
 
+    def pairwise_loss(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, negatives: torch.Tensor,
+                      loss: str = "hinge", margin: float = 1.0, scale: float = 1.0, normalize: bool = True,
+                      distance: Optional[str] = None, known=None, filt_ptr: Optional[torch.Tensor] = None,
+                      filt_idx: Optional[torch.Tensor] = None, query_rows: Optional[torch.Tensor] = None,
+                      query_rel: Optional[torch.Tensor] = None, candidate_bias: Optional[torch.Tensor] = None,
+                      return_active: bool = False):
+        """The pairwise ranking losses on per-query negatives, fp32 ``[B]``: every term couples one negative of query ``i`` to
+        that query's positive.  With ``z[i, j] = scale * embs[query[i]] . embs[negatives[i, j]]`` (``+ candidate_bias[.]``), or
+        ``z = -scale * D(row_i, embs[.])`` under ``distance`` (``"l1"``, ``"l2"``, ``"complex"``, as in ``softmax_loss``), and
+        ``J_i`` the positions of row ``i`` that hold neither ``-1``, the target nor a known partner (``known`` / ``filt_ptr,
+        filt_idx`` as in ``rank_candidates``)::
+
+            u[i, j] = z[i, j] - z[i, target[i]] + margin
+            loss[i] = mean over J_i of max(u, 0)          # loss="hinge": margin ranking (TransE; PinSage / GraphSAGE max-margin)
+            loss[i] = mean over J_i of softplus(u)        # loss="logistic": BPR at margin=0 (LightGCN, NGCF); soft margin ranking
+
+        ``normalize=False`` gives the sum instead of the mean; a query whose ``J_i`` is empty has loss exactly 0.  The
+        published TransE loss is::
+
+            rows = embs[head] + rel_vec[rel]
+            loss = model.pairwise_loss(embs, head, tail, negatives=neg, query_rows=rows, distance="l1", margin=gamma).mean()
+
+        ``negatives`` (int32 / int64 ``[B, K]``, required; ids in ``[0, N)`` or exactly ``-1`` for "no entry"; negative ids do
+        NOT wrap; a multiset in the given order).  ``return_active=True`` returns ``(loss, active)``, ``active`` int32 ``[B]``
+        the number of violated pairs ``u > 0`` — what one logs while training; at ``margin=0`` it is ``rank_candidates``'
+        ``greater``.  Neither the ``[B, K]`` scores nor the ``[B, K, d]`` gather exist, forward or backward: one wave per query
+        (``ghf_pair_fwd`` / ``ghf_pair_bwd``, ``include/ghf_pairwise.h``, ``autograd.PairwiseLossFn``).  Gradients reach
+        ``embs``, ``query_rows`` and (dot product only) ``candidate_bias``; rows of ``embs`` that are no one's negative, target
+        or query get exactly zero; bit-reproducible.  ``scale`` finite and ``> 0``, ``margin`` finite (``ValueError``
+        otherwise); ``candidate_bias`` together with ``distance`` is a ``ValueError``."""
+        if embs.dim() != 2:
+            raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        kind = _native.PAIR_KINDS.get(loss) if isinstance(loss, str) else None
+        if kind is None:
+            raise ValueError(f"loss must be one of {sorted(_native.PAIR_KINDS)}, got {loss!r}")
+        if negatives is None:
+            raise ValueError("pairwise_loss needs negatives= (a set per query): its terms are (positive, negative) pairs")
+        if distance is not None and candidate_bias is not None:
+            raise ValueError("candidate_bias= does not go with distance=: no distance call takes a per-candidate bias")
+        metric = self._distance_arg(distance, negatives, None, None, embs)
+        metric = _native.PAIR_DOT if metric is None else metric
+        bias = self._candidate_bias(candidate_bias, embs)
+        neg, q, t = self._negatives_arg(negatives, None, query, target, embs)
+        self._query_rows(embs, query, query_rows, "pairwise_loss")
+        scale, margin = float(scale), float(margin)
+        if not (0.0 < scale < float("inf")):
+            raise ValueError(f"scale must be finite and positive, got {scale}")
+        if not (float("-inf") < margin < float("inf")):
+            raise ValueError(f"margin must be finite, got {margin}")
+        if not isinstance(normalize, bool) or not isinstance(return_active, bool):
+            raise TypeError(f"normalize and return_active must be bools, got {normalize!r} and {return_active!r}")
+        if not embs.is_cuda:
+            raise RuntimeError(f"pairwise_loss computes on an MI355X HIP device only (input is on {embs.device})")
+        ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
+        grad = embs.requires_grad or (bias is not None and bias.requires_grad) or (query_rows is not None and query_rows.requires_grad)
+        if torch.is_grad_enabled() and grad:
+            from ..autograd import PairwiseLossFn
+            if query_rows is not None:
+                out, active = PairwiseLossFn.apply(embs, query_rows, None, t, ptr, idx, neg, metric, kind, scale, margin, normalize, bias)
+            else:
+                out, active = PairwiseLossFn.apply(embs, None, q, t, ptr, idx, neg, metric, kind, scale, margin, normalize, bias)
+        else:
+            e = embs.detach().float()
+            qm, iq = (e, q) if query_rows is None else (query_rows.detach(), None)
+            out, _, active = _native.score_pair_fwd(metric, kind, qm, e, t, neg, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale,
+                                                    margin=margin, normalize=normalize, bias=bias)
+        return (out, active) if return_active else out
+
     @staticmethod
     def _negatives_loss(mode: int, embs, q, t, ptr, idx, neg, scale: float, margin: float, alpha: float, query_rows, bias):
         """``softmax_loss`` / ``negative_sampling_loss`` with ``negatives=`` once every argument is checked: recorded
