@@ -1260,6 +1260,72 @@ def _neg_arg(neg: torch.Tensor, B: int, c: torch.Tensor, what: str) -> torch.Ten
     return neg
 
 
+def _per_query(symbol: str, what: str, lead, q, c, target, neg, iq, filt_ptr, filt_idx, workspace, ws_fn, out, out_specs,
+               out_err: Optional[str] = None, scale=None, margin=None, alpha=None, normalize=None, bias=None, bias_slot: bool = True,
+               saved=None):
+    """One call of the per-query family (ghf_neg_*, ghf_dist_*, ghf_pair_*): the argument normalisation, the
+    workspace, the outputs and _check, for every member.  `lead`: None or d -> the call's leading selectors (it raises what a bad
+    one deserves); `scale` None: the call has none (rank); `margin`, `alpha`, `normalize`: the scalars the call takes, in the
+    ABI's order; `bias_slot`: whether the ABI has a bias argument; `saved`: None or (tensor, dtype, name, grad_loss) of a
+    backward; `out_specs`: (dtype, shape) per output, the shape "B", "Bd" or "BK" ([B], [B, d], [B, K + 1]); `out_err`: the message for a bad
+    non-float output."""
+    q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, what)
+    target = _req(target, torch.int64, "target")
+    if target.dim() != 1 or target.numel() != B or target.device != q.device:
+        raise ValueError(f"{what}: target must be [B = {B}] on {q.device}, got {tuple(target.shape)} on {target.device}")
+    scalars = [] if scale is None else [_scale_arg(scale, what)]
+    if margin is not None:
+        margin = float(margin)
+        if not (float("-inf") < margin < float("inf")):
+            raise ValueError(f"{what}: margin must be finite, got {margin}")
+        scalars.append(margin)
+    if alpha is not None:
+        alpha = float(alpha)
+        if not (0.0 <= alpha < float("inf")):
+            raise ValueError(f"{what}: adversarial_temperature must be finite and not negative, got {alpha}")
+        scalars.append(alpha)
+    if normalize is not None:
+        if not isinstance(normalize, (bool, int)) or normalize not in (0, 1):
+            raise ValueError(f"{what}: normalize must be a bool, got {normalize!r}")
+        scalars.append(int(normalize))
+    neg = _neg_arg(neg, B, c, what)
+    N, d, K = c.size(0), c.size(1), neg.size(1)
+    lead = () if lead is None else lead(d)
+    tail = [_ptr(_bias_arg(bias, c, what))] if bias_slot else []
+    if saved is not None:
+        t, dtype, name, grad_loss = saved
+        t, grad_loss = _req(t, dtype, name), _req(grad_loss, torch.float32, "grad_loss")
+        if t.numel() != B or grad_loss.numel() != B:
+            raise ValueError(f"{what}: {name} and grad_loss must hold B = {B} values")
+        tail += [_ptr(t), _ptr(grad_loss)]
+    ws = _workspace(workspace, ws_fn, q.device, what, B=B, K=K, d=d, nnz=nnz)
+    dev, outs = q.device, []
+    for k, (dtype, code) in enumerate(out_specs):
+        given = None if out is None else out[k]
+        shape = (B,) if code == "B" else (B, d) if code == "Bd" else (B, K + 1)
+        if given is None:
+            outs.append(torch.empty(shape, dtype=dtype, device=dev))
+        elif dtype == torch.float32:
+            outs.append(_f32_out(given, shape, dev, what))
+        else:
+            t = _req(given, dtype, "out")
+            if t.numel() != B or not given.is_contiguous():           # every non-float output is a [B] vector
+                raise ValueError(f"{what}: {out_err.format(B=B)}")
+            outs.append(t)
+    args = [*lead, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d, *scalars,
+            _ptr(neg), K, *tail, _ptr(ws), ws.numel()]
+    for t in outs:
+        args.append(_ptr(t))
+    _check(getattr(load(), symbol)(*args, _stream()), symbol)
+    return tuple(outs)
+
+
+_PQ_LOSS = ((torch.float32, "B"), (torch.float32, "B"))
+_PQ_COUNTS = ((torch.int64, "B"), (torch.int64, "B"))
+_PQ_GRADS = ((torch.float32, "Bd"), (torch.float32, "BK"))
+_PQ_COUNTS_ERR = "out must be two contiguous int64 [{B}] tensors"
+
+
 def score_neg_rank(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor, iq: Optional[torch.Tensor] = None,
                    filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                    workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
@@ -1268,24 +1334,8 @@ def score_neg_rank(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: 
     (node ids, -1 = no entry, repeats count) score above / the same as row target[i], positions that hold the target or a
     listed id left out.  `bias` (fp32 [N]): every score is s + bias[row].  With `workspace` (uint8, neg_workspace_bytes) and
     `out` given the call allocates nothing."""
-    q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, "score_neg_rank")
-    target = _req(target, torch.int64, "target")
-    if target.dim() != 1 or target.numel() != B or target.device != q.device:
-        raise ValueError(f"score_neg_rank: target must be [B = {B}] on {q.device}, got {tuple(target.shape)} on {target.device}")
-    neg = _neg_arg(neg, B, c, "score_neg_rank")
-    N, d, K = c.size(0), c.size(1), neg.size(1)
-    bias = _bias_arg(bias, c, "score_neg_rank")
-    ws = _workspace(workspace, neg_workspace_bytes, q.device, "score_neg_rank", B=B, K=K, d=d, nnz=nnz)
-    if out is None:
-        greater = torch.empty(B, dtype=torch.int64, device=q.device)
-        equal = torch.empty(B, dtype=torch.int64, device=q.device)
-    else:
-        greater, equal = (_req(t, torch.int64, "out") for t in out)
-        if greater.numel() != B or equal.numel() != B or not (out[0].is_contiguous() and out[1].is_contiguous()):
-            raise ValueError(f"score_neg_rank: out must be two contiguous int64 [{B}] tensors")
-    _check(load().ghf_neg_rank(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d,
-                               _ptr(neg), K, _ptr(bias), _ptr(ws), ws.numel(), _ptr(greater), _ptr(equal), _stream()), "ghf_neg_rank")
-    return greater, equal
+    return _per_query("ghf_neg_rank", "score_neg_rank", None, q, c, target, neg, iq, filt_ptr, filt_idx, workspace, neg_workspace_bytes,
+                      out, _PQ_COUNTS, _PQ_COUNTS_ERR, bias=bias)
 
 
 def score_neg_softmax_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
@@ -1295,17 +1345,8 @@ def score_neg_softmax_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor
     """(loss, lse) fp32 [B] of include/ghf_negatives.h: ghf_neg_softmax_fwd — lse[i] = log(exp(z_it) + sum over query i's own
     negatives neg[i, :] outside its list other than the target of exp(z_ij)), z = scale q . c[row] (+ bias[row]), loss = lse -
     z_it; exactly 0 for a query without negatives."""
-    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale,
-                                                                        "score_neg_softmax_fwd")
-    neg = _neg_arg(neg, B, c, "score_neg_softmax_fwd")
-    N, d, K = c.size(0), c.size(1), neg.size(1)
-    loss, lse = _f32_out_pair(out, (B,), (B,), q.device, "score_neg_softmax_fwd")
-    bias = _bias_arg(bias, c, "score_neg_softmax_fwd")
-    ws = _workspace(workspace, neg_workspace_bytes, q.device, "score_neg_softmax_fwd", B=B, K=K, d=d, nnz=nnz)
-    _check(load().ghf_neg_softmax_fwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d,
-                                      scale, _ptr(neg), K, _ptr(bias), _ptr(ws), ws.numel(), _ptr(loss), _ptr(lse), _stream()),
-           "ghf_neg_softmax_fwd")
-    return loss, lse
+    return _per_query("ghf_neg_softmax_fwd", "score_neg_softmax_fwd", None, q, c, target, neg, iq, filt_ptr, filt_idx, workspace,
+                      neg_workspace_bytes, out, _PQ_LOSS, scale=scale, bias=bias)
 
 
 def score_neg_negsamp_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
@@ -1316,17 +1357,8 @@ def score_neg_negsamp_fwd(q: torch.Tensor, c: torch.Tensor, target: torch.Tensor
     """(loss, lw) fp32 [B] of include/ghf_negatives.h: ghf_neg_negsamp_fwd — score_negsamp_fwd's formulas with J_i the positions
     of query i's own negatives neg[i, :] outside its list other than the target; lw = -inf and the positive term alone where
     there are none."""
-    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, alpha = _negsamp_args(
-        q, c, target, iq, filt_ptr, filt_idx, scale, margin, adversarial_temperature, "score_neg_negsamp_fwd")
-    neg = _neg_arg(neg, B, c, "score_neg_negsamp_fwd")
-    N, d, K = c.size(0), c.size(1), neg.size(1)
-    loss, lw = _f32_out_pair(out, (B,), (B,), q.device, "score_neg_negsamp_fwd")
-    bias = _bias_arg(bias, c, "score_neg_negsamp_fwd")
-    ws = _workspace(workspace, neg_workspace_bytes, q.device, "score_neg_negsamp_fwd", B=B, K=K, d=d, nnz=nnz)
-    _check(load().ghf_neg_negsamp_fwd(_ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d,
-                                      scale, margin, alpha, _ptr(neg), K, _ptr(bias), _ptr(ws), ws.numel(), _ptr(loss), _ptr(lw),
-                                      _stream()), "ghf_neg_negsamp_fwd")
-    return loss, lw
+    return _per_query("ghf_neg_negsamp_fwd", "score_neg_negsamp_fwd", None, q, c, target, neg, iq, filt_ptr, filt_idx, workspace,
+                      neg_workspace_bytes, out, _PQ_LOSS, scale=scale, margin=margin, alpha=adversarial_temperature, bias=bias)
 
 
 def score_neg_bwd(mode: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor, saved: torch.Tensor,
@@ -1337,23 +1369,12 @@ def score_neg_bwd(mode: int, q: torch.Tensor, c: torch.Tensor, target: torch.Ten
     """(dq [B, d], coef [B, K + 1]) fp32 of include/ghf_negatives.h: ghf_neg_bwd, `mode` NEG_SOFTMAX or NEG_NEGSAMP and `saved`
     that forward's lse / lw.  coef[i, j] is the gradient of the loss sum with respect to the score of position j of query i (0
     where the position takes no part), coef[i, K] the target's; dq[i] = sum_j coef[i, j] c[neg[i, j]] + coef[i, K] c[target[i]],
-    per query (not scattered through iq).  The gradient of c is a grouped sum over coef (autograd.NegativesLossFn)."""
+    per query (not scattered through iq).  The gradient of c is a grouped sum over coef (autograd.PerQueryLossFn)."""
     if mode not in (NEG_SOFTMAX, NEG_NEGSAMP):
         raise ValueError(f"score_neg_bwd: mode must be NEG_SOFTMAX or NEG_NEGSAMP, got {mode}")
-    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, alpha = _negsamp_args(
-        q, c, target, iq, filt_ptr, filt_idx, scale, margin, adversarial_temperature, "score_neg_bwd")
-    neg = _neg_arg(neg, B, c, "score_neg_bwd")
-    saved, grad_loss = _req(saved, torch.float32, "saved"), _req(grad_loss, torch.float32, "grad_loss")
-    if saved.numel() != B or grad_loss.numel() != B:
-        raise ValueError(f"score_neg_bwd: saved and grad_loss must hold B = {B} values")
-    N, d, K = c.size(0), c.size(1), neg.size(1)
-    bias = _bias_arg(bias, c, "score_neg_bwd")
-    ws = _workspace(workspace, neg_workspace_bytes, q.device, "score_neg_bwd", B=B, K=K, d=d, nnz=nnz)
-    dq, coef = _f32_out_pair(out, (B, d), (B, K + 1), q.device, "score_neg_bwd")
-    _check(load().ghf_neg_bwd(mode, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B, d,
-                              scale, margin, alpha, _ptr(neg), K, _ptr(bias), _ptr(saved), _ptr(grad_loss), _ptr(ws), ws.numel(),
-                              _ptr(dq), _ptr(coef), _stream()), "ghf_neg_bwd")
-    return dq, coef
+    return _per_query("ghf_neg_bwd", "score_neg_bwd", lambda d: (mode,), q, c, target, neg, iq, filt_ptr, filt_idx, workspace,
+                      neg_workspace_bytes, out, _PQ_GRADS, scale=scale, margin=margin, alpha=adversarial_temperature, bias=bias,
+                      saved=(saved, torch.float32, "saved", grad_loss))
 
 
 # ---- distance scores for per-query negative sets (include/ghf_distance.h, csrc/distance.hip) ----------------------------
@@ -1376,24 +1397,8 @@ def score_dist_rank(metric: int, q: torch.Tensor, c: torch.Tensor, target: torch
     """(greater, equal) int64 [B] of include/ghf_distance.h: ghf_dist_rank — score_neg_rank with the score -D(q_i, c[row]),
     `metric` DIST_L1, DIST_L2 or DIST_COMPLEX: how many of query i's own negatives lie closer to q_i than / exactly as far as
     row target[i]."""
-    q, c, iq, filt_ptr, filt_idx, B, nnz = _rank_args(q, c, iq, filt_ptr, filt_idx, "score_dist_rank")
-    target = _req(target, torch.int64, "target")
-    if target.dim() != 1 or target.numel() != B or target.device != q.device:
-        raise ValueError(f"score_dist_rank: target must be [B = {B}] on {q.device}, got {tuple(target.shape)} on {target.device}")
-    neg = _neg_arg(neg, B, c, "score_dist_rank")
-    N, d, K = c.size(0), c.size(1), neg.size(1)
-    metric = _metric_arg(metric, d, "score_dist_rank")
-    ws = _workspace(workspace, dist_workspace_bytes, q.device, "score_dist_rank", B=B, K=K, d=d, nnz=nnz)
-    if out is None:
-        greater = torch.empty(B, dtype=torch.int64, device=q.device)
-        equal = torch.empty(B, dtype=torch.int64, device=q.device)
-    else:
-        greater, equal = (_req(t, torch.int64, "out") for t in out)
-        if greater.numel() != B or equal.numel() != B or not (out[0].is_contiguous() and out[1].is_contiguous()):
-            raise ValueError(f"score_dist_rank: out must be two contiguous int64 [{B}] tensors")
-    _check(load().ghf_dist_rank(metric, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N, B,
-                                d, _ptr(neg), K, _ptr(ws), ws.numel(), _ptr(greater), _ptr(equal), _stream()), "ghf_dist_rank")
-    return greater, equal
+    return _per_query("ghf_dist_rank", "score_dist_rank", lambda d: (_metric_arg(metric, d, "score_dist_rank"),), q, c, target, neg,
+                      iq, filt_ptr, filt_idx, workspace, dist_workspace_bytes, out, _PQ_COUNTS, _PQ_COUNTS_ERR, bias_slot=False)
 
 
 # ---- distance scores against every node or a candidate subset (include/ghf_distance_sweep.h, csrc/distance_sweep.hip) ---
@@ -1550,17 +1555,9 @@ def score_dist_softmax_fwd(metric: int, q: torch.Tensor, c: torch.Tensor, target
                            out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
     """(loss, lse) fp32 [B] of include/ghf_distance.h: ghf_dist_softmax_fwd — score_neg_softmax_fwd with z = -scale D(q_i,
     c[row])."""
-    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale,
-                                                                        "score_dist_softmax_fwd")
-    neg = _neg_arg(neg, B, c, "score_dist_softmax_fwd")
-    N, d, K = c.size(0), c.size(1), neg.size(1)
-    metric = _metric_arg(metric, d, "score_dist_softmax_fwd")
-    loss, lse = _f32_out_pair(out, (B,), (B,), q.device, "score_dist_softmax_fwd")
-    ws = _workspace(workspace, dist_workspace_bytes, q.device, "score_dist_softmax_fwd", B=B, K=K, d=d, nnz=nnz)
-    _check(load().ghf_dist_softmax_fwd(metric, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0),
-                                       N, B, d, scale, _ptr(neg), K, _ptr(ws), ws.numel(), _ptr(loss), _ptr(lse), _stream()),
-           "ghf_dist_softmax_fwd")
-    return loss, lse
+    return _per_query("ghf_dist_softmax_fwd", "score_dist_softmax_fwd", lambda d: (_metric_arg(metric, d, "score_dist_softmax_fwd"),),
+                      q, c, target, neg, iq, filt_ptr, filt_idx, workspace, dist_workspace_bytes, out, _PQ_LOSS, scale=scale,
+                      bias_slot=False)
 
 
 def score_dist_negsamp_fwd(metric: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
@@ -1570,17 +1567,9 @@ def score_dist_negsamp_fwd(metric: int, q: torch.Tensor, c: torch.Tensor, target
                            out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
     """(loss, lw) fp32 [B] of include/ghf_distance.h: ghf_dist_negsamp_fwd — score_neg_negsamp_fwd with z = -scale D(q_i,
     c[row]); at scale = 1 and margin = gamma the positive term is -log sigmoid(gamma - D_t), RotatE's."""
-    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, alpha = _negsamp_args(
-        q, c, target, iq, filt_ptr, filt_idx, scale, margin, adversarial_temperature, "score_dist_negsamp_fwd")
-    neg = _neg_arg(neg, B, c, "score_dist_negsamp_fwd")
-    N, d, K = c.size(0), c.size(1), neg.size(1)
-    metric = _metric_arg(metric, d, "score_dist_negsamp_fwd")
-    loss, lw = _f32_out_pair(out, (B,), (B,), q.device, "score_dist_negsamp_fwd")
-    ws = _workspace(workspace, dist_workspace_bytes, q.device, "score_dist_negsamp_fwd", B=B, K=K, d=d, nnz=nnz)
-    _check(load().ghf_dist_negsamp_fwd(metric, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0),
-                                       N, B, d, scale, margin, alpha, _ptr(neg), K, _ptr(ws), ws.numel(), _ptr(loss), _ptr(lw),
-                                       _stream()), "ghf_dist_negsamp_fwd")
-    return loss, lw
+    return _per_query("ghf_dist_negsamp_fwd", "score_dist_negsamp_fwd", lambda d: (_metric_arg(metric, d, "score_dist_negsamp_fwd"),),
+                      q, c, target, neg, iq, filt_ptr, filt_idx, workspace, dist_workspace_bytes, out, _PQ_LOSS, scale=scale,
+                      margin=margin, alpha=adversarial_temperature, bias_slot=False)
 
 
 def score_dist_bwd(metric: int, mode: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
@@ -1591,23 +1580,12 @@ def score_dist_bwd(metric: int, mode: int, q: torch.Tensor, c: torch.Tensor, tar
     """(dq [B, d], coef [B, K + 1]) fp32 of include/ghf_distance.h: ghf_dist_bwd, `mode` NEG_SOFTMAX or NEG_NEGSAMP and `saved`
     that forward's lse / lw.  coef means what score_neg_bwd's means (the gradient with respect to the score s = -D of every
     position, the target's last); dq[i] = -(sum_j coef[i, j] g(i, neg[i, j]) + coef[i, K] g(i, target[i])), g = dD / dq.  The
-    gradient of c is dist_rows_grad over coef (autograd.DistanceLossFn)."""
+    gradient of c is dist_rows_grad over coef (autograd.PerQueryLossFn)."""
     if mode not in (NEG_SOFTMAX, NEG_NEGSAMP):
         raise ValueError(f"score_dist_bwd: mode must be NEG_SOFTMAX or NEG_NEGSAMP, got {mode}")
-    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, alpha = _negsamp_args(
-        q, c, target, iq, filt_ptr, filt_idx, scale, margin, adversarial_temperature, "score_dist_bwd")
-    neg = _neg_arg(neg, B, c, "score_dist_bwd")
-    saved, grad_loss = _req(saved, torch.float32, "saved"), _req(grad_loss, torch.float32, "grad_loss")
-    if saved.numel() != B or grad_loss.numel() != B:
-        raise ValueError(f"score_dist_bwd: saved and grad_loss must hold B = {B} values")
-    N, d, K = c.size(0), c.size(1), neg.size(1)
-    metric = _metric_arg(metric, d, "score_dist_bwd")
-    ws = _workspace(workspace, dist_workspace_bytes, q.device, "score_dist_bwd", B=B, K=K, d=d, nnz=nnz)
-    dq, coef = _f32_out_pair(out, (B, d), (B, K + 1), q.device, "score_dist_bwd")
-    _check(load().ghf_dist_bwd(metric, mode, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N,
-                               B, d, scale, margin, alpha, _ptr(neg), K, _ptr(saved), _ptr(grad_loss), _ptr(ws), ws.numel(),
-                               _ptr(dq), _ptr(coef), _stream()), "ghf_dist_bwd")
-    return dq, coef
+    return _per_query("ghf_dist_bwd", "score_dist_bwd", lambda d: (_metric_arg(metric, d, "score_dist_bwd"), mode), q, c, target, neg,
+                      iq, filt_ptr, filt_idx, workspace, dist_workspace_bytes, out, _PQ_GRADS, scale=scale, margin=margin,
+                      alpha=adversarial_temperature, bias_slot=False, saved=(saved, torch.float32, "saved", grad_loss))
 
 
 def dist_rows_grad(metric: int, q: torch.Tensor, c: torch.Tensor, coef: torch.Tensor, perm: torch.Tensor, off: torch.Tensor,
@@ -1637,29 +1615,16 @@ def pair_workspace_bytes(B: int, K: int, d: int, nnz: int) -> int:
     return int(load().ghf_pair_workspace_bytes(B, K, d, nnz))
 
 
-def _pair_selectors(metric: int, kind: int, d: int, what: str) -> Tuple[int, int]:
+def _pair_selectors(metric: int, kind: int, d: int, bias, what: str) -> Tuple[int, int]:
     if metric not in (PAIR_DOT, DIST_L1, DIST_L2, DIST_COMPLEX):
         raise ValueError(f"{what}: metric must be PAIR_DOT, DIST_L1, DIST_L2 or DIST_COMPLEX, got {metric}")
     if metric == DIST_COMPLEX and d % 2:
         raise ValueError(f"{what}: DIST_COMPLEX reads the rows as interleaved re / im pairs and needs an even d, got {d}")
     if kind not in (PAIR_HINGE, PAIR_LOGISTIC):
         raise ValueError(f"{what}: kind must be PAIR_HINGE or PAIR_LOGISTIC, got {kind}")
-    return int(metric), int(kind)
-
-
-def _pair_args(metric, kind, q, c, target, neg, iq, filt_ptr, filt_idx, scale, margin, normalize, bias, what: str):
-    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, what)
-    margin = float(margin)
-    if not (float("-inf") < margin < float("inf")):
-        raise ValueError(f"{what}: margin must be finite, got {margin}")
-    if not isinstance(normalize, (bool, int)) or normalize not in (0, 1):
-        raise ValueError(f"{what}: normalize must be a bool, got {normalize!r}")
-    neg = _neg_arg(neg, B, c, what)
-    metric, kind = _pair_selectors(metric, kind, c.size(1), what)
     if bias is not None and metric != PAIR_DOT:
         raise ValueError(f"{what}: no per-candidate bias under a distance")
-    bias = _bias_arg(bias, c, what)
-    return metric, kind, q, c, target, neg, iq, filt_ptr, filt_idx, B, nnz, scale, margin, int(normalize), bias
+    return int(metric), int(kind)
 
 
 def score_pair_fwd(metric: int, kind: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
@@ -1673,23 +1638,11 @@ def score_pair_fwd(metric: int, kind: int, q: torch.Tensor, c: torch.Tensor, tar
     count[i] with `normalize`), active = #{u_ij > 0}.  `metric` PAIR_DOT: z = scale q . c[row] (+ bias[row]); DIST_L1 / DIST_L2 /
     DIST_COMPLEX: z = -scale D(q_i, c[row]), no bias.  With `workspace` (uint8, pair_workspace_bytes) and `out` given the call
     allocates nothing."""
-    metric, kind, q, c, target, neg, iq, filt_ptr, filt_idx, B, nnz, scale, margin, normalize, bias = _pair_args(
-        metric, kind, q, c, target, neg, iq, filt_ptr, filt_idx, scale, margin, normalize, bias, "score_pair_fwd")
-    N, d, K = c.size(0), c.size(1), neg.size(1)
-    if out is None:
-        loss = torch.empty(B, dtype=torch.float32, device=q.device)
-        count = torch.empty(B, dtype=torch.int32, device=q.device)
-        active = torch.empty(B, dtype=torch.int32, device=q.device)
-    else:
-        loss = _f32_out(out[0], (B,), q.device, "score_pair_fwd")
-        count, active = (_req(t, torch.int32, "out") for t in out[1:])
-        if count.numel() != B or active.numel() != B or not (out[1].is_contiguous() and out[2].is_contiguous()):
-            raise ValueError(f"score_pair_fwd: out must be a contiguous fp32 [{B}] and two contiguous int32 [{B}] tensors")
-    ws = _workspace(workspace, pair_workspace_bytes, q.device, "score_pair_fwd", B=B, K=K, d=d, nnz=nnz)
-    _check(load().ghf_pair_fwd(metric, kind, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N,
-                               B, d, scale, margin, normalize, _ptr(neg), K, _ptr(bias), _ptr(ws), ws.numel(), _ptr(loss), _ptr(count),
-                               _ptr(active), _stream()), "ghf_pair_fwd")
-    return loss, count, active
+    return _per_query("ghf_pair_fwd", "score_pair_fwd", lambda d: _pair_selectors(metric, kind, d, bias, "score_pair_fwd"), q, c, target,
+                      neg, iq, filt_ptr, filt_idx, workspace, pair_workspace_bytes, out,
+                      ((torch.float32, "B"), (torch.int32, "B"), (torch.int32, "B")),
+                      "out must be a contiguous fp32 [{B}] and two contiguous int32 [{B}] tensors", scale=scale, margin=margin,
+                      normalize=normalize, bias=bias)
 
 
 def score_pair_bwd(metric: int, kind: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, neg: torch.Tensor,
@@ -1701,19 +1654,10 @@ def score_pair_bwd(metric: int, kind: int, q: torch.Tensor, c: torch.Tensor, tar
     gradient of the loss sum with respect to the score of position j of query i (0 where the position takes no part), coef[i,
     K] the target's: minus the sum of the row's others.  dq is per query (not scattered through iq), formed from coef as
     score_neg_bwd (PAIR_DOT) or score_dist_bwd (a distance) form it.  The gradient of c is a grouped sum over coef
-    (autograd.PairwiseLossFn)."""
-    metric, kind, q, c, target, neg, iq, filt_ptr, filt_idx, B, nnz, scale, margin, normalize, bias = _pair_args(
-        metric, kind, q, c, target, neg, iq, filt_ptr, filt_idx, scale, margin, normalize, bias, "score_pair_bwd")
-    count, grad_loss = _req(count, torch.int32, "count"), _req(grad_loss, torch.float32, "grad_loss")
-    if count.numel() != B or grad_loss.numel() != B:
-        raise ValueError(f"score_pair_bwd: count and grad_loss must hold B = {B} values")
-    N, d, K = c.size(0), c.size(1), neg.size(1)
-    ws = _workspace(workspace, pair_workspace_bytes, q.device, "score_pair_bwd", B=B, K=K, d=d, nnz=nnz)
-    dq, coef = _f32_out_pair(out, (B, d), (B, K + 1), q.device, "score_pair_bwd")
-    _check(load().ghf_pair_bwd(metric, kind, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N,
-                               B, d, scale, margin, normalize, _ptr(neg), K, _ptr(bias), _ptr(count), _ptr(grad_loss), _ptr(ws),
-                               ws.numel(), _ptr(dq), _ptr(coef), _stream()), "ghf_pair_bwd")
-    return dq, coef
+    (autograd.PerQueryLossFn)."""
+    return _per_query("ghf_pair_bwd", "score_pair_bwd", lambda d: _pair_selectors(metric, kind, d, bias, "score_pair_bwd"), q, c, target,
+                      neg, iq, filt_ptr, filt_idx, workspace, pair_workspace_bytes, out, _PQ_GRADS, scale=scale, margin=margin,
+                      normalize=normalize, bias=bias, saved=(count, torch.int32, "count", grad_loss))
 
 
 # ---- relation-typed query rows (include/ghf.h: ghf_relation_rows, csrc/relation.hip) ------------------------------------

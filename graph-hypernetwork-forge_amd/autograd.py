@@ -550,169 +550,95 @@ class NegSamplingLossFn(torch.autograd.Function):
         return _all_node_loss_grads(ctx, embs, rows, query, res[0], res[1], cand) + (None,) * 8 + (_bias_grad(ctx, 10, db, bias, cand),)
 
 
-class NegativesLossFn(torch.autograd.Function):
-    """The softmax loss (mode = _native.NEG_SOFTMAX) or the negative-sampling loss (NEG_NEGSAMP) of every query against ITS OWN
-    negatives `neg` [B, K] (node ids, -1 = no entry, a multiset in the given order; HyperGNN.softmax_loss /
-    negative_sampling_loss with ``negatives=``; include/ghf_negatives.h), q_i and the pair `rows` / `query` as in
-    SoftmaxLossFn.  Saved is the forward's lse / lw; the backward (ghf_neg_bwd) recomputes the logits, returns dq per query
-    and the coefficients coef [B, K + 1] — one per position, the target's last.  d embs is the sum of coef q_i over the
-    entries that name a node: the B (K + 1) node ids grouped by node (ghf_group_edges, stable; an entry that is padding
-    stands under its query's target with coefficient 0) and summed per node in that order (ghf_segment_axpy), as
-    ScoreEdgesFn does — reproducible, and a row that is no one's negative, target or query gets exactly zero.  The
-    grouping depends on the ids alone: it is made in the forward and saved.  d bias is the same sum over a column of ones,
-    over scale.  Nothing of size [N, d] is made when embs needs no gradient."""
+def per_query_forward(loss: str, metric: int, q, embs, target, neg, iq, ptr, idx, scale: float, margin: float, alpha: float,
+                      normalize: bool, bias):
+    """(loss, saved, active) of the forward call that `loss` ("softmax", "negsamp", "hinge", "logistic") and `metric`
+    (_native.PAIR_DOT or a distance) name among the per-query family's: saved is lse, lw or the pair count, active None but
+    for the pairwise losses."""
+    kw = dict(iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale)
+    dot = metric == _native.PAIR_DOT
+    if loss in _native.PAIR_KINDS:
+        return _native.score_pair_fwd(metric, _native.PAIR_KINDS[loss], q, embs, target, neg, margin=margin, normalize=normalize, bias=bias, **kw)
+    if loss == "negsamp":
+        kw.update(margin=margin, adversarial_temperature=alpha)
+    elif loss != "softmax":
+        raise ValueError(f"no per-query loss {loss!r}")
+    fwd = getattr(_native, f"score_{'neg' if dot else 'dist'}_{loss}_fwd")
+    return (fwd(q, embs, target, neg, bias=bias, **kw) if dot else fwd(metric, q, embs, target, neg, **kw)) + (None,)
+
+
+class PerQueryLossFn(torch.autograd.Function):
+    """A loss of every query against ITS OWN negatives `neg` [B, K] (node ids, -1 = no entry, a multiset in the given order;
+    ``negatives=`` of HyperGNN.softmax_loss / negative_sampling_loss, and HyperGNN.pairwise_loss), q_i and the pair `rows` /
+    `query` as in SoftmaxLossFn.  `loss` names it: "softmax" or "negsamp" (include/ghf_negatives.h, ghf_distance.h; returns the
+    loss) or "hinge" or "logistic" (include/ghf_pairwise.h; returns (loss, active), active — the violated pairs — without a
+    gradient).  `metric` names the score: _native.PAIR_DOT, the dot product, with an optional `bias`, or _native.DIST_L1 /
+    DIST_L2 / DIST_COMPLEX, s = -D(q_i, embs[v]).
+
+    Saved is what the forward's kernel left for the backward (lse, lw or the pair count) and the grouping of the B (K + 1) node
+    ids [neg | target] by node (ghf_group_edges, stable; an entry that is padding stands under its query's target with
+    coefficient 0), which depends on the ids alone.  The backward (ghf_neg_bwd / ghf_dist_bwd / ghf_pair_bwd) recomputes the
+    logits, returns dq per query and the coefficients coef [B, K + 1] — one per position, the target's last.  Under the dot
+    product d embs is the sum of coef q_i over the entries that name a node, per node in the grouping's order
+    (ghf_segment_axpy, as ScoreEdgesFn does), and d bias the same sum over a column of ones, over scale; under a distance the
+    gradient of a candidate row is no multiple of the query's row and d embs is ghf_dist_rows_grad over coef.  Either way dq
+    is folded in through `query` when the queries are embs' own rows.  Reproducible; a row that is no one's negative, target
+    or query gets exactly zero; nothing of size [N, d] is made when embs needs no gradient."""
 
     @staticmethod
-    def forward(ctx, embs, rows, query, target, ptr, idx, neg, mode: int, scale: float, margin: float, alpha: float, bias=None):
-        assert (rows is None) != (query is None)
-        embs = embs.contiguous().float()
-        rows = None if rows is None else rows.contiguous().float()
-        bias = None if bias is None else bias.contiguous()
-        q = embs if rows is None else rows
-        if mode == _native.NEG_SOFTMAX:
-            loss, saved = _native.score_neg_softmax_fwd(q, embs, target, neg, iq=query, filt_ptr=ptr, filt_idx=idx, scale=scale,
-                                                        bias=bias)
-        else:
-            loss, saved = _native.score_neg_negsamp_fwd(q, embs, target, neg, iq=query, filt_ptr=ptr, filt_idx=idx, scale=scale,
-                                                        margin=margin, adversarial_temperature=alpha, bias=bias)
-        perm = off = None
-        if ctx.needs_input_grad[0] or (bias is not None and ctx.needs_input_grad[11]):
-            N = embs.size(0)
-            keys = torch.cat([torch.where(neg < 0, target.unsqueeze(1), neg), target.unsqueeze(1)], 1).reshape(-1).clamp_(0, N - 1)
-            perm, off = _native.group_edges(keys, N)
-        ctx.save_for_backward(embs, rows, query, target, ptr, idx, neg, saved, bias, perm, off)
-        ctx.mode, ctx.scale, ctx.margin, ctx.alpha = mode, scale, margin, alpha
-        return loss
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        embs, rows, query, target, ptr, idx, neg, saved, bias, perm, off = ctx.saved_tensors
-        q = embs if rows is None else rows
-        dq, coef = _native.score_neg_bwd(ctx.mode, q, embs, target, neg, saved, g.contiguous().float(), iq=query, filt_ptr=ptr,
-                                         filt_idx=idx, scale=ctx.scale, margin=ctx.margin, adversarial_temperature=ctx.alpha,
-                                         bias=bias)
-        K1 = neg.size(1) + 1
-        w = coef.reshape(-1)
-        d_embs = d_rows = d_bias = None
-        if ctx.needs_input_grad[0]:
-            owner = torch.div(perm, K1, rounding_mode="floor")                 # the query of every grouped entry
-            if query is not None:
-                owner = query.index_select(0, owner)
-            d_embs = _native.segment_axpy(w, perm, q, owner.clamp_(0, q.size(0) - 1), off)
-            if rows is None:
-                d_embs = _native.add3(d_embs, _fold_rows(dq, query, embs.size(0)), out=d_embs)
-        if rows is not None and ctx.needs_input_grad[1]:
-            d_rows = dq
-        if bias is not None and ctx.needs_input_grad[11]:
-            one = torch.ones(1, 1, dtype=torch.float32, device=embs.device)
-            d_bias = _native.segment_axpy(w, perm, one, torch.zeros_like(perm), off).reshape(-1).mul_(1.0 / ctx.scale)
-        return (d_embs, d_rows) + (None,) * 9 + (d_bias,)
-
-
-class DistanceLossFn(torch.autograd.Function):
-    """NegativesLossFn under a distance score, s = -D(q_i, embs[v]) with `metric` _native.DIST_L1 / DIST_L2 / DIST_COMPLEX
-    (``distance=`` of HyperGNN.softmax_loss / negative_sampling_loss; include/ghf_distance.h).  Saved is the forward's lse / lw
-    and the grouping of the B (K + 1) node ids by node (ghf_group_edges, stable; padding stands under its query's target with
-    coefficient 0), made in the forward.  The backward (ghf_dist_bwd) returns dq per query and coef [B, K + 1]; the gradient
-    of a candidate row under a distance is no multiple of the query's row, so d embs is ghf_dist_rows_grad over coef — per
-    node, its entries in order — plus dq folded through `query` when the queries are embs' own rows.  Reproducible; rows that
-    are no one's negative, target or query get exactly zero; nothing of size [N, d] is made when embs needs no gradient."""
-
-    @staticmethod
-    def forward(ctx, embs, rows, query, target, ptr, idx, neg, metric: int, mode: int, scale: float, margin: float, alpha: float):
-        assert (rows is None) != (query is None)
-        embs = embs.contiguous().float()
-        rows = None if rows is None else rows.contiguous().float()
-        q = embs if rows is None else rows
-        if mode == _native.NEG_SOFTMAX:
-            loss, saved = _native.score_dist_softmax_fwd(metric, q, embs, target, neg, iq=query, filt_ptr=ptr, filt_idx=idx,
-                                                         scale=scale)
-        else:
-            loss, saved = _native.score_dist_negsamp_fwd(metric, q, embs, target, neg, iq=query, filt_ptr=ptr, filt_idx=idx,
-                                                         scale=scale, margin=margin, adversarial_temperature=alpha)
-        perm = off = None
-        if ctx.needs_input_grad[0]:
-            N = embs.size(0)
-            keys = torch.cat([torch.where(neg < 0, target.unsqueeze(1), neg), target.unsqueeze(1)], 1).reshape(-1).clamp_(0, N - 1)
-            perm, off = _native.group_edges(keys, N)
-        ctx.save_for_backward(embs, rows, query, target, ptr, idx, neg, saved, perm, off)
-        ctx.metric, ctx.mode, ctx.scale, ctx.margin, ctx.alpha = metric, mode, scale, margin, alpha
-        return loss
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        embs, rows, query, target, ptr, idx, neg, saved, perm, off = ctx.saved_tensors
-        q = embs if rows is None else rows
-        dq, coef = _native.score_dist_bwd(ctx.metric, ctx.mode, q, embs, target, neg, saved, g.contiguous().float(), iq=query,
-                                          filt_ptr=ptr, filt_idx=idx, scale=ctx.scale, margin=ctx.margin,
-                                          adversarial_temperature=ctx.alpha)
-        d_embs = d_rows = None
-        if ctx.needs_input_grad[0]:
-            d_embs = _native.dist_rows_grad(ctx.metric, q, embs, coef, perm, off, iq=query)
-            if rows is None:
-                d_embs = _native.add3(d_embs, _fold_rows(dq, query, embs.size(0)), out=d_embs)
-        if rows is not None and ctx.needs_input_grad[1]:
-            d_rows = dq
-        return (d_embs, d_rows) + (None,) * 10
-
-
-class PairwiseLossFn(torch.autograd.Function):
-    """The pairwise hinge (kind = _native.PAIR_HINGE) or logistic (PAIR_LOGISTIC) loss of every query's target against ITS OWN
-    negatives `neg` [B, K] (HyperGNN.pairwise_loss; include/ghf_pairwise.h), under the dot product (metric = _native.PAIR_DOT,
-    with an optional `bias`) or a distance (DIST_L1 / DIST_L2 / DIST_COMPLEX); q_i and the pair `rows` / `query` as in
-    SoftmaxLossFn.  Returns (loss, active); active — the violated pairs — carries no gradient.  Saved is the forward's count
-    and the grouping of the B (K + 1) node ids by node, made in the forward.  The backward (ghf_pair_bwd) returns dq per query
-    and coef [B, K + 1], the target's coefficient minus the sum of its row's; from there on the gradients are
-    NegativesLossFn's (dot: ghf_segment_axpy over coef, d bias the same sum over a column of ones, over scale) or
-    DistanceLossFn's (ghf_dist_rows_grad over coef), step for step."""
-
-    @staticmethod
-    def forward(ctx, embs, rows, query, target, ptr, idx, neg, metric: int, kind: int, scale: float, margin: float,
+    def forward(ctx, embs, rows, query, target, ptr, idx, neg, metric: int, loss: str, scale: float, margin: float, alpha: float,
                 normalize: bool, bias=None):
         assert (rows is None) != (query is None)
         embs = embs.contiguous().float()
         rows = None if rows is None else rows.contiguous().float()
         bias = None if bias is None else bias.contiguous()
         q = embs if rows is None else rows
-        loss, count, active = _native.score_pair_fwd(metric, kind, q, embs, target, neg, iq=query, filt_ptr=ptr, filt_idx=idx,
-                                                     scale=scale, margin=margin, normalize=normalize, bias=bias)
+        out, saved, active = per_query_forward(loss, metric, q, embs, target, neg, query, ptr, idx, scale, margin, alpha, normalize, bias)
         perm = off = None
-        if ctx.needs_input_grad[0] or (bias is not None and ctx.needs_input_grad[12]):
+        if ctx.needs_input_grad[0] or (bias is not None and ctx.needs_input_grad[13]):
             N = embs.size(0)
             keys = torch.cat([torch.where(neg < 0, target.unsqueeze(1), neg), target.unsqueeze(1)], 1).reshape(-1).clamp_(0, N - 1)
             perm, off = _native.group_edges(keys, N)
-        ctx.save_for_backward(embs, rows, query, target, ptr, idx, neg, count, bias, perm, off)
-        ctx.metric, ctx.kind, ctx.scale, ctx.margin, ctx.normalize = metric, kind, scale, margin, normalize
+        ctx.save_for_backward(embs, rows, query, target, ptr, idx, neg, saved, bias, perm, off)
+        ctx.metric, ctx.loss, ctx.scale, ctx.margin, ctx.alpha, ctx.normalize = metric, loss, scale, margin, alpha, normalize
+        if active is None:
+            return out
         ctx.mark_non_differentiable(active)
-        return loss, active
+        return out, active
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, g, _g_active):
-        embs, rows, query, target, ptr, idx, neg, count, bias, perm, off = ctx.saved_tensors
+    def backward(ctx, g, _g_active=None):
+        embs, rows, query, target, ptr, idx, neg, saved, bias, perm, off = ctx.saved_tensors
         q = embs if rows is None else rows
-        dq, coef = _native.score_pair_bwd(ctx.metric, ctx.kind, q, embs, target, neg, count, g.contiguous().float(), iq=query,
-                                          filt_ptr=ptr, filt_idx=idx, scale=ctx.scale, margin=ctx.margin, normalize=ctx.normalize,
-                                          bias=bias)
+        g = g.contiguous().float()
+        kw = dict(iq=query, filt_ptr=ptr, filt_idx=idx, scale=ctx.scale, margin=ctx.margin)
+        dot = ctx.metric == _native.PAIR_DOT
+        if ctx.loss in _native.PAIR_KINDS:
+            dq, coef = _native.score_pair_bwd(ctx.metric, _native.PAIR_KINDS[ctx.loss], q, embs, target, neg, saved, g, normalize=ctx.normalize, bias=bias, **kw)
+        else:
+            mode = _native.NEG_SOFTMAX if ctx.loss == "softmax" else _native.NEG_NEGSAMP
+            kw.update(adversarial_temperature=ctx.alpha)
+            dq, coef = (_native.score_neg_bwd(mode, q, embs, target, neg, saved, g, bias=bias, **kw) if dot else
+                        _native.score_dist_bwd(ctx.metric, mode, q, embs, target, neg, saved, g, **kw))
+        w = coef.reshape(-1)
         d_embs = d_rows = d_bias = None
         if ctx.needs_input_grad[0]:
-            if ctx.metric == _native.PAIR_DOT:
+            if dot:
                 owner = torch.div(perm, neg.size(1) + 1, rounding_mode="floor")    # the query of every grouped entry
                 if query is not None:
                     owner = query.index_select(0, owner)
-                d_embs = _native.segment_axpy(coef.reshape(-1), perm, q, owner.clamp_(0, q.size(0) - 1), off)
+                d_embs = _native.segment_axpy(w, perm, q, owner.clamp_(0, q.size(0) - 1), off)
             else:
                 d_embs = _native.dist_rows_grad(ctx.metric, q, embs, coef, perm, off, iq=query)
             if rows is None:
                 d_embs = _native.add3(d_embs, _fold_rows(dq, query, embs.size(0)), out=d_embs)
         if rows is not None and ctx.needs_input_grad[1]:
             d_rows = dq
-        if bias is not None and ctx.needs_input_grad[12]:
+        if bias is not None and ctx.needs_input_grad[13]:
             one = torch.ones(1, 1, dtype=torch.float32, device=embs.device)
-            d_bias = _native.segment_axpy(coef.reshape(-1), perm, one, torch.zeros_like(perm), off).reshape(-1).mul_(1.0 / ctx.scale)
-        return (d_embs, d_rows) + (None,) * 10 + (d_bias,)
+            d_bias = _native.segment_axpy(w, perm, one, torch.zeros_like(perm), off).reshape(-1).mul_(1.0 / ctx.scale)
+        return (d_embs, d_rows) + (None,) * 11 + (d_bias,)
 
 
 class DistanceSweepLossFn(torch.autograd.Function):

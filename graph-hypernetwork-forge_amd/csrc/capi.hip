@@ -958,163 +958,163 @@ int ghf_score_negsamp_bwd(const float* q, const float* c, const int64_t* iq, con
 
 #undef GHF_NEGSAMP_CHECK
 
-// per-query negative sets (include/ghf_negatives.h; csrc/negatives.hip): score_entry_check, then the set itself
-#define GHF_NEG_CHECK(op) GHF_REQUIRE(neg && K > 0, op ": need neg [B, K] with K >= 1")
+// ---- the per-query family: negatives= [B, K] (the fold: §23) -----------------------------------------
+// include/ghf_negatives.h (dot product), ghf_distance.h (a distance) and ghf_pairwise.h (the pairwise losses) share one entry
+// helper.  Each extern "C" function below is its null-pointer expression, the translation of its public mode or kind into
+// the kernels' epilogue (negatives.h: nothing past this file takes a public mode) and one call.
+enum PqFamily { PQ_NEG, PQ_DIST, PQ_PAIR };
+
+// the metric of a distance call; with `dot`, GHF_PAIR_DOT as well
+static int pq_metric_check(const char* op, int metric, int d, bool dot) {
+    if (dot)
+        GHF_REQUIRE(metric == GHF_PAIR_DOT || metric == GHF_DIST_L1 || metric == GHF_DIST_L2 || metric == GHF_DIST_COMPLEX,
+                    "%s: metric must be GHF_PAIR_DOT, GHF_DIST_L1, GHF_DIST_L2 or GHF_DIST_COMPLEX", op);
+    else
+        GHF_REQUIRE(metric == GHF_DIST_L1 || metric == GHF_DIST_L2 || metric == GHF_DIST_COMPLEX,
+                    "%s: metric must be GHF_DIST_L1, GHF_DIST_L2 or GHF_DIST_COMPLEX", op);
+    GHF_REQUIRE(metric != GHF_DIST_COMPLEX || (d & 1) == 0, "%s: GHF_DIST_COMPLEX needs an even d (re / im interleaved)", op);
+    return GHF_OK;
+}
+
+// what every call of the family hands over but its outputs
+static NegArgs pq_args(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                       const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float margin,
+                       float alpha, const int64_t* neg, int64_t K, const float* bias) {
+    NegArgs a{};
+    a.q = q; a.c = c; a.iq = iq; a.target = target; a.filt_ptr = filt_ptr; a.filt_idx = filt_idx; a.nnz = nnz;
+    a.neg = neg; a.K = K; a.rows_q = rows_q; a.N = N; a.B = B; a.d = d; a.bias = bias;
+    a.scale = scale; a.margin = margin; a.alpha = alpha;
+    return a;
+}
+
+// The refusals, in each header's order.  ghf_neg_* : score_entry_check, the mode (a backward), margin and adv_temperature (the
+// negative-sampling loss), the set.  ghf_dist_*: the metric first — an unknown one is refused whatever else the call holds —
+// then the same.  ghf_pair_*: the two selectors, the three scalars, the bias, and only then what the others check.
+// `sel_err`: the message for a mode or kind outside its set, NULL for one inside; `ptrs`: every pointer the call needs is there.
+static int pq_entry(PqFamily fam, const char* op, int metric, PqEpi e, bool bwd, const char* sel_err, bool ptrs, NegArgs a,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    const bool margin_ok = a.margin >= -3.402823466e38f && a.margin <= 3.402823466e38f;
+    if (fam != PQ_NEG) {
+        const int rc = pq_metric_check(op, metric, a.d, fam == PQ_PAIR);
+        if (rc != GHF_OK) return rc;
+    }
+    if (fam == PQ_PAIR) {
+        GHF_REQUIRE(!sel_err, "%s", sel_err);
+        GHF_REQUIRE(a.scale > 0.f && a.scale <= 3.402823466e38f, "%s: scale must be finite and positive", op);
+        GHF_REQUIRE(margin_ok, "%s: margin must be finite", op);
+        GHF_REQUIRE(a.normalize == 0 || a.normalize == 1, "%s: normalize must be 0 or 1", op);
+        GHF_REQUIRE(metric == GHF_PAIR_DOT || !a.bias, "%s: no per-candidate bias under a distance", op);
+    }
+    const int rc = score_entry_check(op, "filter", ptrs, a.filt_ptr, a.filt_idx, a.nnz, a.scale, 0.f, workspace);
+    if (rc != GHF_OK) return rc;
+    if (fam != PQ_PAIR) {
+        GHF_REQUIRE(!sel_err, "%s", sel_err);
+        if (e == PqEpi::Negsamp) {
+            GHF_REQUIRE(margin_ok, "%s: margin must be finite", op);
+            GHF_REQUIRE(a.alpha >= 0.f && a.alpha <= 3.402823466e38f, "%s: adv_temperature must be finite and not negative", op);
+        }
+    }
+    GHF_REQUIRE(a.neg && a.K > 0, "%s: need neg [B, K] with K >= 1", op);
+    if (a.nnz <= 0) a.filt_ptr = nullptr;                // the kernels read `no lists` from the pointer
+    switch (fam) {
+        case PQ_NEG: return launch_neg(e, bwd, op, a, workspace_bytes, (hipStream_t)stream);
+        case PQ_DIST: return launch_dist(metric, e, bwd, op, a, workspace_bytes, (hipStream_t)stream);
+        default: return launch_pair(metric, e, bwd, op, a, workspace_bytes, (hipStream_t)stream);
+    }
+}
 
 size_t ghf_neg_workspace_bytes(int64_t B, int64_t K, int d, int64_t nnz) { return neg_workspace_bytes(B, K, d, nnz); }
 
 int ghf_neg_rank(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                  const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, const int64_t* neg, int64_t K,
                  const float* bias, void* workspace, size_t workspace_bytes, int64_t* greater, int64_t* equal, void* stream) {
-    const int rc = score_entry_check("neg_rank", "filter", q && c && target && greater && equal, filt_ptr, filt_idx, nnz, 1.f, 0.f,
-                                     workspace);
-    if (rc != GHF_OK) return rc;
-    GHF_NEG_CHECK("neg_rank");
-    return launch_neg_rank(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, neg, K, bias, workspace, workspace_bytes,
-                           greater, equal, (hipStream_t)stream);
+    NegArgs a = pq_args(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, 1.f, 0.f, 0.f, neg, K, bias);
+    a.greater = (long long*)greater; a.equal = (long long*)equal;
+    return pq_entry(PQ_NEG, "neg_rank", 0, PqEpi::Rank, false, nullptr, q && c && target && greater && equal, a, workspace,
+                    workspace_bytes, stream);
 }
 
 int ghf_neg_softmax_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                         const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                         const int64_t* neg, int64_t K, const float* bias, void* workspace, size_t workspace_bytes, float* loss,
                         float* lse, void* stream) {
-    const int rc = score_entry_check("neg_softmax_fwd", "filter", q && c && target && loss && lse, filt_ptr, filt_idx, nnz, scale, 0.f,
-                                     workspace);
-    if (rc != GHF_OK) return rc;
-    GHF_NEG_CHECK("neg_softmax_fwd");
-    return launch_neg_loss_fwd(GHF_NEG_SOFTMAX, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, 0.f, 0.f, neg, K,
-                               bias, workspace, workspace_bytes, loss, lse, (hipStream_t)stream);
+    NegArgs a = pq_args(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, 0.f, 0.f, neg, K, bias);
+    a.loss = loss; a.aux = lse;
+    return pq_entry(PQ_NEG, "neg_softmax_fwd", 0, pq_of_neg_mode(GHF_NEG_SOFTMAX), false, nullptr, q && c && target && loss && lse, a,
+                    workspace, workspace_bytes, stream);
 }
-
-#define GHF_NEG_FLOATS(op)                                                                                          \
-    do {                                                                                                            \
-        GHF_REQUIRE(margin >= -3.402823466e38f && margin <= 3.402823466e38f, op ": margin must be finite");         \
-        GHF_REQUIRE(adv_temperature >= 0.f && adv_temperature <= 3.402823466e38f,                                    \
-                    op ": adv_temperature must be finite and not negative");                                        \
-    } while (0)
 
 int ghf_neg_negsamp_fwd(const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                         const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                         float margin, float adv_temperature, const int64_t* neg, int64_t K, const float* bias, void* workspace,
                         size_t workspace_bytes, float* loss, float* lw, void* stream) {
-    const int rc = score_entry_check("neg_negsamp_fwd", "filter", q && c && target && loss && lw, filt_ptr, filt_idx, nnz, scale, 0.f,
-                                     workspace);
-    if (rc != GHF_OK) return rc;
-    GHF_NEG_FLOATS("neg_negsamp_fwd");
-    GHF_NEG_CHECK("neg_negsamp_fwd");
-    return launch_neg_loss_fwd(GHF_NEG_NEGSAMP, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin,
-                               adv_temperature, neg, K, bias, workspace, workspace_bytes, loss, lw, (hipStream_t)stream);
+    NegArgs a = pq_args(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, adv_temperature, neg, K, bias);
+    a.loss = loss; a.aux = lw;
+    return pq_entry(PQ_NEG, "neg_negsamp_fwd", 0, pq_of_neg_mode(GHF_NEG_NEGSAMP), false, nullptr, q && c && target && loss && lw, a,
+                    workspace, workspace_bytes, stream);
 }
 
 int ghf_neg_bwd(int mode, const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                 const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float margin,
                 float adv_temperature, const int64_t* neg, int64_t K, const float* bias, const float* lse_or_lw,
                 const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* coef, void* stream) {
-    const int rc = score_entry_check("neg_bwd", "filter", q && c && target && lse_or_lw && grad_loss && dq && coef, filt_ptr, filt_idx,
-                                     nnz, scale, 0.f, workspace);
-    if (rc != GHF_OK) return rc;
-    GHF_REQUIRE(mode == GHF_NEG_SOFTMAX || mode == GHF_NEG_NEGSAMP, "neg_bwd: mode must be GHF_NEG_SOFTMAX or GHF_NEG_NEGSAMP");
-    if (mode == GHF_NEG_NEGSAMP) GHF_NEG_FLOATS("neg_bwd");
-    GHF_NEG_CHECK("neg_bwd");
-    return launch_neg_bwd(mode, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, adv_temperature, neg, K,
-                          bias, lse_or_lw, grad_loss, workspace, workspace_bytes, dq, coef, (hipStream_t)stream);
+    NegArgs a = pq_args(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, adv_temperature, neg, K, bias);
+    a.saved = lse_or_lw; a.grad = grad_loss; a.dq = dq; a.coef = coef;
+    const bool known = mode == GHF_NEG_SOFTMAX || mode == GHF_NEG_NEGSAMP;
+    return pq_entry(PQ_NEG, "neg_bwd", 0, pq_of_neg_mode(mode), true,
+                    known ? nullptr : "neg_bwd: mode must be GHF_NEG_SOFTMAX or GHF_NEG_NEGSAMP",
+                    q && c && target && lse_or_lw && grad_loss && dq && coef, a, workspace, workspace_bytes, stream);
 }
-
-// distance scores for per-query negative sets (include/ghf_distance.h; csrc/distance.hip): the metric first —
-// an unknown one is refused whatever else the call holds — then the checks of the ghf_neg_* calls
-#define GHF_DIST_METRIC(op, dd)                                                                                              \
-    do {                                                                                                                     \
-        GHF_REQUIRE(metric == GHF_DIST_L1 || metric == GHF_DIST_L2 || metric == GHF_DIST_COMPLEX,                            \
-                    op ": metric must be GHF_DIST_L1, GHF_DIST_L2 or GHF_DIST_COMPLEX");                                     \
-        GHF_REQUIRE(metric != GHF_DIST_COMPLEX || ((dd) & 1) == 0, op ": GHF_DIST_COMPLEX needs an even d (re / im interleaved)"); \
-    } while (0)
 
 size_t ghf_dist_workspace_bytes(int64_t B, int64_t K, int d, int64_t nnz) { return dist_workspace_bytes(B, K, d, nnz); }
 
 int ghf_dist_rank(int metric, const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
                   const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, const int64_t* neg, int64_t K,
                   void* workspace, size_t workspace_bytes, int64_t* greater, int64_t* equal, void* stream) {
-    GHF_DIST_METRIC("dist_rank", d);
-    const int rc = score_entry_check("dist_rank", "filter", q && c && target && greater && equal, filt_ptr, filt_idx, nnz, 1.f, 0.f,
-                                     workspace);
-    if (rc != GHF_OK) return rc;
-    GHF_NEG_CHECK("dist_rank");
-    return launch_dist_rank(metric, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, neg, K, workspace, workspace_bytes,
-                            greater, equal, (hipStream_t)stream);
+    NegArgs a = pq_args(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, 1.f, 0.f, 0.f, neg, K, nullptr);
+    a.greater = (long long*)greater; a.equal = (long long*)equal;
+    return pq_entry(PQ_DIST, "dist_rank", metric, PqEpi::Rank, false, nullptr, q && c && target && greater && equal, a, workspace,
+                    workspace_bytes, stream);
 }
 
 int ghf_dist_softmax_fwd(int metric, const float* q, const float* c, const int64_t* iq, const int64_t* target,
                          const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
                          float scale, const int64_t* neg, int64_t K, void* workspace, size_t workspace_bytes, float* loss,
                          float* lse, void* stream) {
-    GHF_DIST_METRIC("dist_softmax_fwd", d);
-    const int rc = score_entry_check("dist_softmax_fwd", "filter", q && c && target && loss && lse, filt_ptr, filt_idx, nnz, scale, 0.f,
-                                     workspace);
-    if (rc != GHF_OK) return rc;
-    GHF_NEG_CHECK("dist_softmax_fwd");
-    return launch_dist_loss_fwd(metric, GHF_DIST_SOFTMAX, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, 0.f, 0.f,
-                                neg, K, workspace, workspace_bytes, loss, lse, (hipStream_t)stream);
+    NegArgs a = pq_args(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, 0.f, 0.f, neg, K, nullptr);
+    a.loss = loss; a.aux = lse;
+    return pq_entry(PQ_DIST, "dist_softmax_fwd", metric, pq_of_dist_mode(GHF_DIST_SOFTMAX), false, nullptr,
+                    q && c && target && loss && lse, a, workspace, workspace_bytes, stream);
 }
 
 int ghf_dist_negsamp_fwd(int metric, const float* q, const float* c, const int64_t* iq, const int64_t* target,
                          const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
                          float scale, float margin, float adv_temperature, const int64_t* neg, int64_t K, void* workspace,
                          size_t workspace_bytes, float* loss, float* lw, void* stream) {
-    GHF_DIST_METRIC("dist_negsamp_fwd", d);
-    const int rc = score_entry_check("dist_negsamp_fwd", "filter", q && c && target && loss && lw, filt_ptr, filt_idx, nnz, scale, 0.f,
-                                     workspace);
-    if (rc != GHF_OK) return rc;
-    GHF_NEG_FLOATS("dist_negsamp_fwd");
-    GHF_NEG_CHECK("dist_negsamp_fwd");
-    return launch_dist_loss_fwd(metric, GHF_DIST_NEGSAMP, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin,
-                                adv_temperature, neg, K, workspace, workspace_bytes, loss, lw, (hipStream_t)stream);
+    NegArgs a = pq_args(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, adv_temperature, neg, K, nullptr);
+    a.loss = loss; a.aux = lw;
+    return pq_entry(PQ_DIST, "dist_negsamp_fwd", metric, pq_of_dist_mode(GHF_DIST_NEGSAMP), false, nullptr,
+                    q && c && target && loss && lw, a, workspace, workspace_bytes, stream);
 }
 
 int ghf_dist_bwd(int metric, int mode, const float* q, const float* c, const int64_t* iq, const int64_t* target,
                  const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
                  float scale, float margin, float adv_temperature, const int64_t* neg, int64_t K, const float* lse_or_lw,
                  const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* coef, void* stream) {
-    GHF_DIST_METRIC("dist_bwd", d);
-    const int rc = score_entry_check("dist_bwd", "filter", q && c && target && lse_or_lw && grad_loss && dq && coef, filt_ptr, filt_idx,
-                                     nnz, scale, 0.f, workspace);
-    if (rc != GHF_OK) return rc;
-    GHF_REQUIRE(mode == GHF_DIST_SOFTMAX || mode == GHF_DIST_NEGSAMP, "dist_bwd: mode must be GHF_DIST_SOFTMAX or GHF_DIST_NEGSAMP");
-    if (mode == GHF_DIST_NEGSAMP) GHF_NEG_FLOATS("dist_bwd");
-    GHF_NEG_CHECK("dist_bwd");
-    return launch_dist_bwd(metric, mode, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, adv_temperature,
-                           neg, K, lse_or_lw, grad_loss, workspace, workspace_bytes, dq, coef, (hipStream_t)stream);
+    NegArgs a = pq_args(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, adv_temperature, neg, K, nullptr);
+    a.saved = lse_or_lw; a.grad = grad_loss; a.dq = dq; a.coef = coef;
+    const bool known = mode == GHF_DIST_SOFTMAX || mode == GHF_DIST_NEGSAMP;
+    return pq_entry(PQ_DIST, "dist_bwd", metric, pq_of_dist_mode(mode), true,
+                    known ? nullptr : "dist_bwd: mode must be GHF_DIST_SOFTMAX or GHF_DIST_NEGSAMP",
+                    q && c && target && lse_or_lw && grad_loss && dq && coef, a, workspace, workspace_bytes, stream);
 }
 
 int ghf_dist_rows_grad(int metric, const float* q, const float* c, const int64_t* iq, int64_t rows_q, int64_t N, int64_t B, int d,
                        int64_t K, const float* coef, const int64_t* perm, const int64_t* off, float* dc, void* stream) {
-    GHF_DIST_METRIC("dist_rows_grad", d);
+    const int rc = pq_metric_check("dist_rows_grad", metric, d, false);
+    if (rc != GHF_OK) return rc;
     GHF_REQUIRE(q && c && coef && perm && off && dc, "dist_rows_grad: null pointer argument");
     return launch_dist_rows_grad(metric, q, c, iq, rows_q, N, B, d, K, coef, perm, off, dc, (hipStream_t)stream);
-}
-
-#undef GHF_DIST_METRIC
-#undef GHF_NEG_FLOATS
-#undef GHF_NEG_CHECK
-
-// pairwise ranking losses on per-query negative sets (include/ghf_pairwise.h; csrc/pairwise.hip).  The
-// refusals stand in the header's order: the two selectors, the three scalars, the bias, and only then what the ghf_neg_* calls
-// check.  `kind` and `metric` are public values; launch_pair_* turns each into a template parameter once.
-static int pair_entry_check(const char* op, int metric, int kind, int d, float scale, float margin, int normalize,
-                            const float* bias, bool ptrs, const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz,
-                            const void* workspace, const int64_t* neg, int64_t K) {
-    GHF_REQUIRE(metric == GHF_PAIR_DOT || metric == GHF_DIST_L1 || metric == GHF_DIST_L2 || metric == GHF_DIST_COMPLEX,
-                "%s: metric must be GHF_PAIR_DOT, GHF_DIST_L1, GHF_DIST_L2 or GHF_DIST_COMPLEX", op);
-    GHF_REQUIRE(metric != GHF_DIST_COMPLEX || (d & 1) == 0, "%s: GHF_DIST_COMPLEX needs an even d (re / im interleaved)", op);
-    GHF_REQUIRE(kind == GHF_PAIR_HINGE || kind == GHF_PAIR_LOGISTIC, "%s: kind must be GHF_PAIR_HINGE or GHF_PAIR_LOGISTIC", op);
-    GHF_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, "%s: scale must be finite and positive", op);
-    GHF_REQUIRE(margin >= -3.402823466e38f && margin <= 3.402823466e38f, "%s: margin must be finite", op);
-    GHF_REQUIRE(normalize == 0 || normalize == 1, "%s: normalize must be 0 or 1", op);
-    GHF_REQUIRE(metric == GHF_PAIR_DOT || !bias, "%s: no per-candidate bias under a distance", op);
-    GHF_REQUIRE(ptrs && workspace, "%s: null pointer argument", op);
-    GHF_REQUIRE(nnz <= 0 || (filt_ptr && filt_idx), "%s: null filter list with nnz > 0", op);
-    GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: workspace not 256-byte aligned", op);
-    GHF_REQUIRE(neg && K > 0, "%s: need neg [B, K] with K >= 1", op);
-    return GHF_OK;
 }
 
 size_t ghf_pair_workspace_bytes(int64_t B, int64_t K, int d, int64_t nnz) { return pair_workspace_bytes(B, K, d, nnz); }
@@ -1123,22 +1123,24 @@ int ghf_pair_fwd(int metric, int kind, const float* q, const float* c, const int
                  const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
                  float scale, float margin, int normalize, const int64_t* neg, int64_t K, const float* bias, void* workspace,
                  size_t workspace_bytes, float* loss, int32_t* count, int32_t* active, void* stream) {
-    const int rc = pair_entry_check("pair_fwd", metric, kind, d, scale, margin, normalize, bias, q && c && target && loss && count && active,
-                                    filt_ptr, filt_idx, nnz, workspace, neg, K);
-    if (rc != GHF_OK) return rc;
-    return launch_pair_fwd(metric, kind, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, normalize, neg, K,
-                           bias, workspace, workspace_bytes, loss, count, active, (hipStream_t)stream);
+    NegArgs a = pq_args(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, 0.f, neg, K, bias);
+    a.loss = loss; a.count = count; a.active = active; a.normalize = normalize;
+    const bool known = kind == GHF_PAIR_HINGE || kind == GHF_PAIR_LOGISTIC;
+    return pq_entry(PQ_PAIR, "pair_fwd", metric, pq_of_pair_kind(kind), false,
+                    known ? nullptr : "pair_fwd: kind must be GHF_PAIR_HINGE or GHF_PAIR_LOGISTIC",
+                    q && c && target && loss && count && active, a, workspace, workspace_bytes, stream);
 }
 
 int ghf_pair_bwd(int metric, int kind, const float* q, const float* c, const int64_t* iq, const int64_t* target,
                  const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
                  float scale, float margin, int normalize, const int64_t* neg, int64_t K, const float* bias, const int32_t* count,
                  const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* coef, void* stream) {
-    const int rc = pair_entry_check("pair_bwd", metric, kind, d, scale, margin, normalize, bias,
-                                    q && c && target && count && grad_loss && dq && coef, filt_ptr, filt_idx, nnz, workspace, neg, K);
-    if (rc != GHF_OK) return rc;
-    return launch_pair_bwd(metric, kind, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, normalize, neg, K,
-                           bias, count, grad_loss, workspace, workspace_bytes, dq, coef, (hipStream_t)stream);
+    NegArgs a = pq_args(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin, 0.f, neg, K, bias);
+    a.saved_n = count; a.grad = grad_loss; a.dq = dq; a.coef = coef; a.normalize = normalize;
+    const bool known = kind == GHF_PAIR_HINGE || kind == GHF_PAIR_LOGISTIC;
+    return pq_entry(PQ_PAIR, "pair_bwd", metric, pq_of_pair_kind(kind), true,
+                    known ? nullptr : "pair_bwd: kind must be GHF_PAIR_HINGE or GHF_PAIR_LOGISTIC",
+                    q && c && target && count && grad_loss && dq && coef, a, workspace, workspace_bytes, stream);
 }
 
 size_t ghf_relation_rows_workspace_bytes(int64_t B, int R) { return relation_rows_workspace_bytes(B, R); }

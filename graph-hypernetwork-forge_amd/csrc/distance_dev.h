@@ -1,6 +1,6 @@
 // distance_dev.h — the distance chain that distance.hip and pairwise.hip (§26) share: D(x, y) of a group's
-// row pair with what its gradient needs (dist_eval), the score -D (dist_score) and g = dD / dx (dist_grad), under
-// GHF_DIST_L1 / L2 / COMPLEX.  Moved here from distance.hip unchanged; the geometry is negatives_dev.h's.
+// row pair with what its gradient needs (dist_eval), g = dD / dx (dist_grad) and, over the two, the score policy DistScore<M>
+// of the per-query kernel, under GHF_DIST_L1 / L2 / COMPLEX.  The geometry and the kernel are negatives_dev.h's.
 #pragma once
 #include "common.h"
 #include "negatives_dev.h"
@@ -38,12 +38,6 @@ __device__ __forceinline__ float dist_eval(const f32x4 x, const f32x4 y, int gl,
     }
 }
 
-template <int M, int L, bool VEC>
-__device__ __forceinline__ float dist_score(const f32x4 x, const f32x4 y, int gl) {
-    f32x4 dl, rho;
-    return -dist_eval<M, L, VEC>(x, y, gl, dl, rho);
-}
-
 // g = dD / dx of the lane's four floats, from what dist_eval left
 template <int M>
 __device__ __forceinline__ f32x4 dist_grad(const f32x4 dl, const f32x4 rho, float D) {
@@ -62,5 +56,17 @@ __device__ __forceinline__ f32x4 dist_grad(const f32x4 dl, const f32x4 rho, floa
     }
     return g;
 }
+
+// the score policy of pq_kernel (negatives_dev.h): s = -D, and ds / dx = -g with the sign left to the kernel
+template <int M>
+struct DistScore {
+    static constexpr bool NEG = true, BIAS = false;
+    struct Saved { f32x4 dl, rho; };
+    template <int L, bool VEC>
+    static __device__ __forceinline__ float eval(const f32x4 x, const f32x4 y, int gl, Saved& k) {
+        return -dist_eval<M, L, VEC>(x, y, gl, k.dl, k.rho);
+    }
+    static __device__ __forceinline__ f32x4 grad(const Saved& k, const f32x4, float s) { return dist_grad<M>(k.dl, k.rho, -s); }
+};
 
 }  // namespace ghf

@@ -1220,14 +1220,14 @@ class HyperGNN(nn.Module):
         with a set PER QUERY, ``F.cross_entropy`` over ``[z_target | z_negatives]``: ``loss[i] = log(exp(z_it) + sum_j
         exp(z_ij)) - z_it`` over the positions ``j`` of row ``i`` that hold neither ``-1``, the target nor a known partner.  The
         target enters exactly once and always; a query without negatives has loss exactly 0.  Nothing is added to the sets.
-        One wave per query gathers its rows (``ghf_neg_softmax_fwd`` / ``ghf_neg_bwd``, ``autograd.NegativesLossFn``); the
+        One wave per query gathers its rows (``ghf_neg_softmax_fwd`` / ``ghf_neg_bwd``, ``autograd.PerQueryLossFn``); the
         gradient of ``embs`` sums, per node, over every position that names it — a repeated id gets a term per occurrence —
         and rows that are no one's negative, target or query get exactly zero.  Bit-reproducible, and a query's loss does
         not depend on the batch it is in.  ``query_rows``, typed ``known`` and ``candidate_bias`` work as above.
 
         ``distance`` (``"l1"``, ``"l2"`` or ``"complex"``, as in ``rank_candidates``; with ``negatives`` only, and not with
         ``candidate_bias``): the logits become ``z = -scale * D(row_i, embs[j])`` (``ghf_dist_softmax_fwd`` / ``ghf_dist_bwd`` /
-        ``ghf_dist_rows_grad``, ``autograd.DistanceLossFn``).  The gradient of ``embs`` and of ``query_rows`` follows the
+        ``ghf_dist_rows_grad``, ``autograd.PerQueryLossFn``).  The gradient of ``embs`` and of ``query_rows`` follows the
         distance: ``sign(delta)`` under ``"l1"``, ``delta / D`` under ``"l2"``, ``delta / |pair|`` under ``"complex"``, each
         exactly 0 where its denominator is 0 (a candidate equal to the query's row).  Still bit-reproducible, no ``[B, K, d]``
         tensor, forward or backward."""
@@ -1253,10 +1253,9 @@ class HyperGNN(nn.Module):
         if not embs.is_cuda:
             raise RuntimeError(f"softmax_loss computes on an MI355X HIP device only (input is on {embs.device})")
         ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
-        if metric is not None:
-            return self._distance_loss(metric, _native.NEG_SOFTMAX, embs, q, t, ptr, idx, neg, scale, 0.0, 0.0, query_rows)
-        if neg is not None:
-            return self._negatives_loss(_native.NEG_SOFTMAX, embs, q, t, ptr, idx, neg, scale, 0.0, 0.0, query_rows, bias)
+        if neg is not None:                              # with distance= there are always negatives (_distance_arg)
+            return self._per_query_loss("softmax", _native.PAIR_DOT if metric is None else metric, embs, q, t, ptr, idx, neg, scale,
+                                        0.0, 0.0, True, query_rows, bias)
         if cand is not None:
             cand = self._softmax_candidates(cand, t)
         if query_rows is not None:
@@ -1306,13 +1305,13 @@ class HyperGNN(nn.Module):
         QUERY, as RotatE's training loop and PyKEEN's default sampler draw them.  ``J_i`` is then the set of positions of row
         ``i`` that hold neither ``-1``, the target nor a known partner, and the formulas above run over it, the weights
         detached; a query whose ``J_i`` is empty has the positive term alone.  Nothing is added to the sets.  One wave per
-        query (``ghf_neg_negsamp_fwd`` / ``ghf_neg_bwd``, ``autograd.NegativesLossFn``); gradients, reproducibility and the
+        query (``ghf_neg_negsamp_fwd`` / ``ghf_neg_bwd``, ``autograd.PerQueryLossFn``); gradients, reproducibility and the
         other keywords as for ``softmax_loss(negatives=)``.
 
         ``distance`` (``"l1"``, ``"l2"`` or ``"complex"``, as in ``softmax_loss``; with ``negatives`` only, and not with
         ``candidate_bias``): ``z = -scale * D(row_i, embs[j])``.  At ``scale=1`` the positive term is ``-log sigmoid(margin -
         D_target)`` and a negative's ``-log sigmoid(D_j - margin)``: the margin is the distance budget gamma of TransE's and
-        RotatE's published losses (``ghf_dist_negsamp_fwd``, ``autograd.DistanceLossFn``)."""
+        RotatE's published losses (``ghf_dist_negsamp_fwd``, ``autograd.PerQueryLossFn``)."""
         if embs.dim() != 2:
             raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
         metric = self._distance_arg(distance, negatives, candidates, candidate_bias, embs)
@@ -1339,10 +1338,9 @@ class HyperGNN(nn.Module):
         if not embs.is_cuda:
             raise RuntimeError(f"negative_sampling_loss computes on an MI355X HIP device only (input is on {embs.device})")
         ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
-        if metric is not None:
-            return self._distance_loss(metric, _native.NEG_NEGSAMP, embs, q, t, ptr, idx, neg, scale, margin, alpha, query_rows)
-        if neg is not None:
-            return self._negatives_loss(_native.NEG_NEGSAMP, embs, q, t, ptr, idx, neg, scale, margin, alpha, query_rows, bias)
+        if neg is not None:                              # with distance= there are always negatives (_distance_arg)
+            return self._per_query_loss("negsamp", _native.PAIR_DOT if metric is None else metric, embs, q, t, ptr, idx, neg, scale,
+                                        margin, alpha, True, query_rows, bias)
         if cand is not None:
             cand = self._softmax_candidates(cand, t)
         if query_rows is not None:
@@ -1384,7 +1382,7 @@ class HyperGNN(nn.Module):
         NOT wrap; a multiset in the given order).  ``return_active=True`` returns ``(loss, active)``, ``active`` int32 ``[B]``
         the number of violated pairs ``u > 0`` — what one logs while training; at ``margin=0`` it is ``rank_candidates``'
         ``greater``.  Neither the ``[B, K]`` scores nor the ``[B, K, d]`` gather exist, forward or backward: one wave per query
-        (``ghf_pair_fwd`` / ``ghf_pair_bwd``, ``include/ghf_pairwise.h``, ``autograd.PairwiseLossFn``).  Gradients reach
+        (``ghf_pair_fwd`` / ``ghf_pair_bwd``, ``include/ghf_pairwise.h``, ``autograd.PerQueryLossFn``).  Gradients reach
         ``embs``, ``query_rows`` and (dot product only) ``candidate_bias``; rows of ``embs`` that are no one's negative, target
         or query get exactly zero; bit-reproducible.  ``scale`` finite and ``> 0``, ``margin`` finite (``ValueError``
         otherwise); ``candidate_bias`` together with ``distance`` is a ``ValueError``."""
@@ -1412,53 +1410,25 @@ class HyperGNN(nn.Module):
         if not embs.is_cuda:
             raise RuntimeError(f"pairwise_loss computes on an MI355X HIP device only (input is on {embs.device})")
         ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
-        grad = embs.requires_grad or (bias is not None and bias.requires_grad) or (query_rows is not None and query_rows.requires_grad)
-        if torch.is_grad_enabled() and grad:
-            from ..autograd import PairwiseLossFn
-            if query_rows is not None:
-                out, active = PairwiseLossFn.apply(embs, query_rows, None, t, ptr, idx, neg, metric, kind, scale, margin, normalize, bias)
-            else:
-                out, active = PairwiseLossFn.apply(embs, None, q, t, ptr, idx, neg, metric, kind, scale, margin, normalize, bias)
-        else:
-            e = embs.detach().float()
-            qm, iq = (e, q) if query_rows is None else (query_rows.detach(), None)
-            out, _, active = _native.score_pair_fwd(metric, kind, qm, e, t, neg, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale,
-                                                    margin=margin, normalize=normalize, bias=bias)
+        out, active = self._per_query_loss(loss, metric, embs, q, t, ptr, idx, neg, scale, margin, 0.0, normalize, query_rows, bias)
         return (out, active) if return_active else out
 
     @staticmethod
-    def _negatives_loss(mode: int, embs, q, t, ptr, idx, neg, scale: float, margin: float, alpha: float, query_rows, bias):
-        """``softmax_loss`` / ``negative_sampling_loss`` with ``negatives=`` once every argument is checked: recorded
-        (``autograd.NegativesLossFn``) under the rules of the calls without the keyword, else the forward alone."""
+    def _per_query_loss(loss: str, metric: int, embs, q, t, ptr, idx, neg, scale: float, margin: float, alpha: float, normalize: bool,
+                        query_rows, bias):
+        """``softmax_loss`` / ``negative_sampling_loss`` with ``negatives=`` (``loss`` "softmax" / "negsamp") and
+        ``pairwise_loss`` ("hinge" / "logistic") once every argument is checked, under the dot product (``metric``
+        ``_native.PAIR_DOT``) or a distance: recorded (``autograd.PerQueryLossFn``) under the rules of the calls without the
+        keyword, else the forward alone.  Returns the loss, for the pairwise losses ``(loss, active)``."""
+        from ..autograd import PerQueryLossFn, per_query_forward
         grad = embs.requires_grad or (bias is not None and bias.requires_grad) or (query_rows is not None and query_rows.requires_grad)
         if torch.is_grad_enabled() and grad:
-            from ..autograd import NegativesLossFn
-            if query_rows is not None:
-                return NegativesLossFn.apply(embs, query_rows, None, t, ptr, idx, neg, mode, scale, margin, alpha, bias)
-            return NegativesLossFn.apply(embs, None, q, t, ptr, idx, neg, mode, scale, margin, alpha, bias)
+            rows, iq = (None, q) if query_rows is None else (query_rows, None)
+            return PerQueryLossFn.apply(embs, rows, iq, t, ptr, idx, neg, metric, loss, scale, margin, alpha, normalize, bias)
         e = embs.detach().float()
         qm, iq = (e, q) if query_rows is None else (query_rows.detach(), None)
-        if mode == _native.NEG_SOFTMAX:
-            return _native.score_neg_softmax_fwd(qm, e, t, neg, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale, bias=bias)[0]
-        return _native.score_neg_negsamp_fwd(qm, e, t, neg, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale, margin=margin,
-                                             adversarial_temperature=alpha, bias=bias)[0]
-
-    @staticmethod
-    def _distance_loss(metric: int, mode: int, embs, q, t, ptr, idx, neg, scale: float, margin: float, alpha: float, query_rows):
-        """``softmax_loss`` / ``negative_sampling_loss`` with ``negatives=`` and ``distance=`` once every argument is checked:
-        recorded (``autograd.DistanceLossFn``) under the rules of ``_negatives_loss``, else the forward alone."""
-        grad = embs.requires_grad or (query_rows is not None and query_rows.requires_grad)
-        if torch.is_grad_enabled() and grad:
-            from ..autograd import DistanceLossFn
-            if query_rows is not None:
-                return DistanceLossFn.apply(embs, query_rows, None, t, ptr, idx, neg, metric, mode, scale, margin, alpha)
-            return DistanceLossFn.apply(embs, None, q, t, ptr, idx, neg, metric, mode, scale, margin, alpha)
-        e = embs.detach().float()
-        qm, iq = (e, q) if query_rows is None else (query_rows.detach(), None)
-        if mode == _native.NEG_SOFTMAX:
-            return _native.score_dist_softmax_fwd(metric, qm, e, t, neg, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale)[0]
-        return _native.score_dist_negsamp_fwd(metric, qm, e, t, neg, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale, margin=margin,
-                                              adversarial_temperature=alpha)[0]
+        out, _, active = per_query_forward(loss, metric, qm, e, t, neg, iq, ptr, idx, scale, margin, alpha, normalize, bias)
+        return out if active is None else (out, active)
 
     def bce_loss(self, embs: torch.Tensor, query: torch.Tensor, *, known=None, pos_ptr: Optional[torch.Tensor] = None,
                  pos_idx: Optional[torch.Tensor] = None, scale: float = 1.0, smoothing: float = 0.0, normalize: bool = True,

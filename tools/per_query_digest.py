@@ -3,9 +3,10 @@ one sha256 per output tensor, as one JSON line.  Equal lines from two checkouts 
 
     python tools/per_query_digest.py [--timeout 120] > digest.json
 
-For fixed seeds, over the shapes of tests/test_distance_gpu.py::SHAPES: rank_candidates (greater, equal), softmax_loss and
-negative_sampling_loss (the loss, and the gradients of embs, of query_rows and of the bias) under the dot product without and
-with candidate_bias and under each distance=, with query_rows given and not given.  A tenth of the negatives is padding (-1)
+For fixed seeds, over the shapes of tests/test_distance_gpu.py::SHAPES: rank_candidates (greater, equal), softmax_loss,
+negative_sampling_loss and pairwise_loss in both kinds (the loss, for pairwise_loss the active counts, and the gradients of
+embs, of query_rows and of the bias) under the dot product without and with candidate_bias and under each distance=, with
+query_rows given and not given.  A tenth of the negatives is padding (-1)
 and every query meets its own target among its negatives once.  Each score ("dot", "dot_bias", "l1", "l2", "complex") runs in
 a child process under its own time limit; after a child that fails or runs out of time nothing more is started."""
 
@@ -66,19 +67,23 @@ def worker(score: str) -> dict:
                 pre = dict(kw, candidate_bias=bias) if bias is not None else kw
                 g, e = model.rank_candidates(embs, q, t, query_rows=rows if with_rows else None, **pre)
             out[key + "-rank"] = [sha(g), sha(e)]
-            for name in ("softmax", "negsamp"):
+            for name in ("softmax", "negsamp", "hinge", "logistic"):
                 leaf = [embs.clone().requires_grad_(True)]
                 leaf.append(rows.clone().requires_grad_(True) if with_rows else None)
                 leaf.append(bias.clone().requires_grad_(True) if bias is not None else None)
                 args = dict(kw, scale=scale, query_rows=leaf[1])
                 if leaf[2] is not None:
                     args["candidate_bias"] = leaf[2]
+                extra = []
                 if name == "softmax":
                     loss = model.softmax_loss(leaf[0], q, t, **args)
-                else:
+                elif name == "negsamp":
                     loss = model.negative_sampling_loss(leaf[0], q, t, margin=1.5, adversarial_temperature=0.5, **args)
+                else:
+                    loss, active = model.pairwise_loss(leaf[0], q, t, loss=name, margin=0.25, return_active=True, **args)
+                    extra = [sha(active)]
                 (loss * torch.linspace(0.5, 1.5, B, device=dev)).sum().backward()
-                out[f"{key}-{name}"] = [sha(loss)] + [sha(v.grad) for v in leaf if v is not None]
+                out[f"{key}-{name}"] = [sha(loss)] + extra + [sha(v.grad) for v in leaf if v is not None]
     torch.cuda.synchronize()
     return out
 
