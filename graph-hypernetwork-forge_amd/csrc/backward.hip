@@ -65,8 +65,8 @@ __global__ __launch_bounds__(256) void tail_bwd_v4_kernel(const float* __restric
 #pragma unroll
             for (int k = 0; k < 4; ++k) x[j][k] = fmaxf(pre[j][k], 0.f) * dm[j][k];
         }
-        float mean, rstd;                                          // the forward's statistics again (D is a power of two)
-        row_mean_rstd<Row, D, 4 * NV>([&](int i) { return x[i / 4][i % 4]; }, eps, mean, rstd);
+        float mean, rstd;                                          // the forward's statistics again (D is a power of two);
+        row_mean_rstd<Row, D, 4 * NV, (NV > 1)>([&](int i) { return x[i / 4][i % 4]; }, eps, mean, rstd);   // 8 / 16 per lane: as a tree
         float s1 = 0.f, s2 = 0.f;                                  // mean(gamma g'), mean(gamma g' xhat)
         f32x4 gg[NV];
 #pragma unroll
