@@ -676,6 +676,40 @@ class DistanceSweepLossFn(torch.autograd.Function):
         return _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand) + (None,) * 10
 
 
+class DistancePairSweepLossFn(torch.autograd.Function):
+    """The hinge or logistic pairwise loss (`kind` _native.PAIR_HINGE / PAIR_LOGISTIC) of a query's target against EVERY node,
+    or the shared candidate set `cand`, with z_ij = -scale D(q_i, embs[j]) under `metric`
+    (HyperGNN.pairwise_loss_by_distance; include/ghf_pairwise_sweep.h).  q_i and the pair `rows` / `query` as in SoftmaxLossFn.
+    Returns (loss, active), active — the violated pairs — without a gradient.  Saved are the forward's dsum (the sum of phi'
+    over J_i, from which the target's coefficient follows without a second sweep) and count; the backward recomputes every
+    distance (ghf_dist_pair_bwd) and returns dq per query and dc per candidate, which _all_node_loss_grads turns into the
+    gradients exactly as for the other losses against every node: rows of embs that are neither candidate, target nor query
+    get exactly zero."""
+
+    @staticmethod
+    def forward(ctx, embs, rows, query, target, ptr, idx, metric: int, kind: int, scale: float, margin: float, normalize: bool,
+                cand=None):
+        assert (rows is None) != (query is None)
+        embs = embs.contiguous().float()
+        rows = None if rows is None else rows.contiguous().float()
+        loss, dsum, count, active = _native.score_dist_pair_sweep_fwd(metric, kind, embs if rows is None else rows, embs, target,
+                                                                      iq=query, filt_ptr=ptr, filt_idx=idx, scale=scale, margin=margin,
+                                                                      normalize=normalize, ic=cand)
+        ctx.save_for_backward(embs, rows, query, target, ptr, idx, dsum, count, cand)
+        ctx.metric, ctx.kind, ctx.scale, ctx.margin, ctx.normalize = metric, kind, scale, margin, normalize
+        ctx.mark_non_differentiable(active)
+        return loss, active
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_active=None):
+        embs, rows, query, target, ptr, idx, dsum, count, cand = ctx.saved_tensors
+        dq, dc = _native.score_dist_pair_sweep_bwd(ctx.metric, ctx.kind, embs if rows is None else rows, embs, target, dsum, count,
+                                                   g.contiguous().float(), iq=query, filt_ptr=ptr, filt_idx=idx, scale=ctx.scale,
+                                                   margin=ctx.margin, normalize=ctx.normalize, ic=cand)
+        return _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand) + (None,) * 10
+
+
 class ScorePairsFn(torch.autograd.Function):
     """s_i = a_i . b_i (reference score_triple, hypergnn.py:304-318)."""
 

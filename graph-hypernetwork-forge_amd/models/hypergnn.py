@@ -1181,6 +1181,73 @@ class HyperGNN(nn.Module):
         return self._by_distance_loss("negative_sampling_loss_by_distance", _native.NEG_NEGSAMP, embs, query, target, distance, scale,
                                       margin, adversarial_temperature, known, filt_ptr, filt_idx, query_rows, query_rel, candidates)
 
+    def pairwise_loss_by_distance(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, distance: str, *,
+                                  loss: str = "hinge", margin: float = 1.0, scale: float = 1.0, normalize: bool = True, known=None,
+                                  filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+                                  query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
+                                  candidates: Optional[torch.Tensor] = None, return_active: bool = False):
+        """``pairwise_loss`` under a DISTANCE against every node, or one ``candidates`` set shared by the batch (the way DGL-KE
+        and the OGB ``wikikg2`` / ``biokg`` baselines draw negatives), fp32 ``[B]``.  With ``z[i, j] = -scale * D(row_i,
+        embs[j])`` and ``J_i`` = every node (every candidate) except query ``i``'s known partners and its target::
+
+            u[i, j] = z[i, j] - z[i, target[i]] + margin
+            loss[i] = mean over J_i of max(u, 0)          # loss="hinge": TransE's published max(0, gamma + D_pos - D_neg)
+            loss[i] = mean over J_i of softplus(u)        # loss="logistic": the soft margin ranking loss
+
+        ``normalize=False`` gives the sum instead of the mean; a query whose ``J_i`` is empty has loss exactly 0.  TransE with
+        one shared negative set::
+
+            rows = embs[head] + rel_vec[rel]
+            loss = model.pairwise_loss_by_distance(embs, head, tail, "l1", margin=gamma, query_rows=rows, candidates=neg).mean()
+
+        ``distance`` is ``"l1"``, ``"l2"`` or ``"complex"`` (RotatE, ``d`` even) and ``query_rows`` / ``known`` / ``filt_ptr,
+        filt_idx`` / ``query_rel`` / ``candidates`` mean what they mean in ``softmax_loss_by_distance``; with ``candidates`` the
+        batch's targets are added to the set.  ``return_active=True`` returns ``(loss, active)``, ``active`` int32 ``[B]`` the
+        number of violated pairs ``u > 0``; at ``margin=0, scale=1`` it is ``rank_by_distance``'s ``greater``.  There is no
+        ``negatives`` (a set per query is ``pairwise_loss(negatives=, distance=)``) and no ``candidate_bias``.
+
+        The tile sweep of ``rank_by_distance`` with a pairwise epilogue (``ghf_dist_pair_fwd``,
+        ``include/ghf_pairwise_sweep.h``): a candidate row is read once per 64 queries, and neither the ``[B, C]`` distances,
+        ids or coefficients nor the ``[B, C, d]`` differences exist, forward or backward.  Recorded for autograd when grad mode
+        is on and ``embs`` or ``query_rows`` requires grad (``autograd.DistancePairSweepLossFn``, ``ghf_dist_pair_bwd``); rows
+        of ``embs`` that are neither candidate, target nor query get exactly zero.  Bit-reproducible, and a query's loss does
+        not depend on its batch.  ``scale`` finite and ``> 0``, ``margin`` finite (``ValueError`` otherwise)."""
+        what = "pairwise_loss_by_distance"
+        metric = self._sweep_metric(distance, embs)
+        kind = _native.PAIR_KINDS.get(loss) if isinstance(loss, str) else None
+        if kind is None:
+            raise ValueError(f"loss must be one of {sorted(_native.PAIR_KINDS)}, got {loss!r}")
+        self._known_form(known, filt_ptr, filt_idx, query_rel)
+        scale, margin = float(scale), float(margin)
+        if not (0.0 < scale < float("inf")):
+            raise ValueError(f"scale must be finite and positive, got {scale}")
+        if not (float("-inf") < margin < float("inf")):
+            raise ValueError(f"margin must be finite, got {margin}")
+        if not isinstance(normalize, bool) or not isinstance(return_active, bool):
+            raise TypeError(f"normalize and return_active must be bools, got {normalize!r} and {return_active!r}")
+        cand = None if candidates is None else self._candidate_ids(candidates, embs)
+        q = self._rank_ids(query, embs.size(0), embs, "query")
+        t = self._rank_ids(target, embs.size(0), embs, "target")
+        if q.numel() != t.numel():
+            raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
+        self._query_rows(embs, query, query_rows, what)
+        if not embs.is_cuda:
+            raise RuntimeError(f"{what} computes on an MI355X HIP device only (input is on {embs.device})")
+        ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
+        if cand is not None:
+            cand = self._softmax_candidates(cand, t)
+        grad = embs.requires_grad or (query_rows is not None and query_rows.requires_grad)
+        if torch.is_grad_enabled() and grad:
+            from ..autograd import DistancePairSweepLossFn
+            rows, iq = (None, q) if query_rows is None else (query_rows, None)
+            out, active = DistancePairSweepLossFn.apply(embs, rows, iq, t, ptr, idx, metric, kind, scale, margin, normalize, cand)
+        else:
+            e = embs.detach().float()
+            qm, iq = (e, q) if query_rows is None else (query_rows.detach(), None)
+            out, _, _, active = _native.score_dist_pair_sweep_fwd(metric, kind, qm, e, t, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale,
+                                                                  margin=margin, normalize=normalize, ic=cand)
+        return (out, active) if return_active else out
+
     def softmax_loss(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, scale: float = 1.0, known=None,
                      filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                      query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
