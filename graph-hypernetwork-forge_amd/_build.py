@@ -14,8 +14,8 @@ OBJ_DIR = os.path.join(CSRC, "_obj")
 LIB_PATH = os.path.join(PKG_DIR, "libghf_hip.so")
 INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
 
-SOURCES = ["capi.hip", "plan.hip", "text_encoder.hip", "score.hip", "backward.hip", "weightgen.hip", "weightgen_bwd.hip", "input_proj.hip", "message_generic.hip", "message_pp.hip", "message_bx.hip", "message_rs.hip", "exchange.hip", "subgraph.hip", "rank.hip", "softmax.hip", "bce.hip", "negsamp.hip", "negatives.hip", "distance.hip", "pairwise.hip", "distance_sweep.hip", "distance_loss.hip", "pairwise_sweep.hip", "candidates.hip", "relation.hip", "relation_predict.hip"]
-HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(INCLUDE, "ghf.h"), os.path.join(INCLUDE, "ghf_negatives.h"), os.path.join(INCLUDE, "ghf_distance.h"), os.path.join(INCLUDE, "ghf_distance_sweep.h"), os.path.join(INCLUDE, "ghf_distance_loss.h"), os.path.join(INCLUDE, "ghf_pairwise.h"), os.path.join(INCLUDE, "ghf_pairwise_sweep.h")]
+SOURCES = ["capi.hip", "plan.hip", "text_encoder.hip", "score.hip", "backward.hip", "weightgen.hip", "weightgen_bwd.hip", "input_proj.hip", "message_generic.hip", "message_pp.hip", "message_bx.hip", "message_rs.hip", "exchange.hip", "subgraph.hip", "rank.hip", "softmax.hip", "bce.hip", "negsamp.hip", "negatives.hip", "distance.hip", "pairwise.hip", "distance_sweep.hip", "distance_loss.hip", "pairwise_sweep.hip", "pairwise_dot_sweep.hip", "candidates.hip", "relation.hip", "relation_predict.hip"]
+HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(INCLUDE, "ghf.h"), os.path.join(INCLUDE, "ghf_negatives.h"), os.path.join(INCLUDE, "ghf_distance.h"), os.path.join(INCLUDE, "ghf_distance_sweep.h"), os.path.join(INCLUDE, "ghf_distance_loss.h"), os.path.join(INCLUDE, "ghf_pairwise.h"), os.path.join(INCLUDE, "ghf_pairwise_sweep.h"), os.path.join(INCLUDE, "ghf_pairwise_dot_sweep.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"]
 
 

@@ -244,6 +244,18 @@ PAIRSWEEP_SIGNATURES = {
 }
 
 
+# include/ghf_pairwise_dot_sweep.h (the pairwise losses by dot product against every node or a candidate subset,
+# csrc/pairwise_dot_sweep.hip + csrc/softmax.hip): the eighth
+PAIRDOT_SIGNATURES = {
+    "ghf_score_pair_fwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i64]),
+    "ghf_score_pair_fwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _i32, _vp, _i64, _vp, _vp,
+                                  _sz, _vp, _vp, _vp, _vp, _vp]),
+    "ghf_score_pair_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i32, _i64]),
+    "ghf_score_pair_bwd": (_i32, [_i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _f32, _f32, _i32, _vp, _i64, _vp, _vp,
+                                  _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
+}
+
+
 def header_symbols() -> List[str]:
     """Function names declared in include/ghf.h (for the export test)."""
     with open(os.path.join(_build.INCLUDE, "ghf.h")) as f:
@@ -293,6 +305,13 @@ def pairwise_sweep_header_symbols() -> List[str]:
     return sorted(set(re.findall(r"\b(ghf_dist_pair_[a-z_0-9]+)\s*\(", text)))
 
 
+def pairwise_dot_sweep_header_symbols() -> List[str]:
+    """Function names declared in include/ghf_pairwise_dot_sweep.h."""
+    with open(os.path.join(_build.INCLUDE, "ghf_pairwise_dot_sweep.h")) as f:
+        text = re.sub(r"/\*.*?\*/", " ", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(ghf_score_pair_[a-z_0-9]+)\s*\(", text)))
+
+
 def lib_path() -> str:
     return _build.LIB_PATH
 
@@ -316,7 +335,7 @@ def load() -> C.CDLL:
         lib = C.CDLL(path)
         for name, (res, args) in (list(SIGNATURES.items()) + list(NEG_SIGNATURES.items()) + list(DIST_SIGNATURES.items())
                                   + list(DSWEEP_SIGNATURES.items()) + list(DLOSS_SIGNATURES.items()) + list(PAIR_SIGNATURES.items())
-                                  + list(PAIRSWEEP_SIGNATURES.items())):
+                                  + list(PAIRSWEEP_SIGNATURES.items()) + list(PAIRDOT_SIGNATURES.items())):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
@@ -1758,6 +1777,90 @@ def score_dist_pair_sweep_bwd(metric: int, kind: int, q: torch.Tensor, c: torch.
                                     q.size(0), N, B, d, scale, margin, int(normalize), _ptr(ic), C, _ptr(dsum), _ptr(count),
                                     _ptr(grad_loss), _ptr(ws), ws.numel(), _ptr(dq), _ptr(dc), _stream()), "ghf_dist_pair_bwd")
     return dq, dc
+
+
+# ---- the pairwise losses by dot product against every node or a candidate subset (include/ghf_pairwise_dot_sweep.h) -------
+def score_pair_fwd_workspace_bytes(B: int, N: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_pair_fwd_workspace_bytes(B, N, C, d, nnz))
+
+
+def score_pair_bwd_workspace_bytes(B: int, N: int, C: int, d: int, nnz: int) -> int:
+    return int(load().ghf_score_pair_bwd_workspace_bytes(B, N, C, d, nnz))
+
+
+def _pair_dot_sweep_args(kind, q, c, target, iq, filt_ptr, filt_idx, scale, margin, normalize, ic, bias, what: str):
+    q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale = _softmax_args(q, c, target, iq, filt_ptr, filt_idx, scale, what)
+    margin = float(margin)
+    if not (float("-inf") < margin < float("inf")):
+        raise ValueError(f"{what}: margin must be finite, got {margin}")
+    if not isinstance(normalize, bool):
+        raise TypeError(f"{what}: normalize must be a bool, got {normalize!r}")
+    if kind not in (PAIR_HINGE, PAIR_LOGISTIC):
+        raise ValueError(f"{what}: kind must be PAIR_HINGE or PAIR_LOGISTIC, got {kind}")
+    ic = _ic_arg(ic, c, what)
+    bias = _bias_arg(bias, c, what)
+    return int(kind), q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, ic, (0 if ic is None else ic.numel()), bias
+
+
+def score_pair_sweep_fwd(kind: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, iq: Optional[torch.Tensor] = None,
+                         filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0,
+                         margin: float = 1.0, normalize: bool = True, workspace: Optional[torch.Tensor] = None,
+                         out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]] = None,
+                         ic: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None):
+    """(loss fp32 [B], dsum fp32 [B], count int32 [B], active int32 [B]) of include/ghf_pairwise_dot_sweep.h: ghf_score_pair_fwd
+    — the hinge (`kind` PAIR_HINGE) or logistic (PAIR_LOGISTIC) pairwise loss with every row of c (of c[ic] with `ic`, int64 [C]
+    strictly ascending node ids, which must hold every target) as the negatives of every query: u_ij = (z_ij - z_it) + margin
+    with z = scale q . c[j] (+ bias[j]) over J_i, the candidates outside the query's list other than its target; loss = sum
+    phi(u) (over n_i = count[i] with `normalize`), dsum = sum phi'(u) (what the backward needs for the target's coefficient),
+    active = #{u_ij > 0}.  Nothing of size B x C is stored; with `workspace` (uint8, score_pair_fwd_workspace_bytes, C = 0 for
+    every node) and `out` the call allocates nothing."""
+    what = "score_pair_sweep_fwd"
+    kind, q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, ic, C, bias = _pair_dot_sweep_args(
+        kind, q, c, target, iq, filt_ptr, filt_idx, scale, margin, normalize, ic, bias, what)
+    N, d = c.size(0), c.size(1)
+    if out is None:
+        loss, dsum = (torch.empty(B, dtype=torch.float32, device=q.device) for _ in range(2))
+        count, active = (torch.empty(B, dtype=torch.int32, device=q.device) for _ in range(2))
+    else:
+        if len(out) != 4:
+            raise ValueError(f"{what}: out must be two contiguous fp32 [{B}] and two contiguous int32 [{B}] tensors")
+        loss, dsum = _f32_out_pair(out[:2], (B,), (B,), q.device, what)
+        count, active = _req(out[2], torch.int32, "out"), _req(out[3], torch.int32, "out")
+        if any(tuple(t.shape) != (B,) or not t.is_contiguous() for t in out[2:]):
+            raise ValueError(f"{what}: out must be two contiguous fp32 [{B}] and two contiguous int32 [{B}] tensors")
+    ws = _workspace(workspace, score_pair_fwd_workspace_bytes, q.device, what, B=B, N=N, C=C, d=d, nnz=nnz)
+    _check(load().ghf_score_pair_fwd(kind, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N,
+                                     B, d, scale, margin, int(normalize), _ptr(ic), C, _ptr(bias), _ptr(ws), ws.numel(), _ptr(loss),
+                                     _ptr(dsum), _ptr(count), _ptr(active), _stream()), "ghf_score_pair_fwd")
+    return loss, dsum, count, active
+
+
+def score_pair_sweep_bwd(kind: int, q: torch.Tensor, c: torch.Tensor, target: torch.Tensor, dsum: torch.Tensor, count: torch.Tensor,
+                         grad_loss: torch.Tensor, iq: Optional[torch.Tensor] = None, filt_ptr: Optional[torch.Tensor] = None,
+                         filt_idx: Optional[torch.Tensor] = None, scale: float = 1.0, margin: float = 1.0, normalize: bool = True,
+                         workspace: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                         ic: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None, want_db: bool = True):
+    """(dq [B, d], dc [N, d]) fp32 of include/ghf_pairwise_dot_sweep.h: ghf_score_pair_bwd, `dsum` and `count` the forward's —
+    dq per query (not scattered through iq), every row of dc written; G_ij = w_i phi'(u_ij) on J_i, -w_i dsum[i] on the target
+    pair.  With `ic` (the forward's) dc is [C, d], row j the gradient of row ic[j] of c.  With `bias` (the forward's) the result
+    is (dq, dc, db) as score_softmax_bwd's."""
+    what = "score_pair_sweep_bwd"
+    kind, q, c, target, iq, filt_ptr, filt_idx, B, nnz, scale, margin, ic, C, bias = _pair_dot_sweep_args(
+        kind, q, c, target, iq, filt_ptr, filt_idx, scale, margin, normalize, ic, bias, what)
+    dsum, grad_loss = _req(dsum, torch.float32, "dsum"), _req(grad_loss, torch.float32, "grad_loss")
+    count = _req(count, torch.int32, "count")
+    if dsum.numel() != B or count.numel() != B or grad_loss.numel() != B:
+        raise ValueError(f"{what}: dsum, count and grad_loss must hold B = {B} values")
+    N, d = c.size(0), c.size(1)
+    M = C if C else N
+    ws = _workspace(workspace, score_pair_bwd_workspace_bytes, q.device, what, B=B, N=N, C=C, d=d, nnz=nnz)
+    dq, dc = _f32_out_pair(out, (B, d), (M, d), q.device, what)
+    db = torch.empty(M, dtype=torch.float32, device=q.device) if bias is not None and want_db else None
+    _check(load().ghf_score_pair_bwd(kind, _ptr(q), _ptr(c), _ptr(iq), _ptr(target), _ptr(filt_ptr), _ptr(filt_idx), nnz, q.size(0), N,
+                                     B, d, scale, margin, int(normalize), _ptr(ic), C, _ptr(bias), _ptr(dsum), _ptr(count),
+                                     _ptr(grad_loss), _ptr(ws), ws.numel(), _ptr(dq), _ptr(dc), _ptr(db), _stream()),
+           "ghf_score_pair_bwd")
+    return (dq, dc) if bias is None else (dq, dc, db)
 
 
 # ---- relation-typed query rows (include/ghf.h: ghf_relation_rows, csrc/relation.hip) ------------------------------------

@@ -710,6 +710,43 @@ class DistancePairSweepLossFn(torch.autograd.Function):
         return _all_node_loss_grads(ctx, embs, rows, query, dq, dc, cand) + (None,) * 10
 
 
+class DotPairSweepLossFn(torch.autograd.Function):
+    """The hinge or logistic pairwise loss (`kind` _native.PAIR_HINGE / PAIR_LOGISTIC) of a query's target against EVERY node,
+    or the shared candidate set `cand`, by dot product: z_ij = scale q_i . embs[j] (+ bias[j])
+    (HyperGNN.pairwise_loss_by_dot; include/ghf_pairwise_dot_sweep.h).  q_i and the pair `rows` / `query` as in SoftmaxLossFn.
+    Returns (loss, active), active — the violated pairs — without a gradient.  Saved are the forward's dsum (the sum of phi'
+    over J_i, from which the target's coefficient follows without a second sweep) and count; the backward recomputes every
+    score on the matrix cores (ghf_score_pair_bwd) and returns dq per query, dc per candidate and db, which
+    _all_node_loss_grads and _bias_grad turn into the gradients exactly as for the negative-sampling loss: rows of embs that
+    are neither candidate, target nor query get exactly zero."""
+
+    @staticmethod
+    def forward(ctx, embs, rows, query, target, ptr, idx, kind: int, scale: float, margin: float, normalize: bool, cand=None,
+                bias=None):
+        assert (rows is None) != (query is None)
+        embs = embs.contiguous().float()
+        rows = None if rows is None else rows.contiguous().float()
+        bias = None if bias is None else bias.contiguous()
+        loss, dsum, count, active = _native.score_pair_sweep_fwd(kind, embs if rows is None else rows, embs, target, iq=query,
+                                                                 filt_ptr=ptr, filt_idx=idx, scale=scale, margin=margin,
+                                                                 normalize=normalize, ic=cand, bias=bias)
+        ctx.save_for_backward(embs, rows, query, target, ptr, idx, dsum, count, cand, bias)
+        ctx.kind, ctx.scale, ctx.margin, ctx.normalize = kind, scale, margin, normalize
+        ctx.mark_non_differentiable(active)
+        return loss, active
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g, _g_active=None):
+        embs, rows, query, target, ptr, idx, dsum, count, cand, bias = ctx.saved_tensors
+        res = _native.score_pair_sweep_bwd(ctx.kind, embs if rows is None else rows, embs, target, dsum, count, g.contiguous().float(),
+                                           iq=query, filt_ptr=ptr, filt_idx=idx, scale=ctx.scale, margin=ctx.margin,
+                                           normalize=ctx.normalize, ic=cand, bias=bias,
+                                           want_db=bias is not None and ctx.needs_input_grad[11])
+        db = res[2] if bias is not None else None
+        return _all_node_loss_grads(ctx, embs, rows, query, res[0], res[1], cand) + (None,) * 9 + (_bias_grad(ctx, 11, db, bias, cand),)
+
+
 class ScorePairsFn(torch.autograd.Function):
     """s_i = a_i . b_i (reference score_triple, hypergnn.py:304-318)."""
 

@@ -3,6 +3,7 @@
 #include "negatives.h"
 #include "distance.h"
 #include "pairwise.h"
+#include "../../include/ghf_pairwise_dot_sweep.h"
 #include <vector>
 #include <thread>
 #include <algorithm>
@@ -957,6 +958,50 @@ int ghf_score_negsamp_bwd(const float* q, const float* c, const int64_t* iq, con
 }
 
 #undef GHF_NEGSAMP_CHECK
+
+// the pairwise ranking losses by dot product against every node or a shared candidate set (include/ghf_pairwise_dot_sweep.h;
+// DESIGN.md §28): the refusals that stand ahead of the launches' own (score_pair_open), in the header's order.  The public
+// kind becomes the launches' `hinge` here, once.
+#define GHF_SCORE_PAIR_ENTRY(op, ptrs)                                                                                         \
+    do {                                                                                                                       \
+        GHF_REQUIRE(kind == GHF_PAIR_HINGE || kind == GHF_PAIR_LOGISTIC, op ": kind must be GHF_PAIR_HINGE or GHF_PAIR_LOGISTIC"); \
+        GHF_REQUIRE(scale > 0.f && scale <= 3.402823466e38f, op ": scale must be finite and positive");                        \
+        GHF_REQUIRE(margin >= -3.402823466e38f && margin <= 3.402823466e38f, op ": margin must be finite");                    \
+        GHF_REQUIRE(normalize == 0 || normalize == 1, op ": normalize must be 0 or 1");                                        \
+        GHF_REQUIRE((ptrs) && workspace, op ": null pointer argument");                                                        \
+        GHF_REQUIRE(nnz <= 0 || (filt_ptr && filt_idx), op ": null filter list with nnz > 0");                                 \
+        GHF_REQUIRE(((uintptr_t)workspace & 255) == 0, op ": workspace not 256-byte aligned");                                 \
+    } while (0)
+
+size_t ghf_score_pair_fwd_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    return score_pair_workspace_bytes(B, N, C, d, nnz);
+}
+
+int ghf_score_pair_fwd(int kind, const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                       const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float margin,
+                       int normalize, const int64_t* ic, int64_t C, const float* bias, void* workspace, size_t workspace_bytes,
+                       float* loss, float* dsum, int32_t* count, int32_t* active, void* stream) {
+    GHF_SCORE_PAIR_ENTRY("score_pair_fwd", q && c && target && loss && dsum && count && active);
+    return launch_score_pair_fwd(kind == GHF_PAIR_HINGE, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin,
+                                 normalize, ic, C, bias, workspace, workspace_bytes, loss, dsum, count, active, (hipStream_t)stream);
+}
+
+size_t ghf_score_pair_bwd_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    return score_pair_bwd_workspace_bytes(B, N, C, d, nnz);
+}
+
+int ghf_score_pair_bwd(int kind, const float* q, const float* c, const int64_t* iq, const int64_t* target, const int64_t* filt_ptr,
+                       const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale, float margin,
+                       int normalize, const int64_t* ic, int64_t C, const float* bias, const float* dsum, const int32_t* count,
+                       const float* grad_loss, void* workspace, size_t workspace_bytes, float* dq, float* dc, float* db,
+                       void* stream) {
+    GHF_SCORE_PAIR_ENTRY("score_pair_bwd", q && c && target && dsum && count && grad_loss && dq && dc);
+    return launch_score_pair_bwd(kind == GHF_PAIR_HINGE, q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, margin,
+                                 normalize, ic, C, bias, dsum, count, grad_loss, workspace, workspace_bytes, dq, dc, db,
+                                 (hipStream_t)stream);
+}
+
+#undef GHF_SCORE_PAIR_ENTRY
 
 // ---- the per-query family: negatives= [B, K] (the fold: §23) -----------------------------------------
 // include/ghf_negatives.h (dot product), ghf_distance.h (a distance) and ghf_pairwise.h (the pairwise losses) share one entry

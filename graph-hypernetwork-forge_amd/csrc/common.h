@@ -210,6 +210,19 @@ int launch_score_negsamp_bwd(const float* q, const float* c, const int64_t* iq, 
                              const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d, float scale,
                              float margin, float alpha, const float* lw, const float* grad_loss, const int64_t* ic, int64_t C,
                              const float* bias, void* ws, size_t ws_bytes, float* dq, float* dc, float* db, hipStream_t stream);
+// pairwise_dot_sweep.hip (forward) and softmax.hip (backward: softmax_bwd_kernel's fourth loss); C = 0 with ic = NULL: every
+// node; `hinge` chooses between the two losses (include/ghf_pairwise_dot_sweep.h)
+size_t score_pair_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+size_t score_pair_bwd_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz);
+int launch_score_pair_fwd(bool hinge, const float* q, const float* c, const int64_t* iq, const int64_t* target,
+                          const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
+                          float scale, float margin, int normalize, const int64_t* ic, int64_t C, const float* bias, void* ws,
+                          size_t ws_bytes, float* loss, float* dsum, int* count, int* active, hipStream_t stream);
+int launch_score_pair_bwd(bool hinge, const float* q, const float* c, const int64_t* iq, const int64_t* target,
+                          const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
+                          float scale, float margin, int normalize, const int64_t* ic, int64_t C, const float* bias, const float* dsum,
+                          const int* count, const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc, float* db,
+                          hipStream_t stream);
 // bce.hip (forward) and softmax.hip (backward: softmax_bwd_kernel's second loss)
 size_t score_bce_workspace_bytes(int64_t B, int64_t N, int d);
 size_t score_bce_bwd_workspace_bytes(int64_t B, int64_t N, int d);

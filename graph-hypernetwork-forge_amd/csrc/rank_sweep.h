@@ -1,7 +1,8 @@
 // rank_sweep.h — the tiled q . c^T sweep on the exact fp32 matrix instruction that rank.hip (rank counts, top-k),
 // softmax.hip (1-vs-all softmax loss) and bce.hip (multi-label 1-vs-all BCE loss) share: geometry, the VALU form of the
-// accumulator's chain, the LDS layout and rank_tile_kernel with its five epilogues (the fifth: negsamp.hip's negative-sampling
-// loss, with an argument struct of its own for its two extra floats), and the host side around it: the two
+// accumulator's chain, the LDS layout and rank_tile_kernel with its six epilogues (the fifth: negsamp.hip's negative-sampling
+// loss, with an argument struct of its own for its two extra floats; the sixth: pairwise_dot_sweep.hip's pairwise ranking
+// losses, again with a struct of its own), and the host side around it: the two
 // kernels that validate ids ahead of a sweep, the checks that open a launch (score_open) and the choice of the instantiation
 // (launch_rank_tiles).  rank.hip's header comment describes the sweep.  Two template flags select a variant of it, each with an
 // argument struct of its own so that the others keep theirs: SUB (a candidate subset, candidates.hip) and BIAS (a per-candidate
@@ -200,7 +201,7 @@ struct RankArgs {
 // N, the lists and the targets are then the count of, and positions in, ic.  A type of its own, so that the all-node
 // instantiations keep their argument block, and with it their code, as they are.
 struct RankSubArgs : RankArgs { const int64_t* ic; int64_t Nn; };
-template <bool SUB, bool BIAS = false, bool NEG = false> struct RankKernelArgs { typedef RankArgs type; };
+template <bool SUB, bool BIAS = false, bool NEG = false, bool PAIR = false> struct RankKernelArgs { typedef RankArgs type; };
 template <> struct RankKernelArgs<true, false> { typedef RankSubArgs type; };
 
 // a per-candidate bias (the BIAS instantiations): bias[j] is the fp32 term of the
@@ -208,13 +209,20 @@ template <> struct RankKernelArgs<true, false> { typedef RankSubArgs type; };
 // candidates.hip has gathered it into position space ahead of the sweep.  Rank and top-k compare s(i, j) + bias[j], the two
 // losses use fmaf(scale, s(i, j), bias[j]).  Again a type of its own: every other instantiation keeps its argument block.
 struct RankBiasArgs : RankSubArgs { const float* bias; };
-template <bool SUB> struct RankKernelArgs<SUB, true> { typedef RankBiasArgs type; };
+template <bool SUB> struct RankKernelArgs<SUB, true, false, false> { typedef RankBiasArgs type; };
 
 // the negative-sampling loss (the RK_NEGSAMP instantiations; negsamp.hip): its margin and adversarial
 // temperature.  One type for its four (SUB, BIAS) variants (ic / Nn / bias unused where the flag is off), and a type of its
 // own once more: every other instantiation keeps its argument block.
 struct RankNegArgs : RankBiasArgs { float margin, alpha; };
-template <bool SUB, bool BIAS> struct RankKernelArgs<SUB, BIAS, true> { typedef RankNegArgs type; };
+template <bool SUB, bool BIAS> struct RankKernelArgs<SUB, BIAS, true, false> { typedef RankNegArgs type; };
+
+// the pairwise ranking losses (the RK_PAIR instantiations; pairwise_dot_sweep.hip): the margin, every query's
+// z_it (the target's logit, formed ahead of the sweep from the t[i] of score_prep_kernel / launch_cand_map) and the 16-byte
+// partial per (query, slab).  One type for the (SUB, BIAS, HINGE) variants, and once more a type of its own.
+struct __attribute__((aligned(16))) PairPart { float f, g; int n, a; };   // sum phi, sum phi', |J_i|, #{u > 0}
+struct RankPairArgs : RankBiasArgs { float margin; const float* zt; PairPart* ws_pair; };
+template <bool SUB, bool BIAS> struct RankKernelArgs<SUB, BIAS, false, true> { typedef RankPairArgs type; };
 
 // row j of a sweep over the candidate subset ic [C] of a table of `rows` rows: absent past C or when the id is outside the
 // table (candidates.hip reports such a list; the sweep only has to read nothing outside c)
@@ -226,7 +234,7 @@ __device__ __forceinline__ const float* sub_row(const float* __restrict__ c, con
 }
 
 // the epilogue of rank_tile_kernel
-constexpr int RK_RANK = 0, RK_TOPK = 1, RK_SOFTMAX = 2, RK_BCE = 3, RK_NEGSAMP = 4;
+constexpr int RK_RANK = 0, RK_TOPK = 1, RK_SOFTMAX = 2, RK_BCE = 3, RK_NEGSAMP = 4, RK_PAIR = 5;
 
 // first entry of the sorted list [lo, hi) that is not below `first`
 __device__ __forceinline__ int64_t filter_lower_bound(const int64_t* __restrict__ idx, int64_t lo, int64_t hi, int64_t first) {
@@ -262,6 +270,12 @@ __device__ __forceinline__ float log1p_unit(float t) {
 }
 // softplus(z) = log(1 + exp(z)) = max(z, 0) + log(1 + exp(-|z|)): no overflow at either end
 __device__ __forceinline__ float softplus(float z) { return fmaxf(z, 0.f) + log1p_unit(__expf(-fabsf(z))); }
+// sigmoid(u) from e = exp(-|u|) in (0, 1] and the hardware reciprocal, as ghf_pairwise_sweep.h's phi' of the logistic loss
+__device__ __forceinline__ float pair_sigmoid(float u) {
+#pragma clang fp contract(off)
+    const float e = __expf(-fabsf(u)), rcp = __builtin_amdgcn_rcpf(1.f + e);
+    return u >= 0.f ? rcp : e * rcp;
+}
 
 // *owner = the query whose list holds entry e, i.e. the last i with filt_ptr[i] <= e; false when e lies inside no list (a
 // malformed pointer array).  A flag, not a -1 owner: the caller's test is then a branch on the two comparisons themselves,
@@ -317,11 +331,12 @@ static inline size_t rank_lds_bytes(int d, int BK, int CT, bool bias = false) {
     return ((size_t)RK_TILE * (dpad + 4) + 2 * (size_t)CT * (BK + 4) + 2 * RK_TILE + (bias ? 2 * CT : 0)) * 4;
 }
 
-template <int BK, int CT, int MODE, bool SUB = false, bool BIAS = false>
-__global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKernelArgs<SUB, BIAS, MODE == RK_NEGSAMP>::type a) {
+// HINGE: which of the two pairwise losses the RK_PAIR epilogue forms (set once, in the entry point, from the public kind)
+template <int BK, int CT, int MODE, bool SUB = false, bool BIAS = false, bool HINGE = false>
+__global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKernelArgs<SUB, BIAS, MODE == RK_NEGSAMP, MODE == RK_PAIR>::type a) {
     constexpr bool TOPK = MODE == RK_TOPK, RANK = MODE == RK_RANK, SOFTMAX = MODE == RK_SOFTMAX, BCE = MODE == RK_BCE;
-    constexpr bool NEGSAMP = MODE == RK_NEGSAMP;
-    constexpr bool CURSOR = SOFTMAX || BCE || NEGSAMP;  // the lists are walked by a cursor, in step with the sweep
+    constexpr bool NEGSAMP = MODE == RK_NEGSAMP, PAIR = MODE == RK_PAIR;
+    constexpr bool CURSOR = SOFTMAX || BCE || NEGSAMP || PAIR;  // the lists are walked by a cursor, in step with the sweep
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int NT = CT * 2, NW = NT / 64;            // a wave per 64 candidates x 64 queries
     constexpr int LDC = BK + 4, F4 = BK / 4, NL = CT * F4 / NT;
@@ -379,13 +394,16 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
     // negsamp: rm / rs are the running max of alpha z and the sum S of exp(alpha z - max) over the column's negatives, nT the
     // same sum weighted by softplus(z + margin); tgt and the cursor as for the softmax
     float nT[2] = {0.f, 0.f};
+    // pair: tq is the column's z_it; bsp / bsz are its running sums of phi and phi', gt / eq its pairs of J_i and those with
+    // u > 0; tgt and the cursor as for the softmax
 #pragma unroll
     for (int tn = 0; tn < 2; ++tn) {
         const int64_t qi = q0 + wn * 64 + tn * 32 + lr;
         tq[tn] = __int_as_float(0x7FC00000);
         if (qi < a.B) {
             if (RANK) tq[tn] = a.t[qi];
-            if (SOFTMAX || NEGSAMP) tgt[tn] = a.target[qi];
+            if constexpr (PAIR) tq[tn] = a.zt[qi];
+            if (SOFTMAX || NEGSAMP || PAIR) tgt[tn] = a.target[qi];
             if (!RANK && a.filt_ptr) {
                 int64_t lo = a.filt_ptr[qi], hi = a.filt_ptr[qi + 1];
                 lo = lo < 0 ? 0 : (lo > a.nnz ? a.nnz : lo);
@@ -639,6 +657,52 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
                         rm[tn] = mx;
                     }
                 }
+            } else if constexpr (PAIR) {
+                // no contraction in this arm: z is rounded once (scale * s, or the one fmaf with a bias), then u = (z - z_it) +
+                // margin in two operations, so that a bias of zeros keeps the bits and the backward can form the same u
+#pragma clang fp contract(off)
+                // As the negsamp arm: a bit per register that is no pair of J_i where the tile's id range holds a listed id,
+                // the target or the end of the candidates, none on the plain path; then the column's 32 registers enter its
+                // sums in register order, a register left out adding +0.f and 0 by select (the sums are never -0.f).  The
+                // one branch around a column's group skips nothing that counts and keeps the two columns' temporaries from
+                // being scheduled side by side.
+                const int64_t tile_end = tile * CT + CT;
+#pragma unroll
+                for (int tn = 0; tn < 2; ++tn) {
+                    uint32_t outm = 0;
+                    if (!(full && nxt[tn] >= tile_end && (tgt[tn] < tile * CT || tgt[tn] >= tile_end))) {
+                        const bool look = nxt[tn] < tile_end;
+#pragma unroll
+                        for (int e = 0; e < 32; ++e) {
+                            const int64_t cand = base + 32 * (e >> 4) + (e & 3) + 8 * ((e & 15) >> 2);
+                            const bool out = cand >= a.N || cand == tgt[tn] || (look && in_filter(a.filt_idx, f0[tn], f1[tn], cand));
+                            outm |= out ? 1u << e : 0u;
+                        }
+                        while (nxt[tn] < tile_end) {
+                            ++f0[tn];
+                            nxt[tn] = f0[tn] < f1[tn] ? a.filt_idx[f0[tn]] : INT64_MAX;
+                        }
+                    }
+                    if (outm != 0xFFFFFFFFu) {
+                        float f = bsp[tn], g = bsz[tn];
+                        int ac = eq[tn];
+#pragma unroll
+                        for (int e = 0; e < 32; ++e) {
+                            const bool out = (outm >> e) & 1;
+                            const float u = (logit(tn, e) - tq[tn]) + a.margin;
+                            float phi;
+                            if constexpr (HINGE) phi = u <= 0.f ? 0.f : u;      // not fmaxf: a NaN stays a NaN
+                            else phi = softplus(u);
+                            f += out ? 0.f : phi;
+                            if constexpr (!HINGE) g += out ? 0.f : pair_sigmoid(u);
+                            ac += !out && u > 0.f ? 1 : 0;
+                        }
+                        bsp[tn] = f;
+                        bsz[tn] = g;
+                        eq[tn] = ac;
+                        gt[tn] += 32 - __popc(outm);
+                    }
+                }
             } else if (RANK) {
 #pragma unroll
                 for (int tm = 0; tm < 2; ++tm)
@@ -766,6 +830,24 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
             w[1] = m.s;
             w[2] = m.t;
         }
+    } else if constexpr (PAIR) {
+        // as the BCE's triples: the column's NP partials of 16 bytes through LDS, added in that fixed order, one per (query, slab)
+        constexpr int NP = NW;
+        PairPart* part = (PairPart*)Cs;
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) part[(wn * 64 + tn * 32 + lr) * NP + wm * 2 + lh] = PairPart{bsp[tn], bsz[tn], gt[tn], eq[tn]};
+        __syncthreads();
+        if (tid < RK_TILE && q0 + tid < a.B) {
+            PairPart m = part[tid * NP];
+            for (int p = 1; p < NP; ++p) {
+                const PairPart x = part[tid * NP + p];
+                m.f += x.f;
+                m.g += x.g;
+                m.n += x.n;
+                m.a += x.a;
+            }
+            a.ws_pair[(size_t)(q0 + tid) * a.slabs + slab] = m;
+        }
     } else if (RANK) {
 #pragma unroll
         for (int tn = 0; tn < 2; ++tn) {
@@ -794,6 +876,7 @@ __global__ __launch_bounds__(CT * 2) void rank_tile_kernel(const typename RankKe
 // (node ids of the a.N candidates, rows of a table of Nn rows) the sweep over that subset.
 // With `bias` (one value per candidate of the sweep: per node, or gathered through ic) the BIAS instantiations.
 // RK_NEGSAMP: the same 2 x 2 x 2 choice among its own instantiations, which all take RankNegArgs (margin, alpha).
+// RK_PAIR goes through launch_rank_pair_tiles below.
 template <int MODE>
 static int launch_rank_tiles(const RankArgs& a, hipStream_t stream, const int64_t* ic = nullptr, int64_t Nn = 0,
                              const float* bias = nullptr, float margin = 0.f, float alpha = 0.f) {
@@ -855,6 +938,33 @@ static int launch_rank_tiles(const RankArgs& a, hipStream_t stream, const int64_
         GHF_SET_MAX_LDS((rank_tile_kernel<16, 128, MODE>), lds);
         rank_tile_kernel<16, 128, MODE><<<grid, 256, lds, stream>>>(a);
     }
+    GHF_LAUNCH_CHECK();
+    return GHF_OK;
+}
+
+// RK_PAIR: the 2 x 2 x 2 choice of launch_rank_tiles<RK_NEGSAMP> among the instantiations of one loss (HINGE or not), which
+// all take RankPairArgs; `s` comes with every field but ic / Nn / bias
+template <bool HINGE>
+static int launch_rank_pair_tiles(RankPairArgs s, hipStream_t stream, const int64_t* ic, int64_t Nn, const float* bias) {
+    const unsigned grid = (unsigned)(s.qtiles * s.slabs);
+    s.ic = ic; s.Nn = Nn; s.bias = bias;
+    const bool wide = rank_ctile(s.d) == 256;
+    const size_t lds = wide ? rank_lds_bytes(s.d, 32, 256, bias != nullptr) : rank_lds_bytes(s.d, 16, 128, bias != nullptr);
+#define GHF_RANK_PAIR_LAUNCH(BK, CT, SUBSET, BIASED)                                                      \
+    do {                                                                                                   \
+        GHF_SET_MAX_LDS((rank_tile_kernel<BK, CT, RK_PAIR, SUBSET, BIASED, HINGE>), lds);                  \
+        rank_tile_kernel<BK, CT, RK_PAIR, SUBSET, BIASED, HINGE><<<grid, CT * 2, lds, stream>>>(s);        \
+    } while (0)
+#define GHF_RANK_PAIR_SHAPE(BK, CT)                                                                        \
+    do {                                                                                                   \
+        if (ic && bias) GHF_RANK_PAIR_LAUNCH(BK, CT, true, true);                                          \
+        else if (ic) GHF_RANK_PAIR_LAUNCH(BK, CT, true, false);                                            \
+        else if (bias) GHF_RANK_PAIR_LAUNCH(BK, CT, false, true);                                          \
+        else GHF_RANK_PAIR_LAUNCH(BK, CT, false, false);                                                   \
+    } while (0)
+    if (wide) GHF_RANK_PAIR_SHAPE(32, 256); else GHF_RANK_PAIR_SHAPE(16, 128);
+#undef GHF_RANK_PAIR_SHAPE
+#undef GHF_RANK_PAIR_LAUNCH
     GHF_LAUNCH_CHECK();
     return GHF_OK;
 }

@@ -41,6 +41,13 @@
 //   G_ij = grad[i] scale exp(alpha z_ij - lw[i]) sigma(z_ij + margin) on J_i,   G_it = -grad[i] scale sigma(-(z_it + margin)),
 // 0 at a listed candidate; lists, cursor and the dc sweep's zeroed pairs are the softmax's, the target never a negative.
 //
+// The pairwise ranking losses by dot product (pairwise_dot_sweep.hip; include/ghf_pairwise_dot_sweep.h) are the
+// kernel's fourth loss (LOSS = SB_PAIR, HINGE choosing between the two), with three saved per-query values where the others
+// have two — z_it (NaN: the query takes no part), w_i and G_it, formed once for both passes by pair_saved_kernel — and an
+// argument struct of its own for them and the margin:
+//   G_ij = w_i phi'((z_ij - z_it) + margin) on J_i,   G_it = -w_i dsum_i on the target pair, listed or not,
+// 0 at a listed candidate; the hinge's phi' is a compare.  Lists, cursor and the dc sweep's zeroed pairs are the softmax's.
+//
 // A per-candidate bias (BIAS instantiations; include/ghf.h: the _b calls): every logit is fmaf(scale, s(i,j), b_j),
 // forward (rank_sweep.h) and backward, where the softmax forms p_ij = exp(fmaf(scale, s, b_j - lse[i])) so that a zero bias keeps
 // the bits.  The dq sweep stages the 64 bias values of a step with its streamed rows, the dc sweep loads its owner rows' once;
@@ -199,12 +206,16 @@ struct SmBwdArgs {
 };
 // SUB: candidate j is row ic[j] of c, which has Nn rows (rank_sweep.h: sub_row, RankSubArgs)
 struct SmBwdSubArgs : SmBwdArgs { const int64_t* ic; int64_t Nn; };
-template <bool SUB, bool BIAS = false> struct SmBwdKernelArgs { typedef SmBwdArgs type; };
+template <bool SUB, bool BIAS = false, bool PAIR = false> struct SmBwdKernelArgs { typedef SmBwdArgs type; };
 template <> struct SmBwdKernelArgs<true, false> { typedef SmBwdSubArgs type; };
 // BIAS: bias[j] is the term of the sweeps' candidate j (rank_sweep.h: RankBiasArgs),
 // the logit fmaf(scale, s, bias[j]); db [N] (may be NULL) gets sum_i G_ij / scale from the dc pass
 struct SmBwdBiasArgs : SmBwdSubArgs { const float* bias; float* db; };
-template <bool SUB> struct SmBwdKernelArgs<SUB, true> { typedef SmBwdBiasArgs type; };
+template <bool SUB> struct SmBwdKernelArgs<SUB, true, false> { typedef SmBwdBiasArgs type; };
+// SB_PAIR: `lse` holds z_it (NaN: the query takes no part); w and gt are the query's w_i and G_it.  One type
+// for its (SUB, BIAS, HINGE) variants, and a type of its own: every other instantiation keeps its argument block.
+struct SmBwdPairArgs : SmBwdBiasArgs { const float* w; const float* gt; float margin; };
+template <bool SUB, bool BIAS> struct SmBwdKernelArgs<SUB, BIAS, true> { typedef SmBwdPairArgs type; };
 
 constexpr int SB_BIAS = 128;                 // backward: bias values in LDS (the owner tile's, or the streamed tile's)
 static inline size_t sb_lds_bytes(int d, int OT, bool bias = false) {
@@ -219,12 +230,12 @@ struct SmQuery {
 };
 
 // the loss whose G the backward forms
-constexpr int SB_SOFTMAX = 0, SB_BCE = 1, SB_NEGSAMP = 2;
+constexpr int SB_SOFTMAX = 0, SB_BCE = 1, SB_NEGSAMP = 2, SB_PAIR = 3;
 
-template <int OT, int DMAX, bool DC, int LOSS, bool SUB = false, bool BIAS = false>
-__global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwdKernelArgs<SUB, BIAS>::type a) {
+template <int OT, int DMAX, bool DC, int LOSS, bool SUB = false, bool BIAS = false, bool HINGE = false>
+__global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwdKernelArgs<SUB, BIAS, LOSS == SB_PAIR>::type a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr bool BCE = LOSS == SB_BCE, NEG = LOSS == SB_NEGSAMP;
+    constexpr bool BCE = LOSS == SB_BCE, NEG = LOSS == SB_NEGSAMP, PAIR = LOSS == SB_PAIR;
     constexpr int ST = SB_ST, NT = SB_NT, LDG = OT + 1;
     constexpr int QR = DC ? ST : OT, CR = DC ? OT : ST;             // query / candidate rows of a step's score tile
     constexpr int QT = QR / 32, NTW = QT * (CR / 32) / 4;           // a wave: one query column tile, NTW candidate row tiles
@@ -274,7 +285,8 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
             if (!BCE) m.tgt = a.target[qi];
             if (r >= 0 && r < a.rows_q && l == l) {
                 m.lse = l;
-                m.gs = a.grad[qi] * a.scale;
+                if constexpr (PAIR) m.gs = a.w[qi];
+                else m.gs = a.grad[qi] * a.scale;
             }
             if (a.filt_ptr) {
                 int64_t lo = a.filt_ptr[qi], hi = a.filt_ptr[qi + 1];
@@ -327,6 +339,13 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
     const int pl = (lr & ~7) + 4 * (lr & 1) + ((lr >> 1) & 3);  // where store_perm put column lr of a group of 32
 
     SmQuery cur = query(DC ? tile0 * ST + ql : own0 + ql), nxtq = cur;
+    // pair: the G_it of the lane's query (read only where the query is live, whose gt is then a number)
+    float cgt = 0.f, ngt = 0.f;
+    auto query_gt = [&](int64_t qi) -> float {
+        if constexpr (PAIR) return qi < a.B ? a.gt[qi] : 0.f;
+        else return 0.f;
+    };
+    if constexpr (PAIR) cgt = query_gt(DC ? tile0 * ST + ql : own0 + ql);
     int64_t nxt = INT64_MAX;                                    // dq: the first listed id not yet behind the sweep
     if (!DC) {
         cur.f0 = filter_lower_bound(a.filt_idx, cur.f0, cur.f1, tile0 * ST);
@@ -381,6 +400,7 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
         if (more) {
             fetch(tile + 1);
             if (DC) nxtq = query((tile + 1) * ST + ql);
+            if constexpr (PAIR && DC) ngt = query_gt((tile + 1) * ST + ql);
         }
 
         // scores of the step: candidates x queries, the chain of the forward
@@ -428,7 +448,22 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
                 const int64_t cand = cand0 + cl;
                 float gv = 0.f;
                 if (live && cand < a.N) {
-                    if constexpr (NEG) {
+                    if constexpr (PAIR) {
+#pragma clang fp contract(off)                           // z and u by the forward's expressions: u has the forward's bits
+                        float z;
+                        if constexpr (BIAS) z = fmaf(a.scale, s[t][r], bq[r >> 2][r & 3]);
+                        else z = a.scale * s[t][r];
+                        const float u = (z - cur.lse) + a.margin;
+                        float g;
+                        if constexpr (HINGE) g = u > 0.f ? cur.gs : 0.f;
+                        else g = cur.gs * pair_sigmoid(u);
+                        if (cand == cur.tgt) {
+                            gv = cgt;
+                        } else {
+                            const bool masked = look && in_filter(a.filt_idx, cur.f0, cur.f1, cand);
+                            gv = masked ? 0.f : g;
+                        }
+                    } else if constexpr (NEG) {
 #pragma clang fp contract(off)                           // z is rounded before the margin is added, as in the forward
                         // sigma(y), y = z + margin, from e = exp(-|y|) as the BCE's; the target's entry is -gs sigma(-y), a
                         // negative's gs w sigma(y) with w = exp(alpha z - lw), 0 for a query without negatives (lw = -inf)
@@ -507,6 +542,7 @@ __global__ __launch_bounds__(SB_NT) void softmax_bwd_kernel(const typename SmBwd
         if (more) {
             stash();
             if (DC) cur = nxtq;
+            if constexpr (PAIR && DC) cgt = ngt;
         }
         __syncthreads();
     }
@@ -646,6 +682,126 @@ int launch_score_negsamp_bwd(const float* q, const float* c, const int64_t* iq, 
                              const float* bias, void* ws, size_t ws_bytes, float* dq, float* dc, float* db, hipStream_t stream) {
     return launch_score_loss_bwd<SB_NEGSAMP>(q, c, iq, target, filt_ptr, filt_idx, nnz, rows_q, N, B, d, scale, 0.f, lw, grad_loss, ws,
                                              ws_bytes, dq, dc, stream, ic, C, bias, db, margin, alpha);
+}
+
+// ---- the pairwise ranking losses by dot product (pairwise_dot_sweep.hip holds their forward) -----------------
+// The same two sweeps, G formed for that loss.  A sibling of launch_score_loss_bwd, not a fourth arm of it: this call forms
+// the per-query t and valid itself (the others read the forward's lse, whose NaNs say which queries take part), has three
+// saved values and a workspace of its own layout, and its refusals come in its header's order (score_pair_open).
+int score_pair_open(const char* op, size_t need, const int64_t* iq, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
+                    const int64_t* ic, int64_t C, size_t ws_bytes);
+int launch_pair_zt(float* t, const int* valid, int64_t B, float scale, const int64_t* target, const float* bias, hipStream_t stream);
+
+// the softmax's general form (a subset's always with room for its gathered bias), then t -> z_it, valid, w and G_it [B]
+size_t score_pair_bwd_workspace_bytes(int64_t B, int64_t N, int64_t C, int d, int64_t nnz) {
+    if (C < 0 || C > N || nnz < 0) return 0;
+    const size_t base = score_softmax_bwd_b_workspace_bytes(B, N, C, d, nnz);
+    return base ? base + 4 * rk_align((size_t)B * 4) : 0;
+}
+
+// one thread per query, behind launch_pair_zt: what both passes read of a query — z_it (NaN: the query takes no part: not
+// valid, or count <= 0), w_i and G_it
+__global__ __launch_bounds__(256) void pair_saved_kernel(const int* __restrict__ valid, const float* __restrict__ dsum,
+                                                         const int* __restrict__ count, const float* __restrict__ grad, int64_t B,
+                                                         float scale, int normalize, float* __restrict__ zt, float* __restrict__ w,
+                                                         float* __restrict__ gt) {
+#pragma clang fp contract(off)
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B) return;
+    const int n = count[i];
+    const bool part = valid[i] != 0 && n > 0;
+    const float gs = grad[i] * scale;
+    const float wi = normalize ? gs * (n > 0 ? 1.f / (float)n : 0.f) : gs;
+    zt[i] = part ? zt[i] : __int_as_float(0x7FC00000);
+    w[i] = part ? wi : 0.f;
+    gt[i] = part ? -(wi * dsum[i]) : 0.f;
+}
+
+template <int OT, int DMAX, bool SUB, bool BIAS, bool HINGE>
+static int launch_pair_bwd_tiles(const SmBwdPairArgs& a, hipStream_t stream) {
+    const size_t lds = sb_lds_bytes(a.d, OT, BIAS);
+    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, false, SB_PAIR, SUB, BIAS, HINGE>), lds);
+    GHF_SET_MAX_LDS((softmax_bwd_kernel<OT, DMAX, true, SB_PAIR, SUB, BIAS, HINGE>), lds);
+    softmax_bwd_kernel<OT, DMAX, false, SB_PAIR, SUB, BIAS, HINGE><<<(unsigned)(a.qtiles * a.slabs), SB_NT, lds, stream>>>(a);
+    GHF_LAUNCH_CHECK();
+    softmax_bwd_kernel<OT, DMAX, true, SB_PAIR, SUB, BIAS, HINGE><<<(unsigned)cdiv(a.N, OT), SB_NT, lds, stream>>>(a);
+    GHF_LAUNCH_CHECK();
+    return GHF_OK;
+}
+
+template <bool HINGE>
+static int launch_pair_bwd_shape(const SmBwdPairArgs& a, bool sub, bool biased, hipStream_t stream) {
+    const bool wide = sb_otile(a.d) == 128;
+#define GHF_PAIR_BWD(SUBSET, BIASED) \
+    (wide ? launch_pair_bwd_tiles<128, 128, SUBSET, BIASED, HINGE>(a, stream) : launch_pair_bwd_tiles<64, 256, SUBSET, BIASED, HINGE>(a, stream))
+    if (sub && biased) return GHF_PAIR_BWD(true, true);
+    if (sub) return GHF_PAIR_BWD(true, false);
+    if (biased) return GHF_PAIR_BWD(false, true);
+    return GHF_PAIR_BWD(false, false);
+#undef GHF_PAIR_BWD
+}
+
+int launch_score_pair_bwd(bool hinge, const float* q, const float* c, const int64_t* iq, const int64_t* target,
+                          const int64_t* filt_ptr, const int64_t* filt_idx, int64_t nnz, int64_t rows_q, int64_t N, int64_t B, int d,
+                          float scale, float margin, int normalize, const int64_t* ic, int64_t C, const float* bias, const float* dsum,
+                          const int* count, const float* grad_loss, void* ws, size_t ws_bytes, float* dq, float* dc, float* db,
+                          hipStream_t stream) {
+    const int64_t M = ic ? C : N;                    // the candidates the sweeps run over: dc is [M, d]
+    const bool sizes = d > 0 && d <= RK_MAX_D && B > 0 && N > 0;
+    const size_t need = sizes ? score_pair_bwd_workspace_bytes(B, N, ic ? C : 0, d, nnz) : 0;
+    int rc = score_pair_open("score_pair_bwd", need, iq, nnz, rows_q, N, B, d, ic, C, ws_bytes);
+    if (rc != GHF_OK) return rc;
+    RankArgs r;
+    rc = score_open("score_pair_bwd", softmax_bwd_geom, need, q, c, iq, filt_ptr, filt_idx, nnz, rows_q, M, B, d, ws_bytes, &r);
+    if (rc != GHF_OK) return rc;
+    // dq partials; with ic the id map and the gathered bias [C]; then the four per-query arrays
+    const size_t base = score_softmax_bwd_workspace_bytes(B, M, d);
+    const size_t sub = ic ? score_softmax_bwd_sub_workspace_bytes(B, C, d, nnz) : base;
+    const size_t front = need - 4 * rk_align((size_t)B * 4);
+    char* tail = (char*)ws + front;
+    float* zt = (float*)tail;
+    int* valid = (int*)(tail + rk_align((size_t)B * 4));
+    float* w = (float*)(tail + 2 * rk_align((size_t)B * 4));
+    float* gt = (float*)(tail + 3 * rk_align((size_t)B * 4));
+    SmBwdPairArgs a = {};
+    a.bias = bias; a.db = bias ? db : nullptr;
+    if (bias && ic) {
+        a.bias = (float*)((char*)ws + sub);
+        rc = launch_cand_bias(bias, ic, C, N, (float*)((char*)ws + sub), stream);
+        if (rc != GHF_OK) return rc;
+    }
+    const int64_t* tpos = target;
+    const int64_t* list_idx = filt_idx;
+    const unsigned qb = (unsigned)cdiv(B, 256);
+    if (ic) {      // targets and lists as positions in ic; a bad ic or a target outside it rules the query out
+        CandMap m;
+        rc = launch_cand_map(q, c, iq, target, true, filt_ptr, filt_idx, nnz, ic, C, rows_q, N, B, d, nullptr, zt, valid, nullptr,
+                             nullptr, (char*)ws + base, sub - base, &m, stream);
+        if (rc != GHF_OK) return rc;
+        a.ic = ic; a.Nn = N;
+        tpos = m.tpos; r.filt_ptr = m.ptr; list_idx = m.idx;
+    } else {
+        score_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, target, rows_q, N, B, d, zt, valid, nullptr, nullptr);
+        GHF_LAUNCH_CHECK();
+        if (nnz > 0) {
+            list_range_kernel<<<(unsigned)cdiv(nnz, 256), 256, 0, stream>>>(filt_ptr, filt_idx, nnz, N, B, valid);
+            GHF_LAUNCH_CHECK();
+        }
+    }
+    rc = launch_pair_zt(zt, valid, B, scale, target, bias, stream);
+    if (rc != GHF_OK) return rc;
+    pair_saved_kernel<<<qb, 256, 0, stream>>>(valid, dsum, count, grad_loss, B, scale, normalize, zt, w, gt);
+    GHF_LAUNCH_CHECK();
+    a.q = q; a.c = c; a.iq = iq; a.target = tpos;
+    a.filt_ptr = r.filt_ptr; a.filt_idx = list_idx; a.nnz = nnz;
+    a.rows_q = rows_q; a.N = M; a.B = B; a.d = d; a.scale = scale; a.lse = zt; a.grad = grad_loss;
+    a.w = w; a.gt = gt; a.margin = margin;
+    a.qtiles = r.qtiles; a.slab_tiles = r.slab_tiles; a.slabs = r.slabs;
+    a.dq_part = (float*)ws; a.dc = dc;
+    rc = hinge ? launch_pair_bwd_shape<true>(a, ic != nullptr, bias != nullptr, stream)
+               : launch_pair_bwd_shape<false>(a, ic != nullptr, bias != nullptr, stream);
+    if (rc != GHF_OK) return rc;
+    return launch_ordered_sum(a.dq_part, a.slabs, B * (int64_t)d, dq, stream);
 }
 
 }  // namespace ghf

@@ -1248,6 +1248,82 @@ class HyperGNN(nn.Module):
                                                                   margin=margin, normalize=normalize, ic=cand)
         return (out, active) if return_active else out
 
+    def pairwise_loss_by_dot(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, loss: str = "hinge",
+                             margin: float = 1.0, scale: float = 1.0, normalize: bool = True, known=None,
+                             filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
+                             query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,
+                             candidates: Optional[torch.Tensor] = None, candidate_bias: Optional[torch.Tensor] = None,
+                             return_active: bool = False):
+        """``pairwise_loss`` by DOT PRODUCT — this model's own score — against every node, or one ``candidates`` set shared by
+        the batch (sampled or in-batch negatives, the way LightGCN, NGCF and PinSage train), fp32 ``[B]``.  With ``z[i, j] =
+        scale * row_i . embs[j]`` (``fma(scale, ., candidate_bias[j])`` with a bias), ``row_i = embs[query[i]]`` or
+        ``query_rows[i]``, and ``J_i`` = every node (every candidate) except query ``i``'s known partners and its target::
+
+            u[i, j] = z[i, j] - z[i, target[i]] + margin
+            loss[i] = mean over J_i of max(u, 0)          # loss="hinge": the max-margin ranking loss (PinSage, GraphSAGE)
+            loss[i] = mean over J_i of softplus(u)        # loss="logistic": BPR at margin=0 (LightGCN, NGCF)
+
+        ``normalize=False`` gives the sum instead of the mean; a query whose ``J_i`` is empty has loss exactly 0.  BPR with one
+        shared negative set, on ``RelationDecoder`` rows::
+
+            rows = decoder(embs, head, rel, rel_embs)
+            loss = model.pairwise_loss_by_dot(embs, head, tail, loss="logistic", margin=0.0, query_rows=rows,
+                                              candidates=neg).mean()
+
+        ``query_rows`` / ``known`` / ``filt_ptr, filt_idx`` / ``query_rel`` / ``candidates`` / ``candidate_bias`` mean what
+        they mean in ``negative_sampling_loss``; with ``candidates`` the batch's targets are added to the set, so another
+        query's target is an in-batch negative unless that query's ``known`` lists it.  ``return_active=True`` returns ``(loss,
+        active)``, ``active`` int32 ``[B]`` the number of violated pairs ``u > 0``; at ``margin=0, scale=1`` without a bias it
+        is ``rank_candidates``' ``greater``.  There is no ``negatives`` here: a set per query is ``pairwise_loss(negatives=)``,
+        which gathers every row once per query; this call reads a candidate row once per 128 queries.
+
+        The matrix-core sweep of ``rank_candidates`` with a pairwise epilogue (``ghf_score_pair_fwd``,
+        ``include/ghf_pairwise_dot_sweep.h``): neither the ``[B, C]`` scores, ids or coefficients nor the ``[C, d]`` gather
+        exist, forward or backward.  Recorded for autograd when grad mode is on and ``embs``, ``query_rows`` or
+        ``candidate_bias`` requires grad (``autograd.DotPairSweepLossFn``, ``ghf_score_pair_bwd``); rows of ``embs`` that are
+        neither candidate, target nor query get exactly zero, and so do the bias entries of nodes outside the set.
+        Bit-reproducible, a query's loss does not depend on its batch, and a bias of zeros gives the bits of the call without
+        the keyword.  ``scale`` finite and ``> 0``, ``margin`` finite (``ValueError`` otherwise)."""
+        what = "pairwise_loss_by_dot"
+        if embs.dim() != 2:
+            raise ValueError(f"embs must be [N, d], got {tuple(embs.shape)}")
+        kind = _native.PAIR_KINDS.get(loss) if isinstance(loss, str) else None
+        if kind is None:
+            raise ValueError(f"loss must be one of {sorted(_native.PAIR_KINDS)}, got {loss!r}")
+        self._known_form(known, filt_ptr, filt_idx, query_rel)
+        scale, margin = float(scale), float(margin)
+        if not (0.0 < scale < float("inf")):
+            raise ValueError(f"scale must be finite and positive, got {scale}")
+        if not (float("-inf") < margin < float("inf")):
+            raise ValueError(f"margin must be finite, got {margin}")
+        if not isinstance(normalize, bool) or not isinstance(return_active, bool):
+            raise TypeError(f"normalize and return_active must be bools, got {normalize!r} and {return_active!r}")
+        bias = self._candidate_bias(candidate_bias, embs)
+        bias_grad = bias is not None and bias.requires_grad
+        cand = None if candidates is None else self._candidate_ids(candidates, embs)
+        q = self._rank_ids(query, embs.size(0), embs, "query")
+        t = self._rank_ids(target, embs.size(0), embs, "target")
+        if q.numel() != t.numel():
+            raise ValueError(f"{q.numel()} queries and {t.numel()} targets")
+        self._query_rows(embs, query, query_rows, what)
+        if not embs.is_cuda:
+            raise RuntimeError(f"{what} computes on an MI355X HIP device only (input is on {embs.device})")
+        ptr, idx = self._filter_lists(embs, q, known, filt_ptr, filt_idx, query_rel)
+        if cand is not None:
+            cand = self._softmax_candidates(cand, t)
+        grad = embs.requires_grad or (query_rows is not None and query_rows.requires_grad) or bias_grad
+        if torch.is_grad_enabled() and grad:
+            from ..autograd import DotPairSweepLossFn
+            rows, iq = (None, q) if query_rows is None else (query_rows, None)
+            out, active = DotPairSweepLossFn.apply(embs, rows, iq, t, ptr, idx, kind, scale, margin, normalize, cand, bias)
+        else:
+            e = embs.detach().float()
+            qm, iq = (e, q) if query_rows is None else (query_rows.detach(), None)
+            out, _, _, active = _native.score_pair_sweep_fwd(kind, qm, e, t, iq=iq, filt_ptr=ptr, filt_idx=idx, scale=scale,
+                                                             margin=margin, normalize=normalize, ic=cand,
+                                                             bias=None if bias is None else bias.detach())
+        return (out, active) if return_active else out
+
     def softmax_loss(self, embs: torch.Tensor, query: torch.Tensor, target: torch.Tensor, *, scale: float = 1.0, known=None,
                      filt_ptr: Optional[torch.Tensor] = None, filt_idx: Optional[torch.Tensor] = None,
                      query_rows: Optional[torch.Tensor] = None, query_rel: Optional[torch.Tensor] = None,

@@ -4,8 +4,8 @@ the whole instruction stream with comments, directives and label numbers strippe
 LDS and scratch figures.  A kernel of the old listing is looked up in the new one under its own name after the --map
 substitutions (regular expressions over the mangled name).  It complements spills.py, which looks inside one listing.
 
-usage: isa_diff.py old.s new.s [--map REGEX=REPLACEMENT ...] [--show N]
-exit status 1 when a kernel differs or is missing on either side."""
+usage: isa_diff.py old.s new.s [--map REGEX=REPLACEMENT ...] [--show N] [--allow-new]
+exit status 1 when a kernel differs or is missing on either side (with --allow-new: differs, or is missing in the new one)."""
 import argparse, re, sys
 
 FIGURES = ("next_free_vgpr", "next_free_sgpr", "group_segment_fixed_size", "private_segment_fixed_size")
@@ -42,6 +42,8 @@ def main():
     ap.add_argument("old"), ap.add_argument("new")
     ap.add_argument("--map", action="append", default=[], metavar="REGEX=REPLACEMENT")
     ap.add_argument("--show", type=int, default=3, help="differing lines printed per kernel")
+    ap.add_argument("--allow-new", action="store_true",
+                    help="a kernel that only the new listing has is listed, not a failure (a feature adds instantiations)")
     args = ap.parse_args()
     old, new = kernels(args.old), kernels(args.new)
     same, seen, failed = 0, set(), False
@@ -69,7 +71,7 @@ def main():
                 shown += 1
     for name in sorted(set(new) - seen):
         print(f"NEW {name}")
-        failed = True
+        failed = failed or not args.allow_new
     print(f"{same} of {len(old)} kernels identical")
     return 1 if failed else 0
 
