@@ -24,7 +24,7 @@
 // dist_chain() and so compare equal to the tile's value of the same pair.  The vector and the scalar path differ in how the
 // floats are loaded, not in the chain.  (ghf_dist_rank sums across a lane group: its bits are NOT these.)
 //
-// Rank:   as rank.hip — the prep pass validates ids and resets the counters, dsweep_target_kernel forms t_i, the sweep counts
+// Rank:   as rank.hip — the prep pass validates ids and resets the counters, dist_target_kernel forms t_i, the sweep counts
 //         popc(ballot(s > t_i)) / (s == t_i) per query into scalar registers and adds them once per (query, workgroup) with an
 //         integer atomic, dsweep_filter_kernel takes the listed candidates out again, dsweep_finish_kernel the target.
 // Top-k:  rank_sweep.h's keys, append buffers and select_in_place.  A query belongs to ONE wave, so its entry count and threshold
@@ -315,21 +315,6 @@ __global__ __launch_bounds__(256) void dsweep_tile_kernel(const DsweepArgs a) {
 }
 
 // ---- the small kernels around the sweep -------------------------------------------------------------------------------------
-// one thread per query, behind the prep pass (which has validated the ids): the target's score by the sweep's chain, from its
-// own row of c (the target need not be a candidate); NaN for a query that is not valid
-__global__ __launch_bounds__(256) void dsweep_target_kernel(int metric, const float* __restrict__ q, const float* __restrict__ c,
-                                                            const int64_t* __restrict__ iq, const int64_t* __restrict__ target,
-                                                            const int* __restrict__ valid, int64_t B, int d, float* __restrict__ t) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= B) return;
-    float v = __int_as_float(0x7FC00000);
-    if (valid[i]) {
-        const int64_t r = iq ? iq[i] : i;
-        v = -dist_chain(metric, q + (size_t)r * d, c + (size_t)target[i] * d, d, rows_vec(q, d) && rows_vec(c, d));
-    }
-    t[i] = v;
-}
-
 // one thread per filter entry, as rank_filter_kernel: an id out of range marks its query; any other entry's score is recomputed
 // and taken out of the count it went into.  Over a subset the lists and `tpos` are positions in ic (candidates.hip).
 __global__ __launch_bounds__(256) void dsweep_filter_kernel(int metric, const float* __restrict__ q, const float* __restrict__ c,
@@ -476,7 +461,7 @@ static int launch_dsweep_rank(int metric, const float* q, const float* c, const 
         score_prep_kernel<<<qb, 256, 0, stream>>>(q, c, iq, target, rows_q, N, B, d, nullptr, valid, (long long*)greater, (long long*)equal);
         GHF_LAUNCH_CHECK();
     }
-    dsweep_target_kernel<<<qb, 256, 0, stream>>>(metric, q, c, iq, target, valid, B, d, t);
+    dist_target_kernel<<<qb, 256, 0, stream>>>(metric, q, c, iq, target, valid, B, d, t);
     GHF_LAUNCH_CHECK();
     a.t = t; a.greater = (unsigned long long*)greater; a.equal = (unsigned long long*)equal;
     rc = launch_dsweep_tiles<false>(metric, a, stream);

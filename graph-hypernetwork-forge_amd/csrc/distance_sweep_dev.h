@@ -1,6 +1,7 @@
-// distance_sweep_dev.h — what distance_sweep.hip (rank, top-k) and distance_loss.hip (the two losses and their
-// backward; §25) share: the tile constants, the one chain every distance of a pair equals bit for bit, and the types through
-// which a wave-uniform row is read from the constant address space (scalar loads).
+// distance_sweep_dev.h — what distance_sweep.hip (rank, top-k), distance_loss.hip (the two losses and their
+// backward; §25) and pairwise_sweep.hip (§27) share: the tile constants, the one chain every distance of a pair equals bit for
+// bit, the types through which a wave-uniform row is read from the constant address space (scalar loads), and the kernel that
+// forms the targets' scores by that chain.
 #pragma once
 #include "common.h"
 #include "rank_sweep.h"
@@ -63,5 +64,21 @@ __device__ __forceinline__ float dist_chain(int metric, const float* __restrict_
 
 typedef const float __attribute__((address_space(4))) ds_cfloat;
 typedef const f32x4 __attribute__((address_space(4))) ds_cf32x4;
+
+// one thread per query, behind the pass that validated the ids: the target's score by the tile's chain, from its own row of c
+// (node id; the target need not be a candidate); NaN for a query that is not valid
+static __global__ __launch_bounds__(256) void dist_target_kernel(int metric, const float* __restrict__ q, const float* __restrict__ c,
+                                                                 const int64_t* __restrict__ iq, const int64_t* __restrict__ target,
+                                                                 const int* __restrict__ valid, int64_t B, int d,
+                                                                 float* __restrict__ t) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= B) return;
+    float v = __int_as_float(0x7FC00000);
+    if (valid[i]) {
+        const int64_t r = iq ? iq[i] : i;
+        v = -dist_chain(metric, q + (size_t)r * d, c + (size_t)target[i] * d, d, rows_vec(q, d) && rows_vec(c, d));
+    }
+    t[i] = v;
+}
 
 }  // namespace ghf
